@@ -8,9 +8,13 @@
 One process per GPU; each rank trains on its own 32 synthetic 256x256 thermal/visible pairs already resident in HBM
 (weak scaling), gradients are all-reduced over RCCL.  A "step" = the full generator step + discriminator step of
 TFC-GAN-FFT/TFCGAN_multigpu_patchFFT_16P.py:545-638 (without LPIPS / temperature head).  Rank 0 prints ONE
-JSON line.  `roofline` is measured live with hipEvents around the launches of the dominant kernel (tfc_igemm2_kernel, the persistent
-halo-staged implicit-GEMM convolution) in every 4th step of the timed region; `cpu_baseline` times the CPU oracle (torch fp32 restatement
-of the same step) on this box's host cores on a bounded sample (rank 0, N=1 only).
+JSON line.
+
+A plain run sets up, warms up, times --steps product steps and prints the headline (`value`, `ms_per_step`, ...). `--full` adds what the headline
+does not need: `roofline`, measured live with hipEvents around the launches of the dominant kernel (tfc_igemm2_kernel, the persistent
+halo-staged implicit-GEMM convolution) in every 4th step of the timed region; `exposed_allreduce_ms`; `with_lpips`; `generator_l1_vs_oracle`;
+`cpu_baseline`, which times the CPU oracle (torch fp32 restatement of the same step) on the host cores on a bounded sample (rank 0, N=1 only).
+`--dump-outputs DIR` writes what the last timed step returned (rank 0) as DIR/<name>.npy, see dump_outputs().
 """
 import argparse
 import json
@@ -110,6 +114,30 @@ def generator_l1(dev):
     return out
 
 
+DUMP_LIMIT_BYTES = 64 * 10**6              # all files together, .npy headers included
+DUMP_HEADER_BYTES = 1024                   # allowance per file (numpy writes 128 bytes for these shapes)
+DUMP_SAMPLE_MIN = 1 << 20                  # arrays of at most this many elements are always written whole
+
+
+def dump_outputs(dirname, out):
+    """Write the dict one step returned (loss scalars, generated images) as dirname/<name>.npy in float32, so that two builds can be compared output
+    for output. When the whole would exceed DUMP_LIMIT_BYTES, every array above DUMP_SAMPLE_MIN elements is replaced by a fixed, seeded sample of
+    an equal share of the remaining budget: the flattened array at sorted indices from np.random.default_rng(0), identical from run to run."""
+    import numpy as np
+    arrays = {k: v.detach().float().cpu().numpy() for k, v in out.items()}
+    cap = (DUMP_LIMIT_BYTES - DUMP_HEADER_BYTES * len(arrays)) // 4
+    big = [k for k, a in arrays.items() if a.size > DUMP_SAMPLE_MIN]
+    if big and sum(a.size for a in arrays.values()) > cap:
+        share = (cap - sum(a.size for k, a in arrays.items() if k not in big)) // len(big)
+        for k in big:
+            a = arrays[k]
+            if a.size > share:
+                arrays[k] = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, share, replace=False))]
+    os.makedirs(dirname, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(dirname, k + ".npy"), a)
+
+
 def self_launch(ngpus):
     """`python bench.py --gpus N` without an outer launcher: start the N ranks as a CHILD `python -m torch.distributed.run` (this parent has imported
     nothing that touches the GPU and never execs), let the child's stdout / stderr through (rank 0 prints the one JSON line) and exit with its code."""
@@ -131,7 +159,11 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--batch", type=int, default=PER_GPU_BATCH, help="per-GPU batch (BASELINE config: 32)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: roofline (instrumented timed steps), exposed_allreduce_ms, with_lpips, "
+                         "generator_l1_vs_oracle, cpu_baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out with_lpips, generator_l1_vs_oracle and cpu_baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step returned as DIR/<name>.npy (float32, at most 64 MB in all)")
     ap.add_argument("--dtype", choices=["bf16", "fp32"], default="bf16",
                     help="bf16 = the benchmarked arithmetic (BASELINE.json); fp32 = the exact-fp32 parity mode (generator L1 vs oracle 1.9e-6), on the "
                          "legacy one-tile-per-workgroup kernels at 1/16 of the MFMA rate -- reported so that its cost is a number, not a guess")
@@ -227,42 +259,47 @@ def main():
     for _ in range(args.warmup):
         run_step()
     barrier()
-    # The roofline object is measured live, inside the timed region, with hipEvent pairs around the MFMA kernel launches on the launch
+    # --full: the roofline object is measured live, inside the timed region, with hipEvent pairs around the MFMA kernel launches on the launch
     # stream. An event pair costs ~2.3 us of stream time (A/B in scripts/ab_prof.py: 0.45 ms per fully instrumented step, 3.5 %), so
     # every PROF_EVERY-th timed step is instrumented, not all of them: `value` then carries < 1 % of instrumentation overhead.
-    if os.environ.get("TFC_BENCH_NO_EXPOSED", "0") in ("", "0"):   # (A/B knob: what does the measurement itself cost?)
+    if args.full and os.environ.get("TFC_BENCH_NO_EXPOSED", "0") in ("", "0"):   # (A/B knob: what does the measurement itself cost?)
         parallel.exposed_wait_begin()                      # hipEvent pairs around the waits of BucketReducer.finish(): `exposed_allreduce_ms`
     t0 = time.perf_counter()
     # The product runs its weight gradients on a second stream beside the input-gradient chain (nets.py). A launch that shares the chip with another
-    # kernel has no duration of its own, so the INSTRUMENTED steps (and only they) run everything in line on one stream: the roofline object then
-    # prices exclusive launches, `value` is the mix actually run (every PROF_EVERY-th step serial, the rest overlapped).
+    # kernel has no duration of its own, so under --full the INSTRUMENTED steps (and only they) run everything in line on one stream: the roofline object
+    # then prices exclusive launches, `value` is the mix actually run (every PROF_EVERY-th step serial, the rest overlapped). Both forms compute the same bits.
     side_default = T.set_wgrad_stream(True)
     T.set_wgrad_stream(side_default)
     for i in range(args.steps):
-        inst = i % PROF_EVERY == 0
-        T.ops.prof_enable(inst)
-        T.set_wgrad_stream(side_default and not inst)
+        if args.full:
+            inst = i % PROF_EVERY == 0
+            T.ops.prof_enable(inst)
+            T.set_wgrad_stream(side_default and not inst)
         out = run_step()
     barrier()
     elapsed = time.perf_counter() - t0
-    T.ops.prof_enable(False)
-    T.set_wgrad_stream(side_default)
-    recs = T.ops.prof_records(16384)
-    ig_ms, ig_flop, ig_n = T.ops.prof_collect(0)
-    wg_ms, wg_flop, wg_n = T.ops.prof_collect(1)
-    T.ops.prof_collect(2)                                 # wgrad finish passes (no algorithmic FLOP of their own)
-    fb_ms, fb_flop, fb_n = T.ops.prof_collect(3)          # fused first-block backward ([BlurPool]^T + LeakyReLU' + weight gradient in one launch)
-    # the dominant kernel proper: class-0 calls that dispatch tfc_igemm2_kernel (bf16, whole 64-byte channel chunks, NHWC output); the rest of
-    # class 0 (first-layer tfc_conv_c8_kernel, the two 3-channel heads) is reported beside it
-    p8 = lambda c: (c + 7) // 8 * 8  # noqa: E731
-    es = 2 if args.dtype == "bf16" else 4
-    dom = [r for r in recs if r["kclass"] == 0 and (p8(r["Cin"]) * es) % 64 == 0 and (p8(r["Cout"]) * es) % 64 == 0]
-    peak = MFMA_BF16_PEAK_TFLOPS if args.dtype == "bf16" else MFMA_F32_PEAK_TFLOPS
-    kname = DOMINANT_KERNEL if args.dtype == "bf16" else "tfc_igemm_kernel"
-    dom_ms, dom_flop = sum(r["ms"] for r in dom), sum(r["flop"] for r in dom)
-    dom_launches = len(dom)                               # one launch per call: the four sub-pixel phases of a transposed convolution fold into one grid
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out)
     loss_g, loss_d = float(out["loss_G"]), float(out["loss_D"])
-    exposed_ms = parallel.exposed_wait_collect() / args.steps    # stream time spent waiting for gradient buckets, per step (0 at one rank)
+    exposed_ms = 0.0
+    if args.full:
+        T.ops.prof_enable(False)
+        T.set_wgrad_stream(side_default)
+        recs = T.ops.prof_records(16384)
+        ig_ms, ig_flop, ig_n = T.ops.prof_collect(0)
+        wg_ms, wg_flop, wg_n = T.ops.prof_collect(1)
+        T.ops.prof_collect(2)                                 # wgrad finish passes (no algorithmic FLOP of their own)
+        fb_ms, fb_flop, fb_n = T.ops.prof_collect(3)          # fused first-block backward ([BlurPool]^T + LeakyReLU' + weight gradient in one launch)
+        # the dominant kernel proper: class-0 calls that dispatch tfc_igemm2_kernel (bf16, whole 64-byte channel chunks, NHWC output); the rest of
+        # class 0 (first-layer tfc_conv_c8_kernel, the two 3-channel heads) is reported beside it
+        p8 = lambda c: (c + 7) // 8 * 8  # noqa: E731
+        es = 2 if args.dtype == "bf16" else 4
+        dom = [r for r in recs if r["kclass"] == 0 and (p8(r["Cin"]) * es) % 64 == 0 and (p8(r["Cout"]) * es) % 64 == 0]
+        peak = MFMA_BF16_PEAK_TFLOPS if args.dtype == "bf16" else MFMA_F32_PEAK_TFLOPS
+        kname = DOMINANT_KERNEL if args.dtype == "bf16" else "tfc_igemm_kernel"
+        dom_ms, dom_flop = sum(r["ms"] for r in dom), sum(r["flop"] for r in dom)
+        dom_launches = len(dom)                               # one launch per call: the four sub-pixel phases of a transposed convolution fold into one grid
+        exposed_ms = parallel.exposed_wait_collect() / args.steps    # stream time spent waiting for gradient buckets, per step (0 at one rank)
     tmax = torch.tensor([elapsed, exposed_ms], dtype=torch.float64, device=dev)
     if world > 1:
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
@@ -271,9 +308,6 @@ def main():
     if rank == 0:
         ms_per_step = 1e3 * elapsed / args.steps
         value = args.batch * world * args.steps / elapsed
-        achieved = (dom_flop / 1e12) / (dom_ms / 1e3) if dom_ms > 0 else 0.0
-        nprof = len(range(0, args.steps, PROF_EVERY))                       # timed steps that carried the hipEvent instrumentation
-        step_s = elapsed / args.steps
         line = {
             "metric": ("training images/sec at 256x256 STN21_Original_NewModel3_Official (BASELINE.json configs[4]; not the headline metric)" if stn else
                        "training images/sec at 256x256 PATCH-16, 1/2/4/8 MI355X; gen L1 vs ref"),
@@ -291,47 +325,52 @@ def main():
                                     " (step as BASELINE.md section 3 defines it: LPIPS and the temperature head excluded)"),
                        "global_batch": args.batch * world, "per_gpu_batch": args.batch, "parallelism": f"dp{world}",
                        "algorithmic_gflop_per_image": None if stn else T.TrainStep.STEP_GFLOP},
-            "roofline": {"bound": "mfma", "kernel": kname + (" (persistent halo-staged implicit-GEMM conv: fwd / dgrad / convT / upconv, bf16 MFMA 32x32x16)" if args.dtype == "bf16"
-                                                             else " (one-tile-per-workgroup halo-staged implicit GEMM, fp32 MFMA 32x32x2: exact fp32 parity mode)"),
-                         "achieved": achieved, "peak": peak, "unit": "TFLOP/s", "frac": achieved / peak,
-                         "traffic": pmc_traffic(DOMINANT_KERNEL) if args.dtype == "bf16" else None, "traffic_unit": "HBM bytes per launch (PMC)", "launches": dom_launches,
-                         "avg_launch_ms": dom_ms / max(dom_launches, 1), "algorithmic_gflop_per_launch": dom_flop / 1e9 / max(dom_launches, 1),
-                         "instrumented_steps": nprof, "share_of_step_time": (dom_ms / 1e3 / nprof) / step_s,
-                         "instrumented_mode": ("one stream: exclusive launches (the other timed steps run the weight gradients on a second stream)"
-                                               if side_default else "one stream (TFC_WGRAD_STREAM=0: every step)"),
-                         "whole_conv_class": {"kernels": "tfc_igemm2_kernel + tfc_first_block_fwd_kernel (conv + LeakyReLU + BlurPool of the first blocks, priced at the conv FLOP) + 3-channel head kernels", "achieved": (ig_flop / 1e12) / (ig_ms / 1e3) if ig_ms > 0 else 0.0,
-                                              "unit": "TFLOP/s", "calls": ig_n, "share_of_step_time": (ig_ms / 1e3 / nprof) / step_s},
-                         "second_kernel": {"kernel": "tfc_wgrad_kernel family (incl. slab reduction)", "achieved": (wg_flop / 1e12) / (wg_ms / 1e3) if wg_ms > 0 else 0.0,
-                                           "unit": "TFLOP/s", "launches": wg_n, "share_of_step_time": (wg_ms / 1e3 / nprof) / step_s},
-                         "fused_first_block_backward": {"kernel": "tfc_wgrad_c8_fusedm_kernel (transposed blur as a GEMM on the matrix core + first-layer weight gradient; sign words instead of the stored activation)",
-                                                        "calls": fb_n, "avg_call_ms": fb_ms / max(fb_n, 1), "share_of_step_time": (fb_ms / 1e3 / nprof) / step_s}},
             "whole_step_tflops": None if stn else T.TrainStep.STEP_GFLOP * value / 1e3,
+            "allreduce_backend": (dist.get_backend() if parallel.collectives_active() else None),
+            "final_losses": {"loss_G": loss_g, "loss_D": loss_d},
+        }
+        if args.full:
+            achieved = (dom_flop / 1e12) / (dom_ms / 1e3) if dom_ms > 0 else 0.0
+            nprof = len(range(0, args.steps, PROF_EVERY))                       # timed steps that carried the hipEvent instrumentation
+            step_s = elapsed / args.steps
+            line["roofline"] = {"bound": "mfma", "kernel": kname + (" (persistent halo-staged implicit-GEMM conv: fwd / dgrad / convT / upconv, bf16 MFMA 32x32x16)" if args.dtype == "bf16"
+                                                                    else " (one-tile-per-workgroup halo-staged implicit GEMM, fp32 MFMA 32x32x2: exact fp32 parity mode)"),
+                                "achieved": achieved, "peak": peak, "unit": "TFLOP/s", "frac": achieved / peak,
+                                "traffic": pmc_traffic(DOMINANT_KERNEL) if args.dtype == "bf16" else None, "traffic_unit": "HBM bytes per launch (PMC)", "launches": dom_launches,
+                                "avg_launch_ms": dom_ms / max(dom_launches, 1), "algorithmic_gflop_per_launch": dom_flop / 1e9 / max(dom_launches, 1),
+                                "instrumented_steps": nprof, "share_of_step_time": (dom_ms / 1e3 / nprof) / step_s,
+                                "instrumented_mode": ("one stream: exclusive launches (the other timed steps run the weight gradients on a second stream)"
+                                                      if side_default else "one stream (TFC_WGRAD_STREAM=0: every step)"),
+                                "whole_conv_class": {"kernels": "tfc_igemm2_kernel + tfc_first_block_fwd_kernel (conv + LeakyReLU + BlurPool of the first blocks, priced at the conv FLOP) + 3-channel head kernels", "achieved": (ig_flop / 1e12) / (ig_ms / 1e3) if ig_ms > 0 else 0.0,
+                                                     "unit": "TFLOP/s", "calls": ig_n, "share_of_step_time": (ig_ms / 1e3 / nprof) / step_s},
+                                "second_kernel": {"kernel": "tfc_wgrad_kernel family (incl. slab reduction)", "achieved": (wg_flop / 1e12) / (wg_ms / 1e3) if wg_ms > 0 else 0.0,
+                                                  "unit": "TFLOP/s", "launches": wg_n, "share_of_step_time": (wg_ms / 1e3 / nprof) / step_s},
+                                "fused_first_block_backward": {"kernel": "tfc_wgrad_c8_fusedm_kernel (transposed blur as a GEMM on the matrix core + first-layer weight gradient; sign words instead of the stored activation)",
+                                                               "calls": fb_n, "avg_call_ms": fb_ms / max(fb_n, 1), "share_of_step_time": (fb_ms / 1e3 / nprof) / step_s}}
             # stream time between "all buckets issued" and "all buckets arrived" in BucketReducer.finish(), summed over the generator's and the
             # discriminator's exchange, max over ranks (DESIGN section 6 predicts 0.09-0.18 ms at 8 GPUs; the generator's part sits on the side stream
             # beside the discriminator step, so this is an upper bound of what the exchange adds to the step)
-            "exposed_allreduce_ms": exposed_ms, "allreduce_backend": (dist.get_backend() if parallel.collectives_active() else None),
-            "final_losses": {"loss_G": loss_g, "loss_D": loss_d},
-        }
-        if world == 1 and not stn and not args.lpips and not args.no_cpu_baseline and args.dtype == "bf16":
-            # the reference's full loss_G also carries 0.5 * LPIPS (P16:598, :607): the same step with that term, timed right after
-            crit = make_lpips()
-            term = crit.as_extra_loss(0.5)
-            for _ in range(2):
-                ts.step(A, B, extra_loss_G=term)
-            torch.cuda.synchronize()
-            k2 = max(5, args.steps // 2)
-            t1 = time.perf_counter()
-            for _ in range(k2):
-                ts.step(A, B, extra_loss_G=term)
-            torch.cuda.synchronize()
-            dt2 = time.perf_counter() - t1
-            line["with_lpips"] = {"value": args.batch * k2 / dt2, "unit": "images/sec", "ms_per_step": 1e3 * dt2 / k2, "steps": k2,
-                                  "note": "same step + 0.5 * LPIPS(fake_B, real_B): VGG16 forward x2 + backward w.r.t. fake_B, seeded-random weights"}
-        if world == 1 and not args.no_cpu_baseline and not stn:
-            line["generator_l1_vs_oracle"] = generator_l1(dev)
-            line["cpu_baseline"] = cpu_baseline()
-        else:
-            line["cpu_baseline"] = None                           # (stn21: the CPU port in oracle/ is the PATCH-16 / GLO-16 step)
+            line["exposed_allreduce_ms"] = exposed_ms
+            if world == 1 and not stn and not args.lpips and not args.no_cpu_baseline and args.dtype == "bf16":
+                # the reference's full loss_G also carries 0.5 * LPIPS (P16:598, :607): the same step with that term, timed right after
+                crit = make_lpips()
+                term = crit.as_extra_loss(0.5)
+                for _ in range(2):
+                    ts.step(A, B, extra_loss_G=term)
+                torch.cuda.synchronize()
+                k2 = max(5, args.steps // 2)
+                t1 = time.perf_counter()
+                for _ in range(k2):
+                    ts.step(A, B, extra_loss_G=term)
+                torch.cuda.synchronize()
+                dt2 = time.perf_counter() - t1
+                line["with_lpips"] = {"value": args.batch * k2 / dt2, "unit": "images/sec", "ms_per_step": 1e3 * dt2 / k2, "steps": k2,
+                                      "note": "same step + 0.5 * LPIPS(fake_B, real_B): VGG16 forward x2 + backward w.r.t. fake_B, seeded-random weights"}
+            if world == 1 and not args.no_cpu_baseline and not stn:
+                line["generator_l1_vs_oracle"] = generator_l1(dev)
+                line["cpu_baseline"] = cpu_baseline()
+            else:
+                line["cpu_baseline"] = None                           # (stn21: the CPU port in oracle/ is the PATCH-16 / GLO-16 step)
         print(json.dumps(line), flush=True)
     if world > 1:
         dist.barrier()

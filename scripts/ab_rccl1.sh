@@ -3,7 +3,7 @@
 # usage (GPU box): bash scripts/ab_rccl1.sh > gpurun_out/ab_rccl1.log
 run() {
   echo -n "$1: "
-  env $2 timeout -k 10 200 python3 bench.py --no-cpu-baseline --steps 20 --warmup 5 2>/dev/null | tail -1 | python3 -c "import sys,json; b=json.loads(sys.stdin.read()); print(round(b['ms_per_step'],3), 'ms/step, exposed', round(b['exposed_allreduce_ms'],3), b['allreduce_backend'])"
+  env $2 timeout -k 10 200 python3 bench.py --full --no-cpu-baseline --steps 20 --warmup 5 2>/dev/null | tail -1 | python3 -c "import sys,json; b=json.loads(sys.stdin.read()); print(round(b['ms_per_step'],3), 'ms/step, exposed', round(b['exposed_allreduce_ms'],3), b['allreduce_backend'])"
 }
 run "plain, two streams          " "A=1"
 run "rccl1, two streams          " "TFC_FORCE_COLLECTIVES=1"

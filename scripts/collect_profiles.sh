@@ -12,7 +12,7 @@ mkdir -p $o
 export TFC_WGRAD_STREAM=0
 rm -f $o/launch.log
 export TFC_LAUNCH_LOG=$PWD/$o/launch.log
-rocprofv3 --kernel-trace --stats --output-format csv -d $o/trace -o p -- python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline > $o/bench_traced.json 2> $o/bench_traced.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $o/trace -o p -- python3 bench.py --steps 5 --warmup 2 --full --no-cpu-baseline > $o/bench_traced.json 2> $o/bench_traced.err
 unset TFC_LAUNCH_LOG
 python3 scripts/per_layer.py $o/trace $o/launch.log $o/per_layer.md > /dev/null
 echo "trace done" 
@@ -24,7 +24,7 @@ echo "write done"
 python3 scripts/pmc_traffic.py $o/pmc $o/pmc_traffic.json | head -8
 # 3. the un-profiled default run
 unset TFC_WGRAD_STREAM
-python3 bench.py > $o/bench.json 2> $o/bench.err
+python3 bench.py --full > $o/bench.json 2> $o/bench.err
 cut -c1-300 $o/bench.json
 # the raw counter CSVs are large: keep the summaries only
 rm -rf $o/pmc/fetch $o/pmc/write

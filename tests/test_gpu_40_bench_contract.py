@@ -1,4 +1,5 @@
-"""bench.py's one-line JSON contract (driver-facing): run it as the driver does, at a small batch, and check every field the contract names."""
+"""bench.py's one-line JSON contract (driver-facing): run it as the driver does, at a small batch, and check every field the contract names.
+A plain run prints the headline only; the roofline, `exposed_allreduce_ms` and the CPU legs come with --full."""
 import json
 import os
 import subprocess
@@ -20,7 +21,7 @@ def _run(*extra):
 
 
 def test_bench_json_contract():
-    d = _run("--no-cpu-baseline")
+    d = _run("--full", "--no-cpu-baseline")
     for k, t in (("metric", str), ("value", float), ("unit", str), ("n_gpus", int), ("steps", int), ("warmup", int), ("ms_per_step", float),
                  ("higher_is_better", bool), ("scaling", str), ("dtype", str), ("data", str), ("config", dict), ("roofline", dict)):
         assert isinstance(d[k], t), (k, d[k])
@@ -34,19 +35,43 @@ def test_bench_json_contract():
     assert d["cpu_baseline"] is None                                                   # --no-cpu-baseline
 
 
+def test_bench_plain_run_is_lean_and_dumps_outputs(tmp_path):
+    """a plain run prints the headline fields and nothing that needs extra measurements; --dump-outputs writes what the last timed step returned, the
+    same bits from run to run (seeded inputs, a bit-reproducible step)"""
+    import numpy as np
+    dumps = []
+    for i in range(2):
+        out = tmp_path / f"run{i}"
+        d = _run("--dump-outputs", str(out))
+        for k, t in (("metric", str), ("value", float), ("unit", str), ("ms_per_step", float), ("higher_is_better", bool), ("dtype", str)):
+            assert isinstance(d[k], t), (k, d[k])
+        assert d["steps"] == 4 and d["warmup"] == 1 and d["unit"] == "images/sec" and d["dtype"] == "bf16" and "PATCH-16" in d["metric"]
+        assert abs(d["value"] - 4 * 1e3 / d["ms_per_step"]) < 1e-6 * d["value"]
+        assert not {"roofline", "exposed_allreduce_ms", "with_lpips", "generator_l1_vs_oracle", "cpu_baseline"} & set(d)
+        files = {f.name: np.load(f) for f in out.iterdir()}
+        assert sum(f.stat().st_size for f in out.iterdir()) <= 64 * 10**6
+        assert all(a.dtype == np.float32 for a in files.values())
+        assert files["fake_B.npy"].shape == (4, 3, 256, 256) and np.isfinite(files["fake_B.npy"]).all()
+        assert float(files["loss_G.npy"]) == d["final_losses"]["loss_G"] and float(files["loss_D.npy"]) == d["final_losses"]["loss_D"]
+        dumps.append(files)
+    assert dumps[0].keys() == dumps[1].keys()
+    for k in dumps[0]:
+        assert np.array_equal(dumps[0][k], dumps[1][k]), k
+
+
 def test_bench_glo16_and_fp32_modes_run():
     g = _run("--no-cpu-baseline", "--config", "glo16")
     assert "GLO-16" in g["config"]["workload"] and g["value"] > 0
-    f = _run("--no-cpu-baseline", "--dtype", "fp32")
+    f = _run("--full", "--no-cpu-baseline", "--dtype", "fp32")
     assert f["dtype"] == "fp32" and f["roofline"]["peak"] == 157.3 and 0 < f["roofline"]["frac"] < 1
 
 
 def test_bench_stn21_config_and_one_rank_rccl_mode_run():
     """`--config stn21` (BASELINE.json configs[4] on the same line format) and the one-GPU rehearsal of the RCCL path (TFC_FORCE_COLLECTIVES=1: a one-rank
     "nccl" group created by bench.py itself; the collectives are issued and `exposed_allreduce_ms` is measured)"""
-    s = _run("--no-cpu-baseline", "--config", "stn21", "--batch", "2")
+    s = _run("--full", "--no-cpu-baseline", "--config", "stn21", "--batch", "2")
     assert "STN21" in s["config"]["workload"] and s["value"] > 0 and s["cpu_baseline"] is None and s["roofline"]["launches"] > 0
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "1", "--batch", "4", "--no-cpu-baseline"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "1", "--batch", "4", "--full", "--no-cpu-baseline"]
     env = dict(os.environ, TFC_FORCE_COLLECTIVES="1")
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT"):
         env.pop(k, None)
@@ -64,7 +89,7 @@ def test_bench_launches_its_own_ranks():
     env = dict(os.environ, TFC_BENCH_BACKEND="gloo")
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT"):
         env.pop(k, None)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--batch", "2", "--no-cpu-baseline"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--batch", "2", "--full", "--no-cpu-baseline"]
     out = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=900, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]

@@ -221,6 +221,29 @@ def test_synthetic_input_recipe_matches_the_oracle():
     assert t.shape == (2, 256, 256) and t.min() >= 24 and t.max() <= 38
 
 
+def test_bench_dump_outputs_writes_float32_within_budget(tmp_path):
+    """bench.py --dump-outputs: one float32 .npy per returned array, whole while the lot fits in 64 MB; above that the large arrays become fixed,
+    seeded samples (sorted indices) that share the budget, identical from call to call"""
+    import bench
+    small = {"loss_G": torch.tensor(1.5), "fake_B": torch.linspace(-1, 1, 4 * 3 * 64 * 64).to(torch.bfloat16).reshape(4, 3, 64, 64)}
+    bench.dump_outputs(str(tmp_path / "small"), small)
+    got = {k: np.load(tmp_path / "small" / (k + ".npy")) for k in small}
+    assert got["loss_G"].dtype == np.float32 and got["loss_G"].shape == () and float(got["loss_G"]) == 1.5
+    assert got["fake_B"].dtype == np.float32 and np.array_equal(got["fake_B"], small["fake_B"].float().numpy())
+    # arange values are their own flat indices (exact in fp32 below 2^24)
+    big = {"loss_D": torch.tensor(0.25), "x": torch.arange(10_000_000, dtype=torch.float32), "y": torch.arange(9_000_000, dtype=torch.float32)}
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), big)
+    share = ((bench.DUMP_LIMIT_BYTES - 3 * bench.DUMP_HEADER_BYTES) // 4 - 1) // 2
+    for k, n in (("x", 10_000_000), ("y", 9_000_000)):
+        a, b = np.load(tmp_path / "a" / (k + ".npy")), np.load(tmp_path / "b" / (k + ".npy"))
+        assert a.dtype == np.float32 and a.shape == (share,) and np.array_equal(a, b)
+        assert (np.diff(a) > 0).all() and a[0] >= 0 and a[-1] < n
+    assert float(np.load(tmp_path / "a" / "loss_D.npy")) == 0.25
+    total = sum(f.stat().st_size for f in (tmp_path / "a").iterdir())
+    assert total <= bench.DUMP_LIMIT_BYTES
+
+
 def test_dataparallel_replica_is_refused_loudly():
     """nn.DataParallel on several devices replicates the module (`_is_replica`): its copies hold no Parameters and would share the
     operand-stream cache between threads, so forward raises and points at the one-process-per-GPU path (P16:444-445 replaced)"""

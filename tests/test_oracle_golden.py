@@ -1,10 +1,23 @@
 """The CPU oracle against the fixtures produced by the reference's own (ast-lifted) definitions -- tests/golden/make_golden.py.
 This is what pins the oracle; the GPU parity tests then compare the HIP path with the oracle and with the same fixtures."""
 import numpy as np
+import pytest
 import torch
 import torch.nn as nn
 
 from oracle import tfcgan_oracle as O
+
+
+@pytest.fixture(autouse=True)
+def host_independent_cpu_numerics():
+    """the CPU numerics tests/golden/make_golden.py used (with MKL_CBWR from conftest.py): oneDNN's convolutions block by the host's cache sizes and
+    the thread count splits some sums, so both are fixed here; the same bits then come out on any x86 host"""
+    threads, mkldnn = torch.get_num_threads(), torch.backends.mkldnn.enabled
+    torch.set_num_threads(8)
+    torch.backends.mkldnn.enabled = False
+    yield
+    torch.set_num_threads(threads)
+    torch.backends.mkldnn.enabled = mkldnn
 
 
 def t(a):
