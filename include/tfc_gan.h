@@ -222,6 +222,73 @@ int tfc_morph_grad_bwd(void* stream, const float* gout, const uint8_t* arg, floa
 int tfc_row_triplet_grad(void* stream, const float* anchor, const float* positive, const float* negative, long long rows, int W, float margin,
                          float gscale, float* loss, float* danchor);
 
+/* ---- STN21 localiser (STN:150-201, Net.stn_phi): kornia VisionTransformer(256, patch 64, 6 channels; 768 wide, 12 pre-norm blocks of 12 heads,
+ * 4x GELU MLP, LayerNorm eps 1e-6) + the fc_loc MLP, forward and backward on the matrix cores. Activations, gradients, LayerNorm statistics and
+ * softmax are fp32 in every mode; dt = TFC_DT_BF16 rounds the GEMM (and attention matmul) operands to bf16, TFC_DT_F32 keeps them exact (f32 MFMA).
+ * BATCH INVARIANT: no tile size, split-K count or summation order depends on the number of rows; a sample's outputs and input gradient are
+ * bit-identical for any batch. No float atomics: parameter gradients (sums over rows) are chunk partials added in a fixed order (part_ws).
+ *
+ * tfc_vit_gemm: C(m, n) = epilogue(sum_k A(m, k) B(k, n)), M x N x K, all fp32 in memory:
+ *   A: ROWS  A(m, k) = a[row(m) + k]        TRANS A(m, k) = a[row(k) + m]      UNFOLD A(m, k) = patch matrix of the images (a, a2)
+ *      row(r) = a_rg > 0 ? (r / a_rg) * a_rso + (r % a_rg) * lda : r * lda  (patch rows inside the [N][17][768] token tensor)
+ *   B: WEIGHT B(k, n) = b[n * ldb + k] (nn.Linear forward)   ROWS B(k, n) = b[k * ldb + n]   UNFOLD B(k, n) = patch matrix of (b, b2)
+ *   C: ROWS c[row_c(m) + n] (row_c as row() with c_rg / c_rso / ldc)       UNFOLD: scatter to the NCHW images (c, c2; a NULL image is skipped)
+ *   patch matrix: row m = image * patches + patch (row-major over the uh/up x uw/up grid), column k = channel * up^2 + i * up + j; channels
+ *   [0, uc) of the first image, [uc, 2 uc) of the second (Conv2d(2 uc, D, up, stride up) over torch.cat((a, a2), 1) as unfold + GEMM).
+ *   epilogue: + bias[n] (nullable) -> + res[row_c(m) + n] (nullable, ROWS only; may alias c) -> act -> store. act: GELU stores the
+ *   pre-activation in aux[m * ldaux + n]; DACT_* multiply by the derivative of the activation whose input (GELU) / output (ReLU, Sigmoid) is
+ *   aux[m * ldaux + n]. K > 4096 is split into slices of ~3072 (a function of K alone) added in slice order: needs part_ws.
+ * tfc_vit_layernorm_fwd: y = LN(x) rows of D (64 | D <= 1024), saves mean / rstd [rows].
+ * tfc_vit_layernorm_bwd: dx = dres (nullable) + d LN / d x; dgb (nullable) = [2][D]: (d gamma, d beta), overwritten.
+ * tfc_vit_colsum: out[L] = sum over rows of v[r * ld + j] (overwritten): bias, class-token and position gradients.
+ * tfc_vit_attention_fwd / _bwd: per (image, head), T <= 64 tokens, head dim 64, H heads: qkv [N][T][3][H][64] (the qkv Linear's output),
+ *   out / dout [N][T][H][64], probs [N][H][T][T] (softmax(q kt * scale), written by the forward, read by the backward), dqkv like qkv.
+ * tfc_vit_tokens_fwd: x[n][0] = cls + pos[0], x[n][t] += pos[t] (t >= 1), x [N][T][D]. ---- */
+#define TFC_VIT_A_ROWS 0
+#define TFC_VIT_A_TRANS 1
+#define TFC_VIT_A_UNFOLD 2
+#define TFC_VIT_B_WEIGHT 0
+#define TFC_VIT_B_ROWS 1
+#define TFC_VIT_B_UNFOLD 2
+#define TFC_VIT_C_ROWS 0
+#define TFC_VIT_C_UNFOLD 1
+#define TFC_VIT_ACT_NONE 0
+#define TFC_VIT_ACT_GELU 1
+#define TFC_VIT_ACT_RELU 2
+#define TFC_VIT_ACT_SIGMOID 3
+#define TFC_VIT_DACT_GELU 4
+#define TFC_VIT_DACT_RELU 5
+#define TFC_VIT_DACT_SIGMOID 6
+typedef struct TfcVitGemm {
+  int M, N, K;
+  int a_mode, a_rg;
+  const float* a;
+  const float* a2;
+  long long lda, a_rso;
+  int b_mode, c_mode;
+  const float* b;
+  const float* b2;
+  long long ldb;
+  float* c;
+  float* c2;
+  long long ldc, c_rso;
+  int c_rg, act;
+  const float* bias;
+  const float* res;
+  float* aux;
+  long long ldaux;
+  int uc, uh, uw, up;
+} TfcVitGemm;
+int tfc_vit_gemm(void* stream, int dt, const TfcVitGemm* g_host, float* part_ws);
+int tfc_vit_layernorm_fwd(void* stream, const float* x, const float* gamma, const float* beta, float* y, float* mean, float* rstd, int rows, int D,
+                          float eps);
+int tfc_vit_layernorm_bwd(void* stream, const float* dy, const float* x, const float* mean, const float* rstd, const float* gamma, const float* dres,
+                          float* dx, float* dgb, int rows, int D, float* part_ws);
+int tfc_vit_colsum(void* stream, const float* v, long long ld, int rows, int L, float* out, float* part_ws);
+int tfc_vit_attention_fwd(void* stream, int dt, const float* qkv, float* out, float* probs, int N, int T, int H, float scale);
+int tfc_vit_attention_bwd(void* stream, int dt, const float* dout, const float* qkv, const float* probs, float* dqkv, int N, int T, int H, float scale);
+int tfc_vit_tokens_fwd(void* stream, float* x, const float* cls, const float* pos, int N, int T, int D);
+
 /* ---- first block, backward, fused: UNetDown(channels, 64, normalize=False) (P16:133) and discriminator_block(2 * channels, 64) (P16:183-196) are
  * conv -> LeakyReLU -> BlurPool(stride 2) with no normalisation. When the gradient of the convolution OUTPUT is needed by nothing but the weight
  * (and bias) gradient, it is never written: = tfc_act_bwd(mode 0, pool 2) + tfc_conv_wgrad(TFC_OP_CONV) in one kernel, same bits.

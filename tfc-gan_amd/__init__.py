@@ -15,7 +15,7 @@ import os as _os
 # variable when it initialises (first GPU call), so it is set here, before anything of this package touches the GPU; an explicit setting wins.
 _os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 
-from . import _lib, data, engine, inference, losses, lpips, models, nets, ops, parallel, stn, stn21, synthetic  # noqa: F401
+from . import _lib, data, engine, inference, losses, lpips, models, nets, ops, parallel, stn, stn21, synthetic, vit  # noqa: F401
 from ._lib import TfcError, build  # noqa: F401
 from .engine import TrainStep  # noqa: F401
 from .nets import set_wgrad_stream  # noqa: F401

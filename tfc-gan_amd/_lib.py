@@ -12,7 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _ROOT = os.path.dirname(_HERE)
 CSRC = os.path.join(_HERE, "csrc")
 SO_PATH = os.path.join(_HERE, "libtfcgan_hip.so")
-SOURCES = ["api.hip", "igemm.hip", "elementwise.hip", "losses.hip", "stn.hip", "lpips.hip", "input.hip", "probe.hip"]
+SOURCES = ["api.hip", "igemm.hip", "elementwise.hip", "losses.hip", "stn.hip", "lpips.hip", "input.hip", "probe.hip", "vit.hip"]
 HEADERS = ["common.h", "tfc_desc.h", "pack_math.h"]
 PUBLIC_HEADER = os.path.join(_ROOT, "include", "tfc_gan.h")
 
@@ -161,6 +161,13 @@ PROTOTYPES = {
     "tfc_prof_enable": (_i, [_i]),
     "tfc_prof_collect": (_i, [_i, _c.POINTER(_c.c_double), _c.POINTER(_c.c_double), _c.POINTER(_ll)]),
     "tfc_prof_records": (_i, [_i, _c.POINTER(_i), _c.POINTER(_c.c_double), _c.POINTER(_c.c_double), _c.POINTER(_i)]),
+    "tfc_vit_gemm": (_i, [_vp, _i, _vp, _vp]),
+    "tfc_vit_layernorm_fwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _f]),
+    "tfc_vit_layernorm_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp]),
+    "tfc_vit_colsum": (_i, [_vp, _vp, _ll, _i, _i, _vp, _vp]),
+    "tfc_vit_attention_fwd": (_i, [_vp, _i, _vp, _vp, _vp, _i, _i, _i, _f]),
+    "tfc_vit_attention_bwd": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _f]),
+    "tfc_vit_tokens_fwd": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i]),
     "tfc_host_emulate_conv": (_i, [_i, _i, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i]),
     "tfc_debug_set_igemm_config": (_i, [_i]),
     "tfc_probe_mfma": (_i, [_vp, _vp]),

@@ -79,6 +79,16 @@ hipError_t tfc_launch_morph_grad_fwd(const float* x, float* out, unsigned char* 
 hipError_t tfc_launch_morph_grad_bwd(const float* gout, const unsigned char* arg, float* dx, long long planes, int H, int W, hipStream_t st);
 hipError_t tfc_launch_row_triplet_grad(const float* a, const float* p, const float* ng, long long rows, int W, float margin, float eps, float gscale,
                                        float* loss, float* da, hipStream_t st);
+hipError_t tfc_launch_vit_gemm(int dt, const TfcVitGemm& g, float* part_ws, hipStream_t st);
+hipError_t tfc_launch_vit_ln_fwd(const float* x, const float* g, const float* b, float* y, float* mean, float* rstd, int rows, int D, float eps, hipStream_t st);
+hipError_t tfc_launch_vit_ln_bwd(const float* dy, const float* x, const float* mean, const float* rstd, const float* g, const float* dres, float* dx,
+                                 float* dgb, int rows, int D, float* part_ws, hipStream_t st);
+hipError_t tfc_launch_vit_colsum(const float* v, long long ld, int rows, int L, const float* x_ln, const float* mean, const float* rstd, float* out,
+                                 float* part_ws, hipStream_t st);
+hipError_t tfc_launch_vit_attn_fwd(int dt, const float* qkv, float* out, float* probs, int N, int T, int H, float scale, hipStream_t st);
+hipError_t tfc_launch_vit_attn_bwd(int dt, const float* dout, const float* qkv, const float* probs, float* dqkv, int N, int T, int H, float scale,
+                                   hipStream_t st);
+hipError_t tfc_launch_vit_tokens_fwd(float* x, const float* cls, const float* pos, int N, int T, int D, hipStream_t st);
 struct SnBatch {
   const float* W[4];
   float* u[4]; float* v[4]; float* sigma2[4];
@@ -859,6 +869,63 @@ extern "C" int tfc_affine_warp_bwd(void* stream, const float* src, const float* 
                                    int H, int W, float* part_ws) {
   REQUIRE(src && theta && gout && dtheta && part_ws && N > 0 && C > 0 && H > 1 && W > 1, "bad args");
   CHECK_HIP(tfc_launch_affine_warp_bwd(src, theta, gout, dtheta, dsrc, part_ws, N, C, H, W, (hipStream_t)stream), "tfc_affine_warp_bwd");
+  return 0;
+}
+// ---- STN21 localiser (vit.hip) ----
+static bool vit_unfold_ok(const TfcVitGemm& g, int rows, int cols) {
+  if (g.uc <= 0 || g.up <= 0 || g.uh <= 0 || g.uw <= 0 || g.uh % g.up || g.uw % g.up) return false;
+  return cols <= 2 * g.uc * g.up * g.up && rows % ((g.uh / g.up) * (g.uw / g.up)) == 0;
+}
+extern "C" int tfc_vit_gemm(void* stream, int dt, const TfcVitGemm* gp, float* part_ws) {
+  REQUIRE(gp, "bad args");
+  const TfcVitGemm& g = *gp;
+  REQUIRE(dt == TFC_DT_BF16 || dt == TFC_DT_F32, "dt");
+  REQUIRE(g.M > 0 && g.N > 0 && g.K > 0 && g.a && g.b, "tfc_vit_gemm: bad shape / operands (%d x %d x %d)", g.M, g.N, g.K);
+  REQUIRE(g.a_mode >= TFC_VIT_A_ROWS && g.a_mode <= TFC_VIT_A_UNFOLD && g.b_mode >= TFC_VIT_B_WEIGHT && g.b_mode <= TFC_VIT_B_UNFOLD &&
+          (g.c_mode == TFC_VIT_C_ROWS || g.c_mode == TFC_VIT_C_UNFOLD) && g.act >= TFC_VIT_ACT_NONE && g.act <= TFC_VIT_DACT_SIGMOID, "tfc_vit_gemm: mode");
+  REQUIRE(g.a_mode != TFC_VIT_A_ROWS || g.a_rg > 0 || g.lda >= g.K, "tfc_vit_gemm: lda");
+  REQUIRE(g.a_mode != TFC_VIT_A_TRANS || g.a_rg > 0 || g.lda >= g.M, "tfc_vit_gemm: lda");
+  REQUIRE(g.b_mode != TFC_VIT_B_WEIGHT || g.ldb >= g.K, "tfc_vit_gemm: ldb");
+  REQUIRE(g.b_mode != TFC_VIT_B_ROWS || g.ldb >= g.N, "tfc_vit_gemm: ldb");
+  REQUIRE(g.a_mode != TFC_VIT_A_UNFOLD || (g.a2 && vit_unfold_ok(g, g.M, g.K)), "tfc_vit_gemm: A unfold geometry");
+  REQUIRE(g.b_mode != TFC_VIT_B_UNFOLD || (g.b2 && vit_unfold_ok(g, g.K, g.N)), "tfc_vit_gemm: B unfold geometry");
+  REQUIRE(g.c_mode != TFC_VIT_C_ROWS || (g.c && (g.c_rg > 0 || g.ldc >= g.N)), "tfc_vit_gemm: C");
+  REQUIRE(g.c_mode != TFC_VIT_C_UNFOLD || ((g.c || g.c2) && !g.res && vit_unfold_ok(g, g.M, g.N)), "tfc_vit_gemm: C unfold geometry");
+  REQUIRE(g.act == TFC_VIT_ACT_NONE || g.act == TFC_VIT_ACT_RELU || g.act == TFC_VIT_ACT_SIGMOID || (g.aux && g.ldaux >= g.N), "tfc_vit_gemm: aux");
+  CHECK_HIP(tfc_launch_vit_gemm(dt, g, part_ws, (hipStream_t)stream), "tfc_vit_gemm");
+  return 0;
+}
+extern "C" int tfc_vit_layernorm_fwd(void* stream, const float* x, const float* gamma, const float* beta, float* y, float* mean, float* rstd, int rows, int D,
+                                     float eps) {
+  REQUIRE(x && gamma && beta && y && mean && rstd && rows > 0 && D > 0 && D % 64 == 0 && D <= 1024, "bad args");
+  CHECK_HIP(tfc_launch_vit_ln_fwd(x, gamma, beta, y, mean, rstd, rows, D, eps, (hipStream_t)stream), "tfc_vit_layernorm_fwd");
+  return 0;
+}
+extern "C" int tfc_vit_layernorm_bwd(void* stream, const float* dy, const float* x, const float* mean, const float* rstd, const float* gamma, const float* dres,
+                                     float* dx, float* dgb, int rows, int D, float* part_ws) {
+  REQUIRE(dy && x && mean && rstd && gamma && dx && rows > 0 && D > 0 && D % 64 == 0 && D <= 1024 && (!dgb || part_ws), "bad args");
+  CHECK_HIP(tfc_launch_vit_ln_bwd(dy, x, mean, rstd, gamma, dres, dx, dgb, rows, D, part_ws, (hipStream_t)stream), "tfc_vit_layernorm_bwd");
+  return 0;
+}
+extern "C" int tfc_vit_colsum(void* stream, const float* v, long long ld, int rows, int L, float* out, float* part_ws) {
+  REQUIRE(v && out && part_ws && rows > 0 && L > 0 && ld >= L, "bad args");
+  CHECK_HIP(tfc_launch_vit_colsum(v, ld, rows, L, nullptr, nullptr, nullptr, out, part_ws, (hipStream_t)stream), "tfc_vit_colsum");
+  return 0;
+}
+extern "C" int tfc_vit_attention_fwd(void* stream, int dt, const float* qkv, float* out, float* probs, int N, int T, int H, float scale) {
+  REQUIRE(qkv && out && probs && N > 0 && T > 0 && T <= 64 && H > 0 && (dt == TFC_DT_BF16 || dt == TFC_DT_F32), "bad args");
+  CHECK_HIP(tfc_launch_vit_attn_fwd(dt, qkv, out, probs, N, T, H, scale, (hipStream_t)stream), "tfc_vit_attention_fwd");
+  return 0;
+}
+extern "C" int tfc_vit_attention_bwd(void* stream, int dt, const float* dout, const float* qkv, const float* probs, float* dqkv, int N, int T, int H,
+                                     float scale) {
+  REQUIRE(dout && qkv && probs && dqkv && N > 0 && T > 0 && T <= 64 && H > 0 && (dt == TFC_DT_BF16 || dt == TFC_DT_F32), "bad args");
+  CHECK_HIP(tfc_launch_vit_attn_bwd(dt, dout, qkv, probs, dqkv, N, T, H, scale, (hipStream_t)stream), "tfc_vit_attention_bwd");
+  return 0;
+}
+extern "C" int tfc_vit_tokens_fwd(void* stream, float* x, const float* cls, const float* pos, int N, int T, int D) {
+  REQUIRE(x && cls && pos && N > 0 && T > 0 && D > 0, "bad args");
+  CHECK_HIP(tfc_launch_vit_tokens_fwd(x, cls, pos, N, T, D, (hipStream_t)stream), "tfc_vit_tokens_fwd");
   return 0;
 }
 extern "C" int tfc_morph_grad_fwd(void* stream, const float* x, float* out, uint8_t* arg, long long planes, int H, int W) {

@@ -1,0 +1,423 @@
+// Kernels of the STN21 localiser (reference STN:150-201: kornia VisionTransformer(256, 64, 6) + the fc_loc MLP; Net.stn_phi), forward and backward:
+//
+//   tfc_vit_gemm_kernel     one dense GEMM for every nn.Linear pass:  Y = X Wt + b,  dX = dY W,  dW = dYt X  (operand addressing modes below),
+//                           with the patch embedding's unfold as an addressing mode of A (forward) / B (weight gradient) / C (input gradient:
+//                           patches do not overlap, so the scatter back to NCHW is a permutation), and the epilogues bias, residual add,
+//                           GELU (storing the pre-activation), ReLU, Sigmoid and the GELU' / ReLU' / Sigmoid' factor of the dgrad that consumes them.
+//                           v_mfma_f32_32x32x16_bf16 on bf16-rounded operands (bf16 mode) or v_mfma_f32_32x32x2_f32 (fp32 mode: an exact k-ordered
+//                           fmaf chain); fp32 accumulate and fp32 storage in both.
+//   tfc_vit_gemm_reduce     split-K finish: adds the K-slices in slice order, then the same epilogue.
+//   tfc_vit_ln_fwd / _bwd   nn.LayerNorm(768, eps) rows (saving mean / rstd), and its input gradient (+ the residual gradient that flows past it).
+//   tfc_vit_colsum          fixed-order column sums over row chunks (bias, gamma / beta, class-token / position gradients), finished by
+//                           tfc_part_reduce_kernel.
+//   tfc_vit_attn_fwd / _bwd softmax(q kt / sqrt(d)) v per (image, head) for T <= 64 tokens, head dim 64, q / k / v read in place from the qkv GEMM's
+//                           output (the reshape(n, t, 3, heads, d) layout of _Attention); the probabilities are saved for the backward.
+//   tfc_vit_tokens_fwd      class token + positions around the patch tokens.
+//
+// BATCH INVARIANCE: every tile shape and split-K count is a function of the layer shape (N, K), never of M: a sample's rows are computed by the same
+// instruction sequence wherever they sit in the batch, so tokens, theta and the input gradient are bit-identical for any batch size. DETERMINISM:
+// no float atomics; sums across rows (parameter gradients) are chunk partials added in a fixed order.
+#include "../../include/tfc_gan.h"
+#include "common.h"
+
+namespace {
+constexpr int BM = 64, BN = 64, BK = 32, LP = 68;                  // LDS row pitch (floats): 68 keeps the k-major stores of the K-contiguous loader spread
+
+__device__ __forceinline__ float rnd_bf16(float x) { return bf16_to_f32(f32_to_bf16(x)); }
+
+__device__ __forceinline__ long long rowoff(long long r, int rg, long long rso, long long ld) {
+  return rg > 0 ? (r / rg) * rso + (r % rg) * ld : r * ld;
+}
+
+// element (m, k) of the patch matrix: m = image * patches + patch, k = channel * P * P + i * P + j; channels [0, uc) from `a`, [uc, 2 uc) from `a2`
+__device__ __forceinline__ long long unfold_off(const TfcVitGemm& g, long long m, long long k, int& second) {
+  const int pw = g.uw / g.up, np = (g.uh / g.up) * pw, pp = g.up * g.up;
+  const long long n = m / np;
+  const int pi = (int)(m % np), ph = pi / pw, px = pi % pw;
+  int c = (int)(k / pp);
+  const int rem = (int)(k % pp), i = rem / g.up, j = rem % g.up;
+  second = c >= g.uc;
+  if (second) c -= g.uc;
+  return ((n * g.uc + c) * g.uh + (long long)ph * g.up + i) * g.uw + (long long)px * g.up + j;
+}
+
+__device__ __forceinline__ float ld_a(const TfcVitGemm& g, int m, int k, int kend) {
+  if (m >= g.M || k >= kend) return 0.f;
+  if (g.a_mode == TFC_VIT_A_ROWS) return g.a[rowoff(m, g.a_rg, g.a_rso, g.lda) + k];
+  if (g.a_mode == TFC_VIT_A_TRANS) return g.a[rowoff(k, g.a_rg, g.a_rso, g.lda) + m];
+  int s;
+  const long long o = unfold_off(g, m, k, s);
+  return (s ? g.a2 : g.a)[o];
+}
+__device__ __forceinline__ float ld_b(const TfcVitGemm& g, int k, int n, int kend) {
+  if (n >= g.N || k >= kend) return 0.f;
+  if (g.b_mode == TFC_VIT_B_WEIGHT) return g.b[(long long)n * g.ldb + k];
+  if (g.b_mode == TFC_VIT_B_ROWS) return g.b[(long long)k * g.ldb + n];
+  int s;
+  const long long o = unfold_off(g, k, n, s);
+  return (s ? g.b2 : g.b)[o];
+}
+
+__device__ __forceinline__ float gelu_f(float x) { return 0.5f * x * (1.f + erff(x * 0.70710678118654752f)); }
+__device__ __forceinline__ float gelu_d(float x) {
+  const float cdf = 0.5f * (1.f + erff(x * 0.70710678118654752f));
+  const float pdf = expf(-0.5f * x * x) * 0.39894228040143268f;
+  return cdf + x * pdf;
+}
+
+// bias -> residual -> activation / activation-derivative factor -> store (row m, column n of the GEMM)
+__device__ __forceinline__ void epilogue(const TfcVitGemm& g, int m, int n, float v) {
+  if (g.bias) v += g.bias[n];
+  const long long co = g.c_mode == TFC_VIT_C_ROWS ? rowoff(m, g.c_rg, g.c_rso, g.ldc) + n : 0;
+  if (g.res) v += g.res[co];
+  const long long xo = (long long)m * g.ldaux + n;
+  switch (g.act) {
+    case TFC_VIT_ACT_GELU: g.aux[xo] = v; v = gelu_f(v); break;
+    case TFC_VIT_ACT_RELU: v = v > 0.f ? v : 0.f; break;
+    case TFC_VIT_ACT_SIGMOID: v = 1.f / (1.f + expf(-v)); break;
+    case TFC_VIT_DACT_GELU: v *= gelu_d(g.aux[xo]); break;
+    case TFC_VIT_DACT_RELU: v = g.aux[xo] > 0.f ? v : 0.f; break;
+    case TFC_VIT_DACT_SIGMOID: { const float s = g.aux[xo]; v = v * (1.f - s) * s; } break;
+    default: break;
+  }
+  if (g.c_mode == TFC_VIT_C_ROWS) {
+    g.c[co] = v;
+  } else {
+    int s;
+    const long long o = unfold_off(g, m, n, s);
+    float* dst = s ? g.c2 : g.c;
+    if (dst) dst[o] = v;
+  }
+}
+}  // namespace
+
+// grid (N / 64, rows of this launch / 64, K-slices); 4 waves, each owns a 32 x 32 quarter of the 64 x 64 tile. K-slice z covers [z kc, (z+1) kc).
+// part == nullptr: epilogue in place; otherwise the raw slice sums go to part[z][m - m0][n].
+template <int DT>
+__global__ void __launch_bounds__(256)
+tfc_vit_gemm_kernel(const TfcVitGemm g, int m0, int mrows, int kc, float* __restrict__ part) {
+  __shared__ float As[BK][LP], Bs[BK][LP];
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, wm = w & 1, wn = w >> 1;
+  const int tm = m0 + blockIdx.y * BM, tn = blockIdx.x * BN, z = blockIdx.z;
+  const int kbeg = z * kc, kend = min(g.K, kbeg + kc);
+  const int mend = m0 + mrows;
+  // loader lane maps: K-contiguous operands (A rows / unfold, B weight) walk k across lanes, the others walk the row / column index
+  const bool a_kc = g.a_mode != TFC_VIT_A_TRANS, b_kc = g.b_mode == TFC_VIT_B_WEIGHT;
+  float ra[8], rb[8];
+  auto load = [&](int k0) {
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      int m, k;
+      if (a_kc) { k = k0 + (tid & 31); m = tm + (tid >> 5) + 8 * i; }
+      else { m = tm + (tid & 63); k = k0 + (tid >> 6) + 4 * i; }
+      ra[i] = m < mend ? ld_a(g, m, k, kend) : 0.f;
+      int n;
+      if (b_kc) { k = k0 + (tid & 31); n = tn + (tid >> 5) + 8 * i; }
+      else { n = tn + (tid & 63); k = k0 + (tid >> 6) + 4 * i; }
+      rb[i] = ld_b(g, k, n, kend);
+    }
+  };
+  f32x16_t acc;
+#pragma unroll
+  for (int i = 0; i < 16; ++i) acc[i] = 0.f;
+  if (kbeg < kend) load(kbeg);
+  for (int k0 = kbeg; k0 < kend; k0 += BK) {
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      if (a_kc) As[tid & 31][(tid >> 5) + 8 * i] = ra[i];
+      else As[(tid >> 6) + 4 * i][tid & 63] = ra[i];
+      if (b_kc) Bs[tid & 31][(tid >> 5) + 8 * i] = rb[i];
+      else Bs[(tid >> 6) + 4 * i][tid & 63] = rb[i];
+    }
+    __syncthreads();
+    if (k0 + BK < kend) load(k0 + BK);                              // next tile's loads in flight under this tile's MFMAs
+    const int r = lane & 31, h = lane >> 5;
+    if constexpr (DT == TFC_DT_BF16) {
+#pragma unroll
+      for (int s = 0; s < BK / 16; ++s) {
+        bf16x8_t fa, fb;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          fa[j] = (__bf16)As[16 * s + 8 * h + j][wm * 32 + r];
+          fb[j] = (__bf16)Bs[16 * s + 8 * h + j][wn * 32 + r];
+        }
+        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa, fb, acc, 0, 0, 0);
+      }
+    } else {
+#pragma unroll
+      for (int s = 0; s < BK / 2; ++s)
+        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(As[2 * s + h][wm * 32 + r], Bs[2 * s + h][wn * 32 + r], acc, 0, 0, 0);
+    }
+  }
+  const int col = tn + wn * 32 + (lane & 31);
+#pragma unroll
+  for (int i = 0; i < 16; ++i) {
+    const int row = tm + wm * 32 + (i & 3) + 8 * (i >> 2) + 4 * (lane >> 5);
+    if (row < mend && col < g.N) {
+      if (part) part[((size_t)z * mrows + (row - m0)) * g.N + col] = acc[i];
+      else epilogue(g, row, col, acc[i]);
+    }
+  }
+}
+
+__global__ void __launch_bounds__(256)
+tfc_vit_gemm_reduce_kernel(const TfcVitGemm g, int m0, int mrows, int nslices, const float* __restrict__ part) {
+  const long long idx = (long long)blockIdx.x * 256 + threadIdx.x, tot = (long long)mrows * g.N;
+  if (idx >= tot) return;
+  float v = part[idx];
+  for (int z = 1; z < nslices; ++z) v += part[(size_t)z * tot + idx];
+  epilogue(g, m0 + (int)(idx / g.N), (int)(idx % g.N), v);
+}
+
+// K-slices: a function of K alone (the shapes of this network: K = 24576 -> 8 slices of 3072, K = 13056 -> 5 of 2624, K <= 4096 -> 1)
+static int vit_kslice(int K, int* nslices) {
+  const int ktiles = (K + BK - 1) / BK;
+  int s = K > 4096 ? (K + 3071) / 3072 : 1;
+  const int kt = (ktiles + s - 1) / s;
+  *nslices = (ktiles + kt - 1) / kt;
+  return kt * BK;
+}
+
+hipError_t tfc_launch_vit_gemm(int dt, const TfcVitGemm& g, float* part_ws, hipStream_t st) {
+  int ns;
+  const int kc = vit_kslice(g.K, &ns);
+  if (ns == 1) {
+    const dim3 grid((g.N + BN - 1) / BN, (g.M + BM - 1) / BM, 1);
+    if (dt == TFC_DT_BF16) hipLaunchKernelGGL(tfc_vit_gemm_kernel<TFC_DT_BF16>, grid, dim3(256), 0, st, g, 0, g.M, kc, (float*)nullptr);
+    else hipLaunchKernelGGL(tfc_vit_gemm_kernel<TFC_DT_F32>, grid, dim3(256), 0, st, g, 0, g.M, kc, (float*)nullptr);
+    return hipGetLastError();
+  }
+  if (!part_ws) return hipErrorInvalidValue;
+  // rows per launch so that the slices fit the scratch: row chunks are multiples of the tile height, so every row still sees the same tiles
+  long long cap = (long long)TFC_PART_WS_FLOATS / ((long long)ns * g.N) / BM * BM;
+  if (cap < BM) return hipErrorInvalidValue;
+  for (int m0 = 0; m0 < g.M; m0 += (int)cap) {
+    const int mr = (int)std::min<long long>(cap, (long long)g.M - m0);
+    const dim3 grid((g.N + BN - 1) / BN, (mr + BM - 1) / BM, ns);
+    if (dt == TFC_DT_BF16) hipLaunchKernelGGL(tfc_vit_gemm_kernel<TFC_DT_BF16>, grid, dim3(256), 0, st, g, m0, mr, kc, part_ws);
+    else hipLaunchKernelGGL(tfc_vit_gemm_kernel<TFC_DT_F32>, grid, dim3(256), 0, st, g, m0, mr, kc, part_ws);
+    const long long tot = (long long)mr * g.N;
+    hipLaunchKernelGGL(tfc_vit_gemm_reduce_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, g, m0, mr, ns, (const float*)part_ws);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
+}
+
+// ---- LayerNorm: one wave per row of D (a multiple of 64, <= 1024) -------------------------------------------------------------------------------
+__global__ void __launch_bounds__(256)
+tfc_vit_ln_fwd_kernel(const float* __restrict__ x, const float* __restrict__ gam, const float* __restrict__ bet, float* __restrict__ y, float* __restrict__ mean,
+                      float* __restrict__ rstd, int rows, int D, float eps) {
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (row >= rows) return;
+  const int nv = D >> 6;
+  const float* xr = x + (size_t)row * D;
+  float v[16], s = 0.f;
+#pragma unroll
+  for (int i = 0; i < 16; ++i) if (i < nv) { v[i] = xr[i * 64 + lane]; s += v[i]; }
+  const float mu = wave_sum(s) / (float)D;
+  float q = 0.f;
+#pragma unroll
+  for (int i = 0; i < 16; ++i) if (i < nv) { const float d = v[i] - mu; q += d * d; }
+  const float rs = 1.f / sqrtf(wave_sum(q) / (float)D + eps);
+  float* yr = y + (size_t)row * D;
+#pragma unroll
+  for (int i = 0; i < 16; ++i) if (i < nv) { const int c = i * 64 + lane; yr[c] = (v[i] - mu) * rs * gam[c] + bet[c]; }
+  if (lane == 0) { mean[row] = mu; rstd[row] = rs; }
+}
+
+// dx = dres + rstd (gdy - mean(gdy) - xhat mean(gdy xhat)),  gdy = gamma * dy
+__global__ void __launch_bounds__(256)
+tfc_vit_ln_bwd_kernel(const float* __restrict__ dy, const float* __restrict__ x, const float* __restrict__ mean, const float* __restrict__ rstd,
+                      const float* __restrict__ gam, const float* dres, float* dx, int rows, int D) {
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (row >= rows) return;
+  const int nv = D >> 6;
+  const size_t ro = (size_t)row * D;
+  const float mu = mean[row], rs = rstd[row];
+  float gd[16], xh[16], s1 = 0.f, s2 = 0.f;
+#pragma unroll
+  for (int i = 0; i < 16; ++i)
+    if (i < nv) {
+      const int c = i * 64 + lane;
+      gd[i] = gam[c] * dy[ro + c];
+      xh[i] = (x[ro + c] - mu) * rs;
+      s1 += gd[i];
+      s2 += gd[i] * xh[i];
+    }
+  const float m1 = wave_sum(s1) / (float)D, m2 = wave_sum(s2) / (float)D;
+#pragma unroll
+  for (int i = 0; i < 16; ++i)
+    if (i < nv) {
+      const int c = i * 64 + lane;
+      const float v = rs * (gd[i] - m1 - xh[i] * m2);
+      dx[ro + c] = dres ? dres[ro + c] + v : v;
+    }
+}
+
+// ---- column sums over chunks of 32 rows: part[chunk][j] = sum x[r][j]; with x_ln: part[chunk][j] = sum dy xhat, part[chunk][L + j] = sum dy -----------
+constexpr int kColChunk = 32;
+__global__ void __launch_bounds__(256)
+tfc_vit_colsum_kernel(const float* __restrict__ v, long long ld, int rows, int L, const float* __restrict__ x_ln, const float* __restrict__ mean,
+                      const float* __restrict__ rstd, float* __restrict__ part) {
+  const int j = blockIdx.x * 256 + threadIdx.x, ch = blockIdx.y;
+  if (j >= L) return;
+  const int r0 = ch * kColChunk, r1 = min(rows, r0 + kColChunk);
+  float s = 0.f, sx = 0.f;
+  for (int r = r0; r < r1; ++r) {
+    const float d = v[(size_t)r * ld + j];
+    s += d;
+    if (x_ln) sx += d * ((x_ln[(size_t)r * L + j] - mean[r]) * rstd[r]);
+  }
+  if (x_ln) { part[(size_t)ch * 2 * L + j] = sx; part[(size_t)ch * 2 * L + L + j] = s; }
+  else part[(size_t)ch * L + j] = s;
+}
+
+// ---- attention per (image, head): T <= 64 tokens, head dim 64 --------------------------------------------------------------------------------------
+__device__ __forceinline__ float wave_max(float v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
+  return v;
+}
+constexpr int AP = 65;                                             // LDS row pitch of the [T][64] / [T][T] tiles
+
+template <int DT>
+__global__ void __launch_bounds__(256)
+tfc_vit_attn_fwd_kernel(const float* __restrict__ qkv, float* __restrict__ out, float* __restrict__ probs, int T, int H, float scale) {
+  extern __shared__ float sm[];
+  float* q = sm; float* k = q + T * AP; float* v = k + T * AP; float* p = v + T * AP;
+  const int h = blockIdx.x, n = blockIdx.y, D = H * 64, lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  auto op = [](float x) { return DT == TFC_DT_BF16 ? rnd_bf16(x) : x; };
+  for (int i = threadIdx.x; i < T * 64; i += 256) {
+    const int t = i >> 6, d = i & 63;
+    const size_t b = ((size_t)n * T + t) * 3 * D + h * 64 + d;
+    q[t * AP + d] = op(qkv[b]); k[t * AP + d] = op(qkv[b + D]); v[t * AP + d] = op(qkv[b + 2 * D]);
+  }
+  __syncthreads();
+  for (int i = w; i < T; i += 4) {
+    const int j = lane;
+    float s = -INFINITY;
+    if (j < T) {
+      float a = 0.f;
+      for (int d = 0; d < 64; ++d) a = fmaf(q[i * AP + d], k[j * AP + d], a);
+      s = a * scale;
+    }
+    const float mx = wave_max(s);
+    const float e = j < T ? expf(s - mx) : 0.f;
+    const float pij = e / wave_sum(e);
+    if (j < T) { probs[(((size_t)n * H + h) * T + i) * T + j] = pij; p[i * AP + j] = op(pij); }
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < T * 64; i += 256) {
+    const int t = i >> 6, d = i & 63;
+    float a = 0.f;
+    for (int j = 0; j < T; ++j) a = fmaf(p[t * AP + j], v[j * AP + d], a);
+    out[((size_t)n * T + t) * D + h * 64 + d] = a;
+  }
+}
+
+template <int DT>
+__global__ void __launch_bounds__(256)
+tfc_vit_attn_bwd_kernel(const float* __restrict__ dout, const float* __restrict__ qkv, const float* __restrict__ probs, float* __restrict__ dqkv, int T, int H,
+                        float scale) {
+  extern __shared__ float sm[];
+  float* q = sm; float* k = q + T * AP; float* v = k + T * AP; float* go = v + T * AP; float* p = go + T * AP; float* ds = p + T * AP;
+  const int h = blockIdx.x, n = blockIdx.y, D = H * 64, lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  auto op = [](float x) { return DT == TFC_DT_BF16 ? rnd_bf16(x) : x; };
+  for (int i = threadIdx.x; i < T * 64; i += 256) {
+    const int t = i >> 6, d = i & 63;
+    const size_t b = ((size_t)n * T + t) * 3 * D + h * 64 + d;
+    q[t * AP + d] = op(qkv[b]); k[t * AP + d] = op(qkv[b + D]); v[t * AP + d] = op(qkv[b + 2 * D]);
+    go[t * AP + d] = op(dout[((size_t)n * T + t) * D + h * 64 + d]);
+  }
+  for (int i = threadIdx.x; i < T * T; i += 256) p[(i / T) * AP + i % T] = probs[((size_t)n * H + h) * T * T + i];
+  __syncthreads();
+  for (int i = w; i < T; i += 4) {                                  // dS = P (dP - rowsum(P dP)) * scale,  dP = dO vt
+    const int j = lane;
+    float dp = 0.f, pij = 0.f;
+    if (j < T) {
+      for (int d = 0; d < 64; ++d) dp = fmaf(go[i * AP + d], v[j * AP + d], dp);
+      pij = p[i * AP + j];
+    }
+    const float t = wave_sum(pij * dp);
+    if (j < T) ds[i * AP + j] = op(pij * (dp - t) * scale);
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < T * 64; i += 256) {
+    const int t = i >> 6, d = i & 63;
+    float dq = 0.f, dk = 0.f, dv = 0.f;
+    for (int j = 0; j < T; ++j) {
+      dq = fmaf(ds[t * AP + j], k[j * AP + d], dq);               // dQ[t] = sum_j dS[t][j] k[j]
+      dk = fmaf(ds[j * AP + t], q[j * AP + d], dk);               // dK[t] = sum_i dS[i][t] q[i]
+      dv = fmaf(op(p[j * AP + t]), go[j * AP + d], dv);           // dV[t] = sum_i P[i][t] dO[i]
+    }
+    const size_t b = ((size_t)n * T + t) * 3 * D + h * 64 + d;
+    dqkv[b] = dq; dqkv[b + D] = dk; dqkv[b + 2 * D] = dv;
+  }
+}
+
+// x[n][0] = cls + pos[0]; x[n][t] += pos[t] for t >= 1 (the patch GEMM wrote the patch tokens, bias included, into rows 1..T-1)
+__global__ void __launch_bounds__(256)
+tfc_vit_tokens_fwd_kernel(float* __restrict__ x, const float* __restrict__ cls, const float* __restrict__ pos, int N, int T, int D) {
+  const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= (long long)N * T * D) return;
+  const int c = (int)(idx % D), t = (int)((idx / D) % T);
+  x[idx] = (t == 0 ? cls[c] : x[idx]) + pos[(size_t)t * D + c];
+}
+
+hipError_t tfc_launch_vit_ln_fwd(const float* x, const float* g, const float* b, float* y, float* mean, float* rstd, int rows, int D, float eps, hipStream_t st) {
+  hipLaunchKernelGGL(tfc_vit_ln_fwd_kernel, dim3((rows + 3) / 4), dim3(256), 0, st, x, g, b, y, mean, rstd, rows, D, eps);
+  return hipGetLastError();
+}
+
+hipError_t tfc_launch_vit_colsum(const float* v, long long ld, int rows, int L, const float* x_ln, const float* mean, const float* rstd, float* out,
+                                 float* part_ws, hipStream_t st) {
+  const int nch = (rows + kColChunk - 1) / kColChunk, width = x_ln ? 2 * L : L;
+  if (!part_ws || (long long)nch * width > (long long)TFC_PART_WS_FLOATS) return hipErrorInvalidValue;
+  hipError_t e = hipMemsetAsync(out, 0, sizeof(float) * width, st);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(tfc_vit_colsum_kernel, dim3((L + 255) / 256, nch), dim3(256), 0, st, v, ld, rows, L, x_ln, mean, rstd, part_ws);
+  return tfc_launch_part_reduce(part_ws, out, 1, nch, width, st);
+}
+
+hipError_t tfc_launch_vit_ln_bwd(const float* dy, const float* x, const float* mean, const float* rstd, const float* g, const float* dres, float* dx,
+                                 float* dgb, int rows, int D, float* part_ws, hipStream_t st) {
+  if (dgb) {
+    const hipError_t e = tfc_launch_vit_colsum(dy, D, rows, D, x, mean, rstd, dgb, part_ws, st);
+    if (e != hipSuccess) return e;
+  }
+  hipLaunchKernelGGL(tfc_vit_ln_bwd_kernel, dim3((rows + 3) / 4), dim3(256), 0, st, dy, x, mean, rstd, g, dres, dx, rows, D);
+  return hipGetLastError();
+}
+
+static hipError_t attn_lds(const void* fn, size_t bytes) {
+  return bytes > 65536 ? hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) : hipSuccess;
+}
+
+hipError_t tfc_launch_vit_attn_fwd(int dt, const float* qkv, float* out, float* probs, int N, int T, int H, float scale, hipStream_t st) {
+  const size_t lds = sizeof(float) * 4 * T * AP;
+  const void* fn = dt == TFC_DT_BF16 ? (const void*)&tfc_vit_attn_fwd_kernel<TFC_DT_BF16> : (const void*)&tfc_vit_attn_fwd_kernel<TFC_DT_F32>;
+  hipError_t e = attn_lds(fn, lds);
+  if (e != hipSuccess) return e;
+  if (dt == TFC_DT_BF16) hipLaunchKernelGGL(tfc_vit_attn_fwd_kernel<TFC_DT_BF16>, dim3(H, N), dim3(256), lds, st, qkv, out, probs, T, H, scale);
+  else hipLaunchKernelGGL(tfc_vit_attn_fwd_kernel<TFC_DT_F32>, dim3(H, N), dim3(256), lds, st, qkv, out, probs, T, H, scale);
+  return hipGetLastError();
+}
+
+hipError_t tfc_launch_vit_attn_bwd(int dt, const float* dout, const float* qkv, const float* probs, float* dqkv, int N, int T, int H, float scale,
+                                   hipStream_t st) {
+  const size_t lds = sizeof(float) * 6 * T * AP;
+  const void* fn = dt == TFC_DT_BF16 ? (const void*)&tfc_vit_attn_bwd_kernel<TFC_DT_BF16> : (const void*)&tfc_vit_attn_bwd_kernel<TFC_DT_F32>;
+  hipError_t e = attn_lds(fn, lds);
+  if (e != hipSuccess) return e;
+  if (dt == TFC_DT_BF16) hipLaunchKernelGGL(tfc_vit_attn_bwd_kernel<TFC_DT_BF16>, dim3(H, N), dim3(256), lds, st, dout, qkv, probs, dqkv, T, H, scale);
+  else hipLaunchKernelGGL(tfc_vit_attn_bwd_kernel<TFC_DT_F32>, dim3(H, N), dim3(256), lds, st, dout, qkv, probs, dqkv, T, H, scale);
+  return hipGetLastError();
+}
+
+hipError_t tfc_launch_vit_tokens_fwd(float* x, const float* cls, const float* pos, int N, int T, int D, hipStream_t st) {
+  const long long tot = (long long)N * T * D;
+  hipLaunchKernelGGL(tfc_vit_tokens_fwd_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, x, cls, pos, N, T, D);
+  return hipGetLastError();
+}

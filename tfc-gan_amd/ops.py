@@ -495,6 +495,99 @@ def adam_step(p, g, m, v, lr, b1, b2, eps, step, gscale=1.0):
     check(lib().tfc_adam_step(stream_ptr(), _p(p), _p(g), _p(m), _p(v), p.numel(), lr, b1, b2, eps, step, gscale), "tfc_adam_step")
 
 
+# ---- STN21 localiser (vit.hip) ---------------------------------------------------------------------------------
+VIT_A_ROWS, VIT_A_TRANS, VIT_A_UNFOLD = 0, 1, 2
+VIT_B_WEIGHT, VIT_B_ROWS, VIT_B_UNFOLD = 0, 1, 2
+VIT_C_ROWS, VIT_C_UNFOLD = 0, 1
+VIT_ACT_NONE, VIT_ACT_GELU, VIT_ACT_RELU, VIT_ACT_SIGMOID, VIT_DACT_GELU, VIT_DACT_RELU, VIT_DACT_SIGMOID = range(7)
+
+
+class VitGemm(ctypes.Structure):
+    """mirror of TfcVitGemm (include/tfc_gan.h)"""
+    _fields_ = [("M", ctypes.c_int), ("N", ctypes.c_int), ("K", ctypes.c_int), ("a_mode", ctypes.c_int), ("a_rg", ctypes.c_int),
+                ("a", ctypes.c_void_p), ("a2", ctypes.c_void_p), ("lda", ctypes.c_longlong), ("a_rso", ctypes.c_longlong),
+                ("b_mode", ctypes.c_int), ("c_mode", ctypes.c_int), ("b", ctypes.c_void_p), ("b2", ctypes.c_void_p), ("ldb", ctypes.c_longlong),
+                ("c", ctypes.c_void_p), ("c2", ctypes.c_void_p), ("ldc", ctypes.c_longlong), ("c_rso", ctypes.c_longlong),
+                ("c_rg", ctypes.c_int), ("act", ctypes.c_int), ("bias", ctypes.c_void_p), ("res", ctypes.c_void_p), ("aux", ctypes.c_void_p),
+                ("ldaux", ctypes.c_longlong), ("uc", ctypes.c_int), ("uh", ctypes.c_int), ("uw", ctypes.c_int), ("up", ctypes.c_int)]
+
+
+def _fp(t):
+    return None if t is None else t.data_ptr()
+
+
+def vit_gemm(dt, M, N, K, a, b, c, a_mode=VIT_A_ROWS, lda=None, a2=None, a_rg=0, a_rso=0, b_mode=VIT_B_WEIGHT, ldb=None, b2=None,
+             c_mode=VIT_C_ROWS, ldc=None, c2=None, c_rg=0, c_rso=0, bias=None, res=None, act=VIT_ACT_NONE, aux=None, ldaux=None, unfold=(0, 0, 0, 0)):
+    """C(m, n) = epilogue(sum_k A(m, k) B(k, n)) on fp32 CUDA tensors (tfc_vit_gemm: modes and epilogue in include/tfc_gan.h). Defaults: A [M][K]
+    rows, B = an nn.Linear weight [N][K], C [M][N] rows. a / b / c may be views: their data_ptr() is the base the strides count from."""
+    require_gpu(a, a2, b, b2, c, c2, bias, res, aux)
+    for t in (a, a2, b, b2, c, c2, bias, res, aux):
+        assert t is None or t.dtype == torch.float32, t.dtype
+    if lda is None:
+        lda = K if a_mode == VIT_A_ROWS else M
+    if ldb is None:
+        ldb = K if b_mode == VIT_B_WEIGHT else N
+    g = VitGemm(M, N, K, a_mode, a_rg, _fp(a), _fp(a2), lda, a_rso, b_mode, c_mode, _fp(b), _fp(b2), ldb, _fp(c), _fp(c2), N if ldc is None else ldc,
+                c_rso, c_rg, act, _fp(bias), _fp(res), _fp(aux), N if ldaux is None else ldaux, *unfold)
+    dev = (c if c is not None else c2).device
+    check(lib().tfc_vit_gemm(stream_ptr(), dt, ctypes.byref(g), part_ws(dev)), "tfc_vit_gemm")
+
+
+def vit_layernorm_fwd(x, gamma, beta, eps=1e-6):
+    """rows of x [.., D] -> (y, mean, rstd)"""
+    require_gpu(x, gamma, beta)
+    D = x.shape[-1]
+    rows = x.numel() // D
+    y = torch.empty_like(x)
+    mean = torch.empty(rows, dtype=torch.float32, device=x.device)
+    rstd = torch.empty_like(mean)
+    check(lib().tfc_vit_layernorm_fwd(stream_ptr(), _p(x), _p(gamma), _p(beta), _p(y), _p(mean), _p(rstd), rows, D, eps), "tfc_vit_layernorm_fwd")
+    return y, mean, rstd
+
+
+def vit_layernorm_bwd(dy, x, mean, rstd, gamma, dres=None, want_gb=True):
+    """-> (dx = dres + d LN / d x, dgb [2][D] = (d gamma, d beta) or None)"""
+    require_gpu(dy, x, mean, rstd, gamma, dres)
+    D = x.shape[-1]
+    rows = x.numel() // D
+    dx = torch.empty_like(x)
+    dgb = torch.empty((2, D), dtype=torch.float32, device=x.device) if want_gb else None
+    check(lib().tfc_vit_layernorm_bwd(stream_ptr(), _p(dy), _p(x), _p(mean), _p(rstd), _p(gamma), _p(dres), _p(dx), _p(dgb), rows, D, part_ws(x.device)),
+          "tfc_vit_layernorm_bwd")
+    return dx, dgb
+
+
+def vit_colsum(v, rows, L, ld=None):
+    """out[L] = sum over `rows` rows (ld apart) of v, in a fixed order"""
+    require_gpu(v)
+    out = torch.empty(L, dtype=torch.float32, device=v.device)
+    check(lib().tfc_vit_colsum(stream_ptr(), _p(v), L if ld is None else ld, rows, L, _p(out), part_ws(v.device)), "tfc_vit_colsum")
+    return out
+
+
+def vit_attention_fwd(dt, qkv, N, T, H, scale):
+    """qkv [N*T, 3*H*64] -> (out [N*T, H*64], probs [N, H, T, T])"""
+    require_gpu(qkv)
+    out = torch.empty((N * T, H * 64), dtype=torch.float32, device=qkv.device)
+    probs = torch.empty((N, H, T, T), dtype=torch.float32, device=qkv.device)
+    check(lib().tfc_vit_attention_fwd(stream_ptr(), dt, _p(qkv), _p(out), _p(probs), N, T, H, scale), "tfc_vit_attention_fwd")
+    return out, probs
+
+
+def vit_attention_bwd(dt, dout, qkv, probs, N, T, H, scale):
+    require_gpu(dout, qkv, probs)
+    dqkv = torch.empty_like(qkv)
+    check(lib().tfc_vit_attention_bwd(stream_ptr(), dt, _p(dout), _p(qkv), _p(probs), _p(dqkv), N, T, H, scale), "tfc_vit_attention_bwd")
+    return dqkv
+
+
+def vit_tokens_fwd(x, cls, pos):
+    """x [N, T, D] with the patch tokens in rows 1..T-1: row 0 = cls, every row += pos (in place)"""
+    require_gpu(x, cls, pos)
+    N, T, D = x.shape
+    check(lib().tfc_vit_tokens_fwd(stream_ptr(), _p(x), _p(cls), _p(pos), N, T, D), "tfc_vit_tokens_fwd")
+
+
 # ---- measurement ----------------------------------------------------------------------------------------------
 def prof_enable(on):
     check(lib().tfc_prof_enable(1 if on else 0), "tfc_prof_enable")

@@ -12,14 +12,17 @@ configuration adds is
 
 Everything heavy runs on the package's HIP kernels through the modules' autograd Functions (both generators, both discriminators, the warp,
 the morphological gradient, LPIPS); the generator now returns its INPUT gradient, which is how the warp and the localiser train through
-`G2(warped_B)`. The localiser is 17 tokens x 768 channels: plain torch layers (library GEMMs) -- kornia is absent from this image, so
-`VisionTransformer` is restated from its published architecture (patch embedding, class token, learned positions, 12 pre-norm encoder blocks
+`G2(warped_B)`. The localiser is 17 tokens x 768 channels and runs one of two ways (`Net.localiser`, default from TFC_LOCALISER): "torch"
+(default) as plain torch layers (library GEMMs), "hip" on the package's own kernels (vit.py: one autograd Function over csrc/vit.hip, batch
+invariant, compute dtype from `set_compute_dtype`). kornia is absent from this image, so `VisionTransformer` is restated from its published architecture (patch embedding, class token, learned positions, 12 pre-norm encoder blocks
 with 12 heads and a 4x GELU MLP, final LayerNorm) with matmul / softmax / LayerNorm only (no MIOpen convolution, no fused attention: their
 first-use compilation takes minutes on a fresh box): PARITY UNPINNED. The step keeps torch autograd across the five modules (their heavy
 parts are the package's own hand-written forward / backward chains) but owns the parameters the way the PATCH-16 engine does: flat fp32
 buffers, bucketed all-reduce from gradient hooks, `tfc_adam_step` -- so configuration C5 shards over GPUs like C4. A reference `model`
 (STN) checkpoint does NOT load into `Net`: kornia's VisionTransformer key names are not reproduced.
 """
+import os
+
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
@@ -105,12 +108,29 @@ class LocalizerVIT(nn.Module):
         return self.vit(x)
 
 
+LOCALISERS = ("torch", "hip")
+
+
+def _check_localiser(v):
+    if v not in LOCALISERS:
+        raise ValueError(f"localiser must be one of {LOCALISERS}, got {v!r}")
+    return v
+
+
+def default_localiser():
+    """TFC_LOCALISER from the environment: "torch" (unset) or "hip"; anything else raises ValueError"""
+    return _check_localiser(os.environ.get("TFC_LOCALISER", "torch"))
+
+
 class Net(nn.Module):
     """STN:170-231. forward(img_A, img_B, src): theta = identity + fc_loc(ViT(cat(img_A, img_B))), every sample of `src` warped with its own
-    matrix (F.affine_grid + F.grid_sample(bicubic, border, align_corners=True), fused in tfc_affine_warp_fwd/bwd)."""
+    matrix (F.affine_grid + F.grid_sample(bicubic, border, align_corners=True), fused in tfc_affine_warp_fwd/bwd).
+    localiser: "torch" (the ViT and fc_loc as torch layers), "hip" (vit.stn_phi: the package's kernels, GPU tensors only) or None (TFC_LOCALISER,
+    default "torch"); readable and settable as `net.localiser`. Both run on the same parameters."""
 
-    def __init__(self, img_shape=(3, 256, 256)):
+    def __init__(self, img_shape=(3, 256, 256), localiser=None):
         super().__init__()
+        self.localiser = default_localiser() if localiser is None else localiser
         channels, h, w = img_shape
         self.localization = LocalizerVIT(img_shape)
         self.theta_emb = nn.Linear(1, h * w)                      # declared and never used by the reference (STN:178); kept for the state_dict
@@ -120,12 +140,27 @@ class Net(nn.Module):
         self.fc_loc[2].bias.data.zero_()                          # STN:193
         self.warp = stn.Warp()
 
+    @property
+    def localiser(self):
+        return self._localiser
+
+    @localiser.setter
+    def localiser(self, v):
+        object.__setattr__(self, "_localiser", _check_localiser(v))
+
     def stn_phi(self, x):
+        if self._localiser == "hip":
+            from . import vit
+            return vit.stn_phi(self, x)
         xs = self.localization(x)
         return self.fc_loc(xs.reshape(xs.shape[0], -1)).view(-1, 2, 3)
 
     def forward(self, img_A, img_B, src):
-        dtheta = self.stn_phi(torch.cat((img_A, img_B), 1))
+        if self._localiser == "hip":                              # the patch embedding reads both images in place: no torch.cat
+            from . import vit
+            dtheta = vit.stn_phi(self, img_A, img_B)
+        else:
+            dtheta = self.stn_phi(torch.cat((img_A, img_B), 1))
         return self.warp(dtheta, src)
 
 
@@ -142,16 +177,17 @@ class STN21Step:
     launch, and -- one process per GPU, as for PATCH-16 -- the gradient buffers are sum-all-reduced in buckets that are issued from
     post-accumulate hooks while the rest of the backward still runs (the reference wraps all five modules in nn.DataParallel, STN:536-540).
     Every loss of the step is a batch mean except LPIPS, a batch SUM in lpips_pytorch: it is scaled by the world size so that the rank-averaged
-    gradient equals the reference's on the gathered batch. lpips: a module with the reference's call surface (tfc_gan_amd.LPIPS) or None."""
+    gradient equals the reference's on the gathered batch. lpips: a module with the reference's call surface (tfc_gan_amd.LPIPS) or None.
+    localiser: "torch", "hip" or None (TFC_LOCALISER), passed to `Net`."""
 
     def __init__(self, img_shape=(3, 256, 256), lpips=None, lr=2e-4, b1=0.5, b2=0.999, device="cuda:0", alpha2=0.01, eps=1e-8, bucket_bytes=32 << 20,
-                 seed=0):
+                 seed=0, localiser=None):
         from . import ops, parallel
         dev = torch.device(device)
         self.dev = dev
         self.G1, self.G2 = GeneratorUNet(img_shape).to(dev), GeneratorUNet(img_shape).to(dev)
         self.D1, self.D2 = Discriminator1(img_shape).to(dev), Discriminator1(img_shape).to(dev)
-        self.net = Net(img_shape).to(dev)
+        self.net = Net(img_shape, localiser=localiser).to(dev)
         for m in (self.G1, self.G2, self.D1, self.D2, self.net):
             m.apply(weights_init_normal)                          # STN:539-543
         self.lpips, self.alpha2, self._bucket_bytes = lpips, alpha2, bucket_bytes
