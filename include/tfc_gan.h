@@ -31,6 +31,12 @@ extern "C" {
 
 #define TFC_DT_BF16 0
 #define TFC_DT_F32 1
+/* TFC_DT_BF16X3: fp32 storage (every layout, pitch and scratch size as TFC_DT_F32), fp32 results on the bf16 matrix cores. The convolution
+ * family (tfc_conv_pack, the pack plan, tfc_conv_fwd, tfc_conv_dgrad, tfc_conv_wgrad) splits each fp32 operand value a into hi = bf16_rn(a),
+ * lo = bf16_rn(a - hi) and accumulates hi*hi + hi*lo + lo*hi in fp32: at most 2^-16 (3 + 2^-7) |a b| of error per product. Every other entry
+ * point that takes TFC_DT_F32 takes it and computes as in TFC_DT_F32; the bf16-only entry points (first block, generator head kernels,
+ * tfc_conv_dgrad_image) and the tfc_vit_* kernels refuse it. Non-finite inputs stay non-finite. */
+#define TFC_DT_BF16X3 2
 
 /* convolution ops of the path */
 #define TFC_OP_CONV 0     /* nn.Conv2d(k4,s1,p1)                              P16:105 (UNetDown), :189 (Discriminator1 blocks) */

@@ -16,7 +16,7 @@ SOURCES = ["api.hip", "igemm.hip", "elementwise.hip", "losses.hip", "stn.hip", "
 HEADERS = ["common.h", "tfc_desc.h", "pack_math.h"]
 PUBLIC_HEADER = os.path.join(_ROOT, "include", "tfc_gan.h")
 
-DT_BF16, DT_F32 = 0, 1
+DT_BF16, DT_F32, DT_BF16X3 = 0, 1, 2          # DT_BF16X3: fp32 storage, convolutions as bf16 hi/lo three-term products
 OP_CONV, OP_PADCONV, OP_CONVT, OP_UPCONV, OP_CONV3 = 0, 1, 2, 3, 4
 EP_BIAS, EP_STATS, EP_ACCUM, EP_TANH_NCHW, EP_LEAKY, EP_RELU = 1, 2, 4, 8, 16, 32
 

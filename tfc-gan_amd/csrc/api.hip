@@ -12,6 +12,7 @@
 #include "../../include/tfc_gan.h"
 #undef TFC_DT_BF16
 #undef TFC_DT_F32
+#undef TFC_DT_BF16X3
 #undef TFC_EP_BIAS
 #undef TFC_EP_STATS
 #undef TFC_EP_ACCUM
@@ -374,7 +375,7 @@ static int check_desc(const TfcGather& d, int dt) {
 }
 
 static int check_common(int dt, int op, int N, int H, int W, int Cin, int Cout) {
-  REQUIRE(dt == TFC_DT_BF16 || dt == TFC_DT_F32, "bad dtype %d", dt);
+  REQUIRE(dt == TFC_DT_BF16 || dt == TFC_DT_F32 || dt == TFC_DT_BF16X3, "bad dtype %d", dt);
   REQUIRE(op >= 0 && op <= 4, "bad op %d", op);
   REQUIRE(N > 0 && H > 1 && W > 1 && Cin > 0 && Cout > 0, "bad dims N=%d H=%d W=%d Cin=%d Cout=%d", N, H, W, Cin, Cout);
   REQUIRE((long long)N * (2 * H) * (2 * W) * (long long)(pad8(Cin) > pad8(Cout) ? pad8(Cin) : pad8(Cout)) < 2147483647LL,
@@ -392,7 +393,7 @@ static int check_pitch(int dt, int pitch, int cpad, const char* what) {
   return 0;
 }
 static int check_dt(int dt) {
-  REQUIRE(dt == TFC_DT_BF16 || dt == TFC_DT_F32, "bad dtype %d", dt);
+  REQUIRE(dt == TFC_DT_BF16 || dt == TFC_DT_F32 || dt == TFC_DT_BF16X3, "bad dtype %d", dt);
   return 0;
 }
 static int check_ptr16(const void* p, const char* what) {
@@ -597,7 +598,7 @@ extern "C" int tfc_conv_pack_planned(void* stream, int dt, const void* plan_dev,
 
 extern "C" int tfc_patchgan_head_fwd(void* stream, int dt, const void* x, int x_pitch, int N, int H, int W, int C, const float* w,
                                      void* y, int y_pitch) {
-  REQUIRE(dt == TFC_DT_BF16 || dt == TFC_DT_F32, "bad dtype");
+  REQUIRE(dt == TFC_DT_BF16 || dt == TFC_DT_F32 || dt == TFC_DT_BF16X3, "bad dtype");
   if (int e = check_ptr16(x, "x")) return e;
   const int ue = 16 / es_of(dt);
   REQUIRE(w && y && N > 0 && H > 0 && W > 0 && C > 0 && C % ue == 0 && C <= 2048 && x_pitch >= C && x_pitch % ue == 0 && y_pitch >= 1, "bad args");
@@ -690,7 +691,7 @@ extern "C" int tfc_first_block_bwd_wgrad(void* stream, int dt, const void* x, in
 // ---- fused activation family ------------------------------------------------------------------------------------
 static int fill_act(ActParams& p, int dt, int N, int H, int W, int C, int x_pitch, int o_pitch, int norm, float slope, int pool,
                     float drop_p, uint32_t seed) {
-  REQUIRE(dt == TFC_DT_BF16 || dt == TFC_DT_F32, "bad dtype");
+  REQUIRE(dt == TFC_DT_BF16 || dt == TFC_DT_F32 || dt == TFC_DT_BF16X3, "bad dtype");
   const int ue = 16 / es_of(dt);
   REQUIRE(C % ue == 0, "C=%d must be a multiple of %d", C, ue);
   const int cv = C / ue;
@@ -879,7 +880,7 @@ static bool vit_unfold_ok(const TfcVitGemm& g, int rows, int cols) {
 extern "C" int tfc_vit_gemm(void* stream, int dt, const TfcVitGemm* gp, float* part_ws) {
   REQUIRE(gp, "bad args");
   const TfcVitGemm& g = *gp;
-  REQUIRE(dt == TFC_DT_BF16 || dt == TFC_DT_F32, "dt");
+  REQUIRE(dt == TFC_DT_BF16 || dt == TFC_DT_F32, "tfc_vit_gemm: dt %d (bf16 or fp32 only; the ViT kernels do not support TFC_DT_BF16X3)", dt);
   REQUIRE(g.M > 0 && g.N > 0 && g.K > 0 && g.a && g.b, "tfc_vit_gemm: bad shape / operands (%d x %d x %d)", g.M, g.N, g.K);
   REQUIRE(g.a_mode >= TFC_VIT_A_ROWS && g.a_mode <= TFC_VIT_A_UNFOLD && g.b_mode >= TFC_VIT_B_WEIGHT && g.b_mode <= TFC_VIT_B_UNFOLD &&
           (g.c_mode == TFC_VIT_C_ROWS || g.c_mode == TFC_VIT_C_UNFOLD) && g.act >= TFC_VIT_ACT_NONE && g.act <= TFC_VIT_DACT_SIGMOID, "tfc_vit_gemm: mode");
@@ -913,13 +914,15 @@ extern "C" int tfc_vit_colsum(void* stream, const float* v, long long ld, int ro
   return 0;
 }
 extern "C" int tfc_vit_attention_fwd(void* stream, int dt, const float* qkv, float* out, float* probs, int N, int T, int H, float scale) {
-  REQUIRE(qkv && out && probs && N > 0 && T > 0 && T <= 64 && H > 0 && (dt == TFC_DT_BF16 || dt == TFC_DT_F32), "bad args");
+  REQUIRE(qkv && out && probs && N > 0 && T > 0 && T <= 64 && H > 0, "bad args");
+  REQUIRE(dt == TFC_DT_BF16 || dt == TFC_DT_F32, "dt %d: the ViT kernels run bf16 or fp32 only (TFC_DT_BF16X3 is not supported)", dt);
   CHECK_HIP(tfc_launch_vit_attn_fwd(dt, qkv, out, probs, N, T, H, scale, (hipStream_t)stream), "tfc_vit_attention_fwd");
   return 0;
 }
 extern "C" int tfc_vit_attention_bwd(void* stream, int dt, const float* dout, const float* qkv, const float* probs, float* dqkv, int N, int T, int H,
                                      float scale) {
-  REQUIRE(dout && qkv && probs && dqkv && N > 0 && T > 0 && T <= 64 && H > 0 && (dt == TFC_DT_BF16 || dt == TFC_DT_F32), "bad args");
+  REQUIRE(dout && qkv && probs && dqkv && N > 0 && T > 0 && T <= 64 && H > 0, "bad args");
+  REQUIRE(dt == TFC_DT_BF16 || dt == TFC_DT_F32, "dt %d: the ViT kernels run bf16 or fp32 only (TFC_DT_BF16X3 is not supported)", dt);
   CHECK_HIP(tfc_launch_vit_attn_bwd(dt, dout, qkv, probs, dqkv, N, T, H, scale, (hipStream_t)stream), "tfc_vit_attention_bwd");
   return 0;
 }

@@ -81,6 +81,24 @@ template <> __device__ __forceinline__ uint4 pack16<float>(const float* v) {
   return u;
 }
 
+// bf16x3 compute mode (TFC_DT_BF16X3): fp32 in memory; an operand unit of 4 fp32 values a is split, where it is staged or packed, into
+// {hi(a0..a3) | lo(a0..a3)} as 8 bf16 -- hi = bf16_rn(a), lo = bf16_rn(a - hi) (a - hi is exact in fp32) -- the same 16 bytes, so every
+// fp32 address computation stays as it is. Non-finite values stay non-finite (inf - inf gives a NaN lo).
+struct tfc_x3_t { float v; };
+template <> struct ElemTraits<tfc_x3_t> {
+  static constexpr int UE = 4;
+  static __device__ __forceinline__ float ld(const tfc_x3_t* p) { return p->v; }
+  static __device__ __forceinline__ void st(tfc_x3_t* p, float v) { p->v = v; }
+};
+__device__ __forceinline__ uint4 tfc_split_x3(const uint4& u) {
+  const float a0 = __uint_as_float(u.x), a1 = __uint_as_float(u.y), a2 = __uint_as_float(u.z), a3 = __uint_as_float(u.w);
+  const uint32_t h01 = pack_bf16x2(a0, a1), h23 = pack_bf16x2(a2, a3);
+  const uint32_t l01 = pack_bf16x2(a0 - __uint_as_float(h01 << 16), a1 - __uint_as_float(h01 & 0xffff0000u));
+  const uint32_t l23 = pack_bf16x2(a2 - __uint_as_float(h23 << 16), a3 - __uint_as_float(h23 & 0xffff0000u));
+  return make_uint4(h01, h23, l01, l23);
+}
+template <> __device__ __forceinline__ uint4 pack16<tfc_x3_t>(const float* v) { return tfc_split_x3(pack16<float>(v)); }
+
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);

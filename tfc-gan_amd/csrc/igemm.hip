@@ -15,7 +15,8 @@
 //   * LDS image: pixel stride = chunk+16 B, row pitch 24 pixels and rows interleaved over lane parity, which
 //     makes every ds_read_b128 lane group hit 16 distinct 16-byte slots (conflict-free; derivation below);
 //   * bf16 uses v_mfma_f32_32x32x16_bf16, fp32 (parity mode) uses v_mfma_f32_32x32x2_f32 on the same
-//     byte geometry (a 16-byte unit = 8 bf16 = 4 fp32 channels);
+//     byte geometry (a 16-byte unit = 8 bf16 = 4 fp32 channels); bf16x3 (T = tfc_x3_t) keeps the fp32 geometry with each
+//     unit split into bf16 hi / lo where it is staged or packed, and runs three v_mfma_f32_32x32x16_bf16 per two k-substeps;
 //   * epilogue fuses bias, InstanceNorm statistics (wave-shuffle + fp32 atomics), skip-gradient
 //     accumulation, and tanh + NCHW store for the generator head.
 #include <cstdlib>
@@ -40,6 +41,20 @@ template <> struct Mma<float> {
     c = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(a.y), __uint_as_float(b.y), c, 0, 0, 0);
     c = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(a.z), __uint_as_float(b.z), c, 0, 0, 0);
     c = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(a.w), __uint_as_float(b.w), c, 0, 0, 0);
+  }
+};
+// bf16x3 (tfc_x3_t): operands are split units {hi x4 | lo x4} in the fp32 geometry. TWO k-substeps (s, s+1) form one K = 16 instruction: lane
+// (r, h) holds hi(k = 4h+q of s) in elements 0..3 and hi(k = 4h+q of s+1) in 4..7 -- the same map for A and B, so the sum over the 16 channels
+// is exact -- and three v_mfma_f32_32x32x16_bf16 add lo*hi, hi*lo, hi*hi (3 x 32 cycles per 16 channels against 8 x 64 for the fp32 form).
+struct MmaX3 {
+  static __device__ __forceinline__ void run2(const uint4& a0, const uint4& a1, const uint4& b0, const uint4& b1, f32x16_t& c) {
+    const bf16x8_t ah = __builtin_bit_cast(bf16x8_t, make_uint4(a0.x, a0.y, a1.x, a1.y));
+    const bf16x8_t al = __builtin_bit_cast(bf16x8_t, make_uint4(a0.z, a0.w, a1.z, a1.w));
+    const bf16x8_t bh = __builtin_bit_cast(bf16x8_t, make_uint4(b0.x, b0.y, b1.x, b1.y));
+    const bf16x8_t bl = __builtin_bit_cast(bf16x8_t, make_uint4(b0.z, b0.w, b1.z, b1.w));
+    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh, c, 0, 0, 0);
+    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl, c, 0, 0, 0);
+    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh, c, 0, 0, 0);
   }
 };
 
@@ -100,6 +115,7 @@ tfc_igemm_kernel(const TfcGather d, const T* __restrict__ in, const uint4* __res
   constexpr int UE = 16 / ES;
   constexpr int P = TFC_LDS_P;
   constexpr int BD = (PAT == 4 || PAT == 6) ? 2 : TFC_BD;         // weight-stream prefetch distance (k-substeps), PAT != 0
+  constexpr bool X3 = std::is_same<T, tfc_x3_t>::value;          // bf16x3: halo units split when staged, k-substeps consumed in pairs (MmaX3)
 
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -166,6 +182,9 @@ tfc_igemm_kernel(const TfcGather d, const T* __restrict__ in, const uint4* __res
   auto halo_store = [&](unsigned char* buf) {
 #pragma unroll
     for (int i = 0; i < 4; ++i)
+      if constexpr (X3) {                                        // bf16x3: split once per staged unit, not once per tap
+        if (hoff[i] >= 0) *reinterpret_cast<uint4*>(buf + hoff[i]) = tfc_split_x3(hv[i]);
+      } else
       if (hoff[i] >= 0) *reinterpret_cast<uint4*>(buf + hoff[i]) = hv[i];
   };
 
@@ -189,7 +208,54 @@ tfc_igemm_kernel(const TfcGather d, const T* __restrict__ in, const uint4* __res
     bvs[nt] = ((flags & TFC_EP_BIAS) && n < d.Nout) ? bias[n] : 0.f;
   }
 
-  if constexpr (PAT != 0) {
+  if constexpr (PAT != 0 && X3) {
+    // the PAT body below with the two k-substeps of a tap (units 0-1 and 2-3 of its 64-byte chunk) in one MmaX3 step; A fragments one tap ahead
+    constexpr int COLS = TapPat<PAT>::COLS;
+    constexpr int NSR = COLS * 2;
+    static_assert(NSR % BD == 0 && BD % 2 == 0, "register ring must realign every filter row, in k-substep pairs");
+    uint4 br[BD][NT];
+#pragma unroll
+    for (int i = 0; i < BD; ++i) loadB(i, br[i]);
+    halo_load(0);
+    halo_store(smem);
+    __syncthreads();
+    int gs = 0;
+    for (int st = 0; st < nst; ++st) {
+      const bool more = (st + 1) < nst;
+      if (more) halo_load(st + 1);
+      const unsigned char* buf = smem + (st & 1) * buf_bytes + laneBase;
+#pragma unroll 1
+      for (int row = 0; row < TapPat<PAT>::ROWS; ++row) {
+        const unsigned char* rbuf = buf + (PAT == 2 ? (1 - row) : row) * (P * 80);
+        uint4 a[2][2][MT];                                       // [tap parity][k-substep of the tap][M-subtile]
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+          for (int mi = 0; mi < MT; ++mi) a[0][j][mi] = *reinterpret_cast<const uint4*>(rbuf + TapPat<PAT>::dx(0) * 80 + j * 32 + mi * (2 * P * 80));
+#pragma unroll
+        for (int c = 0; c < COLS; ++c) {
+          if (c + 1 < COLS) {
+#pragma unroll
+            for (int j = 0; j < 2; ++j)
+#pragma unroll
+              for (int mi = 0; mi < MT; ++mi)
+                a[(c + 1) & 1][j][mi] = *reinterpret_cast<const uint4*>(rbuf + TapPat<PAT>::dx(c + 1) * 80 + j * 32 + mi * (2 * P * 80));
+          }
+          const int s0 = (2 * c) % BD, s1 = (2 * c + 1) % BD;
+#pragma unroll
+          for (int mi = 0; mi < MT; ++mi)
+#pragma unroll
+            for (int nt = 0; nt < NT; ++nt) MmaX3::run2(a[c & 1][0][mi], a[c & 1][1][mi], br[s0][nt], br[s1][nt], acc[mi][nt]);
+          loadB(gs + 2 * c + BD, br[s0]);
+          loadB(gs + 2 * c + 1 + BD, br[s1]);
+          asm volatile("" ::: "memory");
+        }
+        gs += NSR;
+      }
+      if (more) halo_store(smem + ((st + 1) & 1) * buf_bytes);
+      __syncthreads();
+    }
+  } else if constexpr (PAT != 0) {
     constexpr int NSR = TapPat<PAT>::COLS * 2;                   // k-substeps per filter row (2 per tap: 4 units of 16 B)
     static_assert(NSR % BD == 0, "register ring must realign every filter row");
     uint4 br[BD][NT];
@@ -244,6 +310,28 @@ tfc_igemm_kernel(const TfcGather d, const T* __restrict__ in, const uint4* __res
       const int pl = st % d.nplanes;
       const TfcPlane& pd = d.plane[pl];
       const int nsub = tfc_nsub(pd.ntaps, PB);                    // even by construction
+      if constexpr (X3) {                                        // both k-substeps of the pair in one MmaX3 step
+        for (int s = 0; s < nsub; s += 2) {
+          uint4 a[2][MT];
+#pragma unroll
+          for (int j = 0; j < 2; ++j) {
+            const int u0 = 2 * s + 2 * j, u1 = u0 + 1;
+            const int t0 = u0 >> upp_shift, t1 = u1 >> upp_shift;
+            const int off0 = (pd.tap_dy[t0] * P + pd.tap_dx[t0]) * PS + (u0 & (UPP - 1)) * 16;
+            const int off1 = (pd.tap_dy[t1] * P + pd.tap_dx[t1]) * PS + (u1 & (UPP - 1)) * 16;
+            const int off = h ? off1 : off0;
+#pragma unroll
+            for (int mi = 0; mi < MT; ++mi) a[j][mi] = *reinterpret_cast<const uint4*>(buf + off + mi * MSTRIDE);
+          }
+#pragma unroll
+          for (int mi = 0; mi < MT; ++mi)
+#pragma unroll
+            for (int nt = 0; nt < NT; ++nt) MmaX3::run2(a[0][mi], a[1][mi], b0r[nt], b1r[nt], acc[mi][nt]);
+          loadB(gs + 2, b0r);
+          loadB(gs + 3, b1r);
+          gs += 2;
+        }
+      } else
       for (int s = 0; s < nsub; s += 2) {
         {
           const int u0 = 2 * s, u1 = u0 + 1;
@@ -1989,6 +2077,184 @@ tfc_wgrad_kernel(const TfcGather d, const T* __restrict__ dO, const T* __restric
 }
 
 // ---------------------------------------------------------------------------------------------------
+// bf16x3 weight gradient: the tfc_wgrad_kernel GEMM on fp32 dO / input. Both are split while they are staged, into a hi and a lo bf16 image of
+// the bf16 kernel's LDS layout (32 channels = 64 B per pixel row), so the transposing reads (ds_read_b64_tr_b16) and fragment maps of the bf16
+// form apply to each plane unchanged; every (k-step, tap) issues lo*hi, hi*lo, hi*hi. The two images take the 59.5 KB of the fp32 kernel's one
+// (single-buffered like it: 2 workgroups per CU). Flush: slabs only, never atomics -- the launcher keeps the grid within the slab budget.
+// pair0: first (n-block, c-block) pair of this launch (pair = pair0 + bid % npairs).
+// ---------------------------------------------------------------------------------------------------
+template <int TPW, bool RASTER>
+__global__ void __launch_bounds__(256, 2)
+tfc_wgrad_x3_kernel(const TfcGather d, const float* __restrict__ dO, const float* __restrict__ in, float4* slab, int Nn_pad, int npairs, int ncb,
+                    int nsplit, int pair0) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  constexpr int ROWB = 64;                                       // bytes per LDS row of one plane (32 bf16 channels)
+  constexpr int DO_BYTES = 2 * 128 * ROWB;
+  constexpr int PLANE = DO_BYTES + TFC_MAX_HH * TFC_MAX_HW * ROWB;   // hi image at 0, lo image at PLANE
+  constexpr int UPN = 8;                                         // fp32 16-byte units per 32 channels
+  constexpr int NDO = (2 * 128 * UPN) / 256;
+  constexpr int NHA = (TFC_MAX_HH * TFC_MAX_HW * UPN + 255) / 256;
+
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const TfcPlane& pd = d.plane[0];
+
+  const int bid = tfc_xcd_remap(blockIdx.x, gridDim.x);
+  const int pair = pair0 + bid % npairs;
+  const int sp = bid / npairs;
+  const int cb = pair % ncb, nb = pair / ncb;
+  const int ntiles = d.nimg * d.tiles_y * d.tiles_x;
+
+  f32x16_t acc[TPW][2];
+#pragma unroll
+  for (int ti = 0; ti < TPW; ++ti)
+#pragma unroll
+    for (int ni = 0; ni < 2; ++ni)
+#pragma unroll
+      for (int j = 0; j < 16; ++j) acc[ti][ni][j] = 0.f;
+
+  uint4 vdo[NDO], vha[NHA];
+  int hyq[NHA], hxq[NHA], hcq[NHA];
+  bool hok[NHA];
+  const int nunits = pd.hh * pd.hw * UPN;
+#pragma unroll
+  for (int i = 0; i < NHA; ++i) {
+    const int idx = tid + i * 256;
+    const int g = idx % UPN, pix = idx / UPN;
+    hyq[i] = pix / pd.hw; hxq[i] = pix - hyq[i] * pd.hw;
+    hcq[i] = cb * 32 + g * 4;
+    hok[i] = idx < nunits && hcq[i] < d.Cin_pad;
+  }
+  auto tile_load = [&](int tl) {
+    int t = tl;
+    const int txb = t % d.tiles_x; t /= d.tiles_x;
+    const int tyb = t % d.tiles_y;
+    const int img = t / d.tiles_y;
+    const int a0 = tyb * TFC_TILE_H, b0 = txb * TFC_TILE_W;
+#pragma unroll
+    for (int i = 0; i < NDO; ++i) {
+      const int idx = tid + i * 256;
+      const int g = idx % UPN, px = (idx / UPN) & 127, ni = idx / (UPN * 128);
+      const int a = a0 + (px >> 4), b = b0 + (px & 15);
+      const int n0 = nb * 64 + ni * 32 + g * 4;
+      vdo[i] = make_uint4(0, 0, 0, 0);
+      if (a < d.GH && b < d.GW && n0 < Nn_pad) {
+        const int oy = a * d.OS + d.OOY, ox = b * d.OS + d.OOX;
+        vdo[i] = *reinterpret_cast<const uint4*>(dO + ((size_t)(img * d.OH + oy) * d.OW + ox) * d.out_pitch + n0);
+      }
+    }
+#pragma unroll
+    for (int i = 0; i < NHA; ++i) {
+      vha[i] = make_uint4(0, 0, 0, 0);
+      if (hok[i]) {
+        const int y = (a0 + pd.dy0 + hyq[i]) * d.SS + pd.py;
+        const int x = (b0 + pd.dx0 + hxq[i]) * d.SS + pd.px;
+        if (y >= 0 && y < d.IH && x >= 0 && x < d.IW)
+          vha[i] = *reinterpret_cast<const uint4*>(in + ((size_t)(img * d.IH + y) * d.IW + x) * d.in_pitch + hcq[i]);
+      }
+    }
+  };
+  auto put = [&](int off, const uint4& v) {                      // fp32 unit (4 channels) at byte `off` of the bf16 image: hi and lo 8 bytes
+    const uint4 s = tfc_split_x3(v);
+    *reinterpret_cast<uint2*>(smem + off) = make_uint2(s.x, s.y);
+    *reinterpret_cast<uint2*>(smem + PLANE + off) = make_uint2(s.z, s.w);
+  };
+  auto tile_store = [&]() {
+#pragma unroll
+    for (int i = 0; i < NDO; ++i) put((tid + i * 256) * 8, vdo[i]);          // fp32 unit index idx -> bf16 byte offset idx * 8 (same image order)
+#pragma unroll
+    for (int i = 0; i < NHA; ++i)
+      if (tid + i * 256 < nunits) put(DO_BYTES + (tid + i * 256) * 8, vha[i]);
+  };
+
+  const int nni = (Nn_pad - nb * 64) > 32 ? 2 : 1;
+  const int grp = lane >> 4, li = lane & 15;
+  const int cb16 = grp & 1, hk = grp >> 1, q = li >> 2, p = li & 3;
+  const int trLane = (8 * hk + q) * ROWB + cb16 * 32 + p * 8;
+  auto tr16 = [&](const unsigned char* p0) {
+    s16x4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16(LDS_PTR(s16x4_t, p0));
+    s16x4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16(LDS_PTR(s16x4_t, p0 + 4 * ROWB));
+    uint4 r;
+    r.x = (uint16_t)lo[0] | ((uint32_t)(uint16_t)lo[1] << 16);
+    r.y = (uint16_t)lo[2] | ((uint32_t)(uint16_t)lo[3] << 16);
+    r.z = (uint16_t)hi[0] | ((uint32_t)(uint16_t)hi[1] << 16);
+    r.w = (uint16_t)hi[2] | ((uint32_t)(uint16_t)hi[3] << 16);
+    return r;
+  };
+  auto mma3 = [&](f32x16_t& c, const uint4& ah, const uint4& al, const uint4& bh, const uint4& bl) {
+    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, al), __builtin_bit_cast(bf16x8_t, bh), c, 0, 0, 0);
+    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, ah), __builtin_bit_cast(bf16x8_t, bl), c, 0, 0, 0);
+    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, ah), __builtin_bit_cast(bf16x8_t, bh), c, 0, 0, 0);
+  };
+  auto compute = [&]() {
+    const unsigned char* dob = smem;
+    const unsigned char* hab = smem + DO_BYTES;
+    if constexpr (RASTER) {                                      // wave w owns filter column kx = w; 4-deep sliding window over halo rows
+      const unsigned char* hcol = hab + wave * ROWB + trLane;
+      const int rowb = pd.hw * ROWB;
+      uint4 bh[4], bl[4];
+#pragma unroll
+      for (int i = 0; i < 3; ++i) { bh[i] = tr16(hcol + i * rowb); bl[i] = tr16(hcol + PLANE + i * rowb); }
+#pragma unroll
+      for (int kt = 0; kt < 8; ++kt) {
+        bh[(kt + 3) & 3] = tr16(hcol + (kt + 3) * rowb);
+        bl[(kt + 3) & 3] = tr16(hcol + PLANE + (kt + 3) * rowb);
+        uint4 ah[2], al[2];
+#pragma unroll
+        for (int ni = 0; ni < 2; ++ni) {
+          ah[ni] = tr16(dob + ni * 128 * ROWB + kt * 16 * ROWB + trLane);
+          al[ni] = tr16(dob + PLANE + ni * 128 * ROWB + kt * 16 * ROWB + trLane);
+        }
+#pragma unroll
+        for (int ky = 0; ky < 4; ++ky)
+#pragma unroll
+          for (int ni = 0; ni < 2; ++ni)
+            if (ni < nni) mma3(acc[ky][ni], ah[ni], al[ni], bh[(kt + ky) & 3], bl[(kt + ky) & 3]);
+      }
+    } else {
+#pragma unroll 2
+      for (int kt = 0; kt < 8; ++kt) {
+        uint4 ah[2], al[2];
+#pragma unroll
+        for (int ni = 0; ni < 2; ++ni) {
+          ah[ni] = tr16(dob + ni * 128 * ROWB + kt * 16 * ROWB + trLane);
+          al[ni] = tr16(dob + PLANE + ni * 128 * ROWB + kt * 16 * ROWB + trLane);
+        }
+#pragma unroll
+        for (int ti = 0; ti < TPW; ++ti) {
+          const int tap = ti * 4 + wave;
+          if (tap < pd.ntaps) {                                  // wave-uniform
+            const unsigned char* pb = hab + ((kt + pd.tap_dy[tap]) * pd.hw + pd.tap_dx[tap]) * ROWB + trLane;
+            const uint4 bh = tr16(pb), bl = tr16(pb + PLANE);
+#pragma unroll
+            for (int ni = 0; ni < 2; ++ni)
+              if (ni < nni) mma3(acc[ti][ni], ah[ni], al[ni], bh, bl);
+          }
+        }
+      }
+    }
+  };
+
+  for (int tl = sp; tl < ntiles; tl += nsplit) {
+    tile_load(tl);
+    tile_store();
+    __syncthreads();
+    compute();
+    __syncthreads();
+  }
+
+  float4* ps = slab + ((size_t)bid * 4 + wave) * (TPW * 2 * 4 * 64) + lane;   // register order (tfc_wgrad_reduce_kernel, kind 0)
+#pragma unroll
+  for (int ti = 0; ti < TPW; ++ti)
+#pragma unroll
+    for (int ni = 0; ni < 2; ++ni)
+#pragma unroll
+      for (int q4 = 0; q4 < 4; ++q4)
+        ps[((ti * 2 + ni) * 4 + q4) * 64] = make_float4(acc[ti][ni][4 * q4], acc[ti][ni][4 * q4 + 1], acc[ti][ni][4 * q4 + 2], acc[ti][ni][4 * q4 + 3]);
+}
+
+// ---------------------------------------------------------------------------------------------------
 // Weight gradient of the FIRST layer (8 padded input channels, 4 x 4 raster taps, <= 64 outputs; bf16): G down1 3 -> 64 and D block 1 6 -> 64 at
 // 256 x 256. The generic kernel pads the 8 channels to a 32-wide MFMA tile per tap -- 4x the arithmetic, 127 us for 12.8 GFLOP. Here the four
 // taps of a filter ROW share one tile: the halo is kept at 16 bytes per pixel, so column (kx, c) of pixel x lives at  x * 16 + (kx * 8 + c) * 2
@@ -2736,6 +3002,7 @@ tfc_pack_planned_kernel(const TfcPackJob* __restrict__ jobs, int njobs) {
 }
 hipError_t tfc_launch_pack_planned(int dt, const void* plan_dev, int njobs, int nblocks, hipStream_t st) {
   if (dt == TFC_DT_BF16) TFC_LAUNCH((tfc_pack_planned_kernel<bf16_t>), dim3(nblocks), dim3(256), 0, st, (const TfcPackJob*)plan_dev, njobs);
+  else if (dt == TFC_DT_BF16X3) TFC_LAUNCH((tfc_pack_planned_kernel<tfc_x3_t>), dim3(nblocks), dim3(256), 0, st, (const TfcPackJob*)plan_dev, njobs);
   else TFC_LAUNCH((tfc_pack_planned_kernel<float>), dim3(nblocks), dim3(256), 0, st, (const TfcPackJob*)plan_dev, njobs);
   return hipGetLastError();
 }
@@ -3280,6 +3547,43 @@ tfc_wgrad_reduce_kernel(const float4* __restrict__ slab, float* acc, const TfcPl
       if (n0 + e < Nn_real) acc[((size_t)slot * Nn_real + n0 + e) * Cw_real + c] += sv[e];
   }
 }
+// bf16x3 form of the kind-0 reduction above (tfc_wgrad_x3_kernel's slabs): a layer with more (n-block, c-block) pairs than slabs runs in rounds,
+// and the slabs of one round hold pairs pair0 .. pair0 + npairs - 1
+__global__ void __launch_bounds__(256)
+tfc_wgrad_x3_reduce_kernel(const float4* __restrict__ slab, float* acc, const TfcPlane pd, int T, int nsplit, int npairs, int ncbx, int Nn_real,
+                           int Cw_real, int pair0) {
+  __shared__ float4 part[4][64];
+  const int lane = threadIdx.x & 63, k = threadIdx.x >> 6;
+  int rowid = blockIdx.x;                                        // ((pair * 4 + wave) * T + a) * 4 + q
+  const int q = rowid & 3; rowid >>= 2;
+  const int a = rowid % T; rowid /= T;
+  const int wave = rowid & 3, pair = rowid >> 2;
+  const size_t blk_units = (size_t)4 * T * 4 * 64;
+  const float4* p0 = slab + ((size_t)pair * 4 + wave) * (T * 4 * 64) + (a * 4 + q) * 64 + lane;
+  float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll 4
+  for (int sp = k; sp < nsplit; sp += 4) {
+    const float4 v = p0[(size_t)sp * npairs * blk_units];
+    s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w;
+  }
+  part[k][lane] = s;
+  __syncthreads();
+  if (k != 0) return;
+#pragma unroll
+  for (int i = 1; i < 4; ++i) { const float4 v = part[i][lane]; s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w; }
+  const int gp = pair0 + pair, cbx = gp % ncbx, nb = gp / ncbx;
+  const int tap = (a >> 1) * 4 + wave;
+  const int mask = tap < pd.ntaps ? pd.tap_mask[tap] : 0;
+  const int n0 = nb * 64 + (a & 1) * 32 + 8 * q + 4 * (lane >> 5), c = cbx * 32 + (lane & 31);
+  if (c >= Cw_real) return;
+  const float sv[4] = {s.x, s.y, s.z, s.w};
+  for (int m = mask; m; m &= m - 1) {
+    const int slot = __ffs(m) - 1;
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+      if (n0 + e < Nn_real) acc[((size_t)slot * Nn_real + n0 + e) * Cw_real + c] += sv[e];
+  }
+}
 
 // fp32 accumulator [16 slots][Nn][Cw] -> torch-layout gradient  grad[n*sn + c*sc + slot].  One thread per (n, c): its 16 reads are
 // coalesced across the wave slot by slot (c runs over the lanes), its 16 results are 64 contiguous bytes (both torch layouts keep
@@ -3401,6 +3705,7 @@ static hipError_t launch_pack_t(const TfcGather& d, const float* w, const float*
 }
 hipError_t tfc_launch_pack(int dt, const TfcGather& d, const float* w, const float* scale, void* wp, int Nreal, int Creal,
                            long long sn, long long sc, hipStream_t st) {
+  if (dt == TFC_DT_BF16X3) return launch_pack_t<tfc_x3_t>(d, w, scale, wp, Nreal, Creal, sn, sc, st);
   return dt == TFC_DT_BF16 ? launch_pack_t<bf16_t>(d, w, scale, wp, Nreal, Creal, sn, sc, st)
                            : launch_pack_t<float>(d, w, scale, wp, Nreal, Creal, sn, sc, st);
 }
@@ -3987,6 +4292,7 @@ static hipError_t launch_igemm_t(const TfcGather& d, const void* in, const void*
 }
 hipError_t tfc_launch_igemm(int dt, const TfcGather& d, const void* in, const void* wp, void* out, const float* bias,
                             float* stats, float* part_ws, float* out_nchw, const float* oscale, int flags, hipStream_t st) {
+  if (dt == TFC_DT_BF16X3) return launch_igemm_t<tfc_x3_t>(d, in, wp, out, bias, stats, part_ws, out_nchw, oscale, flags, st);
   return dt == TFC_DT_BF16 ? launch_igemm_t<bf16_t>(d, in, wp, out, bias, stats, part_ws, out_nchw, oscale, flags, st)
                            : launch_igemm_t<float>(d, in, wp, out, bias, stats, part_ws, out_nchw, oscale, flags, st);
 }
@@ -4162,9 +4468,43 @@ bool tfc_launch_wgrad_phases_fused(int up, const void* x, int N, int IH, int IW,
   *err = hipGetLastError();
   return true;
 }
+// bf16x3 weight gradient: never atomics. At most 512 slabs per launch (the budget api.hip reserves): the split over pixel tiles shrinks to fit, and
+// a layer with more than 512 (n-block, c-block) pairs runs in rounds of 512 pairs, each reduced into dwacc before the next reuses the slabs.
+static hipError_t launch_wgrad_x3(const TfcGather& d, const void* dO, const void* in, float* dwacc, float4* slab, int Nn_pad, int Nn_real, int Cw_real,
+                                  hipStream_t st) {
+  if (!slab) return hipErrorInvalidValue;
+  const int nbw = (Nn_pad + 63) / 64, ncb = (d.Cin_pad + 31) / 32;
+  const int ntiles = d.nimg * d.tiles_y * d.tiles_x;
+  const int tpw = (d.plane[0].ntaps + 3) / 4;
+  bool raster = d.plane[0].ntaps == 16;
+  for (int t = 0; t < 16 && raster; ++t) raster = d.plane[0].tap_dy[t] == (t >> 2) && d.plane[0].tap_dx[t] == (t & 3);
+  const int tw = raster ? 4 : (tpw < 1 ? 1 : tpw);
+  const int lds = 2 * (2 * 128 * 64 + TFC_MAX_HH * TFC_MAX_HW * 64);
+  const int npairs_all = nbw * ncb;
+  for (int p0 = 0; p0 < npairs_all; p0 += 512) {
+    const int np = npairs_all - p0 < 512 ? npairs_all - p0 : 512;
+    int nsplit = 512 / np;
+    if (nsplit > ntiles) nsplit = ntiles;
+    if (nsplit < 1) nsplit = 1;
+    const dim3 grid(np * nsplit);
+#define TFC_WG3(TPW_, R_) TFC_LAUNCH((tfc_wgrad_x3_kernel<TPW_, R_>), grid, dim3(256), lds, st, d, (const float*)dO, (const float*)in, slab, Nn_pad, np, \
+                                     ncb, nsplit, p0)
+    if (raster) TFC_WG3(4, true);
+    else if (tw == 1) TFC_WG3(1, false);
+    else if (tw == 2) TFC_WG3(2, false);
+    else if (tw == 3) TFC_WG3(3, false);
+    else TFC_WG3(4, false);
+#undef TFC_WG3
+    TFC_LAUNCH(tfc_wgrad_x3_reduce_kernel, dim3(np * 4 * (tw * 2) * 4), dim3(256), 0, st, (const float4*)slab, dwacc, d.plane[0], tw * 2, nsplit, np,
+               ncb, Nn_real, Cw_real, p0);
+  }
+  return hipGetLastError();
+}
+
 // slab: >= TFC_WGRAD_SLAB_BYTES of scratch for the split-K partials (bf16 path); nullptr = flush with fp32 atomics (fp32 parity mode)
 hipError_t tfc_launch_wgrad(int dt, const TfcGather& d, const void* dO, const void* in, float* dwacc, void* slab, int Nn_pad,
                             int Nn_real, int Cw_real, hipStream_t st, TfcWgradFin* fin) {
+  if (dt == TFC_DT_BF16X3) return launch_wgrad_x3(d, dO, in, dwacc, (float4*)slab, Nn_pad, Nn_real, Cw_real, st);
   return dt == TFC_DT_BF16 ? launch_wgrad_t<bf16_t>(d, dO, in, dwacc, (float4*)slab, Nn_pad, Nn_real, Cw_real, st, fin)
                            : launch_wgrad_t<float>(d, dO, in, dwacc, (float4*)slab, Nn_pad, Nn_real, Cw_real, st, nullptr);   // fp32 too: slabs, not atomics (deterministic)
 }

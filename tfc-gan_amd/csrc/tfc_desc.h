@@ -29,6 +29,7 @@
 
 #define TFC_DT_BF16 0
 #define TFC_DT_F32 1
+#define TFC_DT_BF16X3 2       // fp32 storage; the gather GEMMs split every operand into bf16 hi + lo and sum hi*hi + hi*lo + lo*hi
 
 // epilogue flags
 #define TFC_EP_BIAS 1

@@ -22,7 +22,8 @@ _DEFAULT_DTYPE = torch.bfloat16
 
 
 def set_compute_dtype(dtype):
-    """torch.bfloat16 (default: bf16 storage, fp32 MFMA accumulate) or torch.float32 (exact-fp32 parity mode)."""
+    """torch.bfloat16 (default: bf16 storage, fp32 MFMA accumulate), torch.float32 (exact-fp32 parity mode) or "bf16x3" (fp32 storage, the
+    convolutions as three bf16 products of split operands on the bf16 matrix cores: fp32-parity results at the bf16 MFMA rate)."""
     global _DEFAULT_DTYPE
     ops.dt_of(dtype)
     _DEFAULT_DTYPE = dtype

@@ -10,7 +10,7 @@ from dataclasses import dataclass
 import torch
 
 from . import _lib
-from ._lib import (DT_BF16, DT_F32, EP_ACCUM, EP_BIAS, EP_LEAKY, EP_RELU, EP_STATS, EP_TANH_NCHW, OP_CONV, OP_CONV3, OP_CONVT, OP_PADCONV, OP_UPCONV,
+from ._lib import (DT_BF16, DT_BF16X3, DT_F32, EP_ACCUM, EP_BIAS, EP_LEAKY, EP_RELU, EP_STATS, EP_TANH_NCHW, OP_CONV, OP_CONV3, OP_CONVT, OP_PADCONV, OP_UPCONV,
                    check)
 
 
@@ -22,12 +22,18 @@ def torch_dtype(dt):
     return torch.bfloat16 if dt == DT_BF16 else torch.float32
 
 
+BF16X3 = "bf16x3"                   # the third compute mode: fp32 storage, convolutions split into bf16 hi / lo on the bf16 matrix cores
+
+
 def dt_of(dtype):
-    if dtype == torch.bfloat16:
+    if isinstance(dtype, str):
+        if dtype == BF16X3:
+            return DT_BF16X3
+    elif dtype == torch.bfloat16:
         return DT_BF16
-    if dtype == torch.float32:
+    elif dtype == torch.float32:
         return DT_F32
-    raise ValueError(f"compute dtype must be torch.bfloat16 or torch.float32, got {dtype}")
+    raise ValueError(f"compute dtype must be torch.bfloat16, torch.float32 or \"bf16x3\", got {dtype!r}")
 
 
 def pad8(c):

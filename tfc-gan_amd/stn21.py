@@ -28,7 +28,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import stn
-from .models import Discriminator1, GeneratorUNet, weights_init_normal
+from .models import Discriminator1, GeneratorUNet, get_compute_dtype, weights_init_normal
 
 
 class _Attention(nn.Module):
@@ -170,6 +170,12 @@ def _bce_rel(a, b, target):
     return F.binary_cross_entropy_with_logits(x, torch.full_like(x, target))
 
 
+def _refuse_bf16x3():
+    if get_compute_dtype() == "bf16x3":
+        raise ValueError('STN21Step does not support the "bf16x3" compute mode (its ViT localiser kernels run bf16 or fp32 only): '
+                         'use torch.bfloat16 or torch.float32')
+
+
 class STN21Step:
     """The batch-loop body of STN:609-672 as an engine: the five networks' parameters live in TWO flat fp32 buffers in gradient-completion order
     (generator side: localiser + MLP, generator 2, generator 1 -- optimizer_G of STN:546; discriminator side: both discriminators -- optimizer_D),
@@ -183,6 +189,7 @@ class STN21Step:
     def __init__(self, img_shape=(3, 256, 256), lpips=None, lr=2e-4, b1=0.5, b2=0.999, device="cuda:0", alpha2=0.01, eps=1e-8, bucket_bytes=32 << 20,
                  seed=0, localiser=None):
         from . import ops, parallel
+        _refuse_bf16x3()
         dev = torch.device(device)
         self.dev = dev
         self.G1, self.G2 = GeneratorUNet(img_shape).to(dev), GeneratorUNet(img_shape).to(dev)
@@ -241,6 +248,7 @@ class STN21Step:
                 p.requires_grad_(on)
 
     def step(self, real_A, real_B):
+        _refuse_bf16x3()
         from . import ops, parallel
         valid, fake_t = 0.9, 0.0                                  # STN:613-615
         self.step_no += 1

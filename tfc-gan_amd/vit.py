@@ -191,7 +191,10 @@ class _LocaliserFn(torch.autograd.Function):
 
 
 def _dt():
-    return ops.dt_of(get_compute_dtype())
+    dt = ops.dt_of(get_compute_dtype())
+    if dt == ops.DT_BF16X3:
+        raise ValueError('the HIP ViT localiser does not support the "bf16x3" compute mode (bf16 or fp32 only)')
+    return dt
 
 
 def vit_tokens(vit, img_a, img_b=None):
