@@ -359,6 +359,19 @@ int tfc_host_emulate_conv(int op, int pass, int elem_size, const float* x_host, 
                           int N, int H, int W, int Cin, int Cout);   /* pass 2 = wgrad: w_host is dy, y_host is dw */
 /* force the gather-GEMM workgroup tile (0: 128 px x 128 ch, 1: x64, 2: x32; -1: heuristic) so the tests reach every variant */
 int tfc_debug_set_igemm_config(int cfg);
+/* Batch-invariant mode (per calling thread; 0 = off, the default): every launch choice that shapes the arithmetic of one sample -- tile form, kernel
+ * variant, InstanceNorm / bias partial slots per image, split count, workgroups per image -- is taken from the layer's per-image geometry alone (the rules
+ * are evaluated at the reference batch of 32 on 256 compute units, profiling knobs of the environment ignored), so a sample's activations, statistics
+ * and gradients are bit-identical whatever batch it is computed in. At batch 32 on the MI355X the plans equal the default ones. */
+int tfc_set_batch_invariant(int on);
+int tfc_get_batch_invariant(void);
+/* Host only, launches nothing, works without a GPU: what the launchers of (dt, op, pass: 0 forward, 1 dgrad, 2 wgrad) would choose on a chip of `ncu`
+ * compute units (256 on the MI355X), under the calling thread's batch-invariant setting. flags: the TFC_EP_* bits of the call, | TFC_PLAN_FIRST_BLOCK
+ * for the fused first-block kernels (pass 0 / 2). Writes min(n, 8) ints -- kernel id, tile form (0: 128 px x 128 ch in 2 x 2 waves, 1: x 64, 2: x 32,
+ * 3: 128 x 128 in 4 n-waves, -1: none), partial slots per image, split count, workgroups per image, tap pattern, fp32-atomic flush, tiles per workgroup --
+ * and returns 8, or a negative error. */
+#define TFC_PLAN_FIRST_BLOCK 0x10000
+int tfc_conv_plan_query(int dt, int op, int pass, int N, int H, int W, int Cin, int Cout, int flags, int ncu, int* out, int n);
 /* device probe of the MFMA / transposing-read lane maps the kernels rely on (writes 3*64*16 floats) */
 int tfc_probe_mfma(void* stream, float* out);
 

@@ -170,13 +170,46 @@ PROTOTYPES = {
     "tfc_vit_tokens_fwd": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i]),
     "tfc_host_emulate_conv": (_i, [_i, _i, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i]),
     "tfc_debug_set_igemm_config": (_i, [_i]),
+    "tfc_set_batch_invariant": (_i, [_i]),
+    "tfc_get_batch_invariant": (_i, []),
+    "tfc_conv_plan_query": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _c.POINTER(_i), _i]),
     "tfc_probe_mfma": (_i, [_vp, _vp]),
 }
+
+
+def parse_switch(value):
+    """an on/off knob of the environment: unset, '' and '0' are off, anything else is on"""
+    return value not in (None, "", "0")
+
+
+# Batch-invariant mode (DESIGN.md 3.11). The setting is process-wide HERE and per thread in the library (like every host-side hook of it), and the
+# kernels of one step are launched from several threads (the caller's, autograd's backward workers): every thread re-applies the current setting
+# the next time it fetches the library handle.
+_BATCH_INVARIANT = {"on": parse_switch(os.environ.get("TFC_BATCH_INVARIANT")), "gen": 1}
+_tls = threading.local()
+
+
+def set_batch_invariant(on):
+    _BATCH_INVARIANT["on"] = bool(on)
+    _BATCH_INVARIANT["gen"] += 1
+
+
+def get_batch_invariant():
+    return _BATCH_INVARIANT["on"]
 
 
 def load():
     """Load the shared object (building it when stale) and attach prototypes. torch must be imported first so that the
     process already holds the HIP runtime torch ships; our library then binds to that same libamdhip64.so.7."""
+    lib = _load()
+    gen = _BATCH_INVARIANT["gen"]
+    if getattr(_tls, "gen", 0) != gen:
+        lib.tfc_set_batch_invariant(1 if _BATCH_INVARIANT["on"] else 0)
+        _tls.gen = gen
+    return lib
+
+
+def _load():
     global _lib
     with _lock:
         if _lib is not None:

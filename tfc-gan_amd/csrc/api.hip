@@ -1129,6 +1129,46 @@ extern "C" int tfc_debug_set_igemm_config(int cfg) {
   g_tfc_force_cfg = cfg;
   return 0;
 }
+// ---- batch-invariant mode and the launch-plan query ------------------------------------------------------------------------
+extern "C" int tfc_set_batch_invariant(int on) {                  // per thread, like the other host-side hooks
+  g_tfc_batch_invariant = on ? 1 : 0;
+  return 0;
+}
+extern "C" int tfc_get_batch_invariant(void) { return g_tfc_batch_invariant; }
+// Host only, launches nothing: the plan the launchers of (dt, op, pass) would choose on a chip of `ncu` compute units, through the launchers' own decision
+// functions. flags: the TFC_EP_* bits of the call, | TFC_PLAN_FIRST_BLOCK for the fused first-block kernels (pass 0: forward, pass 2: backward).
+extern "C" int tfc_conv_plan_query(int dt, int op, int pass, int N, int H, int W, int Cin, int Cout, int flags, int ncu, int* out, int n) {
+  if (int e = check_common(dt, op, N, H, W, Cin, Cout)) return e;
+  REQUIRE(pass >= 0 && pass <= 2 && ncu > 0 && out && n >= 0, "bad pass / ncu / out");
+  const bool inv = g_tfc_batch_invariant != 0;
+  TfcConvPlan p{};
+  if (flags & TFC_PLAN_FIRST_BLOCK) {
+    REQUIRE(op == TFC_OP_CONV && pass != 1 && tfc_first_block_bwd_supported(dt, Cin, Cout), "the fused first block: TFC_OP_CONV, bf16, Cin <= 8, Cout == 64, pass 0 or 2");
+    tfc_plan_first_block(pass, N, H, W, ncu, inv, &p);
+    // what the launcher refuses, the query refuses: one 32 KB slab per workgroup, 2048 of them (batch-invariant mode keeps the reference batch's
+    // workgroups per image, so this is N <= 128 at 256 x 256 there)
+    REQUIRE(pass != 2 || (long long)N * p.wpi <= 2048, "fused first-block backward: %d images x %d workgroups per image exceed the 2048 slabs of the scratch", N, p.wpi);
+  } else if (pass == 2) {
+    REQUIRE(op != TFC_OP_CONV3, "TFC_OP_CONV3 has no weight-gradient pass");
+    TfcGather d;
+    WeightMap wm{};
+    if (int e = build_desc(op, 2, 0, N, H, W, Cin, Cout, pad8(Cin), pad8(Cout), &d, &wm)) return e;
+    bool fused = false;
+    if ((op == TFC_OP_CONVT || op == TFC_OP_UPCONV) && dt == TFC_DT_BF16)
+      fused = tfc_plan_wgrad_phases(op == TFC_OP_UPCONV, N, H, W, pad8(Cin), pad8(Cin), Cout, wm.sn % 4 == 0 && wm.sc % 4 == 0, inv, &p);
+    if (!fused) tfc_plan_wgrad(dt, d, pad8(Cout), true, inv, &p);
+  } else {
+    TfcGather d;
+    if (int e = build_desc(op, pass, 0, N, H, W, Cin, Cout, pass ? pad8(Cout) : pad8(Cin), pass ? pad8(Cin) : pad8(Cout), &d, nullptr)) return e;
+    if (pass == 0 && (op == TFC_OP_CONVT || op == TFC_OP_UPCONV)) { d.ph_n = 4; d.ph_d0 = (op == TFC_OP_CONVT) ? 1 : 0; d.ph_oo = 1; }   // as tfc_conv_fwd folds the phases
+    if (int e = check_desc(d, dt)) return e;
+    tfc_plan_igemm(dt, d, flags & 0xffff, ncu, inv, &p);
+    if (!(flags & TFC_EP_STATS)) p.nparts = 0;
+  }
+  const int rec[8] = {p.kernel, p.form, p.nparts, p.nsplit, p.wpi, p.pat, p.atomics, p.per};
+  for (int i = 0; i < n && i < 8; ++i) out[i] = rec[i];
+  return 8;
+}
 extern "C" int tfc_probe_mfma(void* stream, float* out) {
   REQUIRE(out, "out is null");
   CHECK_HIP(tfc_launch_probe(out, (hipStream_t)stream), "tfc_probe_mfma");

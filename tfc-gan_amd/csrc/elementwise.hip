@@ -1221,15 +1221,21 @@ tfc_head_fwd_kernel(const T* __restrict__ x, int x_pitch, const float* __restric
 // ---------------------------------------------------------------------------------------------------
 // launchers
 // ---------------------------------------------------------------------------------------------------
+#ifndef TFC_ACT_CAP
+#define TFC_ACT_CAP 4096                                           // ~16 grid-stride workgroups per CU; 8192 and more measured 0.4-0.6 % slower per step
+#endif
+// Grid-stride workgroups per image. A workgroup's pixels (and with them the order of its per-image partial sums: stats_out, rstats) follow from this
+// count, so batch-invariant mode takes it at the reference batch instead of the actual one.
+int tfc_act_grid_cap(int N, bool inv) {
+  if (inv) N = TFC_REF_BATCH;
+  const int cap = TFC_ACT_CAP / (N > 0 ? N : 1);
+  return cap < 1 ? 1 : cap;
+}
 static inline dim3 act_grid(int npix, int C, int ue, int N) {
   const int cv = C / ue;
   const int ppb = 256 / cv;
   int nb = (npix + ppb - 1) / ppb;
-#ifndef TFC_ACT_CAP
-#define TFC_ACT_CAP 4096                                           // ~16 grid-stride workgroups per CU; 8192 and more measured 0.4-0.6 % slower per step
-#endif
-  int cap = TFC_ACT_CAP / (N > 0 ? N : 1);
-  if (cap < 1) cap = 1;
+  const int cap = tfc_act_grid_cap(N, g_tfc_batch_invariant != 0);
   if (nb > cap) nb = cap;
   return dim3(nb, N);
 }

@@ -3736,6 +3736,104 @@ static int match_pattern(const TfcGather& d, int es) {
   return pat < 0 ? 0 : pat;
 }
 
+static int tfc_num_cus() {
+  static int ncu = 0;
+  if (!ncu) {
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || ncu <= 0) ncu = 256;
+  }
+  return ncu;
+}
+// ---------------------------------------------------------------------------------------------------
+// Launch plans. Every choice that shapes the arithmetic of a convolution pass -- kernel, tile form, InstanceNorm partial slots per image, split count,
+// workgroups per image -- is made HERE, by the launchers and by tfc_conv_plan_query alike. In batch-invariant mode (tfc_set_batch_invariant)
+// the rules are evaluated at the reference batch TFC_REF_BATCH on TFC_REF_CUS compute units, with the profiling knobs of the environment ignored: the
+// answer is then a function of the layer's per-image geometry alone, and at the reference batch it is the default answer.
+// ---------------------------------------------------------------------------------------------------
+thread_local int g_tfc_batch_invariant = 0;
+bool tfc_conv_c8_eligible(const TfcGather& d, int flags);
+static inline int plan_phases(const TfcGather& d) { return d.ph_n > 1 ? d.ph_n : 1; }
+static const int kFormNT[5] = {2, 1, 1, 1, 2}, kFormWM[5] = {2, 2, 4, 1, 1}, kFormWN[5] = {2, 2, 1, 4, 4};   // <2,2,2,2> <2,1,2,2> <1,1,4,1> <4,1,1,4> <4,2,1,4>
+// InstanceNorm partial slots per image: one per (tile, phase) of the persistent kernel, one per (tile, phase, M-wave) of the one-tile-per-workgroup kernel
+static inline int igemm_nparts(const TfcGather& d, bool persistent, int WM) { return d.tiles_y * d.tiles_x * plan_phases(d) * (persistent ? 1 : WM); }
+// dynamic LDS of the persistent kernel (see its LDS map): halo x 2 | staged tile | per-wave statistics slots (EP_STATS) | bias table (EP_BIAS)
+static int igemm2_lds_bytes(const TfcGather& d, int NT, int WN, int flags, int* buf_bytes_out) {
+  const int nblkN = (tfc_nb32(d.Nout) + NT * WN - 1) / (NT * WN);
+  int maxhh = 0;
+  for (int pl = 0; pl < d.nplanes; ++pl) maxhh = d.plane[pl].hh > maxhh ? d.plane[pl].hh : maxhh;
+  const int buf_bytes = maxhh * TFC_LDS_P * 80;
+  const int BN = 32 * NT * WN;
+  const int BNS = BN > 128 ? 32 * WN : BN;                        // channels of one staged epilogue pass
+  const int STG = 128 * (BNS * 2 + 16);
+  if (buf_bytes_out) *buf_bytes_out = buf_bytes;
+  // 256-channel tile: the staged tile overlays a consumed halo buffer
+  return (BN > 128 ? 2 * buf_bytes + (STG > buf_bytes ? STG - buf_bytes : 0) : 2 * buf_bytes + STG) + ((flags & TFC_EP_STATS) ? 8 * BN * 4 : 0) +
+         ((flags & TFC_EP_BIAS) ? nblkN * BN * 4 : 0);
+}
+void tfc_plan_igemm(int dt, const TfcGather& d, int flags, int ncu, bool inv, TfcConvPlan* p) {
+  *p = TfcConvPlan{};
+  const bool b16 = dt == TFC_DT_BF16;
+  const int nimg = inv ? TFC_REF_BATCH : d.nimg;
+  if (inv) ncu = TFC_REF_CUS;
+  const int nb = tfc_nb32(d.Nout);
+  const int fcfg = g_tfc_force_cfg < 0 ? -1 : (g_tfc_force_cfg & 15);     // bit 4 of the test hook selects the one-tile-per-workgroup kernel
+  p->nsplit = 1;
+  p->form = -1;
+  if (b16 && g_tfc_force_cfg < 0 && tfc_conv_c8_eligible(d, flags)) { p->kernel = TFC_K_CONV_C8; return; }
+  const int ntiles = nimg * d.tiles_y * d.tiles_x;
+  const int target = 512;
+  int form = -1;
+#ifdef TFC_PROBE_W64
+  if (b16 && fcfg == 4 && nb >= 8) form = 4;
+#endif
+  if (form >= 0) {}
+  else if (fcfg == 3 && nb >= 4) form = 3;
+  else if (fcfg == 0 && nb >= 4) form = 0;
+  else if ((fcfg == 0 || fcfg == 1) && nb >= 2) form = 1;
+  else if (fcfg >= 0 && fcfg != 15) form = 2;
+  else {
+    if (b16) {
+      // Few tiles, many output channels (the deep 16 x 16 ... 4 x 4 layers): the weight stream dominates. One 128-channel tile per workgroup with
+      // each wave owning 32 channels for all 128 pixels (no weight fragment is fetched by two waves) beats two 64-channel workgroups as soon as
+      // it still gives every CU a workgroup -- measured at batch 32: conv 16x16 512->512 70 -> 66 us, convT 16x16 1024->256 86 -> 67 us,
+      // convT 8x8 1024->512 84 -> 66 us, convT 4x4 512->512 44 -> 32 us, convT 32x32 512->128 100 -> 69 us (conv 8x8 512->512 would leave half
+      // the CUs idle: 50 -> 57 us, excluded; the four sub-pixel phases of a transposed convolution count as tiles).
+      static const bool old_rule_env = [] { const char* e = getenv("TFC_TILE_RULE_OLD"); return e && atoi(e) != 0; }();   // A/B knob for profiling
+      const bool old_rule = old_rule_env && !inv;
+      const int w128 = ntiles * plan_phases(d) * ((nb + 3) / 4);
+      if (!old_rule && nb >= 4 && d.Cin_pad >= 64 && w128 >= ncu && (w128 < 2048 || d.Cin_pad >= 128))   // (128 -> 256 at 64 x 64: 130 -> 124 us; 64 -> 128 at 128 x 128 stays on <2,2,2,2>: 132 vs 157)   // (also 1-3 % ahead of <2,2,2,2> at 32 x 32 256->512; the two are equal beyond)
+        form = 3;
+    }
+    if (form >= 0) {}
+    else if (nb >= 4 && ntiles * ((nb + 3) / 4) >= target) form = 0;
+    else if (nb >= 2 && (ntiles * ((nb + 1) / 2) >= target || nb < 4)) form = 1;
+    else if (nb >= 4 && ntiles * nb < target / 2) form = 2;
+    else if (nb >= 2) form = 1;
+    else form = 2;
+  }
+  p->form = form;
+  p->pat = match_pattern(d, b16 ? 2 : 4);
+  p->kernel = TFC_K_IGEMM;
+  if (b16) {
+    // bf16, compile-time tap pattern, whole 16-byte output units, NHWC output: the persistent kernel (test hook: config | 16 = one tile per workgroup)
+    static const bool legacy_env = [] { const char* e = getenv("TFC_LEGACY_IGEMM"); return e && atoi(e) != 0; }();   // A/B knob for profiling
+    if (p->pat != 0 && d.Nout % 8 == 0 && !(flags & TFC_EP_TANH_NCHW) && !(g_tfc_force_cfg >= 0 && (g_tfc_force_cfg & 16)) && !(legacy_env && !inv))
+      p->kernel = TFC_K_IGEMM2;
+  }
+  if (p->kernel == TFC_K_IGEMM2 && 32 * kFormNT[form] * kFormWN[form] <= 128) {
+    // two-half form (see the kernel): one 512-thread workgroup per CU, halves (nst + 1) / 2 barrier slots apart. Needs two LDS regions (<= 160 KiB) and
+    // enough work for both halves of every CU. MEASURED NEUTRAL (scripts/ab_halves.py, DESIGN 3.1: conv shapes x0.98-1.02, transposed x0.87-0.93, with or
+    // without s_setprio in the K loop or a deeper weight ring), so it is OFF by default: TFC_IGEMM_HALVES=2 or test config | 32 select it
+    static const int halves_env = [] { const char* e = getenv("TFC_IGEMM_HALVES"); return e ? atoi(e) : 1; }();
+    const int nblkN = (nb + kFormNT[form] * kFormWN[form] - 1) / (kFormNT[form] * kFormWN[form]);
+    const int nwork = ntiles * plan_phases(d) * nblkN;
+    const int half_bytes = (igemm2_lds_bytes(d, kFormNT[form], kFormWN[form], flags, nullptr) + 255) & ~255;
+    if (halves_env == 2 && !inv && 2 * half_bytes <= 160 * 1024 && nwork >= 2 * ncu && (g_tfc_force_cfg < 0 || (g_tfc_force_cfg & 32)))   // test hook: forced tiles run the two-workgroup form unless bit 5 is set
+      p->kernel = TFC_K_IGEMM2_HALVES;
+  }
+  p->nparts = igemm_nparts(d, p->kernel != TFC_K_IGEMM, kFormWM[form]);
+}
+
 template <typename T, int MT, int NT, int WM, int WN, int PAT>
 static hipError_t launch_igemm_pat(const TfcGather& d, const void* in, const void* wp, void* out, const float* bias,
                                    float* stats, float* part_ws, float* out_nchw, const float* oscale, int flags, hipStream_t st) {
@@ -3755,7 +3853,7 @@ static hipError_t launch_igemm_pat(const TfcGather& d, const void* in, const voi
   const int ntiles = d.nimg * d.tiles_y * d.tiles_x * (d.ph_n > 1 ? d.ph_n : 1);
   const long long phase_wbytes = (long long)tfc_packed_bytes(d, ES);
   // InstanceNorm sums: every (tile, M-wave) stores its partial into part_ws[img][tile * WM + wm][Nout][2]; a fixed-order pass adds them to stats
-  const int nparts = d.tiles_y * d.tiles_x * WM * (d.ph_n > 1 ? d.ph_n : 1);
+  const int nparts = igemm_nparts(d, false, WM);
   if (flags & TFC_EP_STATS) {
     if (!part_ws || (long long)d.nimg * nparts * d.Nout * 2 > (long long)TFC_PART_WS_FLOATS) return hipErrorInvalidValue;
   }
@@ -3766,31 +3864,16 @@ static hipError_t launch_igemm_pat(const TfcGather& d, const void* in, const voi
 }
 
 // persistent bf16 kernel: 2 workgroups per CU walk the work items (tile x n-block x phase)
-static int tfc_num_cus() {
-  static int ncu = 0;
-  if (!ncu) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || ncu <= 0) ncu = 256;
-  }
-  return ncu;
-}
 template <int MT, int NT, int WM, int WN, int PAT>
-static hipError_t launch_igemm2_pat(const TfcGather& d, const void* in, const void* wp, void* out, const float* bias,
+static hipError_t launch_igemm2_pat(const TfcConvPlan& plan, const TfcGather& d, const void* in, const void* wp, void* out, const float* bias,
                                     float* stats, float* part_ws, float* dbg, const float* oscale, int flags, hipStream_t st) {
   const int NB32 = tfc_nb32_padded(d.Nout);
   const int per_blk = NT * WN;
   const int nblkN = (tfc_nb32(d.Nout) + per_blk - 1) / per_blk;
-  int maxhh = 0;
-  for (int pl = 0; pl < d.nplanes; ++pl) maxhh = d.plane[pl].hh > maxhh ? d.plane[pl].hh : maxhh;
-  const int buf_bytes = maxhh * TFC_LDS_P * 80;
   constexpr int BN = 32 * NT * WN;
-  constexpr int BNS = BN > 128 ? 32 * WN : BN;                    // channels of one staged epilogue pass
-  constexpr int STG = 128 * (BNS * 2 + 16);
-  // 256-channel tile: the staged tile overlays a consumed halo buffer (see the kernel's LDS map)
-  // halo x 2 | staged tile | per-wave statistics slots (EP_STATS) | bias table (EP_BIAS)
-  const int lds = (BN > 128 ? 2 * buf_bytes + (STG > buf_bytes ? STG - buf_bytes : 0) : 2 * buf_bytes + STG) + ((flags & TFC_EP_STATS) ? 8 * BN * 4 : 0) +
-                  ((flags & TFC_EP_BIAS) ? nblkN * BN * 4 : 0);
-  const int nparts = d.tiles_y * d.tiles_x * (d.ph_n > 1 ? d.ph_n : 1);   // InstanceNorm partial slots per image: part_ws[img][phase][tile][Nout][2]
+  int buf_bytes = 0;
+  const int lds = igemm2_lds_bytes(d, NT, WN, flags, &buf_bytes);
+  const int nparts = igemm_nparts(d, true, WM);                   // part_ws[img][phase][tile][Nout][2]
   if (flags & TFC_EP_STATS) {
     if (!part_ws || (long long)d.nimg * nparts * d.Nout * 2 > (long long)TFC_PART_WS_FLOATS) return hipErrorInvalidValue;
   }
@@ -3807,13 +3890,9 @@ static hipError_t launch_igemm2_pat(const TfcGather& d, const void* in, const vo
   const int cap = occ_cache * tfc_num_cus();
   const long long phase_wbytes = (long long)tfc_packed_bytes(d, 2);
   if constexpr (BN <= 128) {
-    // two-half form (see the kernel): one 512-thread workgroup per CU, halves (nst + 1) / 2 barrier slots apart. Needs two LDS regions (<= 160 KiB) and
-    // enough work for both halves of every CU. MEASURED NEUTRAL (scripts/ab_halves.py, DESIGN 3.1: conv shapes x0.98-1.02, transposed x0.87-0.93, with or
-    // without s_setprio in the K loop or a deeper weight ring), so it is OFF by default: TFC_IGEMM_HALVES=2 or test config | 32 select it
-    static const int halves_env = [] { const char* e = getenv("TFC_IGEMM_HALVES"); return e ? atoi(e) : 1; }();
     const int nst = ((d.Cin_pad * 2) / 64) * d.nplanes;
     const int half_bytes = (lds + 255) & ~255;
-    if (halves_env == 2 && 2 * half_bytes <= 160 * 1024 && nwork >= 2 * tfc_num_cus() && (g_tfc_force_cfg < 0 || (g_tfc_force_cfg & 32))) {   // test hook: forced tiles run the two-workgroup form unless bit 5 is set
+    if (plan.kernel == TFC_K_IGEMM2_HALVES) {                     // the two-half form (tfc_plan_igemm)
       static const int shift_env = [] { const char* e = getenv("TFC_IGEMM_SHIFT"); return e ? atoi(e) : -1; }();
       static const int prio_env = [] { const char* e = getenv("TFC_IGEMM_PRIO"); return e ? atoi(e) : 0; }();
       const int shift = (shift_env >= 0 ? shift_env : (nst + 1) / 2) | (prio_env ? 256 : 0);
@@ -3830,27 +3909,23 @@ static hipError_t launch_igemm2_pat(const TfcGather& d, const void* in, const vo
   return hipGetLastError();
 }
 template <int MT, int NT, int WM, int WN>
-static hipError_t launch_igemm2_cfg(int pat, const TfcGather& d, const void* in, const void* wp, void* out, const float* bias,
+static hipError_t launch_igemm2_cfg(const TfcConvPlan& plan, const TfcGather& d, const void* in, const void* wp, void* out, const float* bias,
                                     float* stats, float* part_ws, float* dbg, const float* oscale, int flags, hipStream_t st) {
-  switch (pat) {
-    case 1: return launch_igemm2_pat<MT, NT, WM, WN, 1>(d, in, wp, out, bias, stats, part_ws, dbg, oscale, flags, st);
-    case 2: return launch_igemm2_pat<MT, NT, WM, WN, 2>(d, in, wp, out, bias, stats, part_ws, dbg, oscale, flags, st);
-    case 3: return launch_igemm2_pat<MT, NT, WM, WN, 3>(d, in, wp, out, bias, stats, part_ws, dbg, oscale, flags, st);
-    default: return launch_igemm2_pat<MT, NT, WM, WN, 6>(d, in, wp, out, bias, stats, part_ws, dbg, oscale, flags, st);
+  switch (plan.pat) {
+    case 1: return launch_igemm2_pat<MT, NT, WM, WN, 1>(plan, d, in, wp, out, bias, stats, part_ws, dbg, oscale, flags, st);
+    case 2: return launch_igemm2_pat<MT, NT, WM, WN, 2>(plan, d, in, wp, out, bias, stats, part_ws, dbg, oscale, flags, st);
+    case 3: return launch_igemm2_pat<MT, NT, WM, WN, 3>(plan, d, in, wp, out, bias, stats, part_ws, dbg, oscale, flags, st);
+    default: return launch_igemm2_pat<MT, NT, WM, WN, 6>(plan, d, in, wp, out, bias, stats, part_ws, dbg, oscale, flags, st);
   }
 }
 
 template <typename T, int MT, int NT, int WM, int WN>
-static hipError_t launch_igemm_cfg(const TfcGather& d, const void* in, const void* wp, void* out, const float* bias,
+static hipError_t launch_igemm_cfg(const TfcConvPlan& plan, const TfcGather& d, const void* in, const void* wp, void* out, const float* bias,
                                    float* stats, float* part_ws, float* out_nchw, const float* oscale, int flags, hipStream_t st) {
   if constexpr (sizeof(T) == 2) {
-    // bf16, compile-time tap pattern, whole 16-byte output units, NHWC output: the persistent kernel (test hook: config | 16 = one tile per workgroup)
-    const int pat = match_pattern(d, 2);
-    static const bool legacy_env = [] { const char* e = getenv("TFC_LEGACY_IGEMM"); return e && atoi(e) != 0; }();   // A/B knob for profiling
-    if (pat != 0 && d.Nout % 8 == 0 && !(flags & TFC_EP_TANH_NCHW) && !(g_tfc_force_cfg >= 0 && (g_tfc_force_cfg & 16)) && !legacy_env)
-      return launch_igemm2_cfg<MT, NT, WM, WN>(pat, d, in, wp, out, bias, stats, part_ws, out_nchw, oscale, flags, st);
+    if (plan.kernel != TFC_K_IGEMM) return launch_igemm2_cfg<MT, NT, WM, WN>(plan, d, in, wp, out, bias, stats, part_ws, out_nchw, oscale, flags, st);
   }
-  switch (match_pattern(d, sizeof(T))) {
+  switch (plan.pat) {
     case 1: return launch_igemm_pat<T, MT, NT, WM, WN, 1>(d, in, wp, out, bias, stats, part_ws, out_nchw, oscale, flags, st);
     case 2: return launch_igemm_pat<T, MT, NT, WM, WN, 2>(d, in, wp, out, bias, stats, part_ws, out_nchw, oscale, flags, st);
     case 3: return launch_igemm_pat<T, MT, NT, WM, WN, 3>(d, in, wp, out, bias, stats, part_ws, out_nchw, oscale, flags, st);
@@ -4234,6 +4309,35 @@ hipError_t tfc_launch_conv_c8(const TfcGather& d, const void* in, const void* wp
   return hipGetLastError();
 }
 
+// pass 0: tiles per workgroup of the fused first-block forward; pass 2: workgroups per image (= partial slots of the per-image bias sums) and tiles per
+// workgroup of the fused first-block backward. H, W: the block's input image.
+void tfc_plan_first_block(int pass, int N, int H, int W, int ncu, bool inv, TfcConvPlan* p) {
+  *p = TfcConvPlan{};
+  p->form = -1; p->nsplit = 1;
+  const int nimg = inv ? TFC_REF_BATCH : N;
+  if (inv) ncu = TFC_REF_CUS;
+  if (pass == 0) {
+    const int CH = H - 1, CW = W - 1;
+    const int Ho = (CH - 1) / 2 + 1, Wo = (CW - 1) / 2 + 1;
+    const int ntiles = nimg * ((Ho + 3) / 4) * ((Wo + 14) / 15);
+    int nwg = 2 * ncu;
+    if (nwg > ntiles) nwg = ntiles;
+    p->kernel = TFC_K_FIRST_FWD;
+    p->per = (ntiles + nwg - 1) / nwg;
+    return;
+  }
+  // wpi workgroups per image, each with `per` consecutive tiles of that image: about 512 workgroups in all (2 per CU), at most 2048 (32 KB of slab each)
+  const int tpi = ((H - 1 + TFC_TILE_H - 1) / TFC_TILE_H) * ((W - 1 + TFC_TILE_W - 1) / TFC_TILE_W);
+  int wpi = 512 / nimg;
+  if (wpi < 1) wpi = 1;
+  if (wpi > tpi) wpi = tpi;
+  const int per = (tpi + wpi - 1) / wpi;
+  p->kernel = TFC_K_FIRST_BWD;
+  p->per = per;
+  p->wpi = (tpi + per - 1) / per;
+  p->nparts = p->wpi;
+  p->nsplit = p->wpi;                                             // slabs per image of the weight gradient
+}
 // fused first block forward: x NHWC8 [N][IH][IW][8] -> pooled [N][Ho][Wo] (o_pitch); gform: LeakyReLU after the bf16 rounding of the raw conv output
 hipError_t tfc_launch_first_block_fwd(const void* in, int N, int IH, int IW, const void* wp, const float* bias, const float* oscale, float slope, int gform,
                                       void* out, int o_pitch, unsigned char* sign_mask, hipStream_t st) {
@@ -4241,10 +4345,10 @@ hipError_t tfc_launch_first_block_fwd(const void* in, int N, int IH, int IW, con
   const int Ho = (CH - 1) / 2 + 1, Wo = (CW - 1) / 2 + 1;
   const int tiles_y = (Ho + 3) / 4, tiles_x = (Wo + 14) / 15;
   const int ntiles = N * tiles_y * tiles_x;
-  int nwg = 2 * tfc_num_cus();
-  if (nwg > ntiles) nwg = ntiles;
-  const int per = (ntiles + nwg - 1) / nwg;
-  nwg = (ntiles + per - 1) / per;
+  TfcConvPlan plan;
+  tfc_plan_first_block(0, N, IH, IW, tfc_num_cus(), g_tfc_batch_invariant != 0, &plan);
+  const int per = plan.per;                                       // a run of tiles may cross an image boundary: every tile is computed on its own, no sum is carried
+  const int nwg = (ntiles + per - 1) / per;
   if (gform)
     TFC_LAUNCH(tfc_first_block_fwd_kernel<true>, dim3(nwg), dim3(256), 0, st, (const bf16_t*)in, IH, IW, (const uint4*)wp, tfc_nb32_padded(64), bias, oscale, slope,
                (bf16_t*)out, o_pitch, Ho, Wo, sign_mask, N, tiles_y, tiles_x, per);
@@ -4255,46 +4359,28 @@ hipError_t tfc_launch_first_block_fwd(const void* in, int N, int IH, int IW, con
 }
 
 template <typename T>
-static hipError_t launch_igemm_t(const TfcGather& d, const void* in, const void* wp, void* out, const float* bias,
+static hipError_t launch_igemm_t(int dt, const TfcGather& d, const void* in, const void* wp, void* out, const float* bias,
                                  float* stats, float* part_ws, float* out_nchw, const float* oscale, int flags, hipStream_t st) {
-  const int nb = tfc_nb32(d.Nout);
-  const int fcfg = g_tfc_force_cfg < 0 ? -1 : (g_tfc_force_cfg & 15);     // bit 4 of the test hook selects the one-tile-per-workgroup kernel
+  TfcConvPlan plan;
+  tfc_plan_igemm(dt, d, flags, tfc_num_cus(), g_tfc_batch_invariant != 0, &plan);
   if constexpr (sizeof(T) == 2) {
-    if (g_tfc_force_cfg < 0 && tfc_conv_c8_eligible(d, flags)) return tfc_launch_conv_c8(d, in, wp, out, bias, oscale, flags, nullptr, st);
-  }
+    if (plan.kernel == TFC_K_CONV_C8) return tfc_launch_conv_c8(d, in, wp, out, bias, oscale, flags, nullptr, st);
 #ifdef TFC_PROBE_W64
-  if constexpr (sizeof(T) == 2) {
-    if (fcfg == 4 && nb >= 8) return launch_igemm2_cfg<4, 2, 1, 4>(match_pattern(d, 2), d, in, wp, out, bias, stats, part_ws, out_nchw, oscale, flags, st);
-  }
+    if (plan.form == 4) return launch_igemm2_cfg<4, 2, 1, 4>(plan, d, in, wp, out, bias, stats, part_ws, out_nchw, oscale, flags, st);
 #endif
-  if (fcfg == 3 && nb >= 4) return launch_igemm_cfg<T, 4, 1, 1, 4>(d, in, wp, out, bias, stats, part_ws, out_nchw, oscale, flags, st);
-  if (fcfg == 0 && nb >= 4) return launch_igemm_cfg<T, 2, 2, 2, 2>(d, in, wp, out, bias, stats, part_ws, out_nchw, oscale, flags, st);
-  if ((fcfg == 0 || fcfg == 1) && nb >= 2) return launch_igemm_cfg<T, 2, 1, 2, 2>(d, in, wp, out, bias, stats, part_ws, out_nchw, oscale, flags, st);
-  if (fcfg >= 0 && fcfg != 15) return launch_igemm_cfg<T, 1, 1, 4, 1>(d, in, wp, out, bias, stats, part_ws, out_nchw, oscale, flags, st);
-  const int ntiles = d.nimg * d.tiles_y * d.tiles_x;
-  const int target = 512;
-  if constexpr (sizeof(T) == 2) {
-    // Few tiles, many output channels (the deep 16 x 16 ... 4 x 4 layers): the weight stream dominates. One 128-channel tile per workgroup with
-    // each wave owning 32 channels for all 128 pixels (no weight fragment is fetched by two waves) beats two 64-channel workgroups as soon as
-    // it still gives every CU a workgroup -- measured at batch 32: conv 16x16 512->512 70 -> 66 us, convT 16x16 1024->256 86 -> 67 us,
-    // convT 8x8 1024->512 84 -> 66 us, convT 4x4 512->512 44 -> 32 us, convT 32x32 512->128 100 -> 69 us (conv 8x8 512->512 would leave half
-    // the CUs idle: 50 -> 57 us, excluded; the four sub-pixel phases of a transposed convolution count as tiles).
-    static const bool old_rule = [] { const char* e = getenv("TFC_TILE_RULE_OLD"); return e && atoi(e) != 0; }();   // A/B knob for profiling
-    const int w128 = ntiles * (d.ph_n > 1 ? d.ph_n : 1) * ((nb + 3) / 4);
-    if (!old_rule && nb >= 4 && d.Cin_pad >= 64 && w128 >= tfc_num_cus() && (w128 < 2048 || d.Cin_pad >= 128))   // (128 -> 256 at 64 x 64: 130 -> 124 us; 64 -> 128 at 128 x 128 stays on <2,2,2,2>: 132 vs 157)   // (also 1-3 % ahead of <2,2,2,2> at 32 x 32 256->512; the two are equal beyond)
-      return launch_igemm_cfg<T, 4, 1, 1, 4>(d, in, wp, out, bias, stats, part_ws, out_nchw, oscale, flags, st);
   }
-  if (nb >= 4 && ntiles * ((nb + 3) / 4) >= target) return launch_igemm_cfg<T, 2, 2, 2, 2>(d, in, wp, out, bias, stats, part_ws, out_nchw, oscale, flags, st);
-  if (nb >= 2 && (ntiles * ((nb + 1) / 2) >= target || nb < 4)) return launch_igemm_cfg<T, 2, 1, 2, 2>(d, in, wp, out, bias, stats, part_ws, out_nchw, oscale, flags, st);
-  if (nb >= 4 && ntiles * nb < target / 2) return launch_igemm_cfg<T, 1, 1, 4, 1>(d, in, wp, out, bias, stats, part_ws, out_nchw, oscale, flags, st);
-  if (nb >= 2) return launch_igemm_cfg<T, 2, 1, 2, 2>(d, in, wp, out, bias, stats, part_ws, out_nchw, oscale, flags, st);
-  return launch_igemm_cfg<T, 1, 1, 4, 1>(d, in, wp, out, bias, stats, part_ws, out_nchw, oscale, flags, st);
+  switch (plan.form) {
+    case 0: return launch_igemm_cfg<T, 2, 2, 2, 2>(plan, d, in, wp, out, bias, stats, part_ws, out_nchw, oscale, flags, st);
+    case 1: return launch_igemm_cfg<T, 2, 1, 2, 2>(plan, d, in, wp, out, bias, stats, part_ws, out_nchw, oscale, flags, st);
+    case 3: return launch_igemm_cfg<T, 4, 1, 1, 4>(plan, d, in, wp, out, bias, stats, part_ws, out_nchw, oscale, flags, st);
+    default: return launch_igemm_cfg<T, 1, 1, 4, 1>(plan, d, in, wp, out, bias, stats, part_ws, out_nchw, oscale, flags, st);
+  }
 }
 hipError_t tfc_launch_igemm(int dt, const TfcGather& d, const void* in, const void* wp, void* out, const float* bias,
                             float* stats, float* part_ws, float* out_nchw, const float* oscale, int flags, hipStream_t st) {
-  if (dt == TFC_DT_BF16X3) return launch_igemm_t<tfc_x3_t>(d, in, wp, out, bias, stats, part_ws, out_nchw, oscale, flags, st);
-  return dt == TFC_DT_BF16 ? launch_igemm_t<bf16_t>(d, in, wp, out, bias, stats, part_ws, out_nchw, oscale, flags, st)
-                           : launch_igemm_t<float>(d, in, wp, out, bias, stats, part_ws, out_nchw, oscale, flags, st);
+  if (dt == TFC_DT_BF16X3) return launch_igemm_t<tfc_x3_t>(dt, d, in, wp, out, bias, stats, part_ws, out_nchw, oscale, flags, st);
+  return dt == TFC_DT_BF16 ? launch_igemm_t<bf16_t>(dt, d, in, wp, out, bias, stats, part_ws, out_nchw, oscale, flags, st)
+                           : launch_igemm_t<float>(dt, d, in, wp, out, bias, stats, part_ws, out_nchw, oscale, flags, st);
 }
 
 // fin (nullable): torch-layout destination of the gradient. When the launch can reduce its slabs straight into it (tfc_wgrad_reduce_fin_kernel),
@@ -4303,37 +4389,89 @@ static bool tfc_fin_eligible(const TfcWgradFin* fin, int npairs, int sel) {
   static const bool off = [] { const char* e = getenv("TFC_WGRAD_NO_FIN"); return e && atoi(e) != 0; }();   // A/B knob for profiling
   return fin && fin->grad && !off && fin->sn % 16 == 0 && fin->sc % 16 == 0 && npairs * sel * 4 >= 256;     // enough workgroups to fill the chip
 }
+// split-K over pixel tiles: `target` workgroups in all (one full round of resident workgroups, no half-empty tail), never more splits than tiles
+static inline int wgrad_split(int target, int npairs, int ntiles) {
+  int ns = target / npairs;
+  if (ns > ntiles) ns = ntiles;
+  return ns < 1 ? 1 : ns;
+}
+// Batch-invariant mode takes the split count from the reference batch, and a smaller batch then has fewer tiles than splits. Every split-K kernel numbers its
+// workgroups split-major (workgroup = sp * npairs + pair, tiles sp, sp + nsplit, ...), so the grid stops behind the last split that owns a tile and the
+// slabs of the rest are zero-filled: the reduce pass adds the same numbers in the same order as a full grid would have left. *run = the splits to launch.
+static hipError_t wgrad_run_splits(float4* slab, size_t wg_float4, int npairs, int nsplit, int ntiles, hipStream_t st, int* run) {
+  *run = nsplit <= ntiles ? nsplit : ntiles;
+  if (nsplit <= ntiles || !slab) return hipSuccess;
+  return hipMemsetAsync(slab + (size_t)npairs * ntiles * wg_float4, 0, (size_t)npairs * (nsplit - ntiles) * wg_float4 * sizeof(float4), st);
+}
+// the split count of one round of the bf16x3 weight gradient (np <= 512 (n-block, c-block) pairs): launcher and plan query alike
+static int wgrad_x3_nsplit(const TfcGather& d, int np, bool inv) {
+  return wgrad_split(512, np, (inv ? TFC_REF_BATCH : d.nimg) * d.tiles_y * d.tiles_x);
+}
+static bool plane_is_raster16(const TfcPlane& pl) {
+  bool raster = pl.ntaps == 16;
+  for (int t = 0; t < 16 && raster; ++t) raster = pl.tap_dy[t] == (t >> 2) && pl.tap_dx[t] == (t & 3);
+  return raster;
+}
+void tfc_plan_wgrad(int dt, const TfcGather& d, int Nn_pad, bool have_slab, bool inv, TfcConvPlan* p) {
+  *p = TfcConvPlan{};
+  p->form = -1;
+  const int nbw = (Nn_pad + 63) / 64, ncb = (d.Cin_pad + 31) / 32;
+  const int ntiles = (inv ? TFC_REF_BATCH : d.nimg) * d.tiles_y * d.tiles_x;
+  if (dt == TFC_DT_BF16X3) {                                      // rounds of at most 512 (n-block, c-block) pairs; the record is the first round's
+    const int np = nbw * ncb < 512 ? nbw * ncb : 512;
+    p->kernel = TFC_K_WGRAD_X3;
+    p->nsplit = wgrad_x3_nsplit(d, np, inv);
+    return;
+  }
+  // split-K over pixel tiles: the kernel runs 2 workgroups per CU (208 VGPRs, 60 KB LDS), so aim at exactly 512 of them --
+  // one full round, no half-empty tail, and the fewest atomic flushes
+  p->kernel = TFC_K_WGRAD;
+  p->nsplit = wgrad_split(512, nbw * ncb, ntiles);
+  // slab budget (api.hip reserves 512 workgroups x 128 KiB): a layer with more than 512 (n-block, c-block) pairs (e.g. 2048 x 1024) cannot keep
+  // one slab per workgroup -- such a layer flushes with fp32 atomics instead (slab = nullptr), it never writes past the region
+  p->atomics = !have_slab || (long long)nbw * ncb * p->nsplit > 512;
+  if (dt != TFC_DT_BF16) return;
+  bool t22 = d.plane[0].ntaps == 4 && (g_tfc_force_cfg < 0 || (g_tfc_force_cfg & 15) != 2);
+  int seen = 0;
+  for (int t = 0; t < 4 && t22; ++t) {
+    t22 = (unsigned)d.plane[0].tap_dy[t] < 2u && (unsigned)d.plane[0].tap_dx[t] < 2u;
+    seen |= 1 << (d.plane[0].tap_dy[t] * 2 + d.plane[0].tap_dx[t]);
+  }
+  if (t22 && seen == 15) {                                       // 2 x 2-tap plane: quadrant-per-wave kernel (64 n x 64 c per workgroup)
+    const int ncb2 = (d.Cin_pad + 63) / 64;
+    p->kernel = TFC_K_WGRAD22;
+    p->nsplit = wgrad_split(512, nbw * ncb2, ntiles);
+    p->atomics = !have_slab || (long long)nbw * ncb2 * p->nsplit > 512;   // same slab budget
+    return;
+  }
+  static const bool c8_off_env = [] { const char* e = getenv("TFC_WGRAD_NO_C8"); return e && atoi(e) != 0; }();   // A/B knob for profiling
+  bool ident = plane_is_raster16(d.plane[0]);
+  for (int t = 0; t < 16 && ident; ++t) ident = d.plane[0].tap_mask[t] == (1 << t);
+  if (!p->atomics && ident && !(c8_off_env && !inv) && d.Cin_pad == 8 && d.in_pitch == 8 && Nn_pad <= 64 && d.ph_n <= 1 && d.SS == 1 && d.OS == 1 &&
+      d.plane[0].hh <= TFC_MAX_HH && d.plane[0].hw <= TFC_MAX_HW && (g_tfc_force_cfg < 0 || (g_tfc_force_cfg & 15) == 15)) {
+    p->kernel = TFC_K_WGRAD_C8;
+    p->nsplit = ntiles < 512 ? ntiles : 512;                      // 2 workgroups per CU, 32 KB of slab each
+  }
+}
 template <typename T>
-static hipError_t launch_wgrad_t(const TfcGather& d, const void* dO, const void* in, float* dwacc, float4* slab, int Nn_pad, int Nn_real,
+static hipError_t launch_wgrad_t(int dt, const TfcGather& d, const void* dO, const void* in, float* dwacc, float4* slab, int Nn_pad, int Nn_real,
                                  int Cw_real, hipStream_t st, TfcWgradFin* fin) {
   constexpr int ES = sizeof(T);
   const int nbw = (Nn_pad + 63) / 64, ncb = (d.Cin_pad + 31) / 32;
   const int ntiles = d.nimg * d.tiles_y * d.tiles_x;
-  // split-K over pixel tiles: the kernel runs 2 workgroups per CU (208 VGPRs, 60 KB LDS), so aim at exactly 512 of them --
-  // one full round, no half-empty tail, and the fewest atomic flushes
-  int nsplit = 512 / (nbw * ncb);
-  if (nsplit > ntiles) nsplit = ntiles;
-  if (nsplit < 1) nsplit = 1;
-  // slab budget (api.hip reserves 512 workgroups x 128 KiB): a layer with more than 512 (n-block, c-block) pairs (e.g. 2048 x 1024) cannot keep
-  // one slab per workgroup -- such a layer flushes with fp32 atomics instead (slab = nullptr), it never writes past the region
-  if (slab && (long long)nbw * ncb * nsplit > 512) slab = nullptr;
+  TfcConvPlan plan;
+  tfc_plan_wgrad(dt, d, Nn_pad, slab != nullptr, g_tfc_batch_invariant != 0, &plan);
+  const int nsplit = plan.nsplit;
+  if (plan.atomics) slab = nullptr;
   const int lds = (2 * 128 * 32 * ES + TFC_MAX_HH * TFC_MAX_HW * 32 * ES) * (ES == 2 ? 2 : 1);
-  const dim3 grid(nbw * ncb * nsplit);
   if constexpr (ES == 2) {
-    bool t22 = d.plane[0].ntaps == 4 && (g_tfc_force_cfg < 0 || (g_tfc_force_cfg & 15) != 2);
-    int seen = 0;
-    for (int t = 0; t < 4 && t22; ++t) {
-      t22 = (unsigned)d.plane[0].tap_dy[t] < 2u && (unsigned)d.plane[0].tap_dx[t] < 2u;
-      seen |= 1 << (d.plane[0].tap_dy[t] * 2 + d.plane[0].tap_dx[t]);
-    }
-    if (t22 && seen == 15) {                                     // 2 x 2-tap plane: quadrant-per-wave kernel (64 n x 64 c per workgroup)
+    if (plan.kernel == TFC_K_WGRAD22) {                          // 2 x 2-tap plane: quadrant-per-wave kernel (64 n x 64 c per workgroup)
       const int ncb2 = (d.Cin_pad + 63) / 64;
-      int ns = 512 / (nbw * ncb2);
-      if (ns > ntiles) ns = ntiles;
-      if (ns < 1) ns = 1;
-      if (slab && (long long)nbw * ncb2 * ns > 512) slab = nullptr;   // same slab budget as below
+      const int ns = nsplit;
+      int run = 0;
+      if (hipError_t e = wgrad_run_splits(slab, 4 * 4 * 4 * 64, nbw * ncb2, ns, ntiles, st, &run)) return e;
       const int lds22 = 2 * (2 * 128 * 64 + 2 * d.plane[0].hh * d.plane[0].hw * 64);
-      TFC_LAUNCH((tfc_wgrad22_kernel<T>), dim3(nbw * ncb2 * ns), dim3(256), lds22, st, d, (const T*)dO, (const T*)in, dwacc, slab,
+      TFC_LAUNCH((tfc_wgrad22_kernel<T>), dim3(nbw * ncb2 * run), dim3(256), lds22, st, d, (const T*)dO, (const T*)in, dwacc, slab,
                          Nn_pad, Nn_real, Cw_real, nbw, ncb2, ns);
       if (slab)
         TFC_LAUNCH(tfc_wgrad_reduce_kernel, dim3(nbw * ncb2 * 4 * 4 * 4), dim3(256), 0, st, slab, dwacc, d.plane[0], 1, 4, ns, nbw * ncb2,
@@ -4342,16 +4480,13 @@ static hipError_t launch_wgrad_t(const TfcGather& d, const void* dO, const void*
     }
   }
   const int tpw = (d.plane[0].ntaps + 3) / 4;                    // taps per wave (tap t belongs to wave t % 4)
-  bool raster = (ES == 2) && d.plane[0].ntaps == 16;
-  for (int t = 0; t < 16 && raster; ++t) raster = d.plane[0].tap_dy[t] == (t >> 2) && d.plane[0].tap_dx[t] == (t & 3);
+  const bool raster = (ES == 2) && plane_is_raster16(d.plane[0]);
   if constexpr (ES == 2) {
-    static const bool c8_off = [] { const char* e = getenv("TFC_WGRAD_NO_C8"); return e && atoi(e) != 0; }();   // A/B knob for profiling
-    bool ident = raster;
-    for (int t = 0; t < 16 && ident; ++t) ident = d.plane[0].tap_mask[t] == (1 << t);
-    if (slab && ident && !c8_off && d.Cin_pad == 8 && d.in_pitch == 8 && Nn_pad <= 64 && d.ph_n <= 1 && d.SS == 1 && d.OS == 1 &&
-        d.plane[0].hh <= TFC_MAX_HH && d.plane[0].hw <= TFC_MAX_HW && (g_tfc_force_cfg < 0 || (g_tfc_force_cfg & 15) == 15)) {
-      const int ns = ntiles < 512 ? ntiles : 512;                 // 2 workgroups per CU, 32 KB of slab each
-      TFC_LAUNCH(tfc_wgrad_c8_kernel, dim3(ns), dim3(256), 0, st, d, (const bf16_t*)dO, (const bf16_t*)in, slab, Nn_pad, ns);
+    if (plan.kernel == TFC_K_WGRAD_C8) {
+      const int ns = nsplit;
+      int run = 0;
+      if (hipError_t e = wgrad_run_splits(slab, 4 * 2 * 4 * 64, 1, ns, ntiles, st, &run)) return e;
+      TFC_LAUNCH(tfc_wgrad_c8_kernel, dim3(run), dim3(256), 0, st, d, (const bf16_t*)dO, (const bf16_t*)in, slab, Nn_pad, ns);
       const bool direct = fin && fin->grad;
       TFC_LAUNCH(tfc_wgrad_c8_reduce_kernel, dim3(128), dim3(256), 0, st, slab, dwacc, ns, Nn_real, Cw_real, direct ? fin->grad : nullptr,
                  direct ? fin->sn : 0, direct ? fin->sc : 0, direct ? fin->accumulate : 0);
@@ -4359,11 +4494,15 @@ static hipError_t launch_wgrad_t(const TfcGather& d, const void* dO, const void*
       return hipGetLastError();
     }
   }
+  int tw = 4;
+  if (!raster) tw = tpw <= 1 ? 1 : (tpw >= 4 ? 4 : tpw);
+  int run = 0;
+  if (hipError_t e = wgrad_run_splits(slab, (size_t)4 * tw * 2 * 4 * 64, nbw * ncb, nsplit, ntiles, st, &run)) return e;
+  const dim3 grid(nbw * ncb * run);
 #define TFC_WG(TPW_, R_) TFC_LAUNCH((tfc_wgrad_kernel<T, TPW_, R_>), grid, dim3(256), lds, st, d, (const T*)dO, (const T*)in, dwacc, slab, \
                                             Nn_pad, Nn_real, Cw_real, nbw, ncb, nsplit)
-  int tw = 4;
   if (raster) TFC_WG(4, true);
-  else if (tpw <= 1) { tw = 1; TFC_WG(1, false); } else if (tpw == 2) { tw = 2; TFC_WG(2, false); } else if (tpw == 3) { tw = 3; TFC_WG(3, false); } else TFC_WG(4, false);
+  else if (tw == 1) TFC_WG(1, false); else if (tw == 2) TFC_WG(2, false); else if (tw == 3) TFC_WG(3, false); else TFC_WG(4, false);
 #undef TFC_WG
   bool ident = raster;                                           // identity tap masks: tap t IS filter slot t
   for (int t = 0; t < 16 && ident; ++t) ident = d.plane[0].tap_mask[t] == (1 << t);
@@ -4380,13 +4519,10 @@ static hipError_t launch_wgrad_t(const TfcGather& d, const void* dO, const void*
 hipError_t tfc_launch_first_block_bwd(const TfcGather& d, const void* yact, int y_pitch, const void* dyp, int dyp_pitch, int Ho, int Wo, const void* in,
                                       void* slab, float* dwacc, float* rstats, float* part_ws, float slope, int Nn_real, int Cw_real,
                                       const unsigned char* sign_mask, TfcWgradFin* fin, hipStream_t st) {
-  // wpi workgroups per image, each with `per` consecutive tiles of that image: about 512 workgroups in all (2 per CU), at most 2048 (32 KB of slab each)
-  const int tpi = d.tiles_y * d.tiles_x;
-  int wpi = 512 / d.nimg;
-  if (wpi < 1) wpi = 1;
-  if (wpi > tpi) wpi = tpi;
-  const int per = (tpi + wpi - 1) / wpi;
-  wpi = (tpi + per - 1) / per;
+  TfcConvPlan plan;                                               // wpi workgroups per image, each with `per` consecutive tiles of that image
+  tfc_plan_first_block(2, d.nimg, d.IH, d.IW, tfc_num_cus(), g_tfc_batch_invariant != 0, &plan);
+  if (d.tiles_y * d.tiles_x > plan.wpi * plan.per) return hipErrorInvalidValue;
+  const int wpi = plan.wpi, per = plan.per;
   const int ns = d.nimg * wpi;
   if (ns > 2048 || (rstats && (!part_ws || (long long)ns * 64 > (long long)TFC_PART_WS_FLOATS))) return hipErrorInvalidValue;
   const char* valu_env = getenv("TFC_FIRST_BWD_VALU");            // A/B knob (read per call: the tests compare the two forms in one process)
@@ -4405,58 +4541,81 @@ hipError_t tfc_launch_first_block_bwd(const TfcGather& d, const void* yact, int 
   if (rstats) return tfc_launch_part_reduce(part_ws, rstats, d.nimg, wpi, 64, st);   // rstats[img][64] += the image's workgroup slots, in order
   return hipGetLastError();
 }
-// transposed convolution / upsample conv, bf16: all four phases in one launch; false = not applicable (caller falls back to per-phase launches)
-bool tfc_launch_wgrad_phases_fused(int up, const void* x, int N, int IH, int IW, int x_pitch, int Cin_pad, const void* dy, int dy_pitch, int Cout,
-                                   int Cin, float* dwacc, void* slab, hipStream_t st, hipError_t* err, TfcWgradFin* fin) {
+// transposed convolution / upsample conv, bf16, all four phases in one launch: kernel and split count; false = not applicable
+bool tfc_plan_wgrad_phases(int up, int N, int IH, int IW, int x_pitch, int Cin_pad, int Cout, bool have_fin, bool inv, TfcConvPlan* p) {
+  *p = TfcConvPlan{};
+  p->form = -1;
   if (g_tfc_force_cfg >= 0 && (g_tfc_force_cfg & 15) == 2) return false;   // tests: keep the per-phase kernels reachable
   const int Nn_pad = (Cout + 7) / 8 * 8;
   const int nbw = (Nn_pad + 31) / 32, ncb = (Cin_pad + 31) / 32;
-  const int ntiles = N * ((IH + TFC_TILE_H - 1) / TFC_TILE_H) * ((IW + TFC_TILE_W - 1) / TFC_TILE_W);
+  const int ntiles = (inv ? TFC_REF_BATCH : N) * ((IH + TFC_TILE_H - 1) / TFC_TILE_H) * ((IW + TFC_TILE_W - 1) / TFC_TILE_W);
   const int T = up ? 9 : 4;                                       // accumulator tiles per wave
   const size_t blk_bytes = (size_t)4 * T * 4 * 64 * 16;           // slab bytes per workgroup
-  int nsplit = (up ? 512 : 768) / (nbw * ncb);                    // 2 / 3 workgroups per CU (44 KB LDS; <= 256 / 168 VGPRs)
   const size_t budget = (size_t)512 * 4 * 8 * 4 * 64 * 16;        // slab bytes api.hip reserves
   if ((size_t)nbw * ncb * blk_bytes > budget) return false;
-  if ((size_t)nbw * ncb * nsplit * blk_bytes > budget) nsplit = (int)(budget / ((size_t)nbw * ncb * blk_bytes));
-  if (nsplit > ntiles) nsplit = ntiles;
-  if (nsplit < 1) nsplit = 1;
-  const int lds = 4 * 128 * 64 + (TFC_TILE_H + 2) * (TFC_TILE_W + 2) * 64;
-  const dim3 grid(nbw * ncb * nsplit);
-  TfcPlane none{};
-  static const bool head_off = [] { const char* e = getenv("TFC_WGRAD_NO_HEAD"); return e && atoi(e) != 0; }();   // A/B knob for profiling
-  if (up && !head_off && Cin_pad == 128 && Nn_pad == 8 && x_pitch >= 128) {   // the generator head: phases x padded channels = one 32-row tile
+  static const bool head_off_env = [] { const char* e = getenv("TFC_WGRAD_NO_HEAD"); return e && atoi(e) != 0; }();   // A/B knob for profiling
+  if (up && !(head_off_env && !inv) && Cin_pad == 128 && Nn_pad == 8 && x_pitch >= 128) {   // the generator head: phases x padded channels = one 32-row tile
+    if (!have_fin) return false;                                  // the head's own finish pass writes the torch-layout gradient
     const size_t wg_bytes = (size_t)9216 * 16;
     int ns = (int)(budget / wg_bytes);
     if (ns > 512) ns = 512;
     if (ns > ntiles) ns = ntiles;
-    if (!fin || !fin->grad || fin->sn % 4 != 0 || fin->sc % 4 != 0) return false;   // the head's own finish pass writes the torch-layout gradient
-    TFC_LAUNCH(tfc_wgrad_head_kernel, dim3(ns), dim3(256), 0, st, (const bf16_t*)x, IH, IW, x_pitch, (const bf16_t*)dy, dy_pitch, N, (float4*)slab, ns);
-    TFC_LAUNCH(tfc_wgrad_head_reduce_kernel, dim3(576), dim3(256), 0, st, (float4*)slab, ns);
+    p->kernel = TFC_K_WGRAD_HEAD;
+    p->nsplit = ns;
+    return true;
+  }
+  int target = up ? 512 : 768, npairs = nbw * ncb;                // 2 / 3 workgroups per CU (44 KB LDS; <= 256 / 168 VGPRs)
+  p->kernel = up ? TFC_K_WGRADT_UP : TFC_K_WGRADT;
+  static const bool narrow_env = [] { const char* e = getenv("TFC_WGRADT_NARROW"); return e && atoi(e) != 0; }();   // A/B knob: the 32 x 32 workgroup tile
+  if (!up && !(narrow_env && !inv) && ncb % 2 == 0 && ncb >= 2) {   // 32 n x 64 c tiles, 2 workgroups per CU
+    p->kernel = TFC_K_WGRADT2;
+    target = 512;                                                 // (256 / 384 workgroups measured 8-9 % slower)
+    npairs = nbw * (ncb / 2);
+  }
+  int nsplit = target / npairs;
+  if ((size_t)nbw * ncb * nsplit * blk_bytes > budget) nsplit = (int)(budget / ((size_t)nbw * ncb * blk_bytes));
+  if (nsplit > ntiles) nsplit = ntiles;
+  p->nsplit = nsplit < 1 ? 1 : nsplit;
+  return true;
+}
+bool tfc_launch_wgrad_phases_fused(int up, const void* x, int N, int IH, int IW, int x_pitch, int Cin_pad, const void* dy, int dy_pitch, int Cout,
+                                   int Cin, float* dwacc, void* slab, hipStream_t st, hipError_t* err, TfcWgradFin* fin) {
+  TfcConvPlan plan;
+  const bool have_fin = fin && fin->grad && fin->sn % 4 == 0 && fin->sc % 4 == 0;
+  if (!tfc_plan_wgrad_phases(up, N, IH, IW, x_pitch, Cin_pad, Cout, have_fin, g_tfc_batch_invariant != 0, &plan)) return false;
+  const int Nn_pad = (Cout + 7) / 8 * 8;
+  const int nbw = (Nn_pad + 31) / 32, ncb = (Cin_pad + 31) / 32;
+  const int ntiles = N * ((IH + TFC_TILE_H - 1) / TFC_TILE_H) * ((IW + TFC_TILE_W - 1) / TFC_TILE_W);
+  const int T = up ? 9 : 4;                                       // accumulator tiles per wave
+  const int nsplit = plan.nsplit;
+  const int lds = 4 * 128 * 64 + (TFC_TILE_H + 2) * (TFC_TILE_W + 2) * 64;
+  TfcPlane none{};
+  if (plan.kernel == TFC_K_WGRAD_HEAD) {
+    int run = 0;
+    if ((*err = wgrad_run_splits((float4*)slab, 9216, 1, nsplit, ntiles, st, &run)) != hipSuccess) return true;
+    TFC_LAUNCH(tfc_wgrad_head_kernel, dim3(run), dim3(256), 0, st, (const bf16_t*)x, IH, IW, x_pitch, (const bf16_t*)dy, dy_pitch, N, (float4*)slab, nsplit);
+    TFC_LAUNCH(tfc_wgrad_head_reduce_kernel, dim3(576), dim3(256), 0, st, (float4*)slab, nsplit);
     TFC_LAUNCH(tfc_wgrad_head_finish_kernel, dim3((Cout * Cin + 255) / 256), dim3(256), 0, st, (const float4*)slab, fin->grad, Cout, Cin, fin->sn, fin->sc,
                fin->accumulate);
     fin->done = true;
     *err = hipGetLastError();
     return true;
   }
+  int run = 0;
+  if ((*err = wgrad_run_splits((float4*)slab, (size_t)4 * T * 4 * 64, nbw * ncb, nsplit, ntiles, st, &run)) != hipSuccess) return true;
   if (up) {
-    TFC_LAUNCH(tfc_wgradT_kernel<true>, grid, dim3(256), lds, st, (const bf16_t*)x, IH, IW, x_pitch, Cin_pad, (const bf16_t*)dy, dy_pitch,
+    TFC_LAUNCH(tfc_wgradT_kernel<true>, dim3(nbw * ncb * run), dim3(256), lds, st, (const bf16_t*)x, IH, IW, x_pitch, Cin_pad, (const bf16_t*)dy, dy_pitch,
                        Nn_pad, N, (float4*)slab, nbw, ncb, nsplit);
     for (int wv = 0; wv < 4; ++wv)                                // the phases overlap on the filter taps: one reduce pass per phase, in order
       TFC_LAUNCH(tfc_wgrad_reduce_kernel, dim3(nbw * ncb * T * 4), dim3(256), 0, st, (const float4*)slab, dwacc, none, 3, T, nsplit,
                          nbw * ncb, ncb, Cout, Cin, wv);
   } else {
-    static const bool narrow = [] { const char* e = getenv("TFC_WGRADT_NARROW"); return e && atoi(e) != 0; }();   // A/B knob: the 32 x 32 workgroup tile
-    if (!narrow && ncb % 2 == 0 && ncb >= 2) {                    // 32 n x 64 c tiles, 2 workgroups per CU
-      int ns2 = 512 / (nbw * (ncb / 2));                           // (256 / 384 workgroups measured 8-9 % slower)
-      if ((size_t)nbw * ncb * ns2 * blk_bytes > budget) ns2 = (int)(budget / ((size_t)nbw * ncb * blk_bytes));
-      if (ns2 > ntiles) ns2 = ntiles;
-      if (ns2 < 1) ns2 = 1;
-      nsplit = ns2;
-      TFC_LAUNCH(tfc_wgradT2_kernel, dim3(nbw * (ncb / 2) * nsplit), dim3(256), 4 * 128 * 64 + 2 * (TFC_TILE_H + 2) * (TFC_TILE_W + 2) * 64, st, (const bf16_t*)x, IH, IW,
+    if (plan.kernel == TFC_K_WGRADT2)                             // 32 n x 64 c tiles, 2 workgroups per CU
+      TFC_LAUNCH(tfc_wgradT2_kernel, dim3(nbw * (ncb / 2) * run), dim3(256), 4 * 128 * 64 + 2 * (TFC_TILE_H + 2) * (TFC_TILE_W + 2) * 64, st, (const bf16_t*)x, IH, IW,
                  x_pitch, Cin_pad, (const bf16_t*)dy, dy_pitch, Nn_pad, N, (float4*)slab, nbw, ncb, nsplit);
-    } else
-    TFC_LAUNCH(tfc_wgradT_kernel<false>, grid, dim3(256), lds, st, (const bf16_t*)x, IH, IW, x_pitch, Cin_pad, (const bf16_t*)dy, dy_pitch,
-                       Nn_pad, N, (float4*)slab, nbw, ncb, nsplit);
+    else
+      TFC_LAUNCH(tfc_wgradT_kernel<false>, dim3(nbw * ncb * run), dim3(256), lds, st, (const bf16_t*)x, IH, IW, x_pitch, Cin_pad, (const bf16_t*)dy, dy_pitch,
+                         Nn_pad, N, (float4*)slab, nbw, ncb, nsplit);
     if (tfc_fin_eligible(fin, nbw * ncb, 4)) {
       TFC_LAUNCH(tfc_wgrad_reduce_fin_kernel, dim3(nbw * ncb * 4 * 4), dim3(512), 0, st, (const float4*)slab, fin->grad, 2, T, nsplit, nbw * ncb, ncb,
                  Cout, Cin, fin->sn, fin->sc, fin->accumulate);
@@ -4476,17 +4635,16 @@ static hipError_t launch_wgrad_x3(const TfcGather& d, const void* dO, const void
   const int nbw = (Nn_pad + 63) / 64, ncb = (d.Cin_pad + 31) / 32;
   const int ntiles = d.nimg * d.tiles_y * d.tiles_x;
   const int tpw = (d.plane[0].ntaps + 3) / 4;
-  bool raster = d.plane[0].ntaps == 16;
-  for (int t = 0; t < 16 && raster; ++t) raster = d.plane[0].tap_dy[t] == (t >> 2) && d.plane[0].tap_dx[t] == (t & 3);
+  const bool raster = plane_is_raster16(d.plane[0]);
   const int tw = raster ? 4 : (tpw < 1 ? 1 : tpw);
   const int lds = 2 * (2 * 128 * 64 + TFC_MAX_HH * TFC_MAX_HW * 64);
   const int npairs_all = nbw * ncb;
   for (int p0 = 0; p0 < npairs_all; p0 += 512) {
     const int np = npairs_all - p0 < 512 ? npairs_all - p0 : 512;
-    int nsplit = 512 / np;
-    if (nsplit > ntiles) nsplit = ntiles;
-    if (nsplit < 1) nsplit = 1;
-    const dim3 grid(np * nsplit);
+    const int nsplit = wgrad_x3_nsplit(d, np, g_tfc_batch_invariant != 0);   // tfc_plan_wgrad reports the first round's
+    int run = 0;
+    if (hipError_t e = wgrad_run_splits(slab, (size_t)4 * tw * 2 * 4 * 64, np, nsplit, ntiles, st, &run)) return e;
+    const dim3 grid(np * run);
 #define TFC_WG3(TPW_, R_) TFC_LAUNCH((tfc_wgrad_x3_kernel<TPW_, R_>), grid, dim3(256), lds, st, d, (const float*)dO, (const float*)in, slab, Nn_pad, np, \
                                      ncb, nsplit, p0)
     if (raster) TFC_WG3(4, true);
@@ -4505,8 +4663,8 @@ static hipError_t launch_wgrad_x3(const TfcGather& d, const void* dO, const void
 hipError_t tfc_launch_wgrad(int dt, const TfcGather& d, const void* dO, const void* in, float* dwacc, void* slab, int Nn_pad,
                             int Nn_real, int Cw_real, hipStream_t st, TfcWgradFin* fin) {
   if (dt == TFC_DT_BF16X3) return launch_wgrad_x3(d, dO, in, dwacc, (float4*)slab, Nn_pad, Nn_real, Cw_real, st);
-  return dt == TFC_DT_BF16 ? launch_wgrad_t<bf16_t>(d, dO, in, dwacc, (float4*)slab, Nn_pad, Nn_real, Cw_real, st, fin)
-                           : launch_wgrad_t<float>(d, dO, in, dwacc, (float4*)slab, Nn_pad, Nn_real, Cw_real, st, nullptr);   // fp32 too: slabs, not atomics (deterministic)
+  return dt == TFC_DT_BF16 ? launch_wgrad_t<bf16_t>(dt, d, dO, in, dwacc, (float4*)slab, Nn_pad, Nn_real, Cw_real, st, fin)
+                           : launch_wgrad_t<float>(dt, d, dO, in, dwacc, (float4*)slab, Nn_pad, Nn_real, Cw_real, st, nullptr);   // fp32 too: slabs, not atomics (deterministic)
 }
 hipError_t tfc_launch_wgrad_finish(float* acc, float* grad, int Nn, int Cw, long long sn, long long sc,
                                    int accumulate, hipStream_t st) {

@@ -89,6 +89,33 @@ struct ActParams {
 extern thread_local int g_tfc_force_cfg;          // test hook (tfc_debug_set_igemm_config): -1 = heuristic tile choice
 extern thread_local long long g_tfc_launch_count; // kernel launches issued by the conv-class launchers on this thread (profiling join key)
 #define TFC_LAUNCH(...) do { ++g_tfc_launch_count; hipLaunchKernelGGL(__VA_ARGS__); } while (0)
+extern thread_local int g_tfc_batch_invariant;    // tfc_set_batch_invariant: launch plans from the per-image geometry alone
+
+// Launch plan of one convolution pass: what the launchers choose and what tfc_conv_plan_query reports (one decision function per family, igemm.hip).
+// Batch-invariant mode evaluates every rule at TFC_REF_BATCH images on TFC_REF_CUS compute units -- the batch and the chip the forms were tuned at.
+#define TFC_REF_BATCH 32
+#define TFC_REF_CUS 256
+enum {
+  TFC_K_IGEMM = 0, TFC_K_IGEMM2 = 1, TFC_K_IGEMM2_HALVES = 2, TFC_K_CONV_C8 = 3,                      // forward / dgrad gather GEMM
+  TFC_K_WGRAD = 10, TFC_K_WGRAD22 = 11, TFC_K_WGRAD_C8 = 12, TFC_K_WGRAD_X3 = 13,                     // weight gradient
+  TFC_K_WGRADT_UP = 14, TFC_K_WGRADT = 15, TFC_K_WGRADT2 = 16, TFC_K_WGRAD_HEAD = 17,
+  TFC_K_FIRST_FWD = 20, TFC_K_FIRST_BWD = 21                                                            // fused first block
+};
+struct TfcConvPlan {
+  int kernel;                 // TFC_K_*
+  int form;                   // tile form 0 <2,2,2,2>, 1 <2,1,2,2>, 2 <1,1,4,1>, 3 <4,1,1,4> (4: probe builds); -1 = the kernel has one form
+  int nparts;                 // partial slots per image that tfc_part_reduce_kernel adds in order (0: the pass keeps no per-image sums)
+  int nsplit;                 // split count over pixel tiles (weight gradients; 1 otherwise)
+  int wpi;                    // workgroups per image where the kernel's slot layout depends on it (first-block backward; 0 otherwise)
+  int pat;                    // compile-time tap pattern (0: table driven)
+  int atomics;                // weight gradient flushed with fp32 atomics (no slab budget for the layer)
+  int per;                    // tiles per workgroup where the kernel walks a fixed run of tiles (first-block kernels; 0 otherwise)
+};
+void tfc_plan_igemm(int dt, const TfcGather& d, int flags, int ncu, bool inv, TfcConvPlan* p);
+void tfc_plan_wgrad(int dt, const TfcGather& d, int Nn_pad, bool have_slab, bool inv, TfcConvPlan* p);
+bool tfc_plan_wgrad_phases(int up, int N, int IH, int IW, int x_pitch, int Cin_pad, int Cout, bool have_fin, bool inv, TfcConvPlan* p);
+void tfc_plan_first_block(int pass, int N, int H, int W, int ncu, bool inv, TfcConvPlan* p);
+int tfc_act_grid_cap(int N, bool inv);             // elementwise.hip: grid-stride workgroups per image of the fused activation passes
 
 // fixed-order sum of per-workgroup partials (elementwise.hip): out[g][j] += sum_p part[(g * nparts + p) * L + j]
 hipError_t tfc_launch_part_reduce(const float* part, float* out, int G, int nparts, int L, hipStream_t st);

@@ -23,7 +23,8 @@ from .ops import DT_BF16
 
 class TrainStep:
     def __init__(self, generator, discriminator, lr=2e-4, b1=0.5, b2=0.999, eps=1e-8, compute_dtype=torch.bfloat16,
-                 fft_mode="patch", seed=0, bucket_bytes=16 << 20, lambda_gan=0.5, lambda_fft=0.01, lambda_trip=1.0, d_bucket_bytes=4 << 20):
+                 fft_mode="patch", seed=0, bucket_bytes=16 << 20, lambda_gan=0.5, lambda_fft=0.01, lambda_trip=1.0, d_bucket_bytes=4 << 20,
+                 batch_invariant=None):
         dev = next(generator.parameters()).device
         if dev.type != "cuda":
             raise ops._lib.TfcError("TrainStep needs the modules on a CUDA/HIP device (no CPU fallback)")
@@ -33,6 +34,7 @@ class TrainStep:
         self.lambda_gan, self.lambda_fft, self.lambda_trip = lambda_gan, lambda_fft, lambda_trip
         self.fft_mode = fft_mode
         self.seed = seed
+        self.batch_invariant = batch_invariant                    # None: the global setting (set_batch_invariant / TFC_BATCH_INVARIANT) at each step
         self.step_no = 0
         # flat fp32 parameter / gradient / Adam buffers in backward order; module parameters become views of them, so
         # state_dict()/load_state_dict() keep working and stay in the reference's layout.
@@ -77,6 +79,10 @@ class TrainStep:
         return ops.new_act(like.N, like.H, like.W, 8, self.dt, self.dev)      # tfc_bce_relativistic writes whole 8-channel pixels (logit gradient, 7 zeros)
 
     def step(self, real_A, real_B, neg_idx=None, extra_loss_G=None, T_B=None, B_tf=None):
+        with ops.batch_invariant_scope(self.batch_invariant):     # both streams of the step launch from this thread: one setting for all of it
+            return self._step(real_A, real_B, neg_idx, extra_loss_G, T_B, B_tf)
+
+    def _step(self, real_A, real_B, neg_idx=None, extra_loss_G=None, T_B=None, B_tf=None):
         """real_A, real_B: fp32 NCHW [N,3,256,256] in [-1,1] on the GPU (this rank's shard). Returns a dict of device scalars.
         T_B [N,256,256] + B_tf [N,3,256,256] (augmented real_B) switch the gradient-free temperature term on.
         extra_loss_G(fake, real_B) -> (loss, dfake) runs on the SIDE stream beside the discriminator chain (with the triplet / FFT heads): it may use any

@@ -33,6 +33,18 @@ def get_compute_dtype():
     return _DEFAULT_DTYPE
 
 
+def set_batch_invariant(on):
+    """True: every launch choice that shapes the arithmetic of one sample (tile form, kernel variant, partial slots, split counts) comes from the layer's
+    per-image geometry alone, so a sample's activations, statistics and gradients are bit-identical whatever batch it is computed in -- one rank with 2N
+    images and two ranks with N each then differ only in how the weight gradients are summed. False (default, or TFC_BATCH_INVARIANT unset / '' / '0'):
+    the launchers choose by speed for the batch at hand. At batch 32 the two settings run the same kernels. Applies to every thread of the process."""
+    ops._lib.set_batch_invariant(on)
+
+
+def get_batch_invariant():
+    return ops._lib.get_batch_invariant()
+
+
 class BlurPool(nn.Module):
     """antialiased_cnns.BlurPool(channels, stride) stand-in (third-party, un-vendored in the reference; call sites :109,
     :123, :192): reflect pad (1,2,1,2), depthwise [1,3,3,1] x [1,3,3,1] / 64, buffer `filt` [C,1,4,4]."""

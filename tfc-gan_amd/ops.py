@@ -18,6 +18,24 @@ def lib():
     return _lib.load()
 
 
+class batch_invariant_scope:
+    """`with batch_invariant_scope(x)`: x = None leaves the process's batch-invariant setting (_lib.set_batch_invariant) alone, True / False
+    overrides it inside the block -- for every thread and stream that launches kernels meanwhile"""
+
+    def __init__(self, on):
+        self.on = on
+
+    def __enter__(self):
+        self.prev = _lib.get_batch_invariant()
+        if self.on is not None:
+            _lib.set_batch_invariant(self.on)
+
+    def __exit__(self, *exc):
+        if self.on is not None:
+            _lib.set_batch_invariant(self.prev)
+        return False
+
+
 def torch_dtype(dt):
     return torch.bfloat16 if dt == DT_BF16 else torch.float32
 

@@ -184,12 +184,13 @@ class STN21Step:
     post-accumulate hooks while the rest of the backward still runs (the reference wraps all five modules in nn.DataParallel, STN:536-540).
     Every loss of the step is a batch mean except LPIPS, a batch SUM in lpips_pytorch: it is scaled by the world size so that the rank-averaged
     gradient equals the reference's on the gathered batch. lpips: a module with the reference's call surface (tfc_gan_amd.LPIPS) or None.
-    localiser: "torch", "hip" or None (TFC_LOCALISER), passed to `Net`."""
+    localiser: "torch", "hip" or None (TFC_LOCALISER), passed to `Net`. batch_invariant: True / False, or None for the global setting."""
 
     def __init__(self, img_shape=(3, 256, 256), lpips=None, lr=2e-4, b1=0.5, b2=0.999, device="cuda:0", alpha2=0.01, eps=1e-8, bucket_bytes=32 << 20,
-                 seed=0, localiser=None):
+                 seed=0, localiser=None, batch_invariant=None):
         from . import ops, parallel
         _refuse_bf16x3()
+        self.batch_invariant = batch_invariant                    # None: the global setting (set_batch_invariant / TFC_BATCH_INVARIANT) at each step
         dev = torch.device(device)
         self.dev = dev
         self.G1, self.G2 = GeneratorUNet(img_shape).to(dev), GeneratorUNet(img_shape).to(dev)
@@ -248,6 +249,11 @@ class STN21Step:
                 p.requires_grad_(on)
 
     def step(self, real_A, real_B):
+        from . import ops
+        with ops.batch_invariant_scope(self.batch_invariant):     # covers autograd's backward threads too: the setting is process-wide (_lib.load)
+            return self._step(real_A, real_B)
+
+    def _step(self, real_A, real_B):
         _refuse_bf16x3()
         from . import ops, parallel
         valid, fake_t = 0.9, 0.0                                  # STN:613-615
