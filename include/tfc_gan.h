@@ -116,7 +116,9 @@ int tfc_conv_dgrad(void* stream, int dt, int op, const void* dy, int dy_pitch, i
                    const void* packed, void* dx, int dx_pitch, const float* oscale, int flags);
 /* ---- weight gradient: dw (torch layout, fp32) = or += x (*) dy ; ws: tfc_conv_wgrad_ws_bytes() of scratch = [64 MiB of split-K
  *      slabs | fp32 accumulator]. Zero it once after allocation: the accumulator part must be ALL ZERO on entry and is left all
- *      zero on return (the slab part is scratch). One buffer sized for the largest layer may be shared by every layer. ------- */
+ *      zero on return (the slab part is scratch). One buffer sized for the largest layer may be shared by every layer. The slabs
+ *      hold the partial sums of 512 workgroups in every compute mode; a layer with more (output-block, input-block) pairs than that
+ *      runs in rounds of 512 pairs, each added to the accumulator in a fixed order before the next reuses the slabs. ------------ */
 size_t tfc_conv_wgrad_ws_bytes(int op, int Cin, int Cout);
 int tfc_conv_wgrad(void* stream, int dt, int op, const void* x, int x_pitch, const void* dy, int dy_pitch, int N, int H, int W,
                    int Cin, int Cout, void* ws, float* dw, int accumulate);
@@ -368,8 +370,8 @@ int tfc_get_batch_invariant(void);
 /* Host only, launches nothing, works without a GPU: what the launchers of (dt, op, pass: 0 forward, 1 dgrad, 2 wgrad) would choose on a chip of `ncu`
  * compute units (256 on the MI355X), under the calling thread's batch-invariant setting. flags: the TFC_EP_* bits of the call, | TFC_PLAN_FIRST_BLOCK
  * for the fused first-block kernels (pass 0 / 2). Writes min(n, 8) ints -- kernel id, tile form (0: 128 px x 128 ch in 2 x 2 waves, 1: x 64, 2: x 32,
- * 3: 128 x 128 in 4 n-waves, -1: none), partial slots per image, split count, workgroups per image, tap pattern, fp32-atomic flush, tiles per workgroup --
- * and returns 8, or a negative error. */
+ * 3: 128 x 128 in 4 n-waves, -1: none), partial slots per image, split count (of the first round where a weight gradient runs in several), workgroups per image, tap pattern, 0 (reserved:
+ * once "flushed with float atomics", which no weight gradient does any more), tiles per workgroup -- and returns 8, or a negative error. */
 #define TFC_PLAN_FIRST_BLOCK 0x10000
 int tfc_conv_plan_query(int dt, int op, int pass, int N, int H, int W, int Cin, int Cout, int flags, int ncu, int* out, int n);
 /* device probe of the MFMA / transposing-read lane maps the kernels rely on (writes 3*64*16 floats) */

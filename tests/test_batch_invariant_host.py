@@ -101,6 +101,19 @@ def test_plans_do_depend_on_batch_when_off(lib):
     assert fwd_or_dgrad                                            # not only split counts of weight gradients: the per-sample arithmetic moves
 
 
+@pytest.mark.parametrize("dt,kernel", [(_lib.DT_BF16, 10), (_lib.DT_F32, 10), (_lib.DT_BF16X3, 13)], ids=["bf16", "fp32", "bf16x3"])
+def test_weight_gradient_above_the_slab_budget_plans_rounds_not_atomics(lib, dt, kernel):
+    """1056 -> 1024 channels are 33 x 16 = 528 (n-block, c-block) pairs, more than the 512 split-K slabs: the layer runs in rounds of 512 pairs in every
+    compute mode. The record is the first round's (512 pairs over the 4 one-tile images of batch 4: split 1), and slot 6, once "flushed with float
+    atomics", is 0. The 2 x 2-tap kernel (TFC_K_WGRAD22 = 11; a transposed convolution too wide for the phase-fused kernels) does the same."""
+    T.set_batch_invariant(False)
+    lib = _lib.load()
+    rec = query(lib, ("conv4x4-rounds", dt, _lib.OP_CONV, 2, 8, 8, 1056, 1024, 0), 4)
+    assert (rec[0], rec[3], rec[6]) == (kernel, 1, 0), rec
+    rec = query(lib, ("convT2x2-rounds", dt, _lib.OP_CONVT, 2, 4, 4, 2112, 1024, 0), 4)
+    assert (rec[0], rec[3], rec[6]) == (11 if dt == _lib.DT_BF16 else kernel, 1, 0), rec
+
+
 @pytest.mark.parametrize("case", PLAN_CASES, ids=[c[0] for c in PLAN_CASES])
 def test_reference_batch_keeps_its_tuned_plan(lib, case):
     T.set_batch_invariant(False)

@@ -1,6 +1,8 @@
 """GPU parity tests, kernel level: every HIP entry point of include/tfc_gan.h against the CPU oracle / torch-CPU fp32 on the
 same seeded inputs.  fp32 mode (TFC_DT_F32) must agree to fp32 round-off; bf16 mode is compared against the same
 computation done on bf16-rounded operands, with a tolerance of a few bf16 ulps of the result scale (stated per test)."""
+import functools
+
 import numpy as np
 import pytest
 import torch
@@ -10,6 +12,8 @@ import tfc_gan_amd as T
 from oracle import tfcgan_oracle as O
 from tfc_gan_amd import _lib, ops
 from tfc_gan_amd.ops import DT_BF16, DT_F32, View
+
+from tests import conv_exact as X
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -248,6 +252,48 @@ def test_first_layer_weights_stationary_kernel(N, H, W, Cin, Cout, with_bias):
     assert (dw.cpu() - gw).abs().max().item() <= wtol
     ops.conv_wgrad(dt, ops.OP_CONV, to_view(x, dt), to_view(go, dt), Cin, Cout, dw, accumulate=True)
     assert (dw.cpu() - 2 * gw).abs().max().item() <= 2 * wtol
+
+
+# form -> (op, input H = W, Cin, Cout), batch 4: the smallest layers with more (n-block, c-block) pairs than the 512 split-K slabs.
+#   conv4x4:  16 x 33 = 528 pairs of tfc_wgrad_kernel (8 x 8 input, 7 x 7 output = one pixel tile per image);
+#   convT2x2: too wide for the phase-fused kernels, so each sub-pixel phase is a 2 x 2-tap plane: 16 x 33 = 528 pairs of tfc_wgrad22_kernel in bf16
+#             (16 x 66 = 1056 pairs, three rounds, of tfc_wgrad_kernel in fp32 / bf16x3).
+# Round 1 (512 pairs) runs with split 1, the last round (16 / 32 pairs) with split 4: both split counts and the pair offset are exercised.
+ROUNDS_CASES = {"conv4x4": (ops.OP_CONV, 8, 1056, 1024), "convT2x2": (ops.OP_CONVT, 4, 2112, 1024)}
+ROUNDS_N = 4
+
+
+@functools.lru_cache(maxsize=None)
+def rounds_reference(form):
+    """exact-integer operands (tests/conv_exact.py) and the float64 weight gradient, computed once per form and shared by the compute modes"""
+    op, H, Cin, Cout = ROUNDS_CASES[form]
+    OH = ops.OUT_HW[op](H)
+    x = X.ints((ROUNDS_N, Cin, H, H), 4100 + op)
+    dy = X.ints((ROUNDS_N, Cout, OH, OH), 4200 + op)
+    want = X.ref_dw(op, x, (Cin, Cout, 4, 4) if op == ops.OP_CONVT else (Cout, Cin, 4, 4), dy)
+    X.assert_dyadic(want, 1, form)                                 # |sum| <= 4 images x 49 pixels, far below 2^24: every mode must be exact
+    return x, dy, want
+
+
+@pytest.mark.parametrize("dt", [DT_BF16, DT_F32, _lib.DT_BF16X3], ids=["bf16", "fp32", "bf16x3"])
+@pytest.mark.parametrize("form", list(ROUNDS_CASES))
+def test_wgrad_runs_in_rounds_above_the_slab_budget(form, dt):
+    """A weight gradient with more than 512 (n-block, c-block) pairs runs in rounds of 512 pairs, each reduced in a fixed order before the next reuses
+    the slabs -- in every compute mode, never float atomics: exact against float64 on integer operands, the same bits on a second call, and
+    accumulate=True doubles them exactly."""
+    op, H, Cin, Cout = ROUNDS_CASES[form]
+    x, dy, want = rounds_reference(form)
+    xv, dyv = X.to_view(x.to(DEV), dt), X.to_view(dy.to(DEV), dt)
+    dw = torch.full(tuple(want.shape), 3.0, dtype=torch.float32, device=DEV)
+    ws = ops.conv_wgrad(dt, op, xv, dyv, Cin, Cout, dw)
+    first = dw.clone()
+    X.assert_exact(first.cpu().double(), want, f"{form} weight gradient", X.WGT_DIMS)
+    dw.fill_(-7.0)
+    ops.conv_wgrad(dt, op, xv, dyv, Cin, Cout, dw, ws=ws)
+    assert torch.equal(dw, first), "second call: different bits"
+    ops.conv_wgrad(dt, op, xv, dyv, Cin, Cout, dw, accumulate=True, ws=ws)
+    assert torch.equal(dw, 2 * first), "accumulate=True does not double the gradient exactly"
+    assert not X.ws_accumulator(ws).any(), "the accumulator part of the workspace is not left all-zero"
 
 
 @pytest.mark.parametrize("valu", [True, False])

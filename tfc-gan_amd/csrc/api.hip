@@ -1156,7 +1156,7 @@ extern "C" int tfc_conv_plan_query(int dt, int op, int pass, int N, int H, int W
     bool fused = false;
     if ((op == TFC_OP_CONVT || op == TFC_OP_UPCONV) && dt == TFC_DT_BF16)
       fused = tfc_plan_wgrad_phases(op == TFC_OP_UPCONV, N, H, W, pad8(Cin), pad8(Cin), Cout, wm.sn % 4 == 0 && wm.sc % 4 == 0, inv, &p);
-    if (!fused) tfc_plan_wgrad(dt, d, pad8(Cout), true, inv, &p);
+    if (!fused) tfc_plan_wgrad(dt, d, pad8(Cout), inv, &p, 0);
   } else {
     TfcGather d;
     if (int e = build_desc(op, pass, 0, N, H, W, Cin, Cout, pass ? pad8(Cout) : pad8(Cin), pass ? pad8(Cin) : pad8(Cout), &d, nullptr)) return e;
@@ -1165,7 +1165,7 @@ extern "C" int tfc_conv_plan_query(int dt, int op, int pass, int N, int H, int W
     tfc_plan_igemm(dt, d, flags & 0xffff, ncu, inv, &p);
     if (!(flags & TFC_EP_STATS)) p.nparts = 0;
   }
-  const int rec[8] = {p.kernel, p.form, p.nparts, p.nsplit, p.wpi, p.pat, p.atomics, p.per};
+  const int rec[8] = {p.kernel, p.form, p.nparts, p.nsplit, p.wpi, p.pat, 0, p.per};   // slot 6 (once: flushed with float atomics) is always 0
   for (int i = 0; i < n && i < 8; ++i) out[i] = rec[i];
   return 8;
 }

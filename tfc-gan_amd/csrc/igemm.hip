@@ -17,7 +17,7 @@
 //   * bf16 uses v_mfma_f32_32x32x16_bf16, fp32 (parity mode) uses v_mfma_f32_32x32x2_f32 on the same
 //     byte geometry (a 16-byte unit = 8 bf16 = 4 fp32 channels); bf16x3 (T = tfc_x3_t) keeps the fp32 geometry with each
 //     unit split into bf16 hi / lo where it is staged or packed, and runs three v_mfma_f32_32x32x16_bf16 per two k-substeps;
-//   * epilogue fuses bias, InstanceNorm statistics (wave-shuffle + fp32 atomics), skip-gradient
+//   * epilogue fuses bias, InstanceNorm statistics (per-tile sums in fixed LDS / partial slots, added in a fixed order), skip-gradient
 //     accumulation, and tanh + NCHW store for the generator head.
 #include <cstdlib>
 #include <type_traits>
@@ -1657,16 +1657,88 @@ hipError_t tfc_launch_dgrad_head(const void* dy, int dy_pitch, int N, int H, int
 }
 
 // ---------------------------------------------------------------------------------------------------
+// Shared pieces of the weight-gradient family (the GEMM kernels and their split-K reductions below).
+// ---------------------------------------------------------------------------------------------------
+// Transposing 8 x bf16 fragment read (ds_read_b64_tr_b16 twice) from a K(pixel)-strided LDS matrix: p = the lane's address (tfc_tr_lane) in the
+// fragment's first row, rowb4 = bytes from row r to row r + 4.
+__device__ __forceinline__ uint4 tfc_tr16(const unsigned char* p, int rowb4) {
+  s16x4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16(LDS_PTR(s16x4_t, p));
+  s16x4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16(LDS_PTR(s16x4_t, p + rowb4));
+  uint4 r;
+  r.x = (uint16_t)lo[0] | ((uint32_t)(uint16_t)lo[1] << 16);
+  r.y = (uint16_t)lo[2] | ((uint32_t)(uint16_t)lo[3] << 16);
+  r.z = (uint16_t)hi[0] | ((uint32_t)(uint16_t)hi[1] << 16);
+  r.w = (uint16_t)hi[2] | ((uint32_t)(uint16_t)hi[3] << 16);
+  return r;
+}
+// the lane's byte offset for tfc_tr16 in a matrix of row pitch rowb: row 8 * hk + q, 16-column block cb16, 8-byte group p
+__device__ __forceinline__ int tfc_tr_lane(int lane, int rowb) {
+  const int grp = lane >> 4, li = lane & 15;
+  const int cb16 = grp & 1, hk = grp >> 1, q = li >> 2, p = li & 3;
+  return (8 * hk + q) * rowb + cb16 * 32 + p * 8;
+}
+// pixel tile tl -> image and first (row, column) of the tile on the gather grid
+__device__ __forceinline__ void tfc_tile_decode(int tl, int tiles_x, int tiles_y, int& img, int& a0, int& b0) {
+  const int txb = tl % tiles_x; tl /= tiles_x;
+  const int tyb = tl % tiles_y;
+  img = tl / tiles_y;
+  a0 = tyb * TFC_TILE_H; b0 = txb * TFC_TILE_W;
+}
+// Split-K partial of one wave -> its part of the workgroup's slab, in register order: ps = the wave's base + lane; float4 (a * 4 + q) * 64 + lane holds
+// accumulator registers 4q..4q+3 of tile a (the layout the reduce kernels below read)
+template <int NA>
+__device__ __forceinline__ void tfc_slab_store(float4* ps, const f32x16_t (&acc)[NA]) {
+#pragma unroll
+  for (int a = 0; a < NA; ++a)
+#pragma unroll
+    for (int q4 = 0; q4 < 4; ++q4)
+      ps[(a * 4 + q4) * 64] = make_float4(acc[a][4 * q4], acc[a][4 * q4 + 1], acc[a][4 * q4 + 2], acc[a][4 * q4 + 3]);
+}
+// Fixed-order sum over the split-K slabs: the workgroup is K owners x L lanes (thread = k * L + l), a lane sums R slab positions row[r]. Owner k takes
+// the splits sp = k, k + K, ... ascending, the partials meet in LDS, and owner 0 adds those of owners 1 .. K-1 ascending. True for owner 0, whose s[]
+// holds the totals; the other owners are done.
+template <int K, int L, int R>
+__device__ __forceinline__ bool tfc_slab_sum(const float4* slab, const size_t (&row)[R], size_t split_stride, int nsplit, float4 (&s)[R]) {
+  __shared__ float4 part[K - 1][R][L];
+  constexpr int UNROLL = K == 8 ? 2 : 4;
+  const int l = threadIdx.x % L, k = threadIdx.x / L;
+#pragma unroll
+  for (int r = 0; r < R; ++r) s[r] = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll UNROLL
+  for (int sp = k; sp < nsplit; sp += K) {
+    const size_t o = (size_t)sp * split_stride;
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      const float4 v = slab[o + row[r]];
+      s[r].x += v.x; s[r].y += v.y; s[r].z += v.z; s[r].w += v.w;
+    }
+  }
+  if (k > 0) {
+#pragma unroll
+    for (int r = 0; r < R; ++r) part[k - 1][r][l] = s[r];
+  }
+  __syncthreads();
+  if (k != 0) return false;
+#pragma unroll
+  for (int i = 0; i < K - 1; ++i)
+#pragma unroll
+    for (int r = 0; r < R; ++r) { const float4 v = part[i][r][l]; s[r].x += v.x; s[r].y += v.y; s[r].z += v.z; s[r].w += v.w; }
+  return true;
+}
+// Upsample(2x nearest) -> ZeroPad(1,0,1,0) -> 4-tap filter: source offset + 1 of filter index k in the sub-pixel phase with parity bit ph
+__device__ __forceinline__ int tfc_up_src(int ph, int k) { return ph ? (k == 0 ? 0 : (k == 3 ? 2 : 1)) : (k >> 1); }
+
+// ---------------------------------------------------------------------------------------------------
 // weight-gradient GEMM for 2 x 2-tap planes (bf16): the sub-pixel phases of the transposed convolution and phase (0,0) of the
 // upsample-conv. With only four taps the generic kernel gives each wave ONE tap (3 transposing LDS reads per MFMA); here a
 // workgroup owns 64 n x 64 c and wave (nh, ch) owns the 32 n x 32 c quadrant for ALL four taps: the B fragments of halo rows
 // kt and kt+1 (column shifts 0 / 1) form a sliding register window, so a k-step costs 1 A + 2 new B fragments for 4 MFMAs
-// (1.5 reads per MFMA). Accumulator index = tap_dy * 2 + tap_dx (geometry); the flush maps it back to the filter taps.
+// (1.5 reads per MFMA). Accumulator index = tap_dy * 2 + tap_dx (geometry); the reduce pass maps it back to the filter taps.
 // ---------------------------------------------------------------------------------------------------
 template <typename T>
 __global__ void __launch_bounds__(256, 2)
-tfc_wgrad22_kernel(const TfcGather d, const T* __restrict__ dO, const T* __restrict__ in, float* dwacc, float4* slab,
-                   int Nn_pad, int Nn_real, int Cw_real, int nbw, int ncb2, int nsplit) {
+tfc_wgrad22_kernel(const TfcGather d, const T* __restrict__ dO, const T* __restrict__ in, float4* slab, int Nn_pad, int npairs, int ncb2, int nsplit,
+                   int pair0) {
   static_assert(sizeof(T) == 2, "bf16 only");
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   constexpr int ROWB = 64;                                       // 32 channels x 2 bytes per LDS pixel row
@@ -1681,8 +1753,8 @@ tfc_wgrad22_kernel(const TfcGather d, const T* __restrict__ dO, const T* __restr
   const int BUF_BYTES = DO_BYTES + 2 * HP;
 
   const int bid = tfc_xcd_remap(blockIdx.x, gridDim.x);
-  const int pair = bid % (nbw * ncb2);
-  const int sp = bid / (nbw * ncb2);
+  const int pair = pair0 + bid % npairs;                         // this launch holds the (n-block, c-block) pairs pair0 .. pair0 + npairs - 1
+  const int sp = bid / npairs;
   const int cb = pair % ncb2, nb = pair / ncb2;
   const int ntiles = d.nimg * d.tiles_y * d.tiles_x;
 
@@ -1695,11 +1767,8 @@ tfc_wgrad22_kernel(const TfcGather d, const T* __restrict__ dO, const T* __restr
   uint4 vdo[NDO], vha[NHA];
   const int nunits = pd.hh * pd.hw * 4;                          // per halo plane
   auto tile_load = [&](int tl) {
-    int t = tl;
-    const int txb = t % d.tiles_x; t /= d.tiles_x;
-    const int tyb = t % d.tiles_y;
-    const int img = t / d.tiles_y;
-    const int a0 = tyb * TFC_TILE_H, b0 = txb * TFC_TILE_W;
+    int img, a0, b0;
+    tfc_tile_decode(tl, d.tiles_x, d.tiles_y, img, a0, b0);
 #pragma unroll
     for (int i = 0; i < NDO; ++i) {
       const int idx = tid + i * 256;
@@ -1740,32 +1809,20 @@ tfc_wgrad22_kernel(const TfcGather d, const T* __restrict__ dO, const T* __restr
   };
 
   const bool active = (Nn_pad - nb * 64) > nh * 32 && (cb * 2 + ch) * 32 < d.Cin_pad;   // quadrant outside the real tensor: no MFMAs
-  const int grp = lane >> 4, li = lane & 15;
-  const int cb16 = grp & 1, hk = grp >> 1, q = li >> 2, p = li & 3;
-  const int trLane = (8 * hk + q) * ROWB + cb16 * 32 + p * 8;
-  auto tr16 = [&](const unsigned char* p0) {
-    s16x4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16(LDS_PTR(s16x4_t, p0));
-    s16x4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16(LDS_PTR(s16x4_t, p0 + 4 * ROWB));
-    uint4 r;
-    r.x = (uint16_t)lo[0] | ((uint32_t)(uint16_t)lo[1] << 16);
-    r.y = (uint16_t)lo[2] | ((uint32_t)(uint16_t)lo[3] << 16);
-    r.z = (uint16_t)hi[0] | ((uint32_t)(uint16_t)hi[1] << 16);
-    r.w = (uint16_t)hi[2] | ((uint32_t)(uint16_t)hi[3] << 16);
-    return r;
-  };
+  const int trLane = tfc_tr_lane(lane, ROWB);
   auto compute = [&](const unsigned char* buf) {
     if (!active) return;
     const unsigned char* acol = buf + nh * 128 * ROWB + trLane;
     const unsigned char* hcol = buf + DO_BYTES + ch * HP + trLane;
     const int rowb = pd.hw * ROWB;
     uint4 b0[2], b1[2];
-    b0[0] = tr16(hcol);
-    b0[1] = tr16(hcol + ROWB);
+    b0[0] = tfc_tr16(hcol, 4 * ROWB);
+    b0[1] = tfc_tr16(hcol + ROWB, 4 * ROWB);
 #pragma unroll
     for (int kt = 0; kt < 8; ++kt) {
-      b1[0] = tr16(hcol + (kt + 1) * rowb);
-      b1[1] = tr16(hcol + (kt + 1) * rowb + ROWB);
-      const uint4 a = tr16(acol + kt * 16 * ROWB);
+      b1[0] = tfc_tr16(hcol + (kt + 1) * rowb, 4 * ROWB);
+      b1[1] = tfc_tr16(hcol + (kt + 1) * rowb + ROWB, 4 * ROWB);
+      const uint4 a = tfc_tr16(acol + kt * 16 * ROWB, 4 * ROWB);
       const bf16x8_t av = __builtin_bit_cast(bf16x8_t, a);
       acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av, __builtin_bit_cast(bf16x8_t, b0[0]), acc[0], 0, 0, 0);
       acc[1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av, __builtin_bit_cast(bf16x8_t, b0[1]), acc[1], 0, 0, 0);
@@ -1789,59 +1846,76 @@ tfc_wgrad22_kernel(const TfcGather d, const T* __restrict__ dO, const T* __restr
   }
 
   if (!active) return;
-  if (slab) {                                                    // split-K partial -> this workgroup's slab, register order (see tfc_wgrad_reduce_kernel)
-    float4* ps = slab + ((size_t)bid * 4 + wave) * (4 * 4 * 64) + lane;
-#pragma unroll
-    for (int a = 0; a < 4; ++a)
-#pragma unroll
-      for (int q4 = 0; q4 < 4; ++q4)
-        ps[(a * 4 + q4) * 64] = make_float4(acc[a][4 * q4], acc[a][4 * q4 + 1], acc[a][4 * q4 + 2], acc[a][4 * q4 + 3]);
-    return;
-  }
-  const int c = (cb * 2 + ch) * 32 + (lane & 31);
-  const int hrow = lane >> 5;
-#pragma unroll
-  for (int a = 0; a < 4; ++a) {
-    int mask = 0;
-    for (int t = 0; t < 4; ++t)
-      if (pd.tap_dy[t] == (a >> 1) && pd.tap_dx[t] == (a & 1)) mask = pd.tap_mask[t];
-    for (int m = mask; m; m &= m - 1) {
-      const int slot = __ffs(m) - 1;
-#pragma unroll
-      for (int j = 0; j < 16; ++j) {
-        const int n = nb * 64 + nh * 32 + (j & 3) + 8 * (j >> 2) + 4 * hrow;
-        if (n < Nn_real && c < Cw_real) atomicAdd(&dwacc[((size_t)slot * Nn_real + n) * Cw_real + c], acc[a][j]);
-      }
-    }
-  }
+  tfc_slab_store(slab + ((size_t)bid * 4 + wave) * (4 * 4 * 64) + lane, acc);   // tfc_wgrad_reduce_kernel kind 1
 }
 
 // ---------------------------------------------------------------------------------------------------
 // weight-gradient GEMM:  dWacc[slot][n][c] += sum_pixels dO[pixel][n] * in[src(pixel, tap)][c]
 //   rows = n (64 per workgroup = 2 MFMA row blocks), cols = c (32 per workgroup), K = the 128 pixels of a tile;
 //   wave w owns taps {w*TPW .. w*TPW+TPW-1}; a workgroup walks a strided subset of the pixel tiles (split-K) and
-//   flushes with fp32 atomics (each wave-instruction adds two contiguous 128-B row segments).
-//   bf16: both operands are K(pixel)-strided in LDS, fetched with ds_read_b64_tr_b16 (hardware transpose);
-//   fp32: 32x32x2 operands are one dword per lane, plain ds_read_b32.
+//   stores its accumulators to its slab with plain 16-byte stores; tfc_wgrad_reduce_kernel (kind 0) adds the slabs in a fixed order.
+//   One kernel, three operand policies (WgradOp<T>):
+//   bf16:   both operands are K(pixel)-strided in LDS, fetched with ds_read_b64_tr_b16 (hardware transpose); double-buffered;
+//   fp32:   32x32x2 operands are one dword per lane, plain ds_read_b32;
+//   bf16x3: fp32 dO / input, split while they are staged into a hi and a lo bf16 image of the bf16 policy's LDS layout (32 channels = 64 B per
+//           pixel row), so the transposing reads and fragment maps of the bf16 form apply to each image unchanged; a fragment is a (hi, lo) pair and
+//           every (k-step, tap) issues lo*hi, hi*lo, hi*hi. The two images take the 59.5 KB of the fp32 policy's one (single-buffered like it).
+//   Policy members: ROWB = bytes per LDS row (32 channels) of one image, IMAGE = bytes of one image (dO + halo), LDS_BYTES = the launch's dynamic LDS,
+//   PREFETCH = double-buffered (the next tile is loaded while this one is multiplied), TR = fragments come from transposing reads, put = one staged
+//   16-byte unit -> LDS, frag / load / mma = one MFMA operand of a k-step, its LDS read and the multiply-accumulate.
 // ---------------------------------------------------------------------------------------------------
-template <typename T> struct WgradFrag;
+template <typename T> struct WgradOp;
+template <> struct WgradOp<bf16_t> {
+  static constexpr int ROWB = 64, IMAGE = (2 * 128 + TFC_MAX_HH * TFC_MAX_HW) * ROWB, LDS_BYTES = 2 * IMAGE;
+  static constexpr bool PREFETCH = true, TR = true;
+  typedef uint4 frag;
+  static __device__ __forceinline__ void put(unsigned char* image, int idx, const uint4& v) { *reinterpret_cast<uint4*>(image + idx * 16) = v; }
+  static __device__ __forceinline__ frag load(const unsigned char* p) { return tfc_tr16(p, 4 * ROWB); }
+  static __device__ __forceinline__ void mma(const frag& a, const frag& b, f32x16_t& c) {
+    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, a), __builtin_bit_cast(bf16x8_t, b), c, 0, 0, 0);
+  }
+};
+template <> struct WgradOp<float> {
+  static constexpr int ROWB = 128, IMAGE = (2 * 128 + TFC_MAX_HH * TFC_MAX_HW) * ROWB, LDS_BYTES = IMAGE;
+  static constexpr bool PREFETCH = false, TR = false;
+  typedef float frag;
+  static __device__ __forceinline__ void put(unsigned char* image, int idx, const uint4& v) { *reinterpret_cast<uint4*>(image + idx * 16) = v; }
+  static __device__ __forceinline__ frag load(const unsigned char* p) { return *reinterpret_cast<const float*>(p); }
+  static __device__ __forceinline__ void mma(const frag& a, const frag& b, f32x16_t& c) { c = __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0); }
+};
+template <> struct WgradOp<tfc_x3_t> {
+  static constexpr int ROWB = 64, IMAGE = (2 * 128 + TFC_MAX_HH * TFC_MAX_HW) * ROWB, LDS_BYTES = 2 * IMAGE;   // hi image at 0, lo image at IMAGE
+  static constexpr bool PREFETCH = false, TR = true;
+  struct frag { uint4 hi, lo; };
+  static __device__ __forceinline__ void put(unsigned char* image, int idx, const uint4& v) {   // fp32 unit idx (4 channels) -> 8 bytes of each image
+    const uint4 s = tfc_split_x3(v);
+    *reinterpret_cast<uint2*>(image + idx * 8) = make_uint2(s.x, s.y);
+    *reinterpret_cast<uint2*>(image + IMAGE + idx * 8) = make_uint2(s.z, s.w);
+  }
+  static __device__ __forceinline__ frag load(const unsigned char* p) { return frag{tfc_tr16(p, 4 * ROWB), tfc_tr16(p + IMAGE, 4 * ROWB)}; }
+  static __device__ __forceinline__ void mma(const frag& a, const frag& b, f32x16_t& c) {
+    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, a.lo), __builtin_bit_cast(bf16x8_t, b.hi), c, 0, 0, 0);
+    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, a.hi), __builtin_bit_cast(bf16x8_t, b.lo), c, 0, 0, 0);
+    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, a.hi), __builtin_bit_cast(bf16x8_t, b.hi), c, 0, 0, 0);
+  }
+};
 
-//   RASTER (bf16, 16 taps in 4x4 raster order): wave w owns filter COLUMN kx = w (taps ky*4 + w). The B fragment of (k-step kt,
+//   RASTER (transposing policies, 16 taps in 4x4 raster order): wave w owns filter COLUMN kx = w (taps ky*4 + w). The B fragment of (k-step kt,
 //   filter row ky) is the halo row kt + ky at column shift w, i.e. it only depends on kt + ky: a 4-deep sliding register
 //   window needs ONE new fragment per k-step instead of four.
+//   pair0: first (n-block, c-block) pair of this launch (pair = pair0 + bid % npairs): a layer with more pairs than slabs runs in rounds.
 template <typename T, int TPW, bool RASTER>
 __global__ void __launch_bounds__(256, 2)
-tfc_wgrad_kernel(const TfcGather d, const T* __restrict__ dO, const T* __restrict__ in, float* dwacc, float4* slab,
-                 int Nn_pad, int Nn_real, int Cw_real, int nbw, int ncb, int nsplit) {
+tfc_wgrad_kernel(const TfcGather d, const T* __restrict__ dO, const T* __restrict__ in, float4* slab, int Nn_pad, int npairs, int ncb, int nsplit,
+                 int pair0) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  constexpr int ES = sizeof(T);
-  constexpr int UE = 16 / ES;
+  typedef WgradOp<T> Op;
+  typedef typename Op::frag frag;
+  constexpr int UE = 16 / sizeof(T);                             // elements of dO / input per 16-byte unit
   constexpr int UPN = 32 / UE;                                   // 16-B units per 32 channels
-  constexpr int ROWB = 32 * ES;                                  // bytes per LDS row (32 channels)
+  constexpr int ROWB = Op::ROWB;
   constexpr int DO_BYTES = 2 * 128 * ROWB;
-  constexpr int HALO_BYTES = TFC_MAX_HH * TFC_MAX_HW * ROWB;
-  constexpr int BUF_BYTES = DO_BYTES + HALO_BYTES;
-  constexpr bool PREFETCH = (ES == 2);
+  constexpr int BUF_BYTES = Op::IMAGE;
   constexpr int NDO = (2 * 128 * UPN) / 256;                     // dO units per thread (4 bf16 / 8 fp32)
   constexpr int NHA = (TFC_MAX_HH * TFC_MAX_HW * UPN + 255) / 256;  // halo units per thread (4 / 7)
 
@@ -1851,18 +1925,16 @@ tfc_wgrad_kernel(const TfcGather d, const T* __restrict__ dO, const T* __restric
   const TfcPlane& pd = d.plane[0];
 
   const int bid = tfc_xcd_remap(blockIdx.x, gridDim.x);
-  const int pair = bid % (nbw * ncb);
-  const int sp = bid / (nbw * ncb);
+  const int pair = pair0 + bid % npairs;
+  const int sp = bid / npairs;
   const int cb = pair % ncb, nb = pair / ncb;
   const int ntiles = d.nimg * d.tiles_y * d.tiles_x;
 
-  f32x16_t acc[TPW][2];
+  f32x16_t acc[TPW * 2];                                         // [ti][ni]
 #pragma unroll
-  for (int ti = 0; ti < TPW; ++ti)
+  for (int a = 0; a < TPW * 2; ++a)
 #pragma unroll
-    for (int ni = 0; ni < 2; ++ni)
-#pragma unroll
-      for (int j = 0; j < 16; ++j) acc[ti][ni][j] = 0.f;
+    for (int j = 0; j < 16; ++j) acc[a][j] = 0.f;
 
   uint4 vdo[NDO], vha[NHA];
   int hyq[NHA], hxq[NHA], hcq[NHA];
@@ -1882,11 +1954,8 @@ tfc_wgrad_kernel(const TfcGather d, const T* __restrict__ dO, const T* __restric
 #ifdef TFC_ABL_WG_SAMETILE
     tl = sp;                                                     // ablation: every load hits the workgroup's first (cache-hot) tile
 #endif
-    int t = tl;
-    const int txb = t % d.tiles_x; t /= d.tiles_x;
-    const int tyb = t % d.tiles_y;
-    const int img = t / d.tiles_y;
-    const int a0 = tyb * TFC_TILE_H, b0 = txb * TFC_TILE_W;
+    int img, a0, b0;
+    tfc_tile_decode(tl, d.tiles_x, d.tiles_y, img, a0, b0);
 #pragma unroll
     for (int i = 0; i < NDO; ++i) {
       const int idx = tid + i * 256;
@@ -1912,89 +1981,54 @@ tfc_wgrad_kernel(const TfcGather d, const T* __restrict__ dO, const T* __restric
   };
   auto tile_store = [&](unsigned char* buf) {
 #pragma unroll
-    for (int i = 0; i < NDO; ++i) {
-      const int idx = tid + i * 256;                             // == (ni*128 + px)*UPN + g : the LDS image order
-      *reinterpret_cast<uint4*>(buf + idx * 16) = vdo[i];
-    }
+    for (int i = 0; i < NDO; ++i) Op::put(buf, tid + i * 256, vdo[i]);             // unit (ni*128 + px)*UPN + g : the LDS image order
     const int nunits = pd.hh * pd.hw * UPN;
 #pragma unroll
     for (int i = 0; i < NHA; ++i) {
       const int idx = tid + i * 256;                             // == pix*UPN + g
-      if (idx < nunits) *reinterpret_cast<uint4*>(buf + DO_BYTES + idx * 16) = vha[i];
+      if (idx < nunits) Op::put(buf + DO_BYTES, idx, vha[i]);
     }
   };
 
   const int nni = (Nn_pad - nb * 64) > 32 ? 2 : 1;               // second 32-row block empty (e.g. the 3-channel head)? skip its MFMAs
-  // lane decode for the transposing reads (bf16) / dword reads (fp32)
-  const int grp = lane >> 4, li = lane & 15;
-  const int cb16 = grp & 1, hk = grp >> 1, q = li >> 2, p = li & 3;
-  const int trLane = (8 * hk + q) * ROWB + cb16 * 32 + p * 8;    // bf16 only
+  const int trLane = tfc_tr_lane(lane, ROWB);                    // transposing policies only
 
   auto compute = [&](const unsigned char* buf) {
     const unsigned char* dob = buf;
     const unsigned char* hab = buf + DO_BYTES;
-    if constexpr (ES == 2 && RASTER) {
-      auto tr16 = [&](const unsigned char* p0) {
-        s16x4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16(LDS_PTR(s16x4_t, p0));
-        s16x4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16(LDS_PTR(s16x4_t, p0 + 4 * ROWB));
-        uint4 r;
-        r.x = (uint16_t)lo[0] | ((uint32_t)(uint16_t)lo[1] << 16);
-        r.y = (uint16_t)lo[2] | ((uint32_t)(uint16_t)lo[3] << 16);
-        r.z = (uint16_t)hi[0] | ((uint32_t)(uint16_t)hi[1] << 16);
-        r.w = (uint16_t)hi[2] | ((uint32_t)(uint16_t)hi[3] << 16);
-        return r;
-      };
+    if constexpr (Op::TR && RASTER) {
       const unsigned char* hcol = hab + wave * ROWB + trLane;     // halo column shift kx = wave
       const int rowb = pd.hw * ROWB;
-      uint4 bw[4];
-      bw[0] = tr16(hcol);
-      bw[1] = tr16(hcol + rowb);
-      bw[2] = tr16(hcol + 2 * rowb);
+      frag bw[4];
+      bw[0] = Op::load(hcol);
+      bw[1] = Op::load(hcol + rowb);
+      bw[2] = Op::load(hcol + 2 * rowb);
 #pragma unroll
       for (int kt = 0; kt < 8; ++kt) {
-        bw[(kt + 3) & 3] = tr16(hcol + (kt + 3) * rowb);
-        uint4 a[2];
+        bw[(kt + 3) & 3] = Op::load(hcol + (kt + 3) * rowb);
+        frag a[2];
 #pragma unroll
-        for (int ni = 0; ni < 2; ++ni) a[ni] = tr16(dob + ni * 128 * ROWB + kt * 16 * ROWB + trLane);
+        for (int ni = 0; ni < 2; ++ni) a[ni] = Op::load(dob + ni * 128 * ROWB + kt * 16 * ROWB + trLane);
 #pragma unroll
         for (int ky = 0; ky < 4; ++ky)
 #pragma unroll
           for (int ni = 0; ni < 2; ++ni)
-            if (ni < nni)
-              acc[ky][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, a[ni]),
-                                                                     __builtin_bit_cast(bf16x8_t, bw[(kt + ky) & 3]), acc[ky][ni], 0, 0, 0);
+            if (ni < nni) Op::mma(a[ni], bw[(kt + ky) & 3], acc[ky * 2 + ni]);
       }
-    } else if constexpr (ES == 2) {
+    } else if constexpr (Op::TR) {
 #pragma unroll 2
       for (int kt = 0; kt < 8; ++kt) {
-        uint4 a[2];
+        frag a[2];
 #pragma unroll
-        for (int ni = 0; ni < 2; ++ni) {
-          const unsigned char* pa = dob + ni * 128 * ROWB + kt * 16 * ROWB + trLane;
-          s16x4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16(LDS_PTR(s16x4_t, pa));
-          s16x4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16(LDS_PTR(s16x4_t, pa + 4 * ROWB));
-          a[ni].x = (uint16_t)lo[0] | ((uint32_t)(uint16_t)lo[1] << 16);
-          a[ni].y = (uint16_t)lo[2] | ((uint32_t)(uint16_t)lo[3] << 16);
-          a[ni].z = (uint16_t)hi[0] | ((uint32_t)(uint16_t)hi[1] << 16);
-          a[ni].w = (uint16_t)hi[2] | ((uint32_t)(uint16_t)hi[3] << 16);
-        }
+        for (int ni = 0; ni < 2; ++ni) a[ni] = Op::load(dob + ni * 128 * ROWB + kt * 16 * ROWB + trLane);
 #pragma unroll
         for (int ti = 0; ti < TPW; ++ti) {
           const int tap = ti * 4 + wave;
           if (tap < pd.ntaps) {                                  // wave-uniform
-            const unsigned char* pb = hab + ((kt + pd.tap_dy[tap]) * pd.hw + pd.tap_dx[tap]) * ROWB + trLane;
-            s16x4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16(LDS_PTR(s16x4_t, pb));
-            s16x4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16(LDS_PTR(s16x4_t, pb + 4 * ROWB));
-            uint4 b;
-            b.x = (uint16_t)lo[0] | ((uint32_t)(uint16_t)lo[1] << 16);
-            b.y = (uint16_t)lo[2] | ((uint32_t)(uint16_t)lo[3] << 16);
-            b.z = (uint16_t)hi[0] | ((uint32_t)(uint16_t)hi[1] << 16);
-            b.w = (uint16_t)hi[2] | ((uint32_t)(uint16_t)hi[3] << 16);
+            const frag b = Op::load(hab + ((kt + pd.tap_dy[tap]) * pd.hw + pd.tap_dx[tap]) * ROWB + trLane);
 #pragma unroll
             for (int ni = 0; ni < 2; ++ni)
-              if (ni < nni)
-                acc[ti][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, a[ni]),
-                                                                       __builtin_bit_cast(bf16x8_t, b), acc[ti][ni], 0, 0, 0);
+              if (ni < nni) Op::mma(a[ni], b, acc[ti * 2 + ni]);
           }
         }
       }
@@ -2002,25 +2036,25 @@ tfc_wgrad_kernel(const TfcGather d, const T* __restrict__ dO, const T* __restric
       const int r = lane & 31, kh = lane >> 5;
       for (int kk = 0; kk < 64; ++kk) {
         const int px = 2 * kk + kh;
-        float a[2];
+        frag a[2];
 #pragma unroll
-        for (int ni = 0; ni < 2; ++ni) a[ni] = *reinterpret_cast<const float*>(dob + (ni * 128 + px) * ROWB + r * 4);
+        for (int ni = 0; ni < 2; ++ni) a[ni] = Op::load(dob + (ni * 128 + px) * ROWB + r * 4);
         const int ty = px >> 4, tx = px & 15;
 #pragma unroll
         for (int ti = 0; ti < TPW; ++ti) {
           const int tap = ti * 4 + wave;
           if (tap < pd.ntaps) {
-            const float b = *reinterpret_cast<const float*>(hab + ((ty + pd.tap_dy[tap]) * pd.hw + tx + pd.tap_dx[tap]) * ROWB + r * 4);
+            const frag b = Op::load(hab + ((ty + pd.tap_dy[tap]) * pd.hw + tx + pd.tap_dx[tap]) * ROWB + r * 4);
 #pragma unroll
             for (int ni = 0; ni < 2; ++ni)
-              if (ni < nni) acc[ti][ni] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[ni], b, acc[ti][ni], 0, 0, 0);
+              if (ni < nni) Op::mma(a[ni], b, acc[ti * 2 + ni]);
           }
         }
       }
     }
   };
 
-  if constexpr (PREFETCH) {
+  if constexpr (Op::PREFETCH) {
     int tl = sp;
     int cur = 0;
     if (tl < ntiles) { tile_load(tl); tile_store(smem); }
@@ -2042,216 +2076,7 @@ tfc_wgrad_kernel(const TfcGather d, const T* __restrict__ dO, const T* __restric
       __syncthreads();
     }
   }
-
-  // ---- flush ----
-  if (slab) {                                                    // split-K partial -> this workgroup's slab, register order (see tfc_wgrad_reduce_kernel)
-    float4* ps = slab + ((size_t)bid * 4 + wave) * (TPW * 2 * 4 * 64) + lane;
-#pragma unroll
-    for (int ti = 0; ti < TPW; ++ti)
-#pragma unroll
-      for (int ni = 0; ni < 2; ++ni)
-#pragma unroll
-        for (int q4 = 0; q4 < 4; ++q4)
-          ps[((ti * 2 + ni) * 4 + q4) * 64] = make_float4(acc[ti][ni][4 * q4], acc[ti][ni][4 * q4 + 1], acc[ti][ni][4 * q4 + 2], acc[ti][ni][4 * q4 + 3]);
-    return;
-  }
-  const int c = cb * 32 + (lane & 31);
-  const int hrow = lane >> 5;
-#pragma unroll
-  for (int ti = 0; ti < TPW; ++ti) {
-    const int tap = ti * 4 + wave;
-    if (tap < pd.ntaps) {
-      for (int m = pd.tap_mask[tap]; m; m &= m - 1) {              // a collapsed tap feeds every filter tap it stands for
-        const int slot = __ffs(m) - 1;
-#pragma unroll
-        for (int ni = 0; ni < 2; ++ni)
-#pragma unroll
-          for (int j = 0; j < 16; ++j) {
-            const int n = nb * 64 + ni * 32 + (j & 3) + 8 * (j >> 2) + 4 * hrow;
-            if (ni < nni && n < Nn_real && c < Cw_real)
-              atomicAdd(&dwacc[((size_t)slot * Nn_real + n) * Cw_real + c], acc[ti][ni][j]);
-          }
-      }
-    }
-  }
-}
-
-// ---------------------------------------------------------------------------------------------------
-// bf16x3 weight gradient: the tfc_wgrad_kernel GEMM on fp32 dO / input. Both are split while they are staged, into a hi and a lo bf16 image of
-// the bf16 kernel's LDS layout (32 channels = 64 B per pixel row), so the transposing reads (ds_read_b64_tr_b16) and fragment maps of the bf16
-// form apply to each plane unchanged; every (k-step, tap) issues lo*hi, hi*lo, hi*hi. The two images take the 59.5 KB of the fp32 kernel's one
-// (single-buffered like it: 2 workgroups per CU). Flush: slabs only, never atomics -- the launcher keeps the grid within the slab budget.
-// pair0: first (n-block, c-block) pair of this launch (pair = pair0 + bid % npairs).
-// ---------------------------------------------------------------------------------------------------
-template <int TPW, bool RASTER>
-__global__ void __launch_bounds__(256, 2)
-tfc_wgrad_x3_kernel(const TfcGather d, const float* __restrict__ dO, const float* __restrict__ in, float4* slab, int Nn_pad, int npairs, int ncb,
-                    int nsplit, int pair0) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  constexpr int ROWB = 64;                                       // bytes per LDS row of one plane (32 bf16 channels)
-  constexpr int DO_BYTES = 2 * 128 * ROWB;
-  constexpr int PLANE = DO_BYTES + TFC_MAX_HH * TFC_MAX_HW * ROWB;   // hi image at 0, lo image at PLANE
-  constexpr int UPN = 8;                                         // fp32 16-byte units per 32 channels
-  constexpr int NDO = (2 * 128 * UPN) / 256;
-  constexpr int NHA = (TFC_MAX_HH * TFC_MAX_HW * UPN + 255) / 256;
-
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const TfcPlane& pd = d.plane[0];
-
-  const int bid = tfc_xcd_remap(blockIdx.x, gridDim.x);
-  const int pair = pair0 + bid % npairs;
-  const int sp = bid / npairs;
-  const int cb = pair % ncb, nb = pair / ncb;
-  const int ntiles = d.nimg * d.tiles_y * d.tiles_x;
-
-  f32x16_t acc[TPW][2];
-#pragma unroll
-  for (int ti = 0; ti < TPW; ++ti)
-#pragma unroll
-    for (int ni = 0; ni < 2; ++ni)
-#pragma unroll
-      for (int j = 0; j < 16; ++j) acc[ti][ni][j] = 0.f;
-
-  uint4 vdo[NDO], vha[NHA];
-  int hyq[NHA], hxq[NHA], hcq[NHA];
-  bool hok[NHA];
-  const int nunits = pd.hh * pd.hw * UPN;
-#pragma unroll
-  for (int i = 0; i < NHA; ++i) {
-    const int idx = tid + i * 256;
-    const int g = idx % UPN, pix = idx / UPN;
-    hyq[i] = pix / pd.hw; hxq[i] = pix - hyq[i] * pd.hw;
-    hcq[i] = cb * 32 + g * 4;
-    hok[i] = idx < nunits && hcq[i] < d.Cin_pad;
-  }
-  auto tile_load = [&](int tl) {
-    int t = tl;
-    const int txb = t % d.tiles_x; t /= d.tiles_x;
-    const int tyb = t % d.tiles_y;
-    const int img = t / d.tiles_y;
-    const int a0 = tyb * TFC_TILE_H, b0 = txb * TFC_TILE_W;
-#pragma unroll
-    for (int i = 0; i < NDO; ++i) {
-      const int idx = tid + i * 256;
-      const int g = idx % UPN, px = (idx / UPN) & 127, ni = idx / (UPN * 128);
-      const int a = a0 + (px >> 4), b = b0 + (px & 15);
-      const int n0 = nb * 64 + ni * 32 + g * 4;
-      vdo[i] = make_uint4(0, 0, 0, 0);
-      if (a < d.GH && b < d.GW && n0 < Nn_pad) {
-        const int oy = a * d.OS + d.OOY, ox = b * d.OS + d.OOX;
-        vdo[i] = *reinterpret_cast<const uint4*>(dO + ((size_t)(img * d.OH + oy) * d.OW + ox) * d.out_pitch + n0);
-      }
-    }
-#pragma unroll
-    for (int i = 0; i < NHA; ++i) {
-      vha[i] = make_uint4(0, 0, 0, 0);
-      if (hok[i]) {
-        const int y = (a0 + pd.dy0 + hyq[i]) * d.SS + pd.py;
-        const int x = (b0 + pd.dx0 + hxq[i]) * d.SS + pd.px;
-        if (y >= 0 && y < d.IH && x >= 0 && x < d.IW)
-          vha[i] = *reinterpret_cast<const uint4*>(in + ((size_t)(img * d.IH + y) * d.IW + x) * d.in_pitch + hcq[i]);
-      }
-    }
-  };
-  auto put = [&](int off, const uint4& v) {                      // fp32 unit (4 channels) at byte `off` of the bf16 image: hi and lo 8 bytes
-    const uint4 s = tfc_split_x3(v);
-    *reinterpret_cast<uint2*>(smem + off) = make_uint2(s.x, s.y);
-    *reinterpret_cast<uint2*>(smem + PLANE + off) = make_uint2(s.z, s.w);
-  };
-  auto tile_store = [&]() {
-#pragma unroll
-    for (int i = 0; i < NDO; ++i) put((tid + i * 256) * 8, vdo[i]);          // fp32 unit index idx -> bf16 byte offset idx * 8 (same image order)
-#pragma unroll
-    for (int i = 0; i < NHA; ++i)
-      if (tid + i * 256 < nunits) put(DO_BYTES + (tid + i * 256) * 8, vha[i]);
-  };
-
-  const int nni = (Nn_pad - nb * 64) > 32 ? 2 : 1;
-  const int grp = lane >> 4, li = lane & 15;
-  const int cb16 = grp & 1, hk = grp >> 1, q = li >> 2, p = li & 3;
-  const int trLane = (8 * hk + q) * ROWB + cb16 * 32 + p * 8;
-  auto tr16 = [&](const unsigned char* p0) {
-    s16x4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16(LDS_PTR(s16x4_t, p0));
-    s16x4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16(LDS_PTR(s16x4_t, p0 + 4 * ROWB));
-    uint4 r;
-    r.x = (uint16_t)lo[0] | ((uint32_t)(uint16_t)lo[1] << 16);
-    r.y = (uint16_t)lo[2] | ((uint32_t)(uint16_t)lo[3] << 16);
-    r.z = (uint16_t)hi[0] | ((uint32_t)(uint16_t)hi[1] << 16);
-    r.w = (uint16_t)hi[2] | ((uint32_t)(uint16_t)hi[3] << 16);
-    return r;
-  };
-  auto mma3 = [&](f32x16_t& c, const uint4& ah, const uint4& al, const uint4& bh, const uint4& bl) {
-    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, al), __builtin_bit_cast(bf16x8_t, bh), c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, ah), __builtin_bit_cast(bf16x8_t, bl), c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, ah), __builtin_bit_cast(bf16x8_t, bh), c, 0, 0, 0);
-  };
-  auto compute = [&]() {
-    const unsigned char* dob = smem;
-    const unsigned char* hab = smem + DO_BYTES;
-    if constexpr (RASTER) {                                      // wave w owns filter column kx = w; 4-deep sliding window over halo rows
-      const unsigned char* hcol = hab + wave * ROWB + trLane;
-      const int rowb = pd.hw * ROWB;
-      uint4 bh[4], bl[4];
-#pragma unroll
-      for (int i = 0; i < 3; ++i) { bh[i] = tr16(hcol + i * rowb); bl[i] = tr16(hcol + PLANE + i * rowb); }
-#pragma unroll
-      for (int kt = 0; kt < 8; ++kt) {
-        bh[(kt + 3) & 3] = tr16(hcol + (kt + 3) * rowb);
-        bl[(kt + 3) & 3] = tr16(hcol + PLANE + (kt + 3) * rowb);
-        uint4 ah[2], al[2];
-#pragma unroll
-        for (int ni = 0; ni < 2; ++ni) {
-          ah[ni] = tr16(dob + ni * 128 * ROWB + kt * 16 * ROWB + trLane);
-          al[ni] = tr16(dob + PLANE + ni * 128 * ROWB + kt * 16 * ROWB + trLane);
-        }
-#pragma unroll
-        for (int ky = 0; ky < 4; ++ky)
-#pragma unroll
-          for (int ni = 0; ni < 2; ++ni)
-            if (ni < nni) mma3(acc[ky][ni], ah[ni], al[ni], bh[(kt + ky) & 3], bl[(kt + ky) & 3]);
-      }
-    } else {
-#pragma unroll 2
-      for (int kt = 0; kt < 8; ++kt) {
-        uint4 ah[2], al[2];
-#pragma unroll
-        for (int ni = 0; ni < 2; ++ni) {
-          ah[ni] = tr16(dob + ni * 128 * ROWB + kt * 16 * ROWB + trLane);
-          al[ni] = tr16(dob + PLANE + ni * 128 * ROWB + kt * 16 * ROWB + trLane);
-        }
-#pragma unroll
-        for (int ti = 0; ti < TPW; ++ti) {
-          const int tap = ti * 4 + wave;
-          if (tap < pd.ntaps) {                                  // wave-uniform
-            const unsigned char* pb = hab + ((kt + pd.tap_dy[tap]) * pd.hw + pd.tap_dx[tap]) * ROWB + trLane;
-            const uint4 bh = tr16(pb), bl = tr16(pb + PLANE);
-#pragma unroll
-            for (int ni = 0; ni < 2; ++ni)
-              if (ni < nni) mma3(acc[ti][ni], ah[ni], al[ni], bh, bl);
-          }
-        }
-      }
-    }
-  };
-
-  for (int tl = sp; tl < ntiles; tl += nsplit) {
-    tile_load(tl);
-    tile_store();
-    __syncthreads();
-    compute();
-    __syncthreads();
-  }
-
-  float4* ps = slab + ((size_t)bid * 4 + wave) * (TPW * 2 * 4 * 64) + lane;   // register order (tfc_wgrad_reduce_kernel, kind 0)
-#pragma unroll
-  for (int ti = 0; ti < TPW; ++ti)
-#pragma unroll
-    for (int ni = 0; ni < 2; ++ni)
-#pragma unroll
-      for (int q4 = 0; q4 < 4; ++q4)
-        ps[((ti * 2 + ni) * 4 + q4) * 64] = make_float4(acc[ti][ni][4 * q4], acc[ti][ni][4 * q4 + 1], acc[ti][ni][4 * q4 + 2], acc[ti][ni][4 * q4 + 3]);
+  tfc_slab_store(slab + ((size_t)bid * 4 + wave) * (TPW * 2 * 4 * 64) + lane, acc);   // tfc_wgrad_reduce_kernel kind 0
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -2284,11 +2109,8 @@ tfc_wgrad_c8_kernel(const TfcGather d, const bf16_t* __restrict__ dO, const bf16
 
   uint4 vdo[4], vha;
   auto tile_load = [&](int tl) {
-    int t = tl;
-    const int txb = t % d.tiles_x; t /= d.tiles_x;
-    const int tyb = t % d.tiles_y;
-    const int img = t / d.tiles_y;
-    const int a0 = tyb * TFC_TILE_H, b0 = txb * TFC_TILE_W;
+    int img, a0, b0;
+    tfc_tile_decode(tl, d.tiles_x, d.tiles_y, img, a0, b0);
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       const int idx = tid + i * 256;                             // (ni * 128 + px) * 4 + g
@@ -2311,28 +2133,16 @@ tfc_wgrad_c8_kernel(const TfcGather d, const bf16_t* __restrict__ dO, const bf16
     for (int i = 0; i < 4; ++i) *reinterpret_cast<uint4*>(buf + (tid + i * 256) * 16) = vdo[i];
     if (tid < TFC_MAX_HH * TFC_MAX_HW) *reinterpret_cast<uint4*>(buf + DO_BYTES + tid * 16) = vha;
   };
-  const int grp = lane >> 4, li = lane & 15;
-  const int cb16 = grp & 1, hk = grp >> 1, q = li >> 2, p = li & 3;
-  const int trA = (8 * hk + q) * ROWB + cb16 * 32 + p * 8;        // dO: rows = pixels (64 B), columns = outputs
-  const int trB = (8 * hk + q) * 16 + cb16 * 32 + p * 8;          // halo: rows = pixels (16 B pitch, 64 B long: overlapping), columns = (kx, c)
-  auto tr16 = [&](const unsigned char* p0, int rowb4) {
-    s16x4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16(LDS_PTR(s16x4_t, p0));
-    s16x4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16(LDS_PTR(s16x4_t, p0 + rowb4));
-    uint4 r;
-    r.x = (uint16_t)lo[0] | ((uint32_t)(uint16_t)lo[1] << 16);
-    r.y = (uint16_t)lo[2] | ((uint32_t)(uint16_t)lo[3] << 16);
-    r.z = (uint16_t)hi[0] | ((uint32_t)(uint16_t)hi[1] << 16);
-    r.w = (uint16_t)hi[2] | ((uint32_t)(uint16_t)hi[3] << 16);
-    return r;
-  };
+  const int trA = tfc_tr_lane(lane, ROWB);                       // dO: rows = pixels (64 B), columns = outputs
+  const int trB = tfc_tr_lane(lane, 16);                         // halo: rows = pixels (16 B pitch, 64 B long: overlapping), columns = (kx, c)
   auto compute = [&](const unsigned char* buf) {
     const unsigned char* hrow = buf + DO_BYTES + wave * pd.hw * 16 + trB;   // halo row kt + ky, ky = wave
 #pragma unroll
     for (int kt = 0; kt < 8; ++kt) {
-      const uint4 b = tr16(hrow + kt * pd.hw * 16, 4 * 16);
+      const uint4 b = tfc_tr16(hrow + kt * pd.hw * 16, 4 * 16);
 #pragma unroll
       for (int ni = 0; ni < 2; ++ni) {
-        const uint4 a = tr16(buf + ni * 128 * ROWB + kt * 16 * ROWB + trA, 4 * ROWB);
+        const uint4 a = tfc_tr16(buf + ni * 128 * ROWB + kt * 16 * ROWB + trA, 4 * ROWB);
         acc[ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, a), __builtin_bit_cast(bf16x8_t, b), acc[ni], 0, 0, 0);
       }
     }
@@ -2348,12 +2158,7 @@ tfc_wgrad_c8_kernel(const TfcGather d, const bf16_t* __restrict__ dO, const bf16
     __syncthreads();
     cur ^= 1;
   }
-  float4* ps = slab + ((size_t)sp * 4 + wave) * (2 * 4 * 64) + lane;
-#pragma unroll
-  for (int ni = 0; ni < 2; ++ni)
-#pragma unroll
-    for (int q4 = 0; q4 < 4; ++q4)
-      ps[(ni * 4 + q4) * 64] = make_float4(acc[ni][4 * q4], acc[ni][4 * q4 + 1], acc[ni][4 * q4 + 2], acc[ni][4 * q4 + 3]);
+  tfc_slab_store(slab + ((size_t)sp * 4 + wave) * (2 * 4 * 64) + lane, acc);
 }
 // ---------------------------------------------------------------------------------------------------
 // First block, backward, fused: [BlurPool(stride 2)]^T -> LeakyReLU' -> weight gradient (+ bias gradient), bf16. The unfused chain
@@ -2396,17 +2201,10 @@ tfc_wgrad_c8_fused_kernel(const TfcGather d, const bf16_t* __restrict__ yact, in
 #pragma unroll
     for (int j = 0; j < 16; ++j) acc[ni][j] = 0.f;
 
-  auto decode = [&](int tl, int& img, int& a0, int& b0) {
-    int t = tl;
-    const int txb = t % d.tiles_x; t /= d.tiles_x;
-    const int tyb = t % d.tiles_y;
-    img = t / d.tiles_y;
-    a0 = tyb * TFC_TILE_H; b0 = txb * TFC_TILE_W;
-  };
   uint4 vy[4], vw[3], vha;
   auto tile_load = [&](int tl) {
     int img, a0, b0;
-    decode(tl, img, a0, b0);
+    tfc_tile_decode(tl, d.tiles_x, d.tiles_y, img, a0, b0);
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       const int idx = tid + i * 256;                             // (ni * 128 + px) * 4 + g
@@ -2449,20 +2247,8 @@ tfc_wgrad_c8_fused_kernel(const TfcGather d, const bf16_t* __restrict__ yact, in
     }
     return make_float4(w3[0], w3[1], w3[2], 0.f);
   };
-  const int grp = lane >> 4, li = lane & 15;
-  const int cb16 = grp & 1, hk = grp >> 1, q = li >> 2, p = li & 3;
-  const int trA = (8 * hk + q) * ROWB + cb16 * 32 + p * 8;
-  const int trB = (8 * hk + q) * 16 + cb16 * 32 + p * 8;
-  auto tr16 = [&](const unsigned char* p0, int rowb4) {
-    s16x4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16(LDS_PTR(s16x4_t, p0));
-    s16x4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16(LDS_PTR(s16x4_t, p0 + rowb4));
-    uint4 r;
-    r.x = (uint16_t)lo[0] | ((uint32_t)(uint16_t)lo[1] << 16);
-    r.y = (uint16_t)lo[2] | ((uint32_t)(uint16_t)lo[3] << 16);
-    r.z = (uint16_t)hi[0] | ((uint32_t)(uint16_t)hi[1] << 16);
-    r.w = (uint16_t)hi[2] | ((uint32_t)(uint16_t)hi[3] << 16);
-    return r;
-  };
+  const int trA = tfc_tr_lane(lane, ROWB);
+  const int trB = tfc_tr_lane(lane, 16);
   float bsum[2][8];                                              // this thread's channels: ni = 0 / 1, unit g = tid & 3
 #pragma unroll
   for (int h2 = 0; h2 < 2; ++h2)
@@ -2472,7 +2258,7 @@ tfc_wgrad_c8_fused_kernel(const TfcGather d, const bf16_t* __restrict__ yact, in
   int cur = 0;
   for (int tl = t0; tl < t1; ++tl) {
     int img, a0, b0;
-    decode(tl, img, a0, b0);
+    tfc_tile_decode(tl, d.tiles_x, d.tiles_y, img, a0, b0);
     // A. window, halo, tap tables of this tile -> LDS; the activation units stay in registers
 #pragma unroll
     for (int i = 0; i < 3; ++i) { const int idx = tid + i * 256; if (idx < WH * WW * 8) win[idx] = vw[i]; }
@@ -2529,10 +2315,10 @@ tfc_wgrad_c8_fused_kernel(const TfcGather d, const bf16_t* __restrict__ yact, in
       const unsigned char* hrow = halo0 + cur * HALO_BYTES + wave * pd.hw * 16 + trB;
 #pragma unroll
       for (int kt = 0; kt < 8; ++kt) {
-        const uint4 b = tr16(hrow + kt * pd.hw * 16, 4 * 16);
+        const uint4 b = tfc_tr16(hrow + kt * pd.hw * 16, 4 * 16);
 #pragma unroll
         for (int ni = 0; ni < 2; ++ni) {
-          const uint4 a = tr16(buf + ni * 128 * ROWB + kt * 16 * ROWB + trA, 4 * ROWB);
+          const uint4 a = tfc_tr16(buf + ni * 128 * ROWB + kt * 16 * ROWB + trA, 4 * ROWB);
           acc[ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, a), __builtin_bit_cast(bf16x8_t, b), acc[ni], 0, 0, 0);
         }
       }
@@ -2554,12 +2340,7 @@ tfc_wgrad_c8_fused_kernel(const TfcGather d, const bf16_t* __restrict__ yact, in
     __syncthreads();
     if (tid < 64) rstats[(size_t)sp * 64 + tid] = ((sbias[tid] + sbias[64 + tid]) + sbias[128 + tid]) + sbias[192 + tid];   // part[img][wj][64], sp = img * wpi + wj
   }
-  float4* ps = slab + ((size_t)sp * 4 + wave) * (2 * 4 * 64) + lane;
-#pragma unroll
-  for (int ni = 0; ni < 2; ++ni)
-#pragma unroll
-    for (int q4 = 0; q4 < 4; ++q4)
-      ps[(ni * 4 + q4) * 64] = make_float4(acc[ni][4 * q4], acc[ni][4 * q4 + 1], acc[ni][4 * q4 + 2], acc[ni][4 * q4 + 3]);
+  tfc_slab_store(slab + ((size_t)sp * 4 + wave) * (2 * 4 * 64) + lane, acc);
 }
 // ---------------------------------------------------------------------------------------------------
 // The same fused first-block backward with the transposed blur ON THE MATRIX CORE (round 3). The kernel above spends ~1,200 VALU instructions per
@@ -2674,20 +2455,8 @@ tfc_wgrad_c8_fusedm_kernel(const TfcGather d, const bf16_t* __restrict__ yact, i
     }
     return make_float4(w3[0], w3[1], w3[2], 0.f);
   };
-  const int grp = lane >> 4, li = lane & 15;
-  const int cb16 = grp & 1, hk = grp >> 1, q = li >> 2, p = li & 3;
-  const int trA = (8 * hk + q) * ROWB + cb16 * 32 + p * 8;
-  const int trB = (8 * hk + q) * 16 + cb16 * 32 + p * 8;
-  auto tr16 = [&](const unsigned char* p0, int rowb4) {
-    s16x4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16(LDS_PTR(s16x4_t, p0));
-    s16x4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16(LDS_PTR(s16x4_t, p0 + rowb4));
-    uint4 r;
-    r.x = (uint16_t)lo[0] | ((uint32_t)(uint16_t)lo[1] << 16);
-    r.y = (uint16_t)lo[2] | ((uint32_t)(uint16_t)lo[3] << 16);
-    r.z = (uint16_t)hi[0] | ((uint32_t)(uint16_t)hi[1] << 16);
-    r.w = (uint16_t)hi[2] | ((uint32_t)(uint16_t)hi[3] << 16);
-    return r;
-  };
+  const int trA = tfc_tr_lane(lane, ROWB);
+  const int trB = tfc_tr_lane(lane, 16);
   float bsum[2][16];                                              // bias-gradient sums of this lane's 2 x 16 channels (channel = cb*32 + (j&3) + 8(j>>2) + 4h)
 #pragma unroll
   for (int cb = 0; cb < 2; ++cb)
@@ -2763,7 +2532,7 @@ tfc_wgrad_c8_fusedm_kernel(const TfcGather d, const bf16_t* __restrict__ yact, i
       const uint4 b = *reinterpret_cast<const uint4*>(ttb + pl * TP + (ks * 16 + 8 * hh) * 2);
 #pragma unroll
       for (int cb = 0; cb < 2; ++cb) {
-        const uint4 a = tr16(winb + cb * PLANE + ks * 16 * ROWB + trA, 4 * ROWB);
+        const uint4 a = tfc_tr16(winb + cb * PLANE + ks * 16 * ROWB + trA, 4 * ROWB);
         gacc[cb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, a), __builtin_bit_cast(bf16x8_t, b), gacc[cb], 0, 0, 0);
       }
     }
@@ -2795,10 +2564,10 @@ tfc_wgrad_c8_fusedm_kernel(const TfcGather d, const bf16_t* __restrict__ yact, i
       const unsigned char* hrow = halo0 + cur * HALO_BYTES + wave * pd.hw * 16 + trB;
 #pragma unroll
       for (int kt = 0; kt < 8; ++kt) {
-        const uint4 b = tr16(hrow + kt * pd.hw * 16, 4 * 16);
+        const uint4 b = tfc_tr16(hrow + kt * pd.hw * 16, 4 * 16);
 #pragma unroll
         for (int ni = 0; ni < 2; ++ni) {
-          const uint4 a = tr16(smem + ni * 128 * ROWB + kt * 16 * ROWB + trA, 4 * ROWB);
+          const uint4 a = tfc_tr16(smem + ni * 128 * ROWB + kt * 16 * ROWB + trA, 4 * ROWB);
           acc[ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, a), __builtin_bit_cast(bf16x8_t, b), acc[ni], 0, 0, 0);
         }
       }
@@ -2835,12 +2604,7 @@ tfc_wgrad_c8_fusedm_kernel(const TfcGather d, const bf16_t* __restrict__ yact, i
     __syncthreads();
     if (tid < 64) rstats[(size_t)sp * 64 + tid] = ((sbias[tid] + sbias[64 + tid]) + sbias[128 + tid]) + sbias[192 + tid];
   }
-  float4* ps = slab + ((size_t)sp * 4 + wave) * (2 * 4 * 64) + lane;
-#pragma unroll
-  for (int ni = 0; ni < 2; ++ni)
-#pragma unroll
-    for (int q4 = 0; q4 < 4; ++q4)
-      ps[(ni * 4 + q4) * 64] = make_float4(acc[ni][4 * q4], acc[ni][4 * q4 + 1], acc[ni][4 * q4 + 2], acc[ni][4 * q4 + 3]);
+  tfc_slab_store(slab + ((size_t)sp * 4 + wave) * (2 * 4 * 64) + lane, acc);
 }
 
 // position = ((ky * 2 + ni) * 4 + q4) * 64 + lane of the 2048 float4 of a workgroup slab. A block owns 16 positions; its 16 slab-lanes take the slabs
@@ -2850,20 +2614,11 @@ tfc_wgrad_c8_fusedm_kernel(const TfcGather d, const bf16_t* __restrict__ yact, i
 __global__ void __launch_bounds__(256)
 tfc_wgrad_c8_reduce_kernel(const float4* __restrict__ slab, float* acc, int nsplit, int Nn_real, int Cw_real, float* grad, long long sn, long long sc,
                            int accumulate) {
-  __shared__ float4 red[16][16];
-  const int pl = threadIdx.x & 15, sl = threadIdx.x >> 4;
-  const int pos = blockIdx.x * 16 + pl;
-  float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll 4
-  for (int sp = sl; sp < nsplit; sp += 16) {
-    const float4 v = slab[(size_t)sp * 2048 + pos];
-    s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w;
-  }
-  red[sl][pl] = s;
-  __syncthreads();
-  if (sl != 0) return;
-#pragma unroll
-  for (int i = 1; i < 16; ++i) { const float4 v = red[i][pl]; s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w; }
+  const int pos = blockIdx.x * 16 + (threadIdx.x & 15);
+  const size_t row[1] = {(size_t)pos};
+  float4 sum[1];
+  if (!tfc_slab_sum<16, 16, 1>(slab, row, 2048, nsplit, sum)) return;
+  const float4 s = sum[0];
   const int lane = pos & 63, q4 = (pos >> 6) & 3, ni = (pos >> 8) & 1, ky = pos >> 9;
   const int col = lane & 31, kx = col >> 3, c = col & 7;
   const int n0 = ni * 32 + 8 * q4 + 4 * (lane >> 5);
@@ -3051,11 +2806,8 @@ tfc_wgradT_kernel(const bf16_t* __restrict__ x, int IH, int IW, int x_pitch, int
 
   uint4 vdo[NDO], vha[NHA];
   auto tile_load = [&](int tl) {
-    int t = tl;
-    const int txb = t % tiles_x; t /= tiles_x;
-    const int tyb = t % tiles_y;
-    const int img = t / tiles_y;
-    const int a0 = tyb * TFC_TILE_H, b0 = txb * TFC_TILE_W;
+    int img, a0, b0;
+    tfc_tile_decode(tl, tiles_x, tiles_y, img, a0, b0);
 #pragma unroll
     for (int i = 0; i < NDO; ++i) {
       const int idx = tid + i * 256;                             // ((phase * 128) + pixel) * 4 + g
@@ -3090,19 +2842,7 @@ tfc_wgradT_kernel(const bf16_t* __restrict__ x, int IH, int IW, int x_pitch, int
     }
   };
 
-  const int grp = lane >> 4, li = lane & 15;
-  const int cb16 = grp & 1, hk = grp >> 1, q = li >> 2, p = li & 3;
-  const int trLane = (8 * hk + q) * ROWB + cb16 * 32 + p * 8;
-  auto tr16 = [&](const unsigned char* p0) {
-    s16x4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16(LDS_PTR(s16x4_t, p0));
-    s16x4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16(LDS_PTR(s16x4_t, p0 + 4 * ROWB));
-    uint4 r;
-    r.x = (uint16_t)lo[0] | ((uint32_t)(uint16_t)lo[1] << 16);
-    r.y = (uint16_t)lo[2] | ((uint32_t)(uint16_t)lo[3] << 16);
-    r.z = (uint16_t)hi[0] | ((uint32_t)(uint16_t)hi[1] << 16);
-    r.w = (uint16_t)hi[2] | ((uint32_t)(uint16_t)hi[3] << 16);
-    return r;
-  };
+  const int trLane = tfc_tr_lane(lane, ROWB);
   // Accumulator (r, c): halo row kt + rb + r, column shift cs + c, with a sliding window of NR rows (wave-uniform NR, NC in {2, 3}).
   //   transposed conv: rb = py, cs = px, 2 x 2 (filter tap jy = 1 - r, jx = 1 - c);  upsample conv: rb = cs = 0, (2+py) x (2+px)
   const int rb = UP ? 0 : py, cs = UP ? 0 : px;
@@ -3115,12 +2855,12 @@ tfc_wgradT_kernel(const bf16_t* __restrict__ x, int IH, int IW, int x_pitch, int
 #pragma unroll
     for (int r = 0; r < NR - 1; ++r)
 #pragma unroll
-      for (int c = 0; c < NC; ++c) rw[r][c] = tr16(hcol + r * rowb + c * ROWB);
+      for (int c = 0; c < NC; ++c) rw[r][c] = tfc_tr16(hcol + r * rowb + c * ROWB, 4 * ROWB);
 #pragma unroll
     for (int kt = 0; kt < 8; ++kt) {
 #pragma unroll
-      for (int c = 0; c < NC; ++c) rw[NR - 1][c] = tr16(hcol + (kt + NR - 1) * rowb + c * ROWB);
-      const bf16x8_t av = __builtin_bit_cast(bf16x8_t, tr16(acol + kt * 16 * ROWB));
+      for (int c = 0; c < NC; ++c) rw[NR - 1][c] = tfc_tr16(hcol + (kt + NR - 1) * rowb + c * ROWB, 4 * ROWB);
+      const bf16x8_t av = __builtin_bit_cast(bf16x8_t, tfc_tr16(acol + kt * 16 * ROWB, 4 * ROWB));
 #pragma unroll
       for (int r = 0; r < NR; ++r)
 #pragma unroll
@@ -3149,12 +2889,7 @@ tfc_wgradT_kernel(const bf16_t* __restrict__ x, int IH, int IW, int x_pitch, int
     __syncthreads();
   }
 
-  float4* ps = slab + ((size_t)bid * 4 + wave) * (NA * 4 * 64) + lane;
-#pragma unroll
-  for (int a = 0; a < NA; ++a)
-#pragma unroll
-    for (int q4 = 0; q4 < 4; ++q4)
-      ps[(a * 4 + q4) * 64] = make_float4(acc[a][4 * q4], acc[a][4 * q4 + 1], acc[a][4 * q4 + 2], acc[a][4 * q4 + 3]);
+  tfc_slab_store(slab + ((size_t)bid * 4 + wave) * (NA * 4 * 64) + lane, acc);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -3187,19 +2922,16 @@ tfc_wgradT2_kernel(const bf16_t* __restrict__ x, int IH, int IW, int x_pitch, in
   const int sp = bid / (nbw * ncb2);
   const int cb2 = pair2 % ncb2, nb = pair2 / ncb2;
 
-  f32x16_t acc[8];                                               // [half][row offset][column offset]
+  f32x16_t acc[2][4];                                            // [half][row offset * 2 + column offset]
 #pragma unroll
   for (int a = 0; a < 8; ++a)
 #pragma unroll
-    for (int j = 0; j < 16; ++j) acc[a][j] = 0.f;
+    for (int j = 0; j < 16; ++j) acc[a >> 2][a & 3][j] = 0.f;
 
   uint4 vdo[NDO], vha[NHA];
   auto tile_load = [&](int tl) {
-    int t = tl;
-    const int txb = t % tiles_x; t /= tiles_x;
-    const int tyb = t % tiles_y;
-    const int img = t / tiles_y;
-    const int a0 = tyb * TFC_TILE_H, b0 = txb * TFC_TILE_W;
+    int img, a0, b0;
+    tfc_tile_decode(tl, tiles_x, tiles_y, img, a0, b0);
 #pragma unroll
     for (int i = 0; i < NDO; ++i) {
       const int idx = tid + i * 256;                             // ((phase * 128) + pixel) * 4 + g
@@ -3237,19 +2969,7 @@ tfc_wgradT2_kernel(const bf16_t* __restrict__ x, int IH, int IW, int x_pitch, in
     }
   };
 
-  const int grp = lane >> 4, li = lane & 15;
-  const int cb16 = grp & 1, hk = grp >> 1, q = li >> 2, p = li & 3;
-  const int trLane = (8 * hk + q) * ROWB + cb16 * 32 + p * 8;
-  auto tr16 = [&](const unsigned char* p0) {
-    s16x4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16(LDS_PTR(s16x4_t, p0));
-    s16x4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16(LDS_PTR(s16x4_t, p0 + 4 * ROWB));
-    uint4 r;
-    r.x = (uint16_t)lo[0] | ((uint32_t)(uint16_t)lo[1] << 16);
-    r.y = (uint16_t)lo[2] | ((uint32_t)(uint16_t)lo[3] << 16);
-    r.z = (uint16_t)hi[0] | ((uint32_t)(uint16_t)hi[1] << 16);
-    r.w = (uint16_t)hi[2] | ((uint32_t)(uint16_t)hi[3] << 16);
-    return r;
-  };
+  const int trLane = tfc_tr_lane(lane, ROWB);
   constexpr int rowb = HW * ROWB;
   auto compute = [&]() {
     const unsigned char* acol = smem + wave * 128 * ROWB + trLane;
@@ -3258,21 +2978,21 @@ tfc_wgradT2_kernel(const bf16_t* __restrict__ x, int IH, int IW, int x_pitch, in
 #pragma unroll
     for (int hc = 0; hc < 2; ++hc)
 #pragma unroll
-      for (int c = 0; c < 2; ++c) rw[hc][0][c] = tr16(hcol + hc * HPLANE + c * ROWB);
+      for (int c = 0; c < 2; ++c) rw[hc][0][c] = tfc_tr16(hcol + hc * HPLANE + c * ROWB, 4 * ROWB);
 #pragma unroll
     for (int kt = 0; kt < 8; ++kt) {
 #pragma unroll
       for (int hc = 0; hc < 2; ++hc)
 #pragma unroll
-        for (int c = 0; c < 2; ++c) rw[hc][1][c] = tr16(hcol + hc * HPLANE + (kt + 1) * rowb + c * ROWB);
-      const bf16x8_t av = __builtin_bit_cast(bf16x8_t, tr16(acol + kt * 16 * ROWB));
+        for (int c = 0; c < 2; ++c) rw[hc][1][c] = tfc_tr16(hcol + hc * HPLANE + (kt + 1) * rowb + c * ROWB, 4 * ROWB);
+      const bf16x8_t av = __builtin_bit_cast(bf16x8_t, tfc_tr16(acol + kt * 16 * ROWB, 4 * ROWB));
 #pragma unroll
       for (int hc = 0; hc < 2; ++hc)
 #pragma unroll
         for (int r = 0; r < 2; ++r)
 #pragma unroll
           for (int c = 0; c < 2; ++c)
-            acc[hc * 4 + r * 2 + c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av, __builtin_bit_cast(bf16x8_t, rw[hc][r][c]), acc[hc * 4 + r * 2 + c], 0, 0, 0);
+            acc[hc][r * 2 + c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av, __builtin_bit_cast(bf16x8_t, rw[hc][r][c]), acc[hc][r * 2 + c], 0, 0, 0);
 #pragma unroll
       for (int hc = 0; hc < 2; ++hc)
 #pragma unroll
@@ -3295,12 +3015,7 @@ tfc_wgradT2_kernel(const bf16_t* __restrict__ x, int IH, int IW, int x_pitch, in
 #pragma unroll
   for (int hc = 0; hc < 2; ++hc) {
     const int lbid = sp * (nbw * ncb) + nb * ncb + 2 * cb2 + hc;
-    float4* ps = slab + ((size_t)lbid * 4 + wave) * (4 * 4 * 64) + lane;
-#pragma unroll
-    for (int a = 0; a < 4; ++a)
-#pragma unroll
-      for (int q4 = 0; q4 < 4; ++q4)
-        ps[(a * 4 + q4) * 64] = make_float4(acc[hc * 4 + a][4 * q4], acc[hc * 4 + a][4 * q4 + 1], acc[hc * 4 + a][4 * q4 + 2], acc[hc * 4 + a][4 * q4 + 3]);
+    tfc_slab_store(slab + ((size_t)lbid * 4 + wave) * (4 * 4 * 64) + lane, acc[hc]);
   }
 }
 
@@ -3335,11 +3050,8 @@ tfc_wgrad_head_kernel(const bf16_t* __restrict__ x, int IH, int IW, int x_pitch,
     for (int j = 0; j < 16; ++j) acc[a][j] = 0.f;
 
   auto tile_stage = [&](int tl) {                                 // global -> LDS (through registers, a few units at a time: 144 accumulator VGPRs are live)
-    int t = tl;
-    const int txb = t % tiles_x; t /= tiles_x;
-    const int tyb = t % tiles_y;
-    const int img = t / tiles_y;
-    const int a0 = tyb * TFC_TILE_H, b0 = txb * TFC_TILE_W;
+    int img, a0, b0;
+    tfc_tile_decode(tl, tiles_x, tiles_y, img, a0, b0);
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
       const int idx = tid + i * 256;                             // pixel * 4 + phase
@@ -3370,20 +3082,8 @@ tfc_wgrad_head_kernel(const bf16_t* __restrict__ x, int IH, int IW, int x_pitch,
       }
     }
   };
-  const int grp = lane >> 4, li = lane & 15;
-  const int cb16 = grp & 1, hk = grp >> 1, q = li >> 2, p = li & 3;
-  const int trA = (8 * hk + q) * ROWB + cb16 * 32 + p * 8;
-  const int trB = (8 * hk + q) * HB + wave * 64 + cb16 * 32 + p * 8;
-  auto tr16 = [&](const unsigned char* p0, int rowb4) {
-    s16x4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16(LDS_PTR(s16x4_t, p0));
-    s16x4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16(LDS_PTR(s16x4_t, p0 + rowb4));
-    uint4 r;
-    r.x = (uint16_t)lo[0] | ((uint32_t)(uint16_t)lo[1] << 16);
-    r.y = (uint16_t)lo[2] | ((uint32_t)(uint16_t)lo[3] << 16);
-    r.z = (uint16_t)hi[0] | ((uint32_t)(uint16_t)hi[1] << 16);
-    r.w = (uint16_t)hi[2] | ((uint32_t)(uint16_t)hi[3] << 16);
-    return r;
-  };
+  const int trA = tfc_tr_lane(lane, ROWB);
+  const int trB = tfc_tr_lane(lane, HB) + wave * 64;
   auto compute = [&]() {
     const unsigned char* acol = smem + trA;
     const unsigned char* hcol = smem + DY_BYTES + trB;
@@ -3392,12 +3092,12 @@ tfc_wgrad_head_kernel(const bf16_t* __restrict__ x, int IH, int IW, int x_pitch,
 #pragma unroll
     for (int r = 0; r < 2; ++r)
 #pragma unroll
-      for (int c = 0; c < 3; ++c) rw[r][c] = tr16(hcol + r * rowb + c * HB, 4 * HB);
+      for (int c = 0; c < 3; ++c) rw[r][c] = tfc_tr16(hcol + r * rowb + c * HB, 4 * HB);
 #pragma unroll
     for (int kt = 0; kt < 8; ++kt) {
 #pragma unroll
-      for (int c = 0; c < 3; ++c) rw[2][c] = tr16(hcol + (kt + 2) * rowb + c * HB, 4 * HB);
-      const bf16x8_t av = __builtin_bit_cast(bf16x8_t, tr16(acol + kt * 16 * ROWB, 4 * ROWB));
+      for (int c = 0; c < 3; ++c) rw[2][c] = tfc_tr16(hcol + (kt + 2) * rowb + c * HB, 4 * HB);
+      const bf16x8_t av = __builtin_bit_cast(bf16x8_t, tfc_tr16(acol + kt * 16 * ROWB, 4 * ROWB));
 #pragma unroll
       for (int r = 0; r < 3; ++r)
 #pragma unroll
@@ -3415,32 +3115,16 @@ tfc_wgrad_head_kernel(const bf16_t* __restrict__ x, int IH, int IW, int x_pitch,
     compute();
     __syncthreads();
   }
-  float4* ps = slab + ((size_t)sp * 4 + wave) * (9 * 4 * 64) + lane;
-#pragma unroll
-  for (int a = 0; a < 9; ++a)
-#pragma unroll
-    for (int q4 = 0; q4 < 4; ++q4)
-      ps[(a * 4 + q4) * 64] = make_float4(acc[a][4 * q4], acc[a][4 * q4 + 1], acc[a][4 * q4 + 2], acc[a][4 * q4 + 3]);
+  tfc_slab_store(slab + ((size_t)sp * 4 + wave) * (9 * 4 * 64) + lane, acc);
 }
 // position = ((w * 9 + a) * 4 + q4) * 64 + lane of the 9216 float4 of a workgroup slab. Stage 1 sums the slabs position by position (16 positions x 16
 // slab-lanes per block, slab-lanes take sp = l, l + 16, ... ascending and meet in LDS in lane order) and leaves the total IN PLACE in slab 0.
 __global__ void __launch_bounds__(256)
-tfc_wgrad_head_reduce_kernel(float4* __restrict__ slab, int nsplit) {
-  __shared__ float4 red[16][16];
-  const int pl = threadIdx.x & 15, sl = threadIdx.x >> 4;
-  const int pos = blockIdx.x * 16 + pl;
-  float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll 4
-  for (int sp = sl; sp < nsplit; sp += 16) {
-    const float4 v = slab[(size_t)sp * 9216 + pos];
-    s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w;
-  }
-  red[sl][pl] = s;
-  __syncthreads();
-  if (sl != 0) return;
-#pragma unroll
-  for (int i = 1; i < 16; ++i) { const float4 v = red[i][pl]; s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w; }
-  slab[pos] = s;
+tfc_wgrad_head_reduce_kernel(float4* slab, int nsplit) {
+  const int pos = blockIdx.x * 16 + (threadIdx.x & 15);
+  const size_t row[1] = {(size_t)pos};
+  float4 sum[1];
+  if (tfc_slab_sum<16, 16, 1>(slab, row, 9216, nsplit, sum)) slab[pos] = sum[0];
 }
 // Stage 2 (replaces tfc_wgrad_finish_kernel for the head): one thread per (oc, c) GATHERS its 16 filter taps -- row (phase * 8 + oc) of source offset
 // a = ir * 3 + ic feeds every filter tap that collapses onto that offset in that phase, so a tap is the sum of four rows (one per phase, phase order);
@@ -3460,8 +3144,7 @@ tfc_wgrad_head_finish_kernel(const float4* __restrict__ S, float* __restrict__ g
 #pragma unroll
       for (int ph = 0; ph < 4; ++ph) {
         const int wpy = ph >> 1, wpx = ph & 1;
-        const int sy = wpy ? (ky == 0 ? 0 : (ky == 3 ? 2 : 1)) : (ky >> 1);   // source row offset + 1 of filter row ky in this phase
-        const int sx = wpx ? (kx == 0 ? 0 : (kx == 3 ? 2 : 1)) : (kx >> 1);
+        const int sy = tfc_up_src(wpy, ky), sx = tfc_up_src(wpx, kx);        // source (row, column) offset + 1 of filter tap (ky, kx) in this phase
         const float4 q = S[((size_t)(w * 9 + sy * 3 + sx) * 4 + ph) * 64 + lane];
         t += e == 0 ? q.x : (e == 1 ? q.y : (e == 2 ? q.z : q.w));
       }
@@ -3487,37 +3170,26 @@ tfc_wgrad_head_finish_kernel(const float4* __restrict__ S, float* __restrict__ g
 //   row of register j = 4q+e in lane l:  e + 8q + 4*(l >> 5)
 __global__ void __launch_bounds__(256)
 tfc_wgrad_reduce_kernel(const float4* __restrict__ slab, float* acc, const TfcPlane pd, int kind, int T, int nsplit, int npairs, int ncbx,
-                        int Nn_real, int Cw_real, int wave_only) {
-  __shared__ float4 part[4][64];
-  const int lane = threadIdx.x & 63, k = threadIdx.x >> 6;
+                        int Nn_real, int Cw_real, int wave_only, int pair0) {
+  const int lane = threadIdx.x & 63;
   int rowid = blockIdx.x;                                        // ((pair * 4 + wave) * T + a) * 4 + q   (wave_only >= 0: (pair * T + a) * 4 + q)
   const int q = rowid & 3; rowid >>= 2;
   const int a = rowid % T; rowid /= T;
   const int wave = wave_only >= 0 ? wave_only : (rowid & 3);
   const int pair = wave_only >= 0 ? rowid : (rowid >> 2);
   const size_t blk_units = (size_t)4 * T * 4 * 64;
-  const float4* p0 = slab + ((size_t)pair * 4 + wave) * (T * 4 * 64) + (a * 4 + q) * 64 + lane;
-  float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll 4
-  for (int sp = k; sp < nsplit; sp += 4) {
-    const float4 v = p0[(size_t)sp * npairs * blk_units];
-    s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w;
-  }
-  part[k][lane] = s;
-  __syncthreads();
-  if (k != 0) return;
-#pragma unroll
-  for (int i = 1; i < 4; ++i) { const float4 v = part[i][lane]; s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w; }
-  const int cbx = pair % ncbx, nb = pair / ncbx;
+  const size_t row[1] = {((size_t)pair * 4 + wave) * (T * 4 * 64) + (a * 4 + q) * 64 + lane};
+  float4 sum[1];
+  if (!tfc_slab_sum<4, 64, 1>(slab, row, (size_t)npairs * blk_units, nsplit, sum)) return;
+  const float4 s = sum[0];
+  const int cbx = (pair0 + pair) % ncbx, nb = (pair0 + pair) / ncbx;   // the slabs of one round hold pairs pair0 .. pair0 + npairs - 1
   int mask = 0, n0, c;
   if (kind == 3) {                                               // tfc_wgradT_kernel<true>: wave = phase, a = ir*3 + ic (collapsed taps of the upsample conv)
     const int wpy = wave >> 1, wpx = wave & 1, ir = a / 3, ic = a % 3;
     if (ir < 2 + wpy && ic < 2 + wpx)
       for (int ky = 0; ky < 4; ++ky)
         for (int kx = 0; kx < 4; ++kx) {
-          const int sy = wpy ? (ky == 0 ? 0 : (ky == 3 ? 2 : 1)) : (ky >> 1);   // source row offset + 1 of filter row ky in this phase
-          const int sx = wpx ? (kx == 0 ? 0 : (kx == 3 ? 2 : 1)) : (kx >> 1);
-          if (sy == ir && sx == ic) mask |= 1 << (ky * 4 + kx);
+          if (tfc_up_src(wpy, ky) == ir && tfc_up_src(wpx, kx) == ic) mask |= 1 << (ky * 4 + kx);
         }
     n0 = nb * 32;
     c = cbx * 32 + (lane & 31);
@@ -3538,43 +3210,6 @@ tfc_wgrad_reduce_kernel(const float4* __restrict__ slab, float* acc, const TfcPl
     c = (cbx * 2 + (wave >> 1)) * 32 + (lane & 31);
   }
   n0 += 8 * q + 4 * (lane >> 5);
-  if (c >= Cw_real) return;
-  const float sv[4] = {s.x, s.y, s.z, s.w};
-  for (int m = mask; m; m &= m - 1) {
-    const int slot = __ffs(m) - 1;
-#pragma unroll
-    for (int e = 0; e < 4; ++e)
-      if (n0 + e < Nn_real) acc[((size_t)slot * Nn_real + n0 + e) * Cw_real + c] += sv[e];
-  }
-}
-// bf16x3 form of the kind-0 reduction above (tfc_wgrad_x3_kernel's slabs): a layer with more (n-block, c-block) pairs than slabs runs in rounds,
-// and the slabs of one round hold pairs pair0 .. pair0 + npairs - 1
-__global__ void __launch_bounds__(256)
-tfc_wgrad_x3_reduce_kernel(const float4* __restrict__ slab, float* acc, const TfcPlane pd, int T, int nsplit, int npairs, int ncbx, int Nn_real,
-                           int Cw_real, int pair0) {
-  __shared__ float4 part[4][64];
-  const int lane = threadIdx.x & 63, k = threadIdx.x >> 6;
-  int rowid = blockIdx.x;                                        // ((pair * 4 + wave) * T + a) * 4 + q
-  const int q = rowid & 3; rowid >>= 2;
-  const int a = rowid % T; rowid /= T;
-  const int wave = rowid & 3, pair = rowid >> 2;
-  const size_t blk_units = (size_t)4 * T * 4 * 64;
-  const float4* p0 = slab + ((size_t)pair * 4 + wave) * (T * 4 * 64) + (a * 4 + q) * 64 + lane;
-  float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll 4
-  for (int sp = k; sp < nsplit; sp += 4) {
-    const float4 v = p0[(size_t)sp * npairs * blk_units];
-    s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w;
-  }
-  part[k][lane] = s;
-  __syncthreads();
-  if (k != 0) return;
-#pragma unroll
-  for (int i = 1; i < 4; ++i) { const float4 v = part[i][lane]; s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w; }
-  const int gp = pair0 + pair, cbx = gp % ncbx, nb = gp / ncbx;
-  const int tap = (a >> 1) * 4 + wave;
-  const int mask = tap < pd.ntaps ? pd.tap_mask[tap] : 0;
-  const int n0 = nb * 64 + (a & 1) * 32 + 8 * q + 4 * (lane >> 5), c = cbx * 32 + (lane & 31);
   if (c >= Cw_real) return;
   const float sv[4] = {s.x, s.y, s.z, s.w};
   for (int m = mask; m; m &= m - 1) {
@@ -3619,8 +3254,7 @@ tfc_wgrad_finish_kernel(float* __restrict__ acc, float* __restrict__ grad, int N
 __global__ void __launch_bounds__(512)
 tfc_wgrad_reduce_fin_kernel(const float4* __restrict__ slab, float* __restrict__ grad, int kind, int T, int nsplit, int npairs, int ncbx,
                             int Nn_real, int Cw_real, long long sn, long long sc, int accumulate) {
-  __shared__ float4 part[7][4][64];
-  const int lane = threadIdx.x & 63, k = threadIdx.x >> 6;
+  const int lane = threadIdx.x & 63;
   int b = blockIdx.x;
   const int g = b & 3; b >>= 2;
   const int q = b & 3; b >>= 2;
@@ -3640,27 +3274,7 @@ tfc_wgrad_reduce_fin_kernel(const float4* __restrict__ slab, float* __restrict__
     row[kx] = (size_t)pair * blk_units + ((size_t)wv * T + a) * 256 + q * 64 + lane;
   }
   float4 s[4];
-#pragma unroll
-  for (int kx = 0; kx < 4; ++kx) s[kx] = make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll 2
-  for (int sp = k; sp < nsplit; sp += 8) {
-    const size_t o = (size_t)sp * npairs * blk_units;
-#pragma unroll
-    for (int kx = 0; kx < 4; ++kx) {
-      const float4 v = slab[o + row[kx]];
-      s[kx].x += v.x; s[kx].y += v.y; s[kx].z += v.z; s[kx].w += v.w;
-    }
-  }
-  if (k > 0) {
-#pragma unroll
-    for (int kx = 0; kx < 4; ++kx) part[k - 1][kx][lane] = s[kx];
-  }
-  __syncthreads();
-  if (k != 0) return;
-#pragma unroll
-  for (int i = 0; i < 7; ++i)
-#pragma unroll
-    for (int kx = 0; kx < 4; ++kx) { const float4 v = part[i][kx][lane]; s[kx].x += v.x; s[kx].y += v.y; s[kx].z += v.z; s[kx].w += v.w; }
+  if (!tfc_slab_sum<8, 64, 4>(slab, row, (size_t)npairs * blk_units, nsplit, s)) return;
   const int cbx = pair % ncbx, nb = pair / ncbx;
   const int c = cbx * 32 + (lane & 31);
   const int n0 = (kind == 0 ? nb * 64 + ni * 32 : nb * 32) + 8 * q + 4 * (lane >> 5);
@@ -4403,33 +4017,24 @@ static hipError_t wgrad_run_splits(float4* slab, size_t wg_float4, int npairs, i
   if (nsplit <= ntiles || !slab) return hipSuccess;
   return hipMemsetAsync(slab + (size_t)npairs * ntiles * wg_float4, 0, (size_t)npairs * (nsplit - ntiles) * wg_float4 * sizeof(float4), st);
 }
-// the split count of one round of the bf16x3 weight gradient (np <= 512 (n-block, c-block) pairs): launcher and plan query alike
-static int wgrad_x3_nsplit(const TfcGather& d, int np, bool inv) {
-  return wgrad_split(512, np, (inv ? TFC_REF_BATCH : d.nimg) * d.tiles_y * d.tiles_x);
-}
 static bool plane_is_raster16(const TfcPlane& pl) {
   bool raster = pl.ntaps == 16;
   for (int t = 0; t < 16 && raster; ++t) raster = pl.tap_dy[t] == (t >> 2) && pl.tap_dx[t] == (t & 3);
   return raster;
 }
-void tfc_plan_wgrad(int dt, const TfcGather& d, int Nn_pad, bool have_slab, bool inv, TfcConvPlan* p) {
+// The slab budget (api.hip reserves 512 workgroups x 128 KiB) holds one round of at most 512 (n-block, c-block) pairs, in every compute mode: a layer
+// with more pairs (e.g. 2048 x 1024) runs in rounds, each reduced into the accumulator before the next reuses the slabs. The plan is the one of the
+// round that starts at pair `pair0`; the plan query reports the first round's.
+void tfc_plan_wgrad(int dt, const TfcGather& d, int Nn_pad, bool inv, TfcConvPlan* p, int pair0) {
   *p = TfcConvPlan{};
   p->form = -1;
   const int nbw = (Nn_pad + 63) / 64, ncb = (d.Cin_pad + 31) / 32;
   const int ntiles = (inv ? TFC_REF_BATCH : d.nimg) * d.tiles_y * d.tiles_x;
-  if (dt == TFC_DT_BF16X3) {                                      // rounds of at most 512 (n-block, c-block) pairs; the record is the first round's
-    const int np = nbw * ncb < 512 ? nbw * ncb : 512;
-    p->kernel = TFC_K_WGRAD_X3;
-    p->nsplit = wgrad_x3_nsplit(d, np, inv);
-    return;
-  }
+  const auto round_pairs = [&](int npairs_all) { return npairs_all - pair0 < 512 ? npairs_all - pair0 : 512; };
   // split-K over pixel tiles: the kernel runs 2 workgroups per CU (208 VGPRs, 60 KB LDS), so aim at exactly 512 of them --
-  // one full round, no half-empty tail, and the fewest atomic flushes
-  p->kernel = TFC_K_WGRAD;
-  p->nsplit = wgrad_split(512, nbw * ncb, ntiles);
-  // slab budget (api.hip reserves 512 workgroups x 128 KiB): a layer with more than 512 (n-block, c-block) pairs (e.g. 2048 x 1024) cannot keep
-  // one slab per workgroup -- such a layer flushes with fp32 atomics instead (slab = nullptr), it never writes past the region
-  p->atomics = !have_slab || (long long)nbw * ncb * p->nsplit > 512;
+  // one full round, no half-empty tail, and the fewest slabs to reduce
+  p->kernel = dt == TFC_DT_BF16X3 ? TFC_K_WGRAD_X3 : TFC_K_WGRAD;
+  p->nsplit = wgrad_split(512, round_pairs(nbw * ncb), ntiles);
   if (dt != TFC_DT_BF16) return;
   bool t22 = d.plane[0].ntaps == 4 && (g_tfc_force_cfg < 0 || (g_tfc_force_cfg & 15) != 2);
   int seen = 0;
@@ -4440,50 +4045,46 @@ void tfc_plan_wgrad(int dt, const TfcGather& d, int Nn_pad, bool have_slab, bool
   if (t22 && seen == 15) {                                       // 2 x 2-tap plane: quadrant-per-wave kernel (64 n x 64 c per workgroup)
     const int ncb2 = (d.Cin_pad + 63) / 64;
     p->kernel = TFC_K_WGRAD22;
-    p->nsplit = wgrad_split(512, nbw * ncb2, ntiles);
-    p->atomics = !have_slab || (long long)nbw * ncb2 * p->nsplit > 512;   // same slab budget
+    p->nsplit = wgrad_split(512, round_pairs(nbw * ncb2), ntiles);
     return;
   }
   static const bool c8_off_env = [] { const char* e = getenv("TFC_WGRAD_NO_C8"); return e && atoi(e) != 0; }();   // A/B knob for profiling
   bool ident = plane_is_raster16(d.plane[0]);
   for (int t = 0; t < 16 && ident; ++t) ident = d.plane[0].tap_mask[t] == (1 << t);
-  if (!p->atomics && ident && !(c8_off_env && !inv) && d.Cin_pad == 8 && d.in_pitch == 8 && Nn_pad <= 64 && d.ph_n <= 1 && d.SS == 1 && d.OS == 1 &&
+  if (ident && !(c8_off_env && !inv) && d.Cin_pad == 8 && d.in_pitch == 8 && Nn_pad <= 64 && d.ph_n <= 1 && d.SS == 1 && d.OS == 1 &&
       d.plane[0].hh <= TFC_MAX_HH && d.plane[0].hw <= TFC_MAX_HW && (g_tfc_force_cfg < 0 || (g_tfc_force_cfg & 15) == 15)) {
     p->kernel = TFC_K_WGRAD_C8;
     p->nsplit = ntiles < 512 ? ntiles : 512;                      // 2 workgroups per CU, 32 KB of slab each
   }
 }
+// fin (bf16 only): see tfc_fin_eligible. The reduce-into-gradient pass writes (=) the gradient, so it applies to single-round launches only.
 template <typename T>
 static hipError_t launch_wgrad_t(int dt, const TfcGather& d, const void* dO, const void* in, float* dwacc, float4* slab, int Nn_pad, int Nn_real,
                                  int Cw_real, hipStream_t st, TfcWgradFin* fin) {
-  constexpr int ES = sizeof(T);
+  if (!slab) return hipErrorInvalidValue;
+  constexpr bool BF16 = std::is_same<T, bf16_t>::value;
+  const bool inv = g_tfc_batch_invariant != 0;
   const int nbw = (Nn_pad + 63) / 64, ncb = (d.Cin_pad + 31) / 32;
   const int ntiles = d.nimg * d.tiles_y * d.tiles_x;
   TfcConvPlan plan;
-  tfc_plan_wgrad(dt, d, Nn_pad, slab != nullptr, g_tfc_batch_invariant != 0, &plan);
-  const int nsplit = plan.nsplit;
-  if (plan.atomics) slab = nullptr;
-  const int lds = (2 * 128 * 32 * ES + TFC_MAX_HH * TFC_MAX_HW * 32 * ES) * (ES == 2 ? 2 : 1);
-  if constexpr (ES == 2) {
+  tfc_plan_wgrad(dt, d, Nn_pad, inv, &plan, 0);
+  if constexpr (BF16) {
     if (plan.kernel == TFC_K_WGRAD22) {                          // 2 x 2-tap plane: quadrant-per-wave kernel (64 n x 64 c per workgroup)
       const int ncb2 = (d.Cin_pad + 63) / 64;
-      const int ns = nsplit;
-      int run = 0;
-      if (hipError_t e = wgrad_run_splits(slab, 4 * 4 * 4 * 64, nbw * ncb2, ns, ntiles, st, &run)) return e;
       const int lds22 = 2 * (2 * 128 * 64 + 2 * d.plane[0].hh * d.plane[0].hw * 64);
-      TFC_LAUNCH((tfc_wgrad22_kernel<T>), dim3(nbw * ncb2 * run), dim3(256), lds22, st, d, (const T*)dO, (const T*)in, dwacc, slab,
-                         Nn_pad, Nn_real, Cw_real, nbw, ncb2, ns);
-      if (slab)
-        TFC_LAUNCH(tfc_wgrad_reduce_kernel, dim3(nbw * ncb2 * 4 * 4 * 4), dim3(256), 0, st, slab, dwacc, d.plane[0], 1, 4, ns, nbw * ncb2,
-                           ncb2, Nn_real, Cw_real, -1);
+      for (int p0 = 0; p0 < nbw * ncb2; p0 += 512) {
+        const int np = nbw * ncb2 - p0 < 512 ? nbw * ncb2 - p0 : 512;
+        if (p0) tfc_plan_wgrad(dt, d, Nn_pad, inv, &plan, p0);
+        const int ns = plan.nsplit;
+        int run = 0;
+        if (hipError_t e = wgrad_run_splits(slab, 4 * 4 * 4 * 64, np, ns, ntiles, st, &run)) return e;
+        TFC_LAUNCH((tfc_wgrad22_kernel<T>), dim3(np * run), dim3(256), lds22, st, d, (const T*)dO, (const T*)in, slab, Nn_pad, np, ncb2, ns, p0);
+        TFC_LAUNCH(tfc_wgrad_reduce_kernel, dim3(np * 4 * 4 * 4), dim3(256), 0, st, slab, dwacc, d.plane[0], 1, 4, ns, np, ncb2, Nn_real, Cw_real, -1, p0);
+      }
       return hipGetLastError();
     }
-  }
-  const int tpw = (d.plane[0].ntaps + 3) / 4;                    // taps per wave (tap t belongs to wave t % 4)
-  const bool raster = (ES == 2) && plane_is_raster16(d.plane[0]);
-  if constexpr (ES == 2) {
     if (plan.kernel == TFC_K_WGRAD_C8) {
-      const int ns = nsplit;
+      const int ns = plan.nsplit;
       int run = 0;
       if (hipError_t e = wgrad_run_splits(slab, 4 * 2 * 4 * 64, 1, ns, ntiles, st, &run)) return e;
       TFC_LAUNCH(tfc_wgrad_c8_kernel, dim3(run), dim3(256), 0, st, d, (const bf16_t*)dO, (const bf16_t*)in, slab, Nn_pad, ns);
@@ -4494,25 +4095,31 @@ static hipError_t launch_wgrad_t(int dt, const TfcGather& d, const void* dO, con
       return hipGetLastError();
     }
   }
-  int tw = 4;
-  if (!raster) tw = tpw <= 1 ? 1 : (tpw >= 4 ? 4 : tpw);
-  int run = 0;
-  if (hipError_t e = wgrad_run_splits(slab, (size_t)4 * tw * 2 * 4 * 64, nbw * ncb, nsplit, ntiles, st, &run)) return e;
-  const dim3 grid(nbw * ncb * run);
-#define TFC_WG(TPW_, R_) TFC_LAUNCH((tfc_wgrad_kernel<T, TPW_, R_>), grid, dim3(256), lds, st, d, (const T*)dO, (const T*)in, dwacc, slab, \
-                                            Nn_pad, Nn_real, Cw_real, nbw, ncb, nsplit)
-  if (raster) TFC_WG(4, true);
-  else if (tw == 1) TFC_WG(1, false); else if (tw == 2) TFC_WG(2, false); else if (tw == 3) TFC_WG(3, false); else TFC_WG(4, false);
-#undef TFC_WG
+  const int tpw = (d.plane[0].ntaps + 3) / 4;                    // taps per wave (tap t belongs to wave t % 4)
+  const bool raster = WgradOp<T>::TR && plane_is_raster16(d.plane[0]);
+  const int tw = raster ? 4 : (tpw <= 1 ? 1 : (tpw >= 4 ? 4 : tpw));
   bool ident = raster;                                           // identity tap masks: tap t IS filter slot t
   for (int t = 0; t < 16 && ident; ++t) ident = d.plane[0].tap_mask[t] == (1 << t);
-  if (slab && ident && d.ph_n <= 1 && tfc_fin_eligible(fin, nbw * ncb, 8)) {
-    TFC_LAUNCH(tfc_wgrad_reduce_fin_kernel, dim3(nbw * ncb * 8 * 4), dim3(512), 0, st, slab, fin->grad, 0, 8, nsplit, nbw * ncb, ncb, Nn_real,
-               Cw_real, fin->sn, fin->sc, fin->accumulate);
-    fin->done = true;
-  } else if (slab)
-    TFC_LAUNCH(tfc_wgrad_reduce_kernel, dim3(nbw * ncb * 4 * (tw * 2) * 4), dim3(256), 0, st, slab, dwacc, d.plane[0], 0, tw * 2, nsplit,
-                       nbw * ncb, ncb, Nn_real, Cw_real, -1);
+  for (int p0 = 0; p0 < nbw * ncb; p0 += 512) {
+    const int np = nbw * ncb - p0 < 512 ? nbw * ncb - p0 : 512;
+    if (p0) tfc_plan_wgrad(dt, d, Nn_pad, inv, &plan, p0);
+    const int nsplit = plan.nsplit;
+    int run = 0;
+    if (hipError_t e = wgrad_run_splits(slab, (size_t)4 * tw * 2 * 4 * 64, np, nsplit, ntiles, st, &run)) return e;
+    const dim3 grid(np * run);
+#define TFC_WG(TPW_, R_) TFC_LAUNCH((tfc_wgrad_kernel<T, TPW_, R_>), grid, dim3(256), WgradOp<T>::LDS_BYTES, st, d, (const T*)dO, (const T*)in, slab, \
+                                    Nn_pad, np, ncb, nsplit, p0)
+    if (raster) TFC_WG(4, true);
+    else if (tw == 1) TFC_WG(1, false); else if (tw == 2) TFC_WG(2, false); else if (tw == 3) TFC_WG(3, false); else TFC_WG(4, false);
+#undef TFC_WG
+    if (np == nbw * ncb && ident && d.ph_n <= 1 && tfc_fin_eligible(fin, np, 8)) {
+      TFC_LAUNCH(tfc_wgrad_reduce_fin_kernel, dim3(np * 8 * 4), dim3(512), 0, st, slab, fin->grad, 0, 8, nsplit, np, ncb, Nn_real,
+                 Cw_real, fin->sn, fin->sc, fin->accumulate);
+      fin->done = true;
+    } else
+      TFC_LAUNCH(tfc_wgrad_reduce_kernel, dim3(np * 4 * (tw * 2) * 4), dim3(256), 0, st, slab, dwacc, d.plane[0], 0, tw * 2, nsplit, np, ncb,
+                 Nn_real, Cw_real, -1, p0);
+  }
   return hipGetLastError();
 }
 // fused first-block backward (tfc_wgrad_c8_fused_kernel): d = the TFC_OP_CONV pass-2 descriptor of the layer (8 padded input channels, 64 outputs)
@@ -4608,7 +4215,7 @@ bool tfc_launch_wgrad_phases_fused(int up, const void* x, int N, int IH, int IW,
                        Nn_pad, N, (float4*)slab, nbw, ncb, nsplit);
     for (int wv = 0; wv < 4; ++wv)                                // the phases overlap on the filter taps: one reduce pass per phase, in order
       TFC_LAUNCH(tfc_wgrad_reduce_kernel, dim3(nbw * ncb * T * 4), dim3(256), 0, st, (const float4*)slab, dwacc, none, 3, T, nsplit,
-                         nbw * ncb, ncb, Cout, Cin, wv);
+                         nbw * ncb, ncb, Cout, Cin, wv, 0);
   } else {
     if (plan.kernel == TFC_K_WGRADT2)                             // 32 n x 64 c tiles, 2 workgroups per CU
       TFC_LAUNCH(tfc_wgradT2_kernel, dim3(nbw * (ncb / 2) * run), dim3(256), 4 * 128 * 64 + 2 * (TFC_TILE_H + 2) * (TFC_TILE_W + 2) * 64, st, (const bf16_t*)x, IH, IW,
@@ -4622,49 +4229,17 @@ bool tfc_launch_wgrad_phases_fused(int up, const void* x, int N, int IH, int IW,
       fin->done = true;
     } else
       TFC_LAUNCH(tfc_wgrad_reduce_kernel, dim3(nbw * ncb * 4 * T * 4), dim3(256), 0, st, (const float4*)slab, dwacc, none, 2, T, nsplit,
-                         nbw * ncb, ncb, Cout, Cin, -1);
+                         nbw * ncb, ncb, Cout, Cin, -1, 0);
   }
   *err = hipGetLastError();
   return true;
 }
-// bf16x3 weight gradient: never atomics. At most 512 slabs per launch (the budget api.hip reserves): the split over pixel tiles shrinks to fit, and
-// a layer with more than 512 (n-block, c-block) pairs runs in rounds of 512 pairs, each reduced into dwacc before the next reuses the slabs.
-static hipError_t launch_wgrad_x3(const TfcGather& d, const void* dO, const void* in, float* dwacc, float4* slab, int Nn_pad, int Nn_real, int Cw_real,
-                                  hipStream_t st) {
-  if (!slab) return hipErrorInvalidValue;
-  const int nbw = (Nn_pad + 63) / 64, ncb = (d.Cin_pad + 31) / 32;
-  const int ntiles = d.nimg * d.tiles_y * d.tiles_x;
-  const int tpw = (d.plane[0].ntaps + 3) / 4;
-  const bool raster = plane_is_raster16(d.plane[0]);
-  const int tw = raster ? 4 : (tpw < 1 ? 1 : tpw);
-  const int lds = 2 * (2 * 128 * 64 + TFC_MAX_HH * TFC_MAX_HW * 64);
-  const int npairs_all = nbw * ncb;
-  for (int p0 = 0; p0 < npairs_all; p0 += 512) {
-    const int np = npairs_all - p0 < 512 ? npairs_all - p0 : 512;
-    const int nsplit = wgrad_x3_nsplit(d, np, g_tfc_batch_invariant != 0);   // tfc_plan_wgrad reports the first round's
-    int run = 0;
-    if (hipError_t e = wgrad_run_splits(slab, (size_t)4 * tw * 2 * 4 * 64, np, nsplit, ntiles, st, &run)) return e;
-    const dim3 grid(np * run);
-#define TFC_WG3(TPW_, R_) TFC_LAUNCH((tfc_wgrad_x3_kernel<TPW_, R_>), grid, dim3(256), lds, st, d, (const float*)dO, (const float*)in, slab, Nn_pad, np, \
-                                     ncb, nsplit, p0)
-    if (raster) TFC_WG3(4, true);
-    else if (tw == 1) TFC_WG3(1, false);
-    else if (tw == 2) TFC_WG3(2, false);
-    else if (tw == 3) TFC_WG3(3, false);
-    else TFC_WG3(4, false);
-#undef TFC_WG3
-    TFC_LAUNCH(tfc_wgrad_x3_reduce_kernel, dim3(np * 4 * (tw * 2) * 4), dim3(256), 0, st, (const float4*)slab, dwacc, d.plane[0], tw * 2, nsplit, np,
-               ncb, Nn_real, Cw_real, p0);
-  }
-  return hipGetLastError();
-}
-
-// slab: >= TFC_WGRAD_SLAB_BYTES of scratch for the split-K partials (bf16 path); nullptr = flush with fp32 atomics (fp32 parity mode)
+// slab: >= TFC_WGRAD_SLAB_BYTES of scratch for the split-K partials, required in every compute mode (nullptr: hipErrorInvalidValue)
 hipError_t tfc_launch_wgrad(int dt, const TfcGather& d, const void* dO, const void* in, float* dwacc, void* slab, int Nn_pad,
                             int Nn_real, int Cw_real, hipStream_t st, TfcWgradFin* fin) {
-  if (dt == TFC_DT_BF16X3) return launch_wgrad_x3(d, dO, in, dwacc, (float4*)slab, Nn_pad, Nn_real, Cw_real, st);
+  if (dt == TFC_DT_BF16X3) return launch_wgrad_t<tfc_x3_t>(dt, d, dO, in, dwacc, (float4*)slab, Nn_pad, Nn_real, Cw_real, st, nullptr);
   return dt == TFC_DT_BF16 ? launch_wgrad_t<bf16_t>(dt, d, dO, in, dwacc, (float4*)slab, Nn_pad, Nn_real, Cw_real, st, fin)
-                           : launch_wgrad_t<float>(dt, d, dO, in, dwacc, (float4*)slab, Nn_pad, Nn_real, Cw_real, st, nullptr);   // fp32 too: slabs, not atomics (deterministic)
+                           : launch_wgrad_t<float>(dt, d, dO, in, dwacc, (float4*)slab, Nn_pad, Nn_real, Cw_real, st, nullptr);
 }
 hipError_t tfc_launch_wgrad_finish(float* acc, float* grad, int Nn, int Cw, long long sn, long long sc,
                                    int accumulate, hipStream_t st) {

@@ -108,11 +108,10 @@ struct TfcConvPlan {
   int nsplit;                 // split count over pixel tiles (weight gradients; 1 otherwise)
   int wpi;                    // workgroups per image where the kernel's slot layout depends on it (first-block backward; 0 otherwise)
   int pat;                    // compile-time tap pattern (0: table driven)
-  int atomics;                // weight gradient flushed with fp32 atomics (no slab budget for the layer)
   int per;                    // tiles per workgroup where the kernel walks a fixed run of tiles (first-block kernels; 0 otherwise)
 };
 void tfc_plan_igemm(int dt, const TfcGather& d, int flags, int ncu, bool inv, TfcConvPlan* p);
-void tfc_plan_wgrad(int dt, const TfcGather& d, int Nn_pad, bool have_slab, bool inv, TfcConvPlan* p);
+void tfc_plan_wgrad(int dt, const TfcGather& d, int Nn_pad, bool inv, TfcConvPlan* p, int pair0);   // pair0: first pair of the round (0: what the query reports)
 bool tfc_plan_wgrad_phases(int up, int N, int IH, int IW, int x_pitch, int Cin_pad, int Cout, bool have_fin, bool inv, TfcConvPlan* p);
 void tfc_plan_first_block(int pass, int N, int H, int W, int ncu, bool inv, TfcConvPlan* p);
 int tfc_act_grid_cap(int N, bool inv);             // elementwise.hip: grid-stride workgroups per image of the fused activation passes
