@@ -1,6 +1,7 @@
 """GPU parity tests, kernel level: every HIP entry point of include/tfc_gan.h against the CPU oracle / torch-CPU fp32 on the
 same seeded inputs.  fp32 mode (TFC_DT_F32) must agree to fp32 round-off; bf16 mode is compared against the same
 computation done on bf16-rounded operands, with a tolerance of a few bf16 ulps of the result scale (stated per test)."""
+import ctypes
 import functools
 
 import numpy as np
@@ -296,17 +297,56 @@ def test_wgrad_runs_in_rounds_above_the_slab_budget(form, dt):
     assert not X.ws_accumulator(ws).any(), "the accumulator part of the workspace is not left all-zero"
 
 
-@pytest.mark.parametrize("valu", [True, False])
+# form -> (op, N, Cin, Cout, plan kernel id, split count) on a 17 x 33 input, one form per instantiation of tfc_wgradT_kernel<UP, NH> (two for the wide
+# one): 3 x 3 tiles of 8 x 16 per image whose last row and column hold one pixel, and more tiles than splits, so workgroups walk two tiles (load ->
+# compute -> store hand-over).
+#   narrow:  <false, 1>; odd Cin / 32, the only way to the 32 x 32 workgroup tile without a knob; 8 x 3 = 24 pairs, 768 / 24 = 32 splits, 36 tiles
+#   wide:    <false, 2>; 32 n x 64 c tiles, 3 n-blocks x 4 column pairs = 12 workgroups per split (the pair decode), 512 / 12 = 42 splits, 45 tiles
+#   wide-n:  <false, 2>; an n-block that holds 24 of 32 channels (check_common in api.hip REQUIREs padded channel bytes <= 64 or a multiple of 64, so a partly
+#            valid n-block is the only one), 4 column pairs, 512 / 4 = 128 splits, 135 tiles
+#   up:      <true, 1>; an upsample conv that is not the head (Cout = 64, not 3 padded to 8); 2 x 8 = 16 pairs, the slab budget caps 32 splits at 28,
+#            36 tiles
+PHASE_CASES = {"narrow": (ops.OP_CONVT, 4, 96, 256, 15, 32), "wide": (ops.OP_CONVT, 5, 256, 96, 16, 42), "wide-n": (ops.OP_CONVT, 15, 256, 24, 16, 128),
+               "up": (ops.OP_UPCONV, 4, 256, 64, 14, 28)}
+PHASE_H, PHASE_W = 17, 33
+
+
+@pytest.mark.parametrize("form", list(PHASE_CASES))
+def test_phase_fused_wgrad_is_exact(form):
+    """tfc_wgradT_kernel<UP, NH>, every instantiation (the launch plan's kernel id and split count are asserted): exact against float64 on
+    integer operands (|sum| <= 15 x 17 x 33, far below 2^24) over a destination prefilled with a sentinel, the same bits on a second call,
+    accumulate=True doubles them exactly, and the accumulator part of the workspace is left zero."""
+    op, N, Cin, Cout, kernel, nsplit = PHASE_CASES[form]
+    dt = DT_BF16
+    rec = (ctypes.c_int * 8)()
+    assert ops.lib().tfc_conv_plan_query(dt, op, 2, N, PHASE_H, PHASE_W, Cin, Cout, 0, 256, rec, 8) == 8
+    assert (rec[0], rec[3]) == (kernel, nsplit), tuple(rec)
+    assert N * 9 > nsplit, "every workgroup has one tile only"
+    x = X.ints((N, Cin, PHASE_H, PHASE_W), 4300 + kernel)
+    dy = X.ints((N, Cout, 2 * PHASE_H, 2 * PHASE_W), 4400 + kernel)
+    want = X.ref_dw(op, x, (Cin, Cout, 4, 4) if op == ops.OP_CONVT else (Cout, Cin, 4, 4), dy)
+    X.assert_dyadic(want, 1, form)
+    xv, dyv = X.to_view(x.to(DEV), dt), X.to_view(dy.to(DEV), dt)
+    dw = torch.full(tuple(want.shape), 3.0, dtype=torch.float32, device=DEV)
+    ws = ops.conv_wgrad(dt, op, xv, dyv, Cin, Cout, dw)
+    first = dw.clone()
+    X.assert_exact(first.cpu().double(), want, f"{form} weight gradient", X.WGT_DIMS)
+    dw.fill_(-7.0)
+    ops.conv_wgrad(dt, op, xv, dyv, Cin, Cout, dw, ws=ws)
+    assert torch.equal(dw, first), "second call: different bits"
+    ops.conv_wgrad(dt, op, xv, dyv, Cin, Cout, dw, accumulate=True, ws=ws)
+    assert torch.equal(dw, 2 * first), "accumulate=True does not double the gradient exactly"
+    assert not X.ws_accumulator(ws).any(), "the accumulator part of the workspace is not left all-zero"
+
+
 @pytest.mark.parametrize("N,S,Cin,disc", [(2, 40, 3, False), (1, 70, 6, True), (3, 256, 6, True), (2, 256, 3, False), (2, 251, 6, True), (1, 18, 3, True)])
-def test_fused_first_block_backward_equals_unfused_chain(N, S, Cin, disc, valu, monkeypatch):
+def test_fused_first_block_backward_equals_unfused_chain(N, S, Cin, disc):
     """[BlurPool]^T -> LeakyReLU' -> weight / bias gradient of the first block in one kernel (the 266 MB gradient of the conv output is never
-    written) against the chain it replaces, tfc_act_bwd(mode 0, pool 2) + tfc_conv_wgrad. Two forms: the VALU form (TFC_FIRST_BWD_VALU=1) puts the
-    same d_raw bits into the MFMAs, only the split-K summation order differs (fp32 round-off: 2e-5); the product form runs the transposed blur as
-    a GEMM against the tile's tap matrix on the matrix core (round 3) -- the <= 9 exact products per element are added in another order, so an
-    element of d_raw may round to the neighbouring bf16 (<= 1 ulp on rare elements): 2e-4 on the weight gradient. Reflect aliases on all four
-    borders, partial tiles and sizes whose last TWO tile rows are border rows (S = 251, 18), with and without accumulate."""
-    monkeypatch.setenv("TFC_FIRST_BWD_VALU", "1" if valu else "0")
-    rtol = 2e-5 if valu else 2e-4
+    written) against the chain it replaces, tfc_act_bwd(mode 0, pool 2) + tfc_conv_wgrad. The kernel runs the transposed blur as a GEMM against
+    the tile's tap matrix on the matrix core -- the <= 9 exact products per element are added in another order, so an element of d_raw may round
+    to the neighbouring bf16 (<= 1 ulp on rare elements): 2e-4 on the weight gradient. Reflect aliases on all four borders, partial tiles and
+    sizes whose last TWO tile rows are border rows (S = 251, 18), with and without accumulate."""
+    rtol = 2e-4
     dt = DT_BF16
     assert ops.first_block_bwd_supported(dt, Cin, 64)
     H = S - 1
@@ -332,26 +372,25 @@ def test_fused_first_block_backward_equals_unfused_chain(N, S, Cin, disc, valu, 
     dw2 = torch.zeros_like(dw0)
     ops.conv_wgrad(dt, ops.OP_CONV, xv, d_raw, Cin, 64, dw2, ws=ws)
     assert torch.allclose(dw2, dw0, rtol=1e-5, atol=1e-6 * scale)
-    if not valu:
-        # the sign word the first convolution can leave (tfc_conv_first_fwd): same bits as (y > 0), and the backward that reads it instead of y
-        # gives the SAME weight / bias gradient bits as the one that derives the signs from y itself
-        w1 = rnd((64, Cin, 4, 4), 8, 0.2).to(DEV)
-        pk = ops.pack_weight(dt, ops.OP_CONV, 0, w1, Cin, 64)
-        y2 = ops.new_act(N, H, H, 64, dt, DEV)
-        mask = torch.zeros((N, H, H, 8), dtype=torch.uint8, device=DEV)
-        bias = rnd((64,), 9, 0.3).to(DEV)
-        ops.conv_first_fwd(dt, xv, Cin, 64, pk, y2, bias=bias, flags=ops.EP_LEAKY, sign_mask=mask)
-        y3 = ops.new_act(N, H, H, 64, dt, DEV)
-        ops.conv_fwd(dt, ops.OP_CONV, xv, Cin, 64, pk, y3, bias=bias, flags=ops.EP_LEAKY)
-        assert torch.equal(y2.t, y3.t)
-        want_bits = (y2.t.float() > 0).reshape(N, H, H, 8, 8).to(torch.int32)
-        want = (want_bits << torch.arange(8, device=DEV, dtype=torch.int32)).sum(-1).to(torch.uint8)
-        assert torch.equal(mask, want)
-        dwa, dwb = torch.zeros_like(dw0), torch.zeros_like(dw0)
-        ra, rb2 = torch.zeros((N, 64), device=DEV), torch.zeros((N, 64), device=DEV)
-        ops.first_block_bwd_wgrad(dt, xv, y2, gv, Cin, 64, dwa, slope=0.2, ws=ws, bias_sums=ra)
-        ops.first_block_bwd_wgrad(dt, xv, None, gv, Cin, 64, dwb, slope=0.2, ws=ws, bias_sums=rb2, sign_mask=mask)
-        assert torch.equal(dwa, dwb) and torch.equal(ra, rb2)
+    # the sign word the first convolution can leave (tfc_conv_first_fwd): same bits as (y > 0), and the backward that reads it instead of y
+    # gives the SAME weight / bias gradient bits as the one that derives the signs from y itself
+    w1 = rnd((64, Cin, 4, 4), 8, 0.2).to(DEV)
+    pk = ops.pack_weight(dt, ops.OP_CONV, 0, w1, Cin, 64)
+    y2 = ops.new_act(N, H, H, 64, dt, DEV)
+    mask = torch.zeros((N, H, H, 8), dtype=torch.uint8, device=DEV)
+    bias = rnd((64,), 9, 0.3).to(DEV)
+    ops.conv_first_fwd(dt, xv, Cin, 64, pk, y2, bias=bias, flags=ops.EP_LEAKY, sign_mask=mask)
+    y3 = ops.new_act(N, H, H, 64, dt, DEV)
+    ops.conv_fwd(dt, ops.OP_CONV, xv, Cin, 64, pk, y3, bias=bias, flags=ops.EP_LEAKY)
+    assert torch.equal(y2.t, y3.t)
+    want_bits = (y2.t.float() > 0).reshape(N, H, H, 8, 8).to(torch.int32)
+    want = (want_bits << torch.arange(8, device=DEV, dtype=torch.int32)).sum(-1).to(torch.uint8)
+    assert torch.equal(mask, want)
+    dwa, dwb = torch.zeros_like(dw0), torch.zeros_like(dw0)
+    ra, rb2 = torch.zeros((N, 64), device=DEV), torch.zeros((N, 64), device=DEV)
+    ops.first_block_bwd_wgrad(dt, xv, y2, gv, Cin, 64, dwa, slope=0.2, ws=ws, bias_sums=ra)
+    ops.first_block_bwd_wgrad(dt, xv, None, gv, Cin, 64, dwb, slope=0.2, ws=ws, bias_sums=rb2, sign_mask=mask)
+    assert torch.equal(dwa, dwb) and torch.equal(ra, rb2)
 
 
 @pytest.mark.parametrize("N,S,Cin,gform", [(2, 256, 6, False), (2, 256, 3, True), (3, 70, 6, False), (1, 41, 3, True), (2, 130, 6, False), (1, 18, 3, True), (1, 32, 6, False), (2, 34, 3, True),

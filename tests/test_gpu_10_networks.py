@@ -632,7 +632,7 @@ def test_bf16_discriminator_layers_teacher_forced_vs_storage_oracle():
     """the discriminator (P16:182-211) is 4 of the 5 network forwards of a step and runs bf16-only kernels the generator never touches:
     the TFC_EP_LEAKY epilogue with 1/sigma and bias, the 6 -> 64 first-layer kernel (tfc_conv_c8_kernel), the pure-blur pooling, the wave-per-pixel head
     (tfc_head_fwd_kernel), the rows-packed image gradient (tfc_dgrad_rows4_kernel), the per-image bias-gradient sums, the spectral-norm backward, and --
-    in the discriminator step, where nothing needs the image gradient -- the fused first-block backward (tfc_wgrad_c8_fused_kernel). Every one of the 4
+    in the discriminator step, where nothing needs the image gradient -- the fused first-block backward (tfc_wgrad_c8_fusedm_kernel). Every one of the 4
     spectrally normalised blocks and the head is fed to the oracle's bf16-storage model of that block with the ENGINE's stored input, the engine's
     (u, v) snapshot and the engine's incoming gradient: forward <= 5e-4, backward <= 5e-3 rel-L2, the stored conv-output gradients element by element."""
     T.set_compute_dtype(torch.bfloat16)

@@ -1694,6 +1694,55 @@ __device__ __forceinline__ void tfc_slab_store(float4* ps, const f32x16_t (&acc)
     for (int q4 = 0; q4 < 4; ++q4)
       ps[(a * 4 + q4) * 64] = make_float4(acc[a][4 * q4], acc[a][4 * q4 + 1], acc[a][4 * q4 + 2], acc[a][4 * q4 + 3]);
 }
+// zero-fill of a wave's accumulator tiles
+template <int NA>
+__device__ __forceinline__ void tfc_acc_zero(f32x16_t (&acc)[NA]) {
+#pragma unroll
+  for (int a = 0; a < NA; ++a)
+#pragma unroll
+    for (int j = 0; j < 16; ++j) acc[a][j] = 0.f;
+}
+// First-layer family: four 16-byte units per thread of an 8 x 16 pixel tile of a 64-channel NHWC tensor (rows / columns from (oy, ox) on, GH x GW of
+// them valid), unit tid + 256 i = (ni * 128 + pixel) * 4 + g -- the LDS image [ni][pixel][32 channels] the consumer loop reads. Zero outside the
+// tile's valid pixels and from channel nmax on.
+__device__ __forceinline__ void tfc_c8_tile_load(uint4 (&v)[4], const TfcGather& d, const bf16_t* __restrict__ src, int pitch, int oy, int ox, int nmax,
+                                                 int img, int a0, int b0) {
+  const int tid = threadIdx.x;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int idx = tid + i * 256;
+    const int g = idx & 3, px = (idx >> 2) & 127, ni = idx >> 9;
+    const int a = a0 + (px >> 4), b = b0 + (px & 15);
+    const int n0 = ni * 32 + g * 8;
+    v[i] = make_uint4(0, 0, 0, 0);
+    if (a < d.GH && b < d.GW && n0 < nmax) v[i] = load_stream16(src + ((size_t)(img * d.OH + a + oy) * d.OW + b + ox) * pitch + n0);
+  }
+}
+// First-layer family: the thread's 16-byte pixel (hy, hx) of the tile's input halo (8 padded channels), zero outside the image and beyond the halo
+__device__ __forceinline__ uint4 tfc_c8_halo_load(const TfcGather& d, const bf16_t* __restrict__ in, int img, int a0, int b0, int hy, int hx) {
+  const TfcPlane& pd = d.plane[0];
+  uint4 v = make_uint4(0, 0, 0, 0);
+  if ((int)threadIdx.x < pd.hh * pd.hw) {
+    const int y = a0 + pd.dy0 + hy, x = b0 + pd.dx0 + hx;
+    if (y >= 0 && y < d.IH && x >= 0 && x < d.IW) v = *reinterpret_cast<const uint4*>(in + ((size_t)(img * d.IH + y) * d.IW + x) * d.in_pitch);
+  }
+  return v;
+}
+// First-layer family: the 16 MFMAs of one tile. The halo is kept at 16 bytes per pixel -- a K(pixel)-strided matrix whose rows overlap (row pitch 16 B,
+// row length 64 B: columns (kx, c)) -- and the dO image is [ni][pixel][32 outputs] with 64-byte rows. dO / hrow: the lane's tfc_tr_lane address in the
+// image / in halo row ky of the wave; hw = halo pixels per row. Per k-step (16 pixels of a tile row) 1 B fragment, 2 A fragments, 2 MFMAs.
+__device__ __forceinline__ void tfc_c8_consume(const unsigned char* dO, const unsigned char* hrow, int hw, f32x16_t (&acc)[2]) {
+  constexpr int ROWB = 64;
+#pragma unroll
+  for (int kt = 0; kt < 8; ++kt) {
+    const uint4 b = tfc_tr16(hrow + kt * hw * 16, 4 * 16);
+#pragma unroll
+    for (int ni = 0; ni < 2; ++ni) {
+      const uint4 a = tfc_tr16(dO + ni * 128 * ROWB + kt * 16 * ROWB, 4 * ROWB);
+      acc[ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, a), __builtin_bit_cast(bf16x8_t, b), acc[ni], 0, 0, 0);
+    }
+  }
+}
 // Fixed-order sum over the split-K slabs: the workgroup is K owners x L lanes (thread = k * L + l), a lane sums R slab positions row[r]. Owner k takes
 // the splits sp = k, k + K, ... ascending, the partials meet in LDS, and owner 0 adds those of owners 1 .. K-1 ascending. True for owner 0, whose s[]
 // holds the totals; the other owners are done.
@@ -1727,6 +1776,8 @@ __device__ __forceinline__ bool tfc_slab_sum(const float4* slab, const size_t (&
 }
 // Upsample(2x nearest) -> ZeroPad(1,0,1,0) -> 4-tap filter: source offset + 1 of filter index k in the sub-pixel phase with parity bit ph
 __device__ __forceinline__ int tfc_up_src(int ph, int k) { return ph ? (k == 0 ? 0 : (k == 3 ? 2 : 1)) : (k >> 1); }
+// BlurPool: tap k of the [1, 3, 3, 1] / 8 filter
+__device__ __forceinline__ float fbw(int k) { return (k == 0 || k == 3) ? 0.125f : 0.375f; }
 
 // ---------------------------------------------------------------------------------------------------
 // weight-gradient GEMM for 2 x 2-tap planes (bf16): the sub-pixel phases of the transposed convolution and phase (0,0) of the
@@ -1759,10 +1810,7 @@ tfc_wgrad22_kernel(const TfcGather d, const T* __restrict__ dO, const T* __restr
   const int ntiles = d.nimg * d.tiles_y * d.tiles_x;
 
   f32x16_t acc[4];
-#pragma unroll
-  for (int a = 0; a < 4; ++a)
-#pragma unroll
-    for (int j = 0; j < 16; ++j) acc[a][j] = 0.f;
+  tfc_acc_zero(acc);
 
   uint4 vdo[NDO], vha[NHA];
   const int nunits = pd.hh * pd.hw * 4;                          // per halo plane
@@ -1931,10 +1979,7 @@ tfc_wgrad_kernel(const TfcGather d, const T* __restrict__ dO, const T* __restric
   const int ntiles = d.nimg * d.tiles_y * d.tiles_x;
 
   f32x16_t acc[TPW * 2];                                         // [ti][ni]
-#pragma unroll
-  for (int a = 0; a < TPW * 2; ++a)
-#pragma unroll
-    for (int j = 0; j < 16; ++j) acc[a][j] = 0.f;
+  tfc_acc_zero(acc);
 
   uint4 vdo[NDO], vha[NHA];
   int hyq[NHA], hxq[NHA], hcq[NHA];
@@ -2102,31 +2147,15 @@ tfc_wgrad_c8_kernel(const TfcGather d, const bf16_t* __restrict__ dO, const bf16
   const int sp = tfc_xcd_remap(blockIdx.x, gridDim.x);
   const int ntiles = d.nimg * d.tiles_y * d.tiles_x;
   f32x16_t acc[2];
-#pragma unroll
-  for (int ni = 0; ni < 2; ++ni)
-#pragma unroll
-    for (int j = 0; j < 16; ++j) acc[ni][j] = 0.f;
+  tfc_acc_zero(acc);
 
   uint4 vdo[4], vha;
+  const int hy_t = tid / pd.hw, hx_t = tid - hy_t * pd.hw;
   auto tile_load = [&](int tl) {
     int img, a0, b0;
     tfc_tile_decode(tl, d.tiles_x, d.tiles_y, img, a0, b0);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int idx = tid + i * 256;                             // (ni * 128 + px) * 4 + g
-      const int g = idx & 3, px = (idx >> 2) & 127, ni = idx >> 9;
-      const int a = a0 + (px >> 4), b = b0 + (px & 15);
-      const int n0 = ni * 32 + g * 8;
-      vdo[i] = make_uint4(0, 0, 0, 0);
-      if (a < d.GH && b < d.GW && n0 < Nn_pad)
-        vdo[i] = load_stream16(dO + ((size_t)(img * d.OH + a + d.OOY) * d.OW + b + d.OOX) * d.out_pitch + n0);
-    }
-    vha = make_uint4(0, 0, 0, 0);
-    if (tid < pd.hh * pd.hw) {
-      const int hy = tid / pd.hw, hx = tid - hy * pd.hw;
-      const int y = a0 + pd.dy0 + hy, x = b0 + pd.dx0 + hx;
-      if (y >= 0 && y < d.IH && x >= 0 && x < d.IW) vha = *reinterpret_cast<const uint4*>(in + ((size_t)(img * d.IH + y) * d.IW + x) * d.in_pitch);
-    }
+    tfc_c8_tile_load(vdo, d, dO, d.out_pitch, d.OOY, d.OOX, Nn_pad, img, a0, b0);
+    vha = tfc_c8_halo_load(d, in, img, a0, b0, hy_t, hx_t);
   };
   auto tile_store = [&](unsigned char* buf) {
 #pragma unroll
@@ -2135,17 +2164,8 @@ tfc_wgrad_c8_kernel(const TfcGather d, const bf16_t* __restrict__ dO, const bf16
   };
   const int trA = tfc_tr_lane(lane, ROWB);                       // dO: rows = pixels (64 B), columns = outputs
   const int trB = tfc_tr_lane(lane, 16);                         // halo: rows = pixels (16 B pitch, 64 B long: overlapping), columns = (kx, c)
-  auto compute = [&](const unsigned char* buf) {
-    const unsigned char* hrow = buf + DO_BYTES + wave * pd.hw * 16 + trB;   // halo row kt + ky, ky = wave
-#pragma unroll
-    for (int kt = 0; kt < 8; ++kt) {
-      const uint4 b = tfc_tr16(hrow + kt * pd.hw * 16, 4 * 16);
-#pragma unroll
-      for (int ni = 0; ni < 2; ++ni) {
-        const uint4 a = tfc_tr16(buf + ni * 128 * ROWB + kt * 16 * ROWB + trA, 4 * ROWB);
-        acc[ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, a), __builtin_bit_cast(bf16x8_t, b), acc[ni], 0, 0, 0);
-      }
-    }
+  auto compute = [&](const unsigned char* buf) {                 // halo row kt + ky, ky = wave
+    tfc_c8_consume(buf + trA, buf + DO_BYTES + wave * pd.hw * 16 + trB, pd.hw, acc);
   };
   int tl = sp, cur = 0;
   if (tl < ntiles) { tile_load(tl); tile_store(smem); }
@@ -2165,190 +2185,18 @@ tfc_wgrad_c8_kernel(const TfcGather d, const bf16_t* __restrict__ dO, const bf16
 // (tfc_act_pool2_bwd_kernel, then tfc_wgrad_c8_kernel) is bound by WRITING the 255 x 255 x 64 gradient of the convolution output (266 MB at
 // batch 32; HBM writes run at about half the read rate) and reading it back. When nothing else needs that tensor -- every backward of the first
 // block except the one generator-step pass that continues to the image gradient -- it never has to exist: this kernel is tfc_wgrad_c8_kernel
-// with a PRODUCER in front of its LDS tile. Per 8 x 16 tile of convolution outputs: the 7 x 11 window of the pooled gradient is staged in LDS,
-// every thread turns its four 16-byte units of the stored activation (sign only) into d_raw = (sum of its 2 x 2 -- next to the reflect borders
-// 3 x 3 -- window taps) * (y > 0 ? 1 : slope), rounds to bf16 where the unfused kernel stored it, and writes the dO tile the MFMA loop reads.
-// Reads 266 + 67 + 33 MB, writes 32 KB of slabs per workgroup. Tap weights with the reflect aliases merged are tabulated per tile row / column
-// exactly as in tfc_act_pool2_bwd_kernel, and the arithmetic order is the same, so d_raw -- and with it the weight gradient -- has the same bits.
+// with a PRODUCER in front of its LDS tile. Per 8 x 16 tile of convolution outputs the 7 x 11 window of the pooled gradient is staged in LDS and turned
+// into d_raw = (sum of the 2 x 2 -- next to the reflect borders 3 x 3 -- window taps) * (y > 0 ? 1 : slope), rounded to bf16 where the unfused kernel
+// stored it, as the dO tile the MFMA loop reads. Reads 266 + 67 + 33 MB, writes 32 KB of slabs per workgroup. Tap weights with the reflect aliases
+// merged are tabulated per tile row / column exactly as in tfc_act_pool2_bwd_kernel.
 // Tiles are dealt out CONTIGUOUSLY inside ONE image per workgroup (wpi workgroups per image), so the bias-gradient sums leave as one 64-float slot
 // rstats = part[img][workgroup of the image][64], added in a fixed order by tfc_part_reduce_kernel (round 2 used LDS + memory-side float atomics).
-// ---------------------------------------------------------------------------------------------------
-__device__ __forceinline__ float fbw(int k) { return (k == 0 || k == 3) ? 0.125f : 0.375f; }
-__global__ void __launch_bounds__(256, 2)
-tfc_wgrad_c8_fused_kernel(const TfcGather d, const bf16_t* __restrict__ yact, int y_pitch, const bf16_t* __restrict__ dyp, int dyp_pitch, int Ho, int Wo,
-                          const bf16_t* __restrict__ in, float4* __restrict__ slab, float* rstats, float slope, int wpi, int per) {
-  constexpr int ROWB = 64;
-  constexpr int DO_BYTES = 2 * 128 * ROWB;
-  constexpr int HALO_BYTES = (TFC_MAX_HH * TFC_MAX_HW * 16 + 255) & ~255;
-  constexpr int WH = 7, WW = 11, WIN_BYTES = WH * WW * 8 * 16;     // pooled-gradient window: 77 pixels x 64 channels
-  __shared__ __attribute__((aligned(16))) unsigned char smem[DO_BYTES + 2 * HALO_BYTES + WIN_BYTES + 24 * 16 + 4 * 64 * 4];
-  unsigned char* halo0 = smem + DO_BYTES;
-  uint4* win = reinterpret_cast<uint4*>(smem + DO_BYTES + 2 * HALO_BYTES);
-  float4* wrow = reinterpret_cast<float4*>(smem + DO_BYTES + 2 * HALO_BYTES + WIN_BYTES);   // [8] tap weights of pooled rows o0-1, o0, o0+1
-  float4* wcol = wrow + 8;                                                                  // [16]
-  float* sbias = reinterpret_cast<float*>(wcol + 16);                                       // [4 waves][64] bias-gradient sums of this workgroup
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const TfcPlane& pd = d.plane[0];
-  const int sp = blockIdx.x;
-  const int tpi = d.tiles_y * d.tiles_x;                          // tiles per image; this workgroup: tiles [t0, t1) of image sp / wpi
-  const int wimg = sp / wpi, wj = sp - wimg * wpi;
-  const int t0 = wimg * tpi + wj * per, t1 = (wj * per + per) < tpi ? (t0 + per) : (wimg + 1) * tpi;
-  f32x16_t acc[2];
-#pragma unroll
-  for (int ni = 0; ni < 2; ++ni)
-#pragma unroll
-    for (int j = 0; j < 16; ++j) acc[ni][j] = 0.f;
-
-  uint4 vy[4], vw[3], vha;
-  auto tile_load = [&](int tl) {
-    int img, a0, b0;
-    tfc_tile_decode(tl, d.tiles_x, d.tiles_y, img, a0, b0);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int idx = tid + i * 256;                             // (ni * 128 + px) * 4 + g
-      const int g = idx & 3, px = (idx >> 2) & 127, ni = idx >> 9;
-      const int a = a0 + (px >> 4), b = b0 + (px & 15);
-      vy[i] = make_uint4(0, 0, 0, 0);
-      if (a < d.GH && b < d.GW) vy[i] = load_stream16(yact + ((size_t)(img * d.OH + a) * d.OW + b) * y_pitch + ni * 32 + g * 8);
-    }
-    const int oyb = a0 / 2 - 1, oxb = b0 / 2 - 1;
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-      const int idx = tid + i * 256;                             // window pixel * 8 + unit
-      const int u = idx & 7, wp = idx >> 3;
-      const int oy = oyb + wp / WW, ox = oxb + wp % WW;
-      vw[i] = make_uint4(0, 0, 0, 0);
-      if (wp < WH * WW && oy >= 0 && oy < Ho && ox >= 0 && ox < Wo) vw[i] = *reinterpret_cast<const uint4*>(dyp + ((size_t)(img * Ho + oy) * Wo + ox) * dyp_pitch + u * 8);
-    }
-    vha = make_uint4(0, 0, 0, 0);
-    if (tid < pd.hh * pd.hw) {
-      const int hy = tid / pd.hw, hx = tid - hy * pd.hw;
-      const int y = a0 + pd.dy0 + hy, x = b0 + pd.dx0 + hx;
-      if (y >= 0 && y < d.IH && x >= 0 && x < d.IW) vha = *reinterpret_cast<const uint4*>(in + ((size_t)(img * d.IH + y) * d.IW + x) * d.in_pitch);
-    }
-  };
-  // tap weights of one act row / column q of length L (Lo pooled): pooled rows o0-1, o0, o0+1 with o0 = (q+1) >> 1, reflect aliases merged
-  auto taps3 = [&](int q, int L, int Lo) {
-    float w3[3] = {0.f, 0.f, 0.f};
-    if (q < L) {
-      const int o0 = (q + 1) >> 1;
-      for (int a = 0; a < 4; ++a) {
-        if ((a == 1 && q != 1) || (a == 2 && q != L - 2) || (a == 3 && q != L - 3)) continue;
-        const int pq = a == 0 ? q : (a == 1 ? -1 : (a == 2 ? L : L + 1));
-        for (int k = 0; k < 4; ++k) {
-          const int t = pq + 1 - k;
-          if (t < 0 || (t & 1) || (t >> 1) >= Lo) continue;
-          const int dd = (t >> 1) - o0 + 1;
-          if (dd == 0) w3[0] += fbw(k); else if (dd == 1) w3[1] += fbw(k); else if (dd == 2) w3[2] += fbw(k);
-        }
-      }
-    }
-    return make_float4(w3[0], w3[1], w3[2], 0.f);
-  };
-  const int trA = tfc_tr_lane(lane, ROWB);
-  const int trB = tfc_tr_lane(lane, 16);
-  float bsum[2][8];                                              // this thread's channels: ni = 0 / 1, unit g = tid & 3
-#pragma unroll
-  for (int h2 = 0; h2 < 2; ++h2)
-#pragma unroll
-    for (int e = 0; e < 8; ++e) bsum[h2][e] = 0.f;
-  if (t0 < t1) tile_load(t0);
-  int cur = 0;
-  for (int tl = t0; tl < t1; ++tl) {
-    int img, a0, b0;
-    tfc_tile_decode(tl, d.tiles_x, d.tiles_y, img, a0, b0);
-    // A. window, halo, tap tables of this tile -> LDS; the activation units stay in registers
-#pragma unroll
-    for (int i = 0; i < 3; ++i) { const int idx = tid + i * 256; if (idx < WH * WW * 8) win[idx] = vw[i]; }
-    if (tid < TFC_MAX_HH * TFC_MAX_HW) *reinterpret_cast<uint4*>(halo0 + cur * HALO_BYTES + tid * 16) = vha;
-    if (tid < 8) wrow[tid] = taps3(a0 + tid, d.GH, Ho);
-    else if (tid < 24) wcol[tid - 8] = taps3(b0 + tid - 8, d.GW, Wo);
-    uint4 ycur[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) ycur[i] = vy[i];
-    __syncthreads();
-    // C. next tile's loads
-    if (tl + 1 < t1) tile_load(tl + 1);
-    // D. d_raw of this tile -> the dO image the MFMA loop reads
-    const int oyb = a0 / 2 - 1, oxb = b0 / 2 - 1;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int idx = tid + i * 256;
-      const int g = idx & 3, px = (idx >> 2) & 127, ni = idx >> 9;
-      const int ty = px >> 4, tx = px & 15;
-      const int y = a0 + ty, x = b0 + tx;
-      uint4 res = make_uint4(0, 0, 0, 0);
-      if (y < d.GH && x < d.GW) {
-        float gsum[8];
-#pragma unroll
-        for (int e = 0; e < 8; ++e) gsum[e] = 0.f;
-        const float4 wr = wrow[ty], wc = wcol[tx];
-        const int wy = ((y + 1) >> 1) - oyb, wx = ((x + 1) >> 1) - oxb;
-        const int u = ni * 4 + g;
-        auto tap = [&](int dy, int dx, float w) {
-          float v[8];
-          unpack16<bf16_t>(win[((wy + dy) * WW + wx + dx) * 8 + u], v);
-#pragma unroll
-          for (int e = 0; e < 8; ++e) gsum[e] += w * v[e];
-        };
-        tap(-1, -1, wr.x * wc.x); tap(-1, 0, wr.x * wc.y); tap(0, -1, wr.y * wc.x); tap(0, 0, wr.y * wc.y);
-        if (wr.z != 0.f || wc.z != 0.f) {                          // only next to the bottom / right reflect border
-          tap(-1, 1, wr.x * wc.z); tap(0, 1, wr.y * wc.z);
-          tap(1, -1, wr.z * wc.x); tap(1, 0, wr.z * wc.y); tap(1, 1, wr.z * wc.z);
-        }
-        float yv[8];
-        unpack16<bf16_t>(ycur[i], yv);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) gsum[e] = yv[e] > 0.f ? gsum[e] : gsum[e] * slope;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) bsum[i >> 1][e] += gsum[e];
-        res = pack16<bf16_t>(gsum);
-      }
-      *reinterpret_cast<uint4*>(smem + idx * 16) = res;
-    }
-    __syncthreads();
-    // F. the weight-gradient MFMAs of tfc_wgrad_c8_kernel
-    {
-      const unsigned char* buf = smem;
-      const unsigned char* hrow = halo0 + cur * HALO_BYTES + wave * pd.hw * 16 + trB;
-#pragma unroll
-      for (int kt = 0; kt < 8; ++kt) {
-        const uint4 b = tfc_tr16(hrow + kt * pd.hw * 16, 4 * 16);
-#pragma unroll
-        for (int ni = 0; ni < 2; ++ni) {
-          const uint4 a = tfc_tr16(buf + ni * 128 * ROWB + kt * 16 * ROWB + trA, 4 * ROWB);
-          acc[ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, a), __builtin_bit_cast(bf16x8_t, b), acc[ni], 0, 0, 0);
-        }
-      }
-    }
-    cur ^= 1;
-  }
-  if (rstats) {
-    // bias-gradient sums of this workgroup, in a fixed order: the lanes that share (lane & 3) hold the same 16 channels -> butterfly over lane bits
-    // 2..5, the four waves meet in four LDS slots, 64 threads add the slots in wave order
-#pragma unroll
-    for (int h2 = 0; h2 < 2; ++h2)
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        float v = bsum[h2][e];
-#pragma unroll
-        for (int o = 4; o < 64; o <<= 1) v += __shfl_xor(v, o, 64);
-        if (lane < 4) sbias[wave * 64 + h2 * 32 + lane * 8 + e] = v;
-      }
-    __syncthreads();
-    if (tid < 64) rstats[(size_t)sp * 64 + tid] = ((sbias[tid] + sbias[64 + tid]) + sbias[128 + tid]) + sbias[192 + tid];   // part[img][wj][64], sp = img * wpi + wj
-  }
-  tfc_slab_store(slab + ((size_t)sp * 4 + wave) * (2 * 4 * 64) + lane, acc);
-}
-// ---------------------------------------------------------------------------------------------------
-// The same fused first-block backward with the transposed blur ON THE MATRIX CORE (round 3). The kernel above spends ~1,200 VALU instructions per
-// thread and tile on the 2 x 2 (3 x 3 at the reflect borders) taps -- 5.5 k cycles per tile against 0.5 k for its 16 weight-gradient MFMAs: VALU-bound
-// at 170 us where its 366 MB of HBM traffic need ~80. The transposed blur of a tile is a LINEAR map from the 7 x 11 window of the pooled gradient
-// to the tile's 8 x 16 pixels, the same for every channel:   g[p][c] = sum_q T[p][q] * win[q][c],   T[p][q] = wrow[ty][dy] * wcol[tx][dx].
+// The transposed blur runs ON THE MATRIX CORE (round 3). The round-2 form took the taps on the VALU, ~1,200 instructions per thread and tile -- 5.5 k
+// cycles per tile against 0.5 k for its 16 weight-gradient MFMAs: VALU-bound at 170 us where its 366 MB of HBM traffic need ~80. The transposed blur
+// of a tile is a LINEAR map from the 7 x 11 window of the pooled gradient to the tile's 8 x 16 pixels, the same for every channel:
+//   g[p][c] = sum_q T[p][q] * win[q][c],   T[p][q] = wrow[ty][dy] * wcol[tx][dx].
 // Its entries are products of sums of {1/8, 3/8} -- exactly representable in bf16 -- and win is bf16, so the products are exact in fp32 and only the
-// ORDER of the <= 9 additions differs from the VALU form (fp32 round-off; 1 bf16 ulp on rare elements after rounding). As a GEMM per tile:
+// ORDER of the <= 9 additions differs from the unfused chain (fp32 round-off; 1 bf16 ulp on rare elements after rounding). As a GEMM per tile:
 // 128 pixels x 80 (77 + 3 zero) window positions x 64 channels = 40 MFMAs 32x32x16 -- 10 per wave, 320 cycles. Operands: the window is staged as two
 // 32-channel planes [q][32] of 64-byte rows and fetched with the transposing LDS read the weight-gradient loop already uses (A, rows = channels);
 // T lives in LDS as Tt[pixel][q] (176-byte rows: conflict-free 16-byte reads) and is rebuilt only when the tile's border class changes (first /
@@ -2383,10 +2231,7 @@ tfc_wgrad_c8_fusedm_kernel(const TfcGather d, const bf16_t* __restrict__ yact, i
   const int wimg = sp / wpi, wj = sp - wimg * wpi;
   const int t0 = wimg * tpi + wj * per, t1 = (wj * per + per) < tpi ? (t0 + per) : (wimg + 1) * tpi;
   f32x16_t acc[2];
-#pragma unroll
-  for (int ni = 0; ni < 2; ++ni)
-#pragma unroll
-    for (int j = 0; j < 16; ++j) acc[ni][j] = 0.f;
+  tfc_acc_zero(acc);
   for (int i = tid; i < 2 * 3 * 4; i += 256) {                     // window rows 77..79 of both planes stay zero for the whole launch
     const int pl = i / 12, r = i % 12;
     *reinterpret_cast<uint4*>(winb + pl * PLANE + 77 * ROWB + r * 16) = make_uint4(0, 0, 0, 0);
@@ -2413,14 +2258,7 @@ tfc_wgrad_c8_fusedm_kernel(const TfcGather d, const bf16_t* __restrict__ yact, i
         if (a < d.GH && b < d.GW) vm = *reinterpret_cast<const uint2*>(sign_mask + ((size_t)(img * d.OH + a) * d.OW + b) * 8);
       }
     } else {
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const int idx = tid + i * 256;                           // (ni * 128 + px) * 4 + g
-        const int g = idx & 3, px = (idx >> 2) & 127, ni = idx >> 9;
-        const int a = a0 + (px >> 4), b = b0 + (px & 15);
-        vy[i] = make_uint4(0, 0, 0, 0);
-        if (a < d.GH && b < d.GW) vy[i] = load_stream16(yact + ((size_t)(img * d.OH + a) * d.OW + b) * y_pitch + ni * 32 + g * 8);
-      }
+      tfc_c8_tile_load(vy, d, yact, y_pitch, 0, 0, 64, img, a0, b0);
     }
     const int oyb = a0 / 2 - 1, oxb = b0 / 2 - 1;
 #pragma unroll
@@ -2431,14 +2269,10 @@ tfc_wgrad_c8_fusedm_kernel(const TfcGather d, const bf16_t* __restrict__ yact, i
       vw[i] = make_uint4(0, 0, 0, 0);
       if (wrow_i[i] < WH && oy >= 0 && oy < Ho && ox >= 0 && ox < Wo) vw[i] = *reinterpret_cast<const uint4*>(dyp + ((size_t)(img * Ho + oy) * Wo + ox) * dyp_pitch + u * 8);
     }
-    vha = make_uint4(0, 0, 0, 0);
-    if (tid < pd.hh * pd.hw) {
-      const int hy = hy_t, hx = hx_t;
-      const int y = a0 + pd.dy0 + hy, x = b0 + pd.dx0 + hx;
-      if (y >= 0 && y < d.IH && x >= 0 && x < d.IW) vha = *reinterpret_cast<const uint4*>(in + ((size_t)(img * d.IH + y) * d.IW + x) * d.in_pitch);
-    }
+    vha = tfc_c8_halo_load(d, in, img, a0, b0, hy_t, hx_t);
   };
-  auto taps3 = [&](int q, int L, int Lo) {                         // as in the VALU form: tap weights of pooled rows o0-1, o0, o0+1, reflect aliases merged
+  // tap weights of one act row / column q of length L (Lo pooled): pooled rows o0-1, o0, o0+1 with o0 = (q+1) >> 1, reflect aliases merged
+  auto taps3 = [&](int q, int L, int Lo) {
     float w3[3] = {0.f, 0.f, 0.f};
     if (q < L) {
       const int o0 = (q + 1) >> 1;
@@ -2523,10 +2357,7 @@ tfc_wgrad_c8_fusedm_kernel(const TfcGather d, const bf16_t* __restrict__ yact, i
     if (prefetch) tile_load(S, pa0, pb0);
     // D. transposed blur of the tile: g[channel][pixel] = window^T (A, transposing read) x Tt^T (B, 16 contiguous bytes per lane)
     f32x16_t gacc[2];
-#pragma unroll
-    for (int cb = 0; cb < 2; ++cb)
-#pragma unroll
-      for (int j = 0; j < 16; ++j) gacc[cb][j] = 0.f;
+    tfc_acc_zero(gacc);
 #pragma unroll
     for (int ks = 0; ks < NQ / 16; ++ks) {
       const uint4 b = *reinterpret_cast<const uint4*>(ttb + pl * TP + (ks * 16 + 8 * hh) * 2);
@@ -2560,18 +2391,7 @@ tfc_wgrad_c8_fusedm_kernel(const TfcGather d, const bf16_t* __restrict__ yact, i
     }
     __syncthreads();
     // F. the weight-gradient MFMAs of tfc_wgrad_c8_kernel
-    {
-      const unsigned char* hrow = halo0 + cur * HALO_BYTES + wave * pd.hw * 16 + trB;
-#pragma unroll
-      for (int kt = 0; kt < 8; ++kt) {
-        const uint4 b = tfc_tr16(hrow + kt * pd.hw * 16, 4 * 16);
-#pragma unroll
-        for (int ni = 0; ni < 2; ++ni) {
-          const uint4 a = tfc_tr16(smem + ni * 128 * ROWB + kt * 16 * ROWB + trA, 4 * ROWB);
-          acc[ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, a), __builtin_bit_cast(bf16x8_t, b), acc[ni], 0, 0, 0);
-        }
-      }
-    }
+    tfc_c8_consume(smem + trA, halo0 + cur * HALO_BYTES + wave * pd.hw * 16 + trB, pd.hw, acc);
     cur ^= 1;
   };
   // the workgroup's tiles in order; (tyb, txb): the tile being processed, (pyb, pxb): the tile DEPTH ahead
@@ -2775,16 +2595,24 @@ hipError_t tfc_launch_pack_planned(int dt, const void* plan_dev, int njobs, int 
 //   dW[co][ci][ky][kx] = sum dy[2a+py][2b+px][co] * x[a + off(py,ky)][b + off(px,kx)][ci],  off(0,.) = {-1,-1,0,0}, off(1,.) = {-1,0,0,1}
 // -- phase (py,px) has (2+py) x (2+px) distinct source offsets (collapsed taps; the reduce kernel adds each to all the filter taps it
 // stands for), read from the same 10 x 18 halo.
-template <bool UP>
-__global__ void __launch_bounds__(256, UP ? 2 : 3)
+// NH = 2 (round 3): a 32 n x 64 c workgroup tile. The NH = 1 form is bound by operand re-streaming: a 32 x 32 tile re-reads dy Cin/32 times and x
+// Cout/32 times from L2 (670 MB per launch at 256 -> 64 @ 64^2, 6.7 TB/s at 100 us) and issues six transposing LDS reads per four MFMAs. With NH = 2
+// wave w = phase still owns its 2 x 2 taps, but for TWO 32-channel halves of x: eight accumulator tiles per wave (128 VGPRs), one A fragment serves
+// eight MFMAs, dy is streamed Cin/64 times. Two workgroups per CU (55 KB of LDS). The slabs keep the logical numbering of the 32 x 32 form
+// (pair = nb * ncb + cb, cb = NH * cbn + half), so the reduce kernels do not know NH.
+template <bool UP, int NH>
+__global__ void __launch_bounds__(256, (UP || NH == 2) ? 2 : 3)
 tfc_wgradT_kernel(const bf16_t* __restrict__ x, int IH, int IW, int x_pitch, int Cin_pad, const bf16_t* __restrict__ dy, int dy_pitch,
                   int Nn_pad, int nimg, float4* slab, int nbw, int ncb, int nsplit) {
+  static_assert(NH == 1 || NH == 2, "32-channel halves of x per workgroup");
+  static_assert(!(UP && NH == 2), "18 accumulator tiles do not fit");
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   constexpr int ROWB = 64;                                       // 32 channels x 2 bytes per LDS pixel row
   constexpr int HH = TFC_TILE_H + 2, HW = TFC_TILE_W + 2;
   constexpr int DO_BYTES = 4 * 128 * ROWB;                       // [phase][px][32 n]
-  constexpr int NDO = DO_BYTES / 16 / 256, NHA = (HH * HW * 4 + 255) / 256;   // 8 and 3 units per thread
-  constexpr int NCM = UP ? 3 : 2, NA = NCM * NCM;                // accumulator tiles per wave: (row offset, column offset)
+  constexpr int HPLANE = HH * HW * ROWB;                         // one 32-channel half of the halo: [half][pixel][g]
+  constexpr int NDO = DO_BYTES / 16 / 256, NHA = (HH * HW * 4 * NH + 255) / 256;   // 8 and 3 (NH = 2: 6) units per thread
+  constexpr int NCM = UP ? 3 : 2, NA = NCM * NCM;                // accumulator tiles per wave and half: (row offset, column offset)
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -2792,17 +2620,16 @@ tfc_wgradT_kernel(const bf16_t* __restrict__ x, int IH, int IW, int x_pitch, int
   const int OH = 2 * IH, OW = 2 * IW;
   const int tiles_y = (IH + TFC_TILE_H - 1) / TFC_TILE_H, tiles_x = (IW + TFC_TILE_W - 1) / TFC_TILE_W;
   const int ntiles = nimg * tiles_y * tiles_x;
+  const int ncbn = ncb >> (NH - 1);                              // ncb / NH
 
   const int bid = tfc_xcd_remap(blockIdx.x, gridDim.x);
-  const int pair = bid % (nbw * ncb);
-  const int sp = bid / (nbw * ncb);
-  const int cb = pair % ncb, nb = pair / ncb;
+  const int pair = bid % (nbw * ncbn);
+  const int sp = bid / (nbw * ncbn);
+  const int cbn = pair % ncbn, nb = pair / ncbn;
 
-  f32x16_t acc[NA];
+  f32x16_t acc[NH][NA];
 #pragma unroll
-  for (int a = 0; a < NA; ++a)
-#pragma unroll
-    for (int j = 0; j < 16; ++j) acc[a][j] = 0.f;
+  for (int hc = 0; hc < NH; ++hc) tfc_acc_zero(acc[hc]);
 
   uint4 vdo[NDO], vha[NHA];
   auto tile_load = [&](int tl) {
@@ -2820,13 +2647,13 @@ tfc_wgradT_kernel(const bf16_t* __restrict__ x, int IH, int IW, int x_pitch, int
     }
 #pragma unroll
     for (int i = 0; i < NHA; ++i) {
-      const int idx = tid + i * 256;                             // pixel * 4 + g
+      const int idx = tid + i * 256;                             // (pixel * NH + half) * 4 + g: a pixel's 64 NH bytes are one contiguous run
       vha[i] = make_uint4(0, 0, 0, 0);
-      if (idx < HH * HW * 4) {
-        const int g = idx & 3, pix = idx >> 2;
+      if (idx < HH * HW * 4 * NH) {
+        const int g = idx & 3, hc = (idx >> 2) & (NH - 1), pix = idx >> (NH + 1);   // (idx >> 2) % NH, idx / (4 NH): NH is 1 or 2
         const int hy = pix / HW, hx = pix - hy * HW;
         const int y = a0 - 1 + hy, xx = b0 - 1 + hx;
-        const int c0 = cb * 32 + g * 8;
+        const int c0 = (NH * cbn + hc) * 32 + g * 8;
         if (y >= 0 && y < IH && xx >= 0 && xx < IW && c0 < Cin_pad)
           vha[i] = *reinterpret_cast<const uint4*>(x + ((size_t)(img * IH + y) * IW + xx) * x_pitch + c0);
       }
@@ -2838,43 +2665,52 @@ tfc_wgradT_kernel(const bf16_t* __restrict__ x, int IH, int IW, int x_pitch, int
 #pragma unroll
     for (int i = 0; i < NHA; ++i) {
       const int idx = tid + i * 256;
-      if (idx < HH * HW * 4) *reinterpret_cast<uint4*>(smem + DO_BYTES + idx * 16) = vha[i];
+      if (idx < HH * HW * 4 * NH) {
+        const int g = idx & 3, hc = (idx >> 2) & (NH - 1), pix = idx >> (NH + 1);   // (idx >> 2) % NH, idx / (4 NH): NH is 1 or 2
+        *reinterpret_cast<uint4*>(smem + DO_BYTES + hc * HPLANE + (pix * 4 + g) * 16) = vha[i];
+      }
     }
   };
 
   const int trLane = tfc_tr_lane(lane, ROWB);
-  // Accumulator (r, c): halo row kt + rb + r, column shift cs + c, with a sliding window of NR rows (wave-uniform NR, NC in {2, 3}).
+  // Accumulator (r, c): halo row kt + rb + r, column shift cs + c, with a sliding window of NCM rows.
   //   transposed conv: rb = py, cs = px, 2 x 2 (filter tap jy = 1 - r, jx = 1 - c);  upsample conv: rb = cs = 0, (2+py) x (2+px)
+  // upsample conv: every wave runs the full 3 x 3 offset grid; the offsets a phase does not have (row 2 for py = 0, column 2 for
+  // px = 0) only fill accumulators that the reduce kernel ignores -- cheaper than four differently shaped code paths
   const int rb = UP ? 0 : py, cs = UP ? 0 : px;
   constexpr int rowb = HW * ROWB;
-  auto compute_v = [&](auto nr_tag, auto nc_tag) {
-    constexpr int NR = decltype(nr_tag)::value, NC = decltype(nc_tag)::value;
+  auto compute = [&]() {
     const unsigned char* acol = smem + wave * 128 * ROWB + trLane;
     const unsigned char* hcol = smem + DO_BYTES + (rb * HW + cs) * ROWB + trLane;
-    uint4 rw[NR][NC];
+    uint4 rw[NH][NCM][NCM];                                      // [half][window row][column]
 #pragma unroll
-    for (int r = 0; r < NR - 1; ++r)
+    for (int hc = 0; hc < NH; ++hc)
 #pragma unroll
-      for (int c = 0; c < NC; ++c) rw[r][c] = tfc_tr16(hcol + r * rowb + c * ROWB, 4 * ROWB);
+      for (int r = 0; r < NCM - 1; ++r)
+#pragma unroll
+        for (int c = 0; c < NCM; ++c) rw[hc][r][c] = tfc_tr16(hcol + hc * HPLANE + r * rowb + c * ROWB, 4 * ROWB);
 #pragma unroll
     for (int kt = 0; kt < 8; ++kt) {
 #pragma unroll
-      for (int c = 0; c < NC; ++c) rw[NR - 1][c] = tfc_tr16(hcol + (kt + NR - 1) * rowb + c * ROWB, 4 * ROWB);
+      for (int hc = 0; hc < NH; ++hc)
+#pragma unroll
+        for (int c = 0; c < NCM; ++c) rw[hc][NCM - 1][c] = tfc_tr16(hcol + hc * HPLANE + (kt + NCM - 1) * rowb + c * ROWB, 4 * ROWB);
       const bf16x8_t av = __builtin_bit_cast(bf16x8_t, tfc_tr16(acol + kt * 16 * ROWB, 4 * ROWB));
 #pragma unroll
-      for (int r = 0; r < NR; ++r)
+      for (int hc = 0; hc < NH; ++hc)
 #pragma unroll
-        for (int c = 0; c < NC; ++c)
-          acc[r * NCM + c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av, __builtin_bit_cast(bf16x8_t, rw[r][c]), acc[r * NCM + c], 0, 0, 0);
+        for (int r = 0; r < NCM; ++r)
 #pragma unroll
-      for (int r = 0; r < NR - 1; ++r)
+          for (int c = 0; c < NCM; ++c)
+            acc[hc][r * NCM + c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av, __builtin_bit_cast(bf16x8_t, rw[hc][r][c]), acc[hc][r * NCM + c], 0, 0, 0);
 #pragma unroll
-        for (int c = 0; c < NC; ++c) rw[r][c] = rw[r + 1][c];
+      for (int hc = 0; hc < NH; ++hc)
+#pragma unroll
+        for (int r = 0; r < NCM - 1; ++r)
+#pragma unroll
+          for (int c = 0; c < NCM; ++c) rw[hc][r][c] = rw[hc][r + 1][c];
     }
   };
-  // upsample conv: every wave runs the full 3 x 3 offset grid; the offsets a phase does not have (row 2 for py = 0, column 2 for
-  // px = 0) only fill accumulators that the reduce kernel ignores -- cheaper than four differently shaped code paths
-  auto compute = [&]() { compute_v(std::integral_constant<int, NCM>{}, std::integral_constant<int, NCM>{}); };
 
   int tl = sp;
   if (tl < ntiles) { tile_load(tl); tile_store(); }
@@ -2888,134 +2724,11 @@ tfc_wgradT_kernel(const bf16_t* __restrict__ x, int IH, int IW, int x_pitch, int
     if (more) tile_store();
     __syncthreads();
   }
-
-  tfc_slab_store(slab + ((size_t)bid * 4 + wave) * (NA * 4 * 64) + lane, acc);
-}
-
-// ---------------------------------------------------------------------------------------------------
-// Round 3: the same transposed-convolution weight gradient with a 32 n x 64 c workgroup tile. tfc_wgradT_kernel<false> is bound by operand re-streaming:
-// a 32 x 32 tile re-reads dy Cin/32 times and x Cout/32 times from L2 (670 MB per launch at 256 -> 64 @ 64^2, 6.7 TB/s at 100 us) and issues six
-// transposing LDS reads per four MFMAs. Here wave w = phase still owns its 2 x 2 taps, but for TWO 32-channel halves of x: eight accumulator tiles per wave
-// (128 VGPRs), one A fragment serves eight MFMAs, dy is streamed Cin/64 times. Two workgroups per CU (55 KB of LDS). The slabs keep the logical numbering
-// of the 32 x 32 kernel (pair = nb * ncb + cb, cb = 2 cb2 + half), so the reduce kernels are unchanged.
-// ---------------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(256, 2)
-tfc_wgradT2_kernel(const bf16_t* __restrict__ x, int IH, int IW, int x_pitch, int Cin_pad, const bf16_t* __restrict__ dy, int dy_pitch,
-                   int Nn_pad, int nimg, float4* slab, int nbw, int ncb, int nsplit) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  constexpr int ROWB = 64;
-  constexpr int HH = TFC_TILE_H + 2, HW = TFC_TILE_W + 2;
-  constexpr int DO_BYTES = 4 * 128 * ROWB;                       // [phase][px][32 n]
-  constexpr int HPLANE = HH * HW * ROWB;                         // one 32-channel half of the halo
-  constexpr int NDO = DO_BYTES / 16 / 256, NHA = (HH * HW * 8 + 255) / 256;   // 8 and 6 units per thread
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int py = wave >> 1, px = wave & 1;
-  const int OH = 2 * IH, OW = 2 * IW;
-  const int tiles_y = (IH + TFC_TILE_H - 1) / TFC_TILE_H, tiles_x = (IW + TFC_TILE_W - 1) / TFC_TILE_W;
-  const int ntiles = nimg * tiles_y * tiles_x;
-  const int ncb2 = ncb >> 1;
-
-  const int bid = tfc_xcd_remap(blockIdx.x, gridDim.x);
-  const int pair2 = bid % (nbw * ncb2);
-  const int sp = bid / (nbw * ncb2);
-  const int cb2 = pair2 % ncb2, nb = pair2 / ncb2;
-
-  f32x16_t acc[2][4];                                            // [half][row offset * 2 + column offset]
+  // slabs in the numbering of the 32 x 32 form: logical workgroup (sp, nb, cb = NH * cbn + half)
 #pragma unroll
-  for (int a = 0; a < 8; ++a)
-#pragma unroll
-    for (int j = 0; j < 16; ++j) acc[a >> 2][a & 3][j] = 0.f;
-
-  uint4 vdo[NDO], vha[NHA];
-  auto tile_load = [&](int tl) {
-    int img, a0, b0;
-    tfc_tile_decode(tl, tiles_x, tiles_y, img, a0, b0);
-#pragma unroll
-    for (int i = 0; i < NDO; ++i) {
-      const int idx = tid + i * 256;                             // ((phase * 128) + pixel) * 4 + g
-      const int g = idx & 3, pxl = (idx >> 2) & 127, ph = idx >> 9;
-      const int a = a0 + (pxl >> 4), b = b0 + (pxl & 15);
-      const int n0 = nb * 32 + g * 8;
-      vdo[i] = make_uint4(0, 0, 0, 0);
-      if (a < IH && b < IW && n0 < Nn_pad)
-        vdo[i] = *reinterpret_cast<const uint4*>(dy + ((size_t)(img * OH + 2 * a + (ph >> 1)) * OW + 2 * b + (ph & 1)) * dy_pitch + n0);
-    }
-#pragma unroll
-    for (int i = 0; i < NHA; ++i) {
-      const int idx = tid + i * 256;                             // (pixel * 2 + half) * 4 + g: a pixel's 128 bytes are one contiguous run
-      vha[i] = make_uint4(0, 0, 0, 0);
-      if (idx < HH * HW * 8) {
-        const int g = idx & 3, hc = (idx >> 2) & 1, pix = idx >> 3;
-        const int hy = pix / HW, hx = pix - hy * HW;
-        const int y = a0 - 1 + hy, xx = b0 - 1 + hx;
-        const int c0 = (2 * cb2 + hc) * 32 + g * 8;
-        if (y >= 0 && y < IH && xx >= 0 && xx < IW && c0 < Cin_pad)
-          vha[i] = *reinterpret_cast<const uint4*>(x + ((size_t)(img * IH + y) * IW + xx) * x_pitch + c0);
-      }
-    }
-  };
-  auto tile_store = [&]() {
-#pragma unroll
-    for (int i = 0; i < NDO; ++i) *reinterpret_cast<uint4*>(smem + (tid + i * 256) * 16) = vdo[i];
-#pragma unroll
-    for (int i = 0; i < NHA; ++i) {
-      const int idx = tid + i * 256;
-      if (idx < HH * HW * 8) {
-        const int g = idx & 3, hc = (idx >> 2) & 1, pix = idx >> 3;
-        *reinterpret_cast<uint4*>(smem + DO_BYTES + hc * HPLANE + (pix * 4 + g) * 16) = vha[i];
-      }
-    }
-  };
-
-  const int trLane = tfc_tr_lane(lane, ROWB);
-  constexpr int rowb = HW * ROWB;
-  auto compute = [&]() {
-    const unsigned char* acol = smem + wave * 128 * ROWB + trLane;
-    const unsigned char* hcol = smem + DO_BYTES + (py * HW + px) * ROWB + trLane;    // halo row kt + py + r, column shift px + c (filter tap jy = 1 - r, jx = 1 - c)
-    uint4 rw[2][2][2];                                           // [half][window row][column]
-#pragma unroll
-    for (int hc = 0; hc < 2; ++hc)
-#pragma unroll
-      for (int c = 0; c < 2; ++c) rw[hc][0][c] = tfc_tr16(hcol + hc * HPLANE + c * ROWB, 4 * ROWB);
-#pragma unroll
-    for (int kt = 0; kt < 8; ++kt) {
-#pragma unroll
-      for (int hc = 0; hc < 2; ++hc)
-#pragma unroll
-        for (int c = 0; c < 2; ++c) rw[hc][1][c] = tfc_tr16(hcol + hc * HPLANE + (kt + 1) * rowb + c * ROWB, 4 * ROWB);
-      const bf16x8_t av = __builtin_bit_cast(bf16x8_t, tfc_tr16(acol + kt * 16 * ROWB, 4 * ROWB));
-#pragma unroll
-      for (int hc = 0; hc < 2; ++hc)
-#pragma unroll
-        for (int r = 0; r < 2; ++r)
-#pragma unroll
-          for (int c = 0; c < 2; ++c)
-            acc[hc][r * 2 + c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av, __builtin_bit_cast(bf16x8_t, rw[hc][r][c]), acc[hc][r * 2 + c], 0, 0, 0);
-#pragma unroll
-      for (int hc = 0; hc < 2; ++hc)
-#pragma unroll
-        for (int c = 0; c < 2; ++c) rw[hc][0][c] = rw[hc][1][c];
-    }
-  };
-
-  int tl = sp;
-  if (tl < ntiles) { tile_load(tl); tile_store(); }
-  __syncthreads();
-  for (; tl < ntiles; tl += nsplit) {
-    const bool more = (tl + nsplit) < ntiles;
-    if (more) tile_load(tl + nsplit);                            // next tile -> registers while this one is multiplied
-    compute();
-    __syncthreads();                                             // single LDS image: everyone is done reading it
-    if (more) tile_store();
-    __syncthreads();
-  }
-  // slabs in the numbering of the 32 x 32 kernel: logical workgroup (sp, nb, cb = 2 cb2 + half)
-#pragma unroll
-  for (int hc = 0; hc < 2; ++hc) {
-    const int lbid = sp * (nbw * ncb) + nb * ncb + 2 * cb2 + hc;
-    tfc_slab_store(slab + ((size_t)lbid * 4 + wave) * (4 * 4 * 64) + lane, acc[hc]);
+  for (int hc = 0; hc < NH; ++hc) {
+    const int lbid = sp * (nbw * ncb) + nb * ncb + NH * cbn + hc;
+    tfc_slab_store(slab + ((size_t)lbid * 4 + wave) * (NA * 4 * 64) + lane, acc[hc]);
   }
 }
 
@@ -3044,10 +2757,7 @@ tfc_wgrad_head_kernel(const bf16_t* __restrict__ x, int IH, int IW, int x_pitch,
   const int ntiles = nimg * tiles_y * tiles_x;
   const int sp = tfc_xcd_remap(blockIdx.x, gridDim.x);
   f32x16_t acc[9];
-#pragma unroll
-  for (int a = 0; a < 9; ++a)
-#pragma unroll
-    for (int j = 0; j < 16; ++j) acc[a][j] = 0.f;
+  tfc_acc_zero(acc);
 
   auto tile_stage = [&](int tl) {                                 // global -> LDS (through registers, a few units at a time: 144 accumulator VGPRs are live)
     int img, a0, b0;
@@ -3687,7 +3397,7 @@ tfc_first_block_fwd_kernel(const bf16_t* __restrict__ in, int IH, int IW, const 
       float w = 0.f;
       if (pc < 15 && ox < Wo)
         for (int j = 0; j < 4; ++j)
-          if (refl(2 * ox - 1 + j, CW) - cc0 == cc) w += (j == 0 || j == 3) ? 0.125f : 0.375f;
+          if (refl(2 * ox - 1 + j, CW) - cc0 == cc) w += fbw(j);
       Ct[e] = w;
     }
     if (tid < 16) {
@@ -3696,7 +3406,7 @@ tfc_first_block_fwd_kernel(const bf16_t* __restrict__ in, int IH, int IW, const 
       float w = 0.f;
       if (rr < 6 && oy < Ho)
         for (int i = 0; i < 4; ++i)
-          if (refl(2 * oy - 1 + i, CH) - cr0 == rr) w += (i == 0 || i == 3) ? 0.125f : 0.375f;
+          if (refl(2 * oy - 1 + i, CH) - cr0 == rr) w += fbw(i);
       Rt[tid] = w;
     }
     __syncthreads();
@@ -4122,7 +3832,7 @@ static hipError_t launch_wgrad_t(int dt, const TfcGather& d, const void* dO, con
   }
   return hipGetLastError();
 }
-// fused first-block backward (tfc_wgrad_c8_fused_kernel): d = the TFC_OP_CONV pass-2 descriptor of the layer (8 padded input channels, 64 outputs)
+// fused first-block backward (tfc_wgrad_c8_fusedm_kernel): d = the TFC_OP_CONV pass-2 descriptor of the layer (8 padded input channels, 64 outputs)
 hipError_t tfc_launch_first_block_bwd(const TfcGather& d, const void* yact, int y_pitch, const void* dyp, int dyp_pitch, int Ho, int Wo, const void* in,
                                       void* slab, float* dwacc, float* rstats, float* part_ws, float slope, int Nn_real, int Cw_real,
                                       const unsigned char* sign_mask, TfcWgradFin* fin, hipStream_t st) {
@@ -4132,11 +3842,7 @@ hipError_t tfc_launch_first_block_bwd(const TfcGather& d, const void* yact, int 
   const int wpi = plan.wpi, per = plan.per;
   const int ns = d.nimg * wpi;
   if (ns > 2048 || (rstats && (!part_ws || (long long)ns * 64 > (long long)TFC_PART_WS_FLOATS))) return hipErrorInvalidValue;
-  const char* valu_env = getenv("TFC_FIRST_BWD_VALU");            // A/B knob (read per call: the tests compare the two forms in one process)
-  if (valu_env && atoi(valu_env) != 0 && yact)
-    TFC_LAUNCH(tfc_wgrad_c8_fused_kernel, dim3(ns), dim3(256), 0, st, d, (const bf16_t*)yact, y_pitch, (const bf16_t*)dyp, dyp_pitch, Ho, Wo,
-               (const bf16_t*)in, (float4*)slab, rstats ? part_ws : nullptr, slope, wpi, per);
-  else if (sign_mask)                                             // transposed blur on the matrix core, signs from the forward pass's sign words
+  if (sign_mask)                                                  // transposed blur on the matrix core, signs from the forward pass's sign words
     TFC_LAUNCH(tfc_wgrad_c8_fusedm_kernel<true>, dim3(ns), dim3(256), 0, st, d, (const bf16_t*)yact, y_pitch, (const bf16_t*)dyp, dyp_pitch, Ho, Wo,
                (const bf16_t*)in, (float4*)slab, rstats ? part_ws : nullptr, slope, wpi, per, sign_mask);
   else
@@ -4195,7 +3901,6 @@ bool tfc_launch_wgrad_phases_fused(int up, const void* x, int N, int IH, int IW,
   const int ntiles = N * ((IH + TFC_TILE_H - 1) / TFC_TILE_H) * ((IW + TFC_TILE_W - 1) / TFC_TILE_W);
   const int T = up ? 9 : 4;                                       // accumulator tiles per wave
   const int nsplit = plan.nsplit;
-  const int lds = 4 * 128 * 64 + (TFC_TILE_H + 2) * (TFC_TILE_W + 2) * 64;
   TfcPlane none{};
   if (plan.kernel == TFC_K_WGRAD_HEAD) {
     int run = 0;
@@ -4210,19 +3915,20 @@ bool tfc_launch_wgrad_phases_fused(int up, const void* x, int N, int IH, int IW,
   }
   int run = 0;
   if ((*err = wgrad_run_splits((float4*)slab, (size_t)4 * T * 4 * 64, nbw * ncb, nsplit, ntiles, st, &run)) != hipSuccess) return true;
+  const int nh = plan.kernel == TFC_K_WGRADT2 ? 2 : 1;            // 32-channel halves of x per workgroup: 32 n x 64 c tiles, 2 workgroups per CU
+  const dim3 grid(nbw * (ncb / nh) * run);
+  const int lds = 4 * 128 * 64 + nh * (TFC_TILE_H + 2) * (TFC_TILE_W + 2) * 64;   // dy image + nh halo planes
+#define TFC_WGT(UP_, NH_) TFC_LAUNCH((tfc_wgradT_kernel<UP_, NH_>), grid, dim3(256), lds, st, (const bf16_t*)x, IH, IW, x_pitch, Cin_pad, (const bf16_t*)dy, \
+                                     dy_pitch, Nn_pad, N, (float4*)slab, nbw, ncb, nsplit)
+  if (up) TFC_WGT(true, 1);
+  else if (nh == 2) TFC_WGT(false, 2);
+  else TFC_WGT(false, 1);
+#undef TFC_WGT
   if (up) {
-    TFC_LAUNCH(tfc_wgradT_kernel<true>, dim3(nbw * ncb * run), dim3(256), lds, st, (const bf16_t*)x, IH, IW, x_pitch, Cin_pad, (const bf16_t*)dy, dy_pitch,
-                       Nn_pad, N, (float4*)slab, nbw, ncb, nsplit);
     for (int wv = 0; wv < 4; ++wv)                                // the phases overlap on the filter taps: one reduce pass per phase, in order
       TFC_LAUNCH(tfc_wgrad_reduce_kernel, dim3(nbw * ncb * T * 4), dim3(256), 0, st, (const float4*)slab, dwacc, none, 3, T, nsplit,
                          nbw * ncb, ncb, Cout, Cin, wv, 0);
   } else {
-    if (plan.kernel == TFC_K_WGRADT2)                             // 32 n x 64 c tiles, 2 workgroups per CU
-      TFC_LAUNCH(tfc_wgradT2_kernel, dim3(nbw * (ncb / 2) * run), dim3(256), 4 * 128 * 64 + 2 * (TFC_TILE_H + 2) * (TFC_TILE_W + 2) * 64, st, (const bf16_t*)x, IH, IW,
-                 x_pitch, Cin_pad, (const bf16_t*)dy, dy_pitch, Nn_pad, N, (float4*)slab, nbw, ncb, nsplit);
-    else
-      TFC_LAUNCH(tfc_wgradT_kernel<false>, dim3(nbw * ncb * run), dim3(256), lds, st, (const bf16_t*)x, IH, IW, x_pitch, Cin_pad, (const bf16_t*)dy, dy_pitch,
-                         Nn_pad, N, (float4*)slab, nbw, ncb, nsplit);
     if (tfc_fin_eligible(fin, nbw * ncb, 4)) {
       TFC_LAUNCH(tfc_wgrad_reduce_fin_kernel, dim3(nbw * ncb * 4 * 4), dim3(512), 0, st, (const float4*)slab, fin->grad, 2, T, nsplit, nbw * ncb, ncb,
                  Cout, Cin, fin->sn, fin->sc, fin->accumulate);

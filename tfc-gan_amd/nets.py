@@ -324,7 +324,7 @@ class GeneratorCore:
             if (i == 0 and not need_input_grad and not normalize and dp == 0.0 and dbg is None and ops.first_block_bwd_supported(dt, cin, cout)
                     and pooled(Hc) >= 2):
                 # nothing but this weight gradient needs the 266 MB gradient of the first convolution's output: it is never written (igemm.hip:
-                # tfc_wgrad_c8_fused_kernel = tfc_act_bwd(mode 0, pool 2) + tfc_conv_wgrad in one kernel, same d_raw bits)
+                # tfc_wgrad_c8_fusedm_kernel = tfc_act_bwd(mode 0, pool 2) + tfc_conv_wgrad in one kernel, same d_raw bits)
                 def _first_wgrad(din=din, raw=raw, g_cur=g_cur, cin=cin, cout=cout, key=key):
                     self._ws = ops.first_block_bwd_wgrad(dt, din, raw, g_cur, cin, cout, grads[key], slope=0.2, accumulate=accumulate, ws=self._ws,
                                                          sign_mask=getattr(ctx, "mask1", None))
