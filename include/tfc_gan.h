@@ -191,6 +191,48 @@ size_t tfc_fft_spectrum_ws_bytes(int S, int nwin);
 int tfc_logmag_mse(void* stream, const float* amp_a, const float* amp_b, int S, int nwin, float* out);
 /* the companion metric of TFC-GAN-FFT/eval/Eurecom/Eurecom_MagOther.py:90-118 (other_spec): mean_absolute_error of the same two log-magnitude spectra */
 int tfc_logmag_mae(void* stream, const float* amp_a, const float* amp_b, int S, int nwin, float* out);
+/* ---- evaluation metrics ---- */
+/* What the reference reads off saved PNGs with cv2 / scikit-image / numpy (TFC-GAN-FFT/eval/<set>/evaluation_psnr_ssim.py, evaluation_bhatt.py;
+ * TFC-STN/evaluation/calc_NCC.py, calc_MI.py), on uint8 images that are already on the device. Every sum over pixels is an integer sum (exact, in
+ * any order); the finalisers are fp64 and add in a fixed order; no float atomics. The workgroups of an image depend on its size alone, so the
+ * result of a pair is the same bits in any batch. At most 65535 images of at most 2^23 elements per call. Images a / b: image n at a + n * a_stride
+ * (bytes), `count` contiguous bytes each (any channel count: count = H * W * C).
+ *
+ * tfc_pair_moments_u8: moments[n][10] (int64) = sum a, sum b, sum a^2, sum b^2, sum ab, sum (a-b)^2, min a, max a, min b, max b.
+ *   psnr (nullable) [N] = calculate_psnr of evaluation_psnr_ssim.py:56-64: mse == 0 -> 100, else 20 log10(255 / sqrt(mse));
+ *   ncc (nullable) [N] = ncc of calc_NCC.py:44-64 = Pearson's r with ddof = 1 (the /255 of ToTensor cancels; a constant image gives NaN).
+ *   ws: tfc_pair_moments_ws_bytes(N, count) bytes of scratch, 8-byte aligned. 128-bit loads when both bases and strides are 16-byte aligned. */
+size_t tfc_pair_moments_ws_bytes(int N, long long count);
+int tfc_pair_moments_u8(void* stream, const uint8_t* a, long long a_stride, const uint8_t* b, long long b_stride, long long count, int N, void* ws,
+                        long long* moments, double* psnr, double* ncc);
+/* skimage.metrics.structural_similarity on uint8 gray images (evaluation_psnr_ssim.py:119): uniform window of wy rows x wx columns, K1 = 0.01,
+ * K2 = 0.03, sample covariance (cov_norm = NP / (NP - 1)), data_range in uint8 units (255); out[n] = mean of the SSIM map over the positions whose
+ * window lies inside the image -- skimage's crop by (w - 1) / 2, which makes the filter's border mode irrelevant. (wy, wx) = (7, 7): the 2-D metric.
+ * (7, 1): what the script's multichannel=True computes on a 2-D image (every column a 1-D channel): 3 rows cropped at the top and bottom only,
+ * the mean over (H - 6) * W values. Rows are a_row_stride / b_row_stride bytes apart (unit stride along W). Refuses H < wy or W < wx.
+ * ws: tfc_ssim_ws_bytes() bytes, 8-byte aligned (one fp64 partial per 16 x 64 output tile, added in a fixed order). */
+size_t tfc_ssim_ws_bytes(int N, int H, int W, int wy, int wx);
+int tfc_ssim_u8(void* stream, const uint8_t* a, long long a_img_stride, int a_row_stride, const uint8_t* b, long long b_img_stride, int b_row_stride,
+                int N, int H, int W, int wy, int wx, double data_range, void* ws, double* out);
+/* tfc_hist_u8, (a) colour: cv2.calcHist([img], [0, 1, 2], None, [8, 8, 8], [0, 256] * 3) of evaluation_bhatt.py:55: hist[n][c0 >> 5][c1 >> 5][c2 >> 5]
+ * (uint32 [N][512], overwritten). Channel c of pixel p of image n is img[n * img_stride + p * pix_stride + c * chan_stride]: (3, 1) for HWC, (1, H * W)
+ * for CHW, (1, 0) reads a gray image as R = G = B. */
+int tfc_hist_u8_color(void* stream, const uint8_t* img, long long img_stride, long long pix_stride, long long chan_stride, long long npix, int N,
+                      uint32_t* hist);
+/* tfc_hist_u8, (b) joint: hist[n][lut_a[n][a]][lut_b[n][b]] over the `count` pixels of two gray images (uint32 [N][nb][nb], overwritten; nb <= 32);
+ * lut_a / lut_b: uint8 [N][256], gray level -> bin. */
+int tfc_hist_u8_joint(void* stream, const uint8_t* a, long long a_stride, const uint8_t* b, long long b_stride, long long count, int N,
+                      const uint8_t* lut_a, const uint8_t* lut_b, int nb, uint32_t* hist);
+/* the bin tables of np.histogram2d(a / 255, b / 255, bins = nb) on float32 pixels (calc_MI.py:59) from the min / max in `moments` (as
+ * tfc_pair_moments_u8 wrote them): edges linspace(min, max, nb + 1), bins right-open except the last, range (min - 0.5, max + 0.5) when min == max.
+ * edge_f32 = 0: float64 edges (numpy 1.x, the reference's); 1: float32 edges (numpy >= 2 keeps the pixels' dtype). Each edge is one multiply and
+ * one add, rounded separately, as numpy's. */
+int tfc_mi_bin_lut(void* stream, const long long* moments, int N, int nb, int edge_f32, uint8_t* lut_a, uint8_t* lut_b);
+/* cv2.compareHist(h1, h2, HISTCMP_BHATTACHARYYA) per image: out[n] = sqrt(max(1 - sum sqrt(h1 h2) / sqrt(sum h1 * sum h2), 0)); h1, h2: [N][nbins] counts */
+int tfc_bhattacharyya(void* stream, const uint32_t* h1, const uint32_t* h2, int N, int nbins, double* out);
+/* mutual_information of calc_MI.py:72-82 per image: out[n] = sum over the non-zero cells of pxy log(pxy / (px py)); hist: [N][nb][nb] counts */
+int tfc_mutual_information(void* stream, const uint32_t* hist, int N, int nb, double* out);
+
 /* temperature head, P16:255-268 (vectorize_temps) over TFC-GAN-FFT/datasets_temp.py:14-35 (TempVector_PyTorch): the red channel of
  * ToPILImage(img[n]) = (uint8) trunc(x*255) (wraps mod 256) looked up in lut256 (float32(np.linspace(24,38,256)), device).
  * img: fp32 NCHW, channel 0 is read ([n*batch_stride + y*row_stride + x]); out: [N][H][W] fp32 temperatures in Celsius. */

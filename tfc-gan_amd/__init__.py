@@ -15,7 +15,7 @@ import os as _os
 # variable when it initialises (first GPU call), so it is set here, before anything of this package touches the GPU; an explicit setting wins.
 _os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 
-from . import _lib, data, engine, inference, losses, lpips, models, nets, ops, parallel, stn, stn21, synthetic, vit  # noqa: F401
+from . import _lib, data, engine, inference, losses, lpips, metrics, models, nets, ops, parallel, stn, stn21, synthetic, vit  # noqa: F401
 from ._lib import TfcError, build  # noqa: F401
 from .engine import TrainStep  # noqa: F401
 from .nets import set_wgrad_stream  # noqa: F401
@@ -28,10 +28,12 @@ from .inference import global_grid, load_clean_state, save_checkpoint, stitch_16
 from .losses import (ContrastiveLoss, FFT_Components, calculate_ffts, color_jitter_params, color_jitter_thermal,  # noqa: F401
                      fft_components, global_fft_loss, make_16_patches, mse_spec, other_spec, patch_fft_loss, patch_first_flat_index,
                      patch_triplet_loss, sample_spectra, temperature_triplet_loss, vectorize_temps)
+from .metrics import EvalAccumulator, bhattacharyya, mutual_information, ncc, psnr, ssim, to_gray, to_uint8  # noqa: F401
 from .models import (BlurPool, Discriminator, Discriminator1, GeneratorUNet, UNetDown, UNetUp, get_batch_invariant,  # noqa: F401
                      get_compute_dtype, set_batch_invariant, set_compute_dtype, weights_init_normal)
 
 __all__ = ["UNetDown", "UNetUp", "GeneratorUNet", "Discriminator1", "Discriminator", "BlurPool", "weights_init_normal",
            "make_16_patches", "ContrastiveLoss", "patch_triplet_loss", "FFT_Components", "fft_components", "calculate_ffts",
-           "patch_fft_loss", "global_fft_loss", "mse_spec", "other_spec", "sample_spectra", "vectorize_temps", "temperature_triplet_loss", "color_jitter_thermal",
+           "patch_fft_loss", "global_fft_loss", "mse_spec", "other_spec", "psnr", "ssim", "bhattacharyya", "ncc", "mutual_information", "to_uint8", "to_gray",
+           "EvalAccumulator", "sample_spectra", "vectorize_temps", "temperature_triplet_loss", "color_jitter_thermal",
            "color_jitter_params", "synthetic_pairs", "synthetic_temperatures", "load_clean_state", "save_checkpoint", "stitch_16_patches", "global_grid", "TrainStep", "STN21Step", "LPIPS", "ImageDataset", "TestImageDataset", "DeviceLoader", "pair_resize_normalize", "Warp", "affine_warp", "morph_gradient", "morph_triplet", "triplet_margin_rows", "set_compute_dtype", "get_compute_dtype", "set_batch_invariant", "get_batch_invariant", "build", "TfcError"]

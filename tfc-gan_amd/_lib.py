@@ -12,7 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _ROOT = os.path.dirname(_HERE)
 CSRC = os.path.join(_HERE, "csrc")
 SO_PATH = os.path.join(_HERE, "libtfcgan_hip.so")
-SOURCES = ["api.hip", "igemm.hip", "elementwise.hip", "losses.hip", "stn.hip", "lpips.hip", "input.hip", "probe.hip", "vit.hip"]
+SOURCES = ["api.hip", "igemm.hip", "elementwise.hip", "losses.hip", "stn.hip", "lpips.hip", "input.hip", "probe.hip", "vit.hip", "metrics.hip"]
 HEADERS = ["common.h", "tfc_desc.h", "pack_math.h"]
 PUBLIC_HEADER = os.path.join(_ROOT, "include", "tfc_gan.h")
 
@@ -134,6 +134,15 @@ PROTOTYPES = {
     "tfc_fft_spectrum_ws_bytes": (_sz, [_i, _i]),
     "tfc_logmag_mse": (_i, [_vp, _vp, _vp, _i, _i, _vp]),
     "tfc_logmag_mae": (_i, [_vp, _vp, _vp, _i, _i, _vp]),
+    "tfc_pair_moments_ws_bytes": (_sz, [_i, _ll]),
+    "tfc_pair_moments_u8": (_i, [_vp, _vp, _ll, _vp, _ll, _ll, _i, _vp, _vp, _vp, _vp]),
+    "tfc_ssim_ws_bytes": (_sz, [_i, _i, _i, _i, _i]),
+    "tfc_ssim_u8": (_i, [_vp, _vp, _ll, _i, _vp, _ll, _i, _i, _i, _i, _i, _i, _c.c_double, _vp, _vp]),
+    "tfc_hist_u8_color": (_i, [_vp, _vp, _ll, _ll, _ll, _ll, _i, _vp]),
+    "tfc_hist_u8_joint": (_i, [_vp, _vp, _ll, _vp, _ll, _ll, _i, _vp, _vp, _i, _vp]),
+    "tfc_mi_bin_lut": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),
+    "tfc_bhattacharyya": (_i, [_vp, _vp, _vp, _i, _i, _vp]),
+    "tfc_mutual_information": (_i, [_vp, _vp, _i, _i, _vp]),
     "tfc_vectorize_temps": (_i, [_vp, _vp, _ll, _i, _i, _i, _i, _vp, _vp]),
     "tfc_row_triplet": (_i, [_vp, _vp, _vp, _vp, _ll, _i, _f, _vp]),
     "tfc_l1_sum": (_i, [_vp, _vp, _vp, _ll, _f, _vp, _i]),

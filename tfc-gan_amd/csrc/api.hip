@@ -70,6 +70,20 @@ size_t tfc_fft_ws_bytes(int S, int nwin);
 hipError_t tfc_launch_l1_sum(const float* a, const float* b, long long n, float scale, float* out, hipStream_t st);
 hipError_t tfc_launch_probe(float* out, hipStream_t st);
 hipError_t tfc_launch_logmag_mse(const float* a, const float* b, int S, int nwin, float* out, int absolute, hipStream_t st);
+// metrics.hip
+int tfc_moments_groups(long long count);
+void tfc_ssim_tiles(int H, int W, int wy, int wx, int* tx, int* ty);
+hipError_t tfc_launch_pair_moments(const uint8_t* a, const uint8_t* b, long long a_stride, long long b_stride, long long count, int N, long long* ws,
+                                   long long* mom, double* psnr, double* ncc, hipStream_t st);
+hipError_t tfc_launch_ssim(const uint8_t* a, long long a_is, int a_rs, const uint8_t* b, long long b_is, int b_rs, int N, int H, int W, int wy, int wx,
+                           double data_range, double* ws, double* out, hipStream_t st);
+hipError_t tfc_launch_hist_color(const uint8_t* img, long long img_stride, long long pix_stride, long long chan_stride, long long npix, int N, unsigned* hist,
+                                 hipStream_t st);
+hipError_t tfc_launch_hist_joint(const uint8_t* a, const uint8_t* b, long long a_stride, long long b_stride, long long count, int N, const uint8_t* lut_a,
+                                 const uint8_t* lut_b, int nb, unsigned* hist, hipStream_t st);
+hipError_t tfc_launch_mi_lut(const long long* mom, int N, int nb, int edge_f32, uint8_t* lut_a, uint8_t* lut_b, hipStream_t st);
+hipError_t tfc_launch_bhattacharyya(const unsigned* h1, const unsigned* h2, int N, int nbins, double* out, hipStream_t st);
+hipError_t tfc_launch_mutual_information(const unsigned* hist, int N, int nb, double* out, hipStream_t st);
 hipError_t tfc_launch_vectorize_temps(const float* x, long long bs, int rs, int N, int H, int W, const float* lut, float* out, hipStream_t st);
 hipError_t tfc_launch_row_triplet(const float* a, const float* p, const float* ng, long long rows, int W, float margin, float eps,
                                   float* loss, hipStream_t st);
@@ -847,6 +861,79 @@ extern "C" int tfc_logmag_mse(void* stream, const float* amp_a, const float* amp
 extern "C" int tfc_logmag_mae(void* stream, const float* amp_a, const float* amp_b, int S, int nwin, float* out) {
   REQUIRE(amp_a && amp_b && out && (S == 64 || S == 256) && nwin > 0, "bad args");
   CHECK_HIP(tfc_launch_logmag_mse(amp_a, amp_b, S, nwin, out, 1, (hipStream_t)stream), "tfc_logmag_mae");
+  return 0;
+}
+// ---- evaluation metrics (metrics.hip) ----------------------------------------------------------------------------------------------------------
+#define TFC_METRIC_MAX_COUNT (1ll << 23)    // elements per image: keeps count * (sum of squares) of the NCC finaliser inside 63 bits
+#define TFC_METRIC_MAX_N 65535              // images per call (a grid dimension)
+extern "C" size_t tfc_pair_moments_ws_bytes(int N, long long count) {
+  return N > 0 && count > 0 && count <= TFC_METRIC_MAX_COUNT ? (size_t)N * tfc_moments_groups(count) * 10 * sizeof(long long) : 0;
+}
+extern "C" int tfc_pair_moments_u8(void* stream, const uint8_t* a, long long a_stride, const uint8_t* b, long long b_stride, long long count, int N,
+                                   void* ws, long long* moments, double* psnr, double* ncc) {
+  REQUIRE(a && b && ws && moments, "a, b, ws and moments must be device pointers");
+  REQUIRE(N > 0 && N <= TFC_METRIC_MAX_N, "N = %d: 1 .. %d images per call", N, TFC_METRIC_MAX_N);
+  REQUIRE(count > 0 && count <= TFC_METRIC_MAX_COUNT, "count = %lld: 1 .. 2^23 elements per image", count);
+  REQUIRE(a_stride >= count && b_stride >= count, "image strides (%lld, %lld) are smaller than the image (%lld bytes)", a_stride, b_stride, count);
+  REQUIRE((((uintptr_t)ws | (uintptr_t)moments) & 7) == 0, "ws and moments must be 8-byte aligned");
+  CHECK_HIP(tfc_launch_pair_moments(a, b, a_stride, b_stride, count, N, (long long*)ws, moments, psnr, ncc, (hipStream_t)stream), "tfc_pair_moments_u8");
+  return 0;
+}
+extern "C" size_t tfc_ssim_ws_bytes(int N, int H, int W, int wy, int wx) {
+  if (N <= 0 || wy <= 0 || wx <= 0 || H < wy || W < wx) return 0;
+  int tx, ty;
+  tfc_ssim_tiles(H, W, wy, wx, &tx, &ty);
+  return (size_t)N * tx * ty * sizeof(double);
+}
+extern "C" int tfc_ssim_u8(void* stream, const uint8_t* a, long long a_img_stride, int a_row_stride, const uint8_t* b, long long b_img_stride,
+                           int b_row_stride, int N, int H, int W, int wy, int wx, double data_range, void* ws, double* out) {
+  REQUIRE(a && b && ws && out, "a, b, ws and out must be device pointers");
+  REQUIRE((wy == 7 && wx == 7) || (wy == 7 && wx == 1), "window (wy, wx) = (%d, %d): (7, 7) and (7, 1) are supported", wy, wx);
+  REQUIRE(H >= wy && W >= wx, "image %d x %d is smaller than the %d x %d SSIM window", H, W, wy, wx);
+  REQUIRE(N > 0 && N <= TFC_METRIC_MAX_N, "N = %d: 1 .. %d images per call", N, TFC_METRIC_MAX_N);
+  REQUIRE((long long)H * W <= TFC_METRIC_MAX_COUNT, "image %d x %d: at most 2^23 pixels", H, W);
+  REQUIRE(a_row_stride >= W && b_row_stride >= W && a_img_stride >= (long long)(H - 1) * a_row_stride + W &&
+          b_img_stride >= (long long)(H - 1) * b_row_stride + W, "strides do not cover a %d x %d image", H, W);
+  REQUIRE(data_range > 0.0, "data_range must be positive");
+  REQUIRE((((uintptr_t)ws | (uintptr_t)out) & 7) == 0, "ws and out must be 8-byte aligned");
+  CHECK_HIP(tfc_launch_ssim(a, a_img_stride, a_row_stride, b, b_img_stride, b_row_stride, N, H, W, wy, wx, data_range, (double*)ws, out, (hipStream_t)stream),
+            "tfc_ssim_u8");
+  return 0;
+}
+extern "C" int tfc_hist_u8_color(void* stream, const uint8_t* img, long long img_stride, long long pix_stride, long long chan_stride, long long npix, int N,
+                                 uint32_t* hist) {
+  REQUIRE(img && hist && (((uintptr_t)hist) & 3) == 0, "img and hist must be device pointers");
+  REQUIRE(N > 0 && N <= TFC_METRIC_MAX_N, "N = %d: 1 .. %d images per call", N, TFC_METRIC_MAX_N);
+  REQUIRE(npix > 0 && npix <= TFC_METRIC_MAX_COUNT, "npix = %lld: 1 .. 2^23 pixels per image", npix);
+  REQUIRE(pix_stride > 0 && chan_stride >= 0 && img_stride >= (npix - 1) * pix_stride + 2 * chan_stride + 1,
+          "strides (image %lld, pixel %lld, channel %lld) do not cover %lld pixels", img_stride, pix_stride, chan_stride, npix);
+  CHECK_HIP(tfc_launch_hist_color(img, img_stride, pix_stride, chan_stride, npix, N, hist, (hipStream_t)stream), "tfc_hist_u8_color");
+  return 0;
+}
+extern "C" int tfc_hist_u8_joint(void* stream, const uint8_t* a, long long a_stride, const uint8_t* b, long long b_stride, long long count, int N,
+                                 const uint8_t* lut_a, const uint8_t* lut_b, int nb, uint32_t* hist) {
+  REQUIRE(a && b && lut_a && lut_b && hist && (((uintptr_t)hist) & 3) == 0, "a, b, the tables and hist must be device pointers");
+  REQUIRE(N > 0 && N <= TFC_METRIC_MAX_N, "N = %d: 1 .. %d images per call", N, TFC_METRIC_MAX_N);
+  REQUIRE(count > 0 && count <= TFC_METRIC_MAX_COUNT && a_stride >= count && b_stride >= count, "count = %lld (1 .. 2^23) with strides %lld, %lld", count,
+          a_stride, b_stride);
+  REQUIRE(nb >= 1 && nb <= 32, "nb = %d: 1 .. 32 bins per axis", nb);
+  CHECK_HIP(tfc_launch_hist_joint(a, b, a_stride, b_stride, count, N, lut_a, lut_b, nb, hist, (hipStream_t)stream), "tfc_hist_u8_joint");
+  return 0;
+}
+extern "C" int tfc_mi_bin_lut(void* stream, const long long* moments, int N, int nb, int edge_f32, uint8_t* lut_a, uint8_t* lut_b) {
+  REQUIRE(moments && lut_a && lut_b, "moments and the tables must be device pointers");
+  REQUIRE(N > 0 && N <= TFC_METRIC_MAX_N && nb >= 1 && nb <= 32, "N = %d (1 .. %d), nb = %d (1 .. 32)", N, TFC_METRIC_MAX_N, nb);
+  CHECK_HIP(tfc_launch_mi_lut(moments, N, nb, edge_f32 ? 1 : 0, lut_a, lut_b, (hipStream_t)stream), "tfc_mi_bin_lut");
+  return 0;
+}
+extern "C" int tfc_bhattacharyya(void* stream, const uint32_t* h1, const uint32_t* h2, int N, int nbins, double* out) {
+  REQUIRE(h1 && h2 && out && N > 0 && nbins > 0 && (((uintptr_t)out) & 7) == 0, "bad args");
+  CHECK_HIP(tfc_launch_bhattacharyya(h1, h2, N, nbins, out, (hipStream_t)stream), "tfc_bhattacharyya");
+  return 0;
+}
+extern "C" int tfc_mutual_information(void* stream, const uint32_t* hist, int N, int nb, double* out) {
+  REQUIRE(hist && out && N > 0 && nb >= 1 && nb <= 32 && (((uintptr_t)out) & 7) == 0, "bad args");
+  CHECK_HIP(tfc_launch_mutual_information(hist, N, nb, out, (hipStream_t)stream), "tfc_mutual_information");
   return 0;
 }
 extern "C" int tfc_vectorize_temps(void* stream, const float* img, long long batch_stride, int row_stride, int N, int H, int W,

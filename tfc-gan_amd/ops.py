@@ -634,3 +634,92 @@ def prof_collect(kclass):
     ms, fl, n = ctypes.c_double(), ctypes.c_double(), ctypes.c_longlong()
     check(lib().tfc_prof_collect(kclass, ctypes.byref(ms), ctypes.byref(fl), ctypes.byref(n)), "tfc_prof_collect")
     return ms.value, fl.value, n.value
+
+
+# ---- evaluation metrics (include/tfc_gan.h, "evaluation metrics"; csrc/metrics.hip) ------------------------------------------------------------
+# Operands: uint8 device tensors [N, ...] whose images are contiguous blocks (stride(0) may be anything >= the image). Scratch is a fresh torch
+# allocation per call (the caching allocator: no synchronisation), so calls on different streams never share it.
+def _flat_u8(t):
+    """[N, ...] uint8 on the device with every image contiguous -> (tensor, bytes per image)"""
+    require_gpu(t)
+    assert t.dtype == torch.uint8 and t.dim() >= 2, "uint8 [N, ...] images expected"
+    if not t[0].is_contiguous() or (t.shape[0] > 1 and t.stride(0) < t[0].numel()):
+        t = t.contiguous()
+    return t, t[0].numel()
+
+
+def _img_stride(t, count):
+    """bytes between images; a batch of one has none, and says "aligned" so that its single image may take the 128-bit loads"""
+    return t.stride(0) if t.shape[0] > 1 else (count + 15) // 16 * 16
+
+
+def pair_moments(a, b, want_psnr=True, want_ncc=True):
+    """Exact integer moments of N image pairs: int64 [N,10] = sum a, sum b, sum a^2, sum b^2, sum ab, sum (a-b)^2, min a, max a, min b, max b;
+    plus PSNR and NCC (fp64 [N], or None when not wanted)."""
+    a, count = _flat_u8(a)
+    b, cb = _flat_u8(b)
+    assert a.shape[0] == b.shape[0] and count == cb, "a and b must hold the same number of images of the same size"
+    N = a.shape[0]
+    ws = torch.empty(max(lib().tfc_pair_moments_ws_bytes(N, count), 8) // 8, dtype=torch.int64, device=a.device)
+    mom = torch.empty((N, 10), dtype=torch.int64, device=a.device)
+    psnr = torch.empty(N, dtype=torch.float64, device=a.device) if want_psnr else None
+    ncc = torch.empty(N, dtype=torch.float64, device=a.device) if want_ncc else None
+    check(lib().tfc_pair_moments_u8(stream_ptr(), _p(a), _img_stride(a, count), _p(b), _img_stride(b, count), count, N, _p(ws),
+                                    _p(mom), _p(psnr), _p(ncc)), "tfc_pair_moments_u8")
+    return mom, psnr, ncc
+
+
+def ssim_u8(a, b, wy=7, wx=7, data_range=255.0):
+    """a, b: uint8 [N,H,W] gray on the device (unit stride along W; row and image strides are passed through). fp64 [N]."""
+    require_gpu(a, b)
+    assert a.dtype == torch.uint8 and b.dtype == torch.uint8 and a.dim() == 3 and a.shape == b.shape, "uint8 [N,H,W] pairs of one shape expected"
+    if a.stride(2) != 1:
+        a = a.contiguous()
+    if b.stride(2) != 1:
+        b = b.contiguous()
+    N, H, W = a.shape
+    ws = torch.empty(max(lib().tfc_ssim_ws_bytes(N, H, W, wy, wx), 8) // 8, dtype=torch.float64, device=a.device)
+    out = torch.empty(N, dtype=torch.float64, device=a.device)
+    span = (H - 1) * max(a.stride(1), b.stride(1)) + W
+    check(lib().tfc_ssim_u8(stream_ptr(), _p(a), a.stride(0) if N > 1 else span, a.stride(1), _p(b), b.stride(0) if N > 1 else span, b.stride(1),
+                            N, H, W, wy, wx, float(data_range), _p(ws), _p(out)), "tfc_ssim_u8")
+    return out
+
+
+def hist_color(img, layout):
+    """8 x 8 x 8 colour histogram, uint32 [N,512]. layout: "hwc" [N,H,W,3], "chw" [N,3,H,W], "gray" [N,H,W] (read as R = G = B)."""
+    img, count = _flat_u8(img)
+    N = img.shape[0]
+    npix = count if layout == "gray" else count // 3
+    pix, chan = {"hwc": (3, 1), "chw": (1, npix), "gray": (1, 0)}[layout]
+    hist = torch.empty((N, 512), dtype=torch.int32, device=img.device)
+    check(lib().tfc_hist_u8_color(stream_ptr(), _p(img), _img_stride(img, count), pix, chan, npix, N, _p(hist)), "tfc_hist_u8_color")
+    return hist
+
+
+def bhattacharyya(h1, h2):
+    """h1, h2: int32 [N,nbins] counts -> fp64 [N]"""
+    out = torch.empty(h1.shape[0], dtype=torch.float64, device=h1.device)
+    check(lib().tfc_bhattacharyya(stream_ptr(), _p(h1), _p(h2), h1.shape[0], h1.shape[1], _p(out)), "tfc_bhattacharyya")
+    return out
+
+
+def joint_hist(a, b, moments, nb, edge_f32=False):
+    """[N,nb,nb] int32 joint histogram of np.histogram2d(a / 255, b / 255, bins = nb) on float32 pixels; moments: pair_moments(a, b)[0]"""
+    a, count = _flat_u8(a)
+    b, cb = _flat_u8(b)
+    assert a.shape[0] == b.shape[0] and count == cb
+    N = a.shape[0]
+    luts = torch.empty((2, N, 256), dtype=torch.uint8, device=a.device)
+    check(lib().tfc_mi_bin_lut(stream_ptr(), _p(moments), N, nb, 1 if edge_f32 else 0, _p(luts[0]), _p(luts[1])), "tfc_mi_bin_lut")
+    hist = torch.empty((N, nb, nb), dtype=torch.int32, device=a.device)
+    check(lib().tfc_hist_u8_joint(stream_ptr(), _p(a), _img_stride(a, count), _p(b), _img_stride(b, count), count, N,
+                                  _p(luts[0]), _p(luts[1]), nb, _p(hist)), "tfc_hist_u8_joint")
+    return hist
+
+
+def mutual_information(hist):
+    """hist: int32 [N,nb,nb] counts -> fp64 [N]"""
+    out = torch.empty(hist.shape[0], dtype=torch.float64, device=hist.device)
+    check(lib().tfc_mutual_information(stream_ptr(), _p(hist), hist.shape[0], hist.shape[1], _p(out)), "tfc_mutual_information")
+    return out
