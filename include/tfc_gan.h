@@ -178,16 +178,21 @@ int tfc_spectral_norm_bwd(void* stream, const float* G, const float* W, const fl
  * loss[0] = (1/16) sum_k mean(...);  dfake (nullable) = gscale * d loss / d fake. */
 int tfc_patch16_triplet(void* stream, const float* fake, const float* real, const int* neg_idx_host, int N, int C,
                         float* loss, float* dfake, float gscale);
+/* the same head on a grid x grid patch grid (patches of 256/grid pixels): grid 4 IS tfc_patch16_triplet (same bits); grid 2 = the four 128 x 128
+ * patches of TFCGAN_multigpu_patchFFT.py:468-481, loss[0] = (1/4) sum_k mean(...).  neg_idx_host: grid*grid ints in [0, grid*grid).
+ * dfake (nullable) is written for every pixel (zero where the hinge is inactive). */
+int tfc_patch_triplet(void* stream, const float* fake, const float* real, const int* neg_idx_host, int grid, int N, int C,
+                      float* loss, float* dfake, float gscale);
 /* spectra: ToPILImage -> convert("L") -> np.fft.rfft2 -> fftshift -> abs / arctan2, P16:271-319.
- * img: fp32 [N][C][rows][rs] window grid: S in {64,256}; windows per image = wins_x*wins_y tiles of S x S starting at the
+ * img: fp32 [N][C][rows][rs] window grid: S in {64,128,256}; windows per image = wins_x*wins_y tiles of S x S starting at the
  * image origin; amp/pha: [N*wins][S][S/2+1] fp32; shift != 0 applies np.fft.fftshift to both axes. */
 int tfc_fft_spectrum(void* stream, const float* img, long long batch_stride, long long chan_stride, int row_stride, int C, int S,
                      int wins_x, int wins_y, int N, float* amp, float* pha, int shift, void* ws);
 /* ws: tfc_fft_spectrum_ws_bytes(S, N * wins_x * wins_y) bytes of scratch (row-transformed half spectra) -> radix-4 FFT in LDS (rows, then
- * columns); ws == NULL -> direct DFT (S^2 work per output row: fine for one 64 x 64 window, 1 ms per call for 32 whole 256 x 256 images). */
+ * columns; S = 128 = 4^3 * 2 adds one radix-2 pass); ws == NULL -> direct DFT (S^2 work per output row: fine for one 64 x 64 window, 1 ms per call for 32 whole 256 x 256 images). */
 size_t tfc_fft_spectrum_ws_bytes(int S, int nwin);
 /* evaluation metric of TFC-GAN-FFT/Devcom_MagMSE.py:91-118 (mse_spec): per window MSE(log|fft2(a)|, log|fft2(b)|) over the FULL S x S
- * spectrum, computed from the half spectra amp_a / amp_b [nwin][S][S/2+1] of tfc_fft_spectrum; out[nwin] */
+ * spectrum, computed from the half spectra amp_a / amp_b [nwin][S][S/2+1] of tfc_fft_spectrum (S in {64,128,256}); out[nwin] */
 int tfc_logmag_mse(void* stream, const float* amp_a, const float* amp_b, int S, int nwin, float* out);
 /* the companion metric of TFC-GAN-FFT/eval/Eurecom/Eurecom_MagOther.py:90-118 (other_spec): mean_absolute_error of the same two log-magnitude spectra */
 int tfc_logmag_mae(void* stream, const float* amp_a, const float* amp_b, int S, int nwin, float* out);

@@ -74,7 +74,10 @@ def _build_locked(verbose):
 # while hipcc keeps their destination registers in place (no scratch, no VGPR spill) between the load and the wait. The compiler's resource remarks
 # (-Rpass-analysis=kernel-resource-usage) are checked at every build, so a toolchain or flag change that makes one of them spill fails loudly here
 # instead of silently producing wrong convolutions.
-GUARDED_KERNELS = ("tfc_igemm2_kernel", "tfc_wgrad")
+# The 4-patch loss heads (tfc_triplet4_kernel with four float2 rows in flight, the 128-point FFT kernels) ride the same check: they were sized to run
+# without scratch, and a spill there would be a silent slowdown of every PATCH-4 / GLO-4 step.
+GUARDED_KERNELS = ("tfc_igemm2_kernel", "tfc_wgrad", "tfc_triplet4_kernel", "tfc_fft_rows_kernelILi128E", "tfc_fft_cols_kernelILi128E",
+                   "tfc_spectrum_kernelILi128E")
 
 
 def check_no_spills(remarks):
@@ -130,6 +133,7 @@ PROTOTYPES = {
                                             _c.POINTER(_vp), _c.POINTER(_i), _c.POINTER(_i), _vp, _i]),
     "tfc_spectral_norm_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i]),
     "tfc_patch16_triplet": (_i, [_vp, _vp, _vp, _c.POINTER(_i), _i, _i, _vp, _vp, _f]),
+    "tfc_patch_triplet": (_i, [_vp, _vp, _vp, _c.POINTER(_i), _i, _i, _i, _vp, _vp, _f]),
     "tfc_fft_spectrum": (_i, [_vp, _vp, _ll, _ll, _i, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp]),
     "tfc_fft_spectrum_ws_bytes": (_sz, [_i, _i]),
     "tfc_logmag_mse": (_i, [_vp, _vp, _vp, _i, _i, _vp]),

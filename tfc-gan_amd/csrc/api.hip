@@ -65,6 +65,7 @@ hipError_t tfc_launch_axpby(float* out, const float* x, const float* y, long lon
 hipError_t tfc_launch_dropout_mask(unsigned char* out, long long n, unsigned seed, unsigned thresh24, hipStream_t st);
 hipError_t tfc_launch_cast(int dt, int to_f32, const void* x, void* y, long long n, hipStream_t st);
 hipError_t tfc_launch_triplet16(const float* fake, const float* real, const int* neg_idx, int N, int C, float margin, float eps, float* loss, float* dfake, float gscale, hipStream_t st);
+hipError_t tfc_launch_triplet4(const float* fake, const float* real, const int* neg_idx, int N, int C, float margin, float eps, float* loss, float* dfake, float gscale, hipStream_t st);
 hipError_t tfc_launch_spectrum(const float* img, long long bs, long long cs, int rs, int C, int S, int wins_x, int wins_per_img, int nwin, float* amp, float* pha, int shift, void* ws, hipStream_t st);
 size_t tfc_fft_ws_bytes(int S, int nwin);
 hipError_t tfc_launch_l1_sum(const float* a, const float* b, long long n, float scale, float* out, hipStream_t st);
@@ -845,21 +846,31 @@ extern "C" int tfc_patch16_triplet(void* stream, const float* fake, const float*
   CHECK_HIP(tfc_launch_triplet16(fake, real, neg_idx_host, N, C, 1.0f, 1e-6f, loss, dfake, gscale, (hipStream_t)stream), "tfc_patch16_triplet");
   return 0;
 }
-extern "C" size_t tfc_fft_spectrum_ws_bytes(int S, int nwin) { return (S == 64 || S == 256) && nwin > 0 ? tfc_fft_ws_bytes(S, nwin) : 0; }
+extern "C" int tfc_patch_triplet(void* stream, const float* fake, const float* real, const int* neg_idx_host, int grid, int N, int C,
+                                 float* loss, float* dfake, float gscale) {
+  REQUIRE(grid == 2 || grid == 4, "grid=%d: the patch grid is 2 (four 128 x 128 patches) or 4 (sixteen 64 x 64 patches)", grid);
+  if (grid == 4) return tfc_patch16_triplet(stream, fake, real, neg_idx_host, N, C, loss, dfake, gscale);
+  REQUIRE(fake && real && neg_idx_host && loss && N > 0 && C > 0, "bad args");
+  REQUIRE(((uintptr_t)fake & 7) == 0 && ((uintptr_t)real & 7) == 0 && ((uintptr_t)dfake & 7) == 0, "fake / real / dfake must be 8-byte aligned (pixel pairs)");
+  for (int i = 0; i < 4; ++i) REQUIRE(neg_idx_host[i] >= 0 && neg_idx_host[i] < 4, "neg_idx[%d]=%d out of range", i, neg_idx_host[i]);
+  CHECK_HIP(tfc_launch_triplet4(fake, real, neg_idx_host, N, C, 1.0f, 1e-6f, loss, dfake, gscale, (hipStream_t)stream), "tfc_patch_triplet");
+  return 0;
+}
+extern "C" size_t tfc_fft_spectrum_ws_bytes(int S, int nwin) { return (S == 64 || S == 128 || S == 256) && nwin > 0 ? tfc_fft_ws_bytes(S, nwin) : 0; }
 extern "C" int tfc_fft_spectrum(void* stream, const float* img, long long batch_stride, long long chan_stride, int row_stride, int C, int S,
                                 int wins_x, int wins_y, int N, float* amp, float* pha, int shift, void* ws) {
-  REQUIRE(img && amp && pha && (S == 64 || S == 256) && (C == 1 || C == 3) && wins_x > 0 && wins_y > 0 && N > 0, "bad args");
+  REQUIRE(img && amp && pha && (S == 64 || S == 128 || S == 256) && (C == 1 || C == 3) && wins_x > 0 && wins_y > 0 && N > 0, "bad args");
   if (ws) { if (int e = check_ptr16(ws, "ws")) return e; }
   CHECK_HIP(tfc_launch_spectrum(img, batch_stride, chan_stride, row_stride, C, S, wins_x, wins_x * wins_y, N * wins_x * wins_y, amp, pha, shift, ws, (hipStream_t)stream), "tfc_fft_spectrum");
   return 0;
 }
 extern "C" int tfc_logmag_mse(void* stream, const float* amp_a, const float* amp_b, int S, int nwin, float* out) {
-  REQUIRE(amp_a && amp_b && out && (S == 64 || S == 256) && nwin > 0, "bad args");
+  REQUIRE(amp_a && amp_b && out && (S == 64 || S == 128 || S == 256) && nwin > 0, "bad args");
   CHECK_HIP(tfc_launch_logmag_mse(amp_a, amp_b, S, nwin, out, 0, (hipStream_t)stream), "tfc_logmag_mse");
   return 0;
 }
 extern "C" int tfc_logmag_mae(void* stream, const float* amp_a, const float* amp_b, int S, int nwin, float* out) {
-  REQUIRE(amp_a && amp_b && out && (S == 64 || S == 256) && nwin > 0, "bad args");
+  REQUIRE(amp_a && amp_b && out && (S == 64 || S == 128 || S == 256) && nwin > 0, "bad args");
   CHECK_HIP(tfc_launch_logmag_mse(amp_a, amp_b, S, nwin, out, 1, (hipStream_t)stream), "tfc_logmag_mae");
   return 0;
 }

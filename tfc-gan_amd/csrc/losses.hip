@@ -72,11 +72,76 @@ tfc_triplet16_kernel(const float* __restrict__ fake, const float* __restrict__ r
 }
 
 // ---------------------------------------------------------------------------------------------------
+// 4-patch triplet (PATCH-4 / GLO-4, reference TFCGAN_multigpu_patchFFT.py:468-481).  Patch k = rows 128*(k/2).., cols 128*(k%2)..; first flat
+// index of patch k = 128*(k%2) + 32768*(k/2).  Same head as above with 128-pixel patch rows: one wave per row, two adjacent pixels per lane
+// (float2), total = (1/4) sum_k loss_k.  Row id = ((n*C + c)*256 + y)*2 + kx.  A slot of its own: the head may run beside a 16-patch call
+// of another stream.  The gradient's factor coef = gscale / (4 N C 128) is rounded ONCE, on the host: a sample's gradient at batch N with
+// gscale = N is then the same bits as that sample alone with gscale = 1 (everything else in a row's arithmetic is per sample).
+// ---------------------------------------------------------------------------------------------------
+struct NegIdx4 { int r[4]; };
+static __device__ TfcRedSlot g_trip4_slot;
+
+__global__ void __launch_bounds__(256)
+tfc_triplet4_kernel(const float* __restrict__ fake, const float* __restrict__ real, const NegIdx4 neg, int N, int C,
+                    float margin, float eps, float* loss, float* dfake, float coef) {
+  __shared__ float red[4];
+  const int lane = threadIdx.x & 63;
+  const int w = threadIdx.x >> 6;
+  const long long nrows = (long long)N * C * 256 * 2;
+  float lsum = 0.f;
+  constexpr int R = 4;                                           // rows in flight, as in the 16-patch kernel
+  const long long stride = (long long)gridDim.x * 4;
+  for (long long row0 = (long long)blockIdx.x * 4 + w; row0 < nrows; row0 += stride * R) {
+    float2 a[R], p[R], ng[R];
+    size_t ia[R];
+    bool ok[R];
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      const long long row = row0 + r * stride;
+      ok[r] = row < nrows;
+      const long long rw = ok[r] ? row : row0;
+      const int kx = (int)(rw & 1);
+      const long long r2 = rw >> 1;
+      const int y = (int)(r2 & 255);
+      const long long nc = r2 >> 8;                              // n*C + c
+      const int k = (y >> 7) * 2 + kx;
+      const int rk = neg.r[k];
+      const size_t plane = (size_t)nc * 65536;
+      ia[r] = plane + (size_t)y * 256 + kx * 128 + 2 * lane;
+      const size_t in_ = plane + (size_t)((rk >> 1) * 128 + (y & 127)) * 256 + (rk & 1) * 128 + 2 * lane;
+      a[r] = *reinterpret_cast<const float2*>(fake + ia[r]);
+      p[r] = *reinterpret_cast<const float2*>(real + ia[r]);
+      ng[r] = *reinterpret_cast<const float2*>(real + in_);
+    }
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      if (!ok[r]) continue;                                      // wave-uniform
+      const float dpx = a[r].x - p[r].x + eps, dpy = a[r].y - p[r].y + eps;
+      const float dnx = a[r].x - ng[r].x + eps, dny = a[r].y - ng[r].y + eps;
+      const float sp = wave_sum(dpx * dpx + dpy * dpy), sn = wave_sum(dnx * dnx + dny * dny);
+      const float dap = sqrtf(sp), dan = sqrtf(sn);
+      const float hinge = margin + dap - dan;
+      float2 g = make_float2(0.f, 0.f);
+      if (hinge > 0.f) {
+        lsum += hinge;                                           // identical on all lanes
+        g.x = ((dap > 0.f ? dpx / dap : 0.f) - (dan > 0.f ? dnx / dan : 0.f)) * coef;
+        g.y = ((dap > 0.f ? dpy / dap : 0.f) - (dan > 0.f ? dny / dan : 0.f)) * coef;
+      }
+      if (dfake) *reinterpret_cast<float2*>(dfake + ia[r]) = g;
+    }
+  }
+  if (lane == 0) red[w] = lsum;
+  __syncthreads();
+  if (threadIdx.x == 0)
+    tfc_block_commit(&g_trip4_slot, ((double)red[0] + (double)red[1] + (double)red[2] + (double)red[3]) / (4.0 * N * C * 128.0), loss, true);
+}
+
+// ---------------------------------------------------------------------------------------------------
 // Spectrum of an S x S window of an NCHW fp32 image in [-1,1]:
 //   u8 = (uint8) trunc(x*255)  (wraps mod 256 exactly like tensor.mul(255).byte());  L = (19595 R + 38470 G + 7471 B + 32768) >> 16
 //   F = rfft2(L)  (S x (S/2+1)),  amp = |F|, pha = atan2(Im, Re); optional fftshift of both axes on store.
 // Direct DFT in LDS with an exact sincospi twiddle table: rows (real input) then columns. A workgroup owns one window
-// and a group of KG output columns, so S=256 (GLO-16) fits LDS as well as S=64 (PATCH-16).
+// and a group of KG output columns, so S=256 (GLO-16) fits LDS as well as S=64 (PATCH-16) and S=128 (PATCH-4).
 // The four self-conjugate bins have Im forced to +0 (numpy's pocketfft yields exact zeros there).
 // window w -> (n = w / wins_per_img, k = w % wins_per_img), origin row (k / wins_x)*S, col (k % wins_x)*S.
 // ---------------------------------------------------------------------------------------------------
@@ -258,27 +323,45 @@ hipError_t tfc_launch_triplet16(const float* fake, const float* real, const int*
   hipLaunchKernelGGL(tfc_triplet16_kernel, dim3((int)nb), dim3(256), 0, st, fake, real, ni, N, C, margin, eps, loss, dfake, gscale);
   return hipGetLastError();
 }
+hipError_t tfc_launch_triplet4(const float* fake, const float* real, const int* neg_idx, int N, int C, float margin, float eps,
+                               float* loss, float* dfake, float gscale, hipStream_t st) {
+  NegIdx4 ni;
+  for (int i = 0; i < 4; ++i) ni.r[i] = neg_idx[i];
+  long long nrows = (long long)N * C * 512;
+  long long nb = (nrows + 3) / 4;
+  if (nb > 512) nb = 512;                                        // as above
+  const float coef = (float)((double)gscale / (4.0 * N * C * 128.0));
+  hipLaunchKernelGGL(tfc_triplet4_kernel, dim3((int)nb), dim3(256), 0, st, fake, real, ni, N, C, margin, eps, loss, dfake, coef);
+  return hipGetLastError();
+}
 
-// S in {64, 256}; windows = N * wins_per_img; amp/pha: [windows][S][S/2+1]
+// S in {64, 128, 256}; windows = N * wins_per_img; amp/pha: [windows][S][S/2+1]
 
 // ---------------------------------------------------------------------------------------------------
-// The same spectra by FFT (S = 64 or 256 = 4^3 / 4^4): radix-4 Stockham autosort passes in LDS, no bit reversal, exact sincospi twiddle table.
+// The same spectra by FFT (S = 64 or 256 = 4^3 / 4^4, or S = 128 = 4^3 * 2 for the 2x2 patch grid of PATCH-4): radix-4 Stockham autosort passes
+// in LDS (at S = 128 followed by one radix-2 pass), no bit reversal, exact sincospi twiddle table.
 // The direct DFT above costs S^2 MACs per output row; at S = 256 (GLO-16, G16:294-313) that was 1.04 ms per call = 15 % of the GLO-16 step.
 //   pass 1 (rows)   : a workgroup owns 32 consecutive rows of one window; two REAL rows are packed into one complex transform
 //                     (z = row0 + i row1;  R0[k] = (Z[k] + conj Z[S-k]) / 2,  R1[k] = (Z[k] - conj Z[S-k]) / 2i); the half spectra go through an
 //                     LDS tile to the scratch  T[window][kx][y]  (transposed, so that pass 2 reads whole columns as contiguous runs);
 //   pass 2 (columns): complex transforms of CB columns per workgroup; amp = |F|, pha = atan2(Im, Re) (Im forced to +0 at the four self-conjugate
 //                     bins, as the direct kernel does), staged in LDS and stored with the optional fftshift of both axes.
-// One transform is carried by S/4 lanes (one radix-4 butterfly each per pass): a wave runs one 256-point or four 64-point transforms at a time.
+// One transform is carried by S/4 lanes (one radix-4 butterfly each per pass): a wave runs one 256-point, two 128-point or four 64-point transforms
+// at a time.
 // ---------------------------------------------------------------------------------------------------
 __device__ __forceinline__ float2 cmul(const float2 a, const float2 b) { return make_float2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x); }
 
 // N-point forward transform of b0 (natural order in, natural order out); j = this lane's butterfly index 0 .. N/4-1; tw[k] = exp(-2 pi i k / N).
 // The N/4 lanes of a transform belong to ONE wave: LDS accesses of a wave execute in program order, a compiler-level fence is all that is needed.
+// N = 4^m: m radix-4 passes.  N = 2 * 4^m (128): the same m passes (Ns = 1, 4, .., 4^(m-1)), then one radix-2 pass with Ns = N/2, in which each of
+// the N/4 lanes does two of the N/2 butterflies  out[jj] = in[jj] + tw[jj] in[jj + N/2],  out[jj + N/2] = in[jj] - tw[jj] in[jj + N/2].
+constexpr int tfc_pow4_floor(int n) { int p = 1; while (p * 4 <= n) p *= 4; return p; }
 template <int N>
 __device__ __forceinline__ float2* tfc_fft_r4(float2* b0, float2* b1, const float2* __restrict__ tw, int j) {
+  constexpr int N4 = tfc_pow4_floor(N);                          // product of the radix-4 passes
+  static_assert(N4 == N || 2 * N4 == N, "N must be 4^m or 2 * 4^m");
 #pragma unroll
-  for (int Ns = 1; Ns < N; Ns *= 4) {
+  for (int Ns = 1; Ns < N4; Ns *= 4) {
     const int k = j & (Ns - 1);
     const int ts = k * (N / (4 * Ns));
     float2 v0 = b0[j], v1 = b0[j + N / 4], v2 = b0[j + N / 2], v3 = b0[j + 3 * N / 4];
@@ -290,6 +373,17 @@ __device__ __forceinline__ float2* tfc_fft_r4(float2* b0, float2* b1, const floa
     b1[j0 + Ns] = make_float2(a1.x + a3.x, a1.y + a3.y);
     b1[j0 + 2 * Ns] = make_float2(a0.x - a2.x, a0.y - a2.y);
     b1[j0 + 3 * Ns] = make_float2(a1.x - a3.x, a1.y - a3.y);
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    float2* t = b0; b0 = b1; b1 = t;
+  }
+  if constexpr (2 * N4 == N) {
+#pragma unroll
+    for (int jj = j; jj < N / 2; jj += N / 4) {
+      const float2 v0 = b0[jj], v1 = cmul(b0[jj + N / 2], tw[jj]);
+      b1[jj] = make_float2(v0.x + v1.x, v0.y + v1.y);
+      b1[jj + N / 2] = make_float2(v0.x - v1.x, v0.y - v1.y);
+    }
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     __builtin_amdgcn_wave_barrier();
     float2* t = b0; b0 = b1; b1 = t;
@@ -410,6 +504,7 @@ template <int S, int CB>
 static hipError_t launch_fft_t(const float* img, long long bs, long long cs, int rs, int C, int wins_x, int wins_per_img, int nwin, float* amp,
                                float* pha, int shift, void* ws, hipStream_t st) {
   constexpr int NB = S / 2 + 1, FPW = 64 / (S / 4);
+  static_assert(CB % (4 * FPW) == 0, "a workgroup's four waves transform 4 * FPW columns at a time");
   const size_t lds_r = (size_t)(S + 4 * 2 * FPW * S + NB * 32) * sizeof(float2);
   const size_t lds_c = (size_t)(S + 4 * 2 * FPW * S) * sizeof(float2) + (size_t)2 * S * CB * sizeof(float);
   hipLaunchKernelGGL((tfc_fft_rows_kernel<S>), dim3(nwin * (S / 32)), dim3(256), lds_r, st, img, bs, cs, rs, C, wins_x, wins_per_img, (float2*)ws);
@@ -419,11 +514,16 @@ static hipError_t launch_fft_t(const float* img, long long bs, long long cs, int
 hipError_t tfc_launch_spectrum(const float* img, long long bs, long long cs, int rs, int C, int S, int wins_x, int wins_per_img,
                                int nwin, float* amp, float* pha, int shift, void* ws, hipStream_t st) {
   if (ws && S == 64) return launch_fft_t<64, 16>(img, bs, cs, rs, C, wins_x, wins_per_img, nwin, amp, pha, shift, ws, st);
+  if (ws && S == 128) return launch_fft_t<128, 8>(img, bs, cs, rs, C, wins_x, wins_per_img, nwin, amp, pha, shift, ws, st);
   if (ws && S == 256) return launch_fft_t<256, 8>(img, bs, cs, rs, C, wins_x, wins_per_img, nwin, amp, pha, shift, ws, st);
   if (S == 64) {                                                  // no scratch given: direct DFT (also the independent cross-check of the FFT path)
     constexpr int KG = 33;
     const size_t lds = 64 * 64 + 2 * 64 * 4 + 64 * KG * 2 * 4;
     hipLaunchKernelGGL((tfc_spectrum_kernel<64, KG>), dim3(nwin, 1), dim3(256), lds, st, img, bs, cs, rs, C, wins_x, wins_per_img, amp, pha, shift);
+  } else if (S == 128) {                                          // two column groups (33 + 32 of the 65 columns); 51 200 B of LDS
+    constexpr int KG = 33;
+    const size_t lds = 128 * 128 + 2 * 128 * 4 + 128 * KG * 2 * 4;
+    hipLaunchKernelGGL((tfc_spectrum_kernel<128, KG>), dim3(nwin, (65 + KG - 1) / KG), dim3(256), lds, st, img, bs, cs, rs, C, wins_x, wins_per_img, amp, pha, shift);
   } else if (S == 256) {
     constexpr int KG = 16;
     const size_t lds = 256 * 256 + 2 * 256 * 4 + 256 * KG * 2 * 4;

@@ -1,4 +1,5 @@
-"""The PATCH-16 training step (reference TFCGAN_multigpu_patchFFT_16P.py:545-638) as one engine object.
+"""The PATCH-16 training step (reference TFCGAN_multigpu_patchFFT_16P.py:545-638) as one engine object; `patches=4` runs the same step with the
+2x2 patch grid of TFCGAN_multigpu_patchFFT.py (PATCH-4, fft_mode="patch") / TFCGAN_multigpu_globalFFT.py (GLO-4, fft_mode="global").
 
     G step : fake = G(A); pf = D(fake, A); pr = D(B, A)
              loss_G = 0.5 * BCE(pf - pr.detach(), 0.9) + triplet16(fake, B, neg_idx) + 0.01 * patchFFT(fake, B)   (:554-607)
@@ -24,8 +25,11 @@ from .ops import DT_BF16
 class TrainStep:
     def __init__(self, generator, discriminator, lr=2e-4, b1=0.5, b2=0.999, eps=1e-8, compute_dtype=torch.bfloat16,
                  fft_mode="patch", seed=0, bucket_bytes=16 << 20, lambda_gan=0.5, lambda_fft=0.01, lambda_trip=1.0, d_bucket_bytes=4 << 20,
-                 batch_invariant=None):
+                 batch_invariant=None, patches=16):
         dev = next(generator.parameters()).device
+        if patches not in (4, 16):
+            raise ops._lib.TfcError(f"TrainStep: patches={patches} (16: the 4x4 grid of 64x64 patches, 4: the 2x2 grid of 128x128 patches)")
+        self.patches = patches
         if dev.type != "cuda":
             raise ops._lib.TfcError("TrainStep needs the modules on a CUDA/HIP device (no CPU fallback)")
         self.dev, self.dt = dev, ops.dt_of(compute_dtype)
@@ -91,7 +95,9 @@ class TrainStep:
         self.step_no += 1
         t = self.step_no
         if neg_idx is None:
-            neg_idx = parallel.shared_neg_idx(t, self.seed)
+            neg_idx = parallel.shared_neg_idx(t, self.seed, self.patches)
+        if len(neg_idx) != self.patches:
+            raise ops._lib.TfcError(f"TrainStep(patches={self.patches}): neg_idx has {len(neg_idx)} entries")
         drop_seed = (self.seed * 7919 + t * 104729 + parallel.rank() * 1299709) & 0x3FFFFFF
         train = self.G_mod.training
         pv = self._param_versions()
@@ -103,8 +109,8 @@ class TrainStep:
         ops.arena_begin(self.dev)                                 # one fill for all the small zero-initialised buffers of this step
         # ---------------- generator step ----------------
         def pixel_losses():                                       # everything that needs only the generated image (beside the discriminator chain)
-            lt, gt = ops.patch16_triplet(fake, real_B, neg_idx, want_grad=True, gscale=self.lambda_trip)
-            lf = patch_fft_loss(fake, real_B) if self.fft_mode == "patch" else global_fft_loss(fake, real_B)
+            lt, gt = ops.patch_triplet(fake, real_B, neg_idx, want_grad=True, gscale=self.lambda_trip)
+            lf = patch_fft_loss(fake, real_B, self.patches) if self.fft_mode == "patch" else global_fft_loss(fake, real_B)
             ex = extra_loss_G(fake, real_B) if extra_loss_G is not None else None     # optional pluggable term (LPIPS, P16:598): (loss, dfake), already weighted
             return lt, gt, lf, ex
         if nets.side_stream_on() and os.environ.get("TFC_NO_GSTEP_OVERLAP", "0") in ("", "0"):

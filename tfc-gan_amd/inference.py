@@ -11,7 +11,7 @@ from collections import OrderedDict
 
 import torch
 
-from .losses import make_16_patches
+from .losses import make_4_patches, make_16_patches
 
 
 def save_checkpoint(model, path):
@@ -35,6 +35,16 @@ def load_clean_state(model_name, checkpoint_path):
 def stitch_16_patches(fake_B, real_B):
     """[N,3,256,256] x2 -> [N,48,128,64]: channel group k holds fake patch k stacked over real patch k (T16:217-263)."""
     fb, rb = make_16_patches(fake_B), make_16_patches(real_B)
+    return torch.cat([torch.cat((f.data, r.data), -2) for f, r in zip(fb, rb)], 1)
+
+
+def stitch_patches(fake_B, real_B, patches=16):
+    """patches=16: stitch_16_patches. patches=4: [N,3,256,256] x2 -> [N,12,256,128], channel group k = fake patch k (128 x 128) stacked over real
+    patch k (the 2x2 grid of TFCGAN_multigpu_patchFFT.py:310-316)."""
+    if patches == 16:
+        return stitch_16_patches(fake_B, real_B)
+    assert patches == 4
+    fb, rb = make_4_patches(fake_B), make_4_patches(real_B)
     return torch.cat([torch.cat((f.data, r.data), -2) for f, r in zip(fb, rb)], 1)
 
 

@@ -5,6 +5,12 @@
   FFT_Components / fft_components / calculate_ffts   :271-375
   relativistic BCE                       :554, :628-630 (engine.py uses the fused kernel directly)
 
+and the 4-patch family (TFCGAN_multigpu_patchFFT.py = "4P", TFCGAN_multigpu_globalFFT.py): the same heads on a 2x2 grid of 128x128 patches
+
+  make_4_patches(B)                      4P:468-471   4 views, patch k -> rows 128*(k//2).., cols 128*(k%2)..
+  patch_triplet_loss with 4 indices      4P:474-481   0.25 * sum of 4 nn.TripletMarginLoss
+  fft_components on 128x128 patches      4P:263-288   128 x 65 spectra;  patch_fft_loss(patches=4)  4P:499-511
+
 The reference has no class called ContrastiveLoss: the "16-patch contrastive head" named by the project brief IS the
 16-fold triplet mean above; `ContrastiveLoss` here is defined as exactly that.
 """
@@ -24,15 +30,23 @@ def make_16_patches(B):
     return tuple(B[:, :, 64 * (k // GRID):64 * (k // GRID) + PATCH, 64 * (k % GRID):64 * (k % GRID) + PATCH] for k in range(16))
 
 
-def patch_first_flat_index(k, width=256):
-    """flat NCHW offset (within one channel plane) of the first element of patch k: 0,64,128,192,16384,..."""
-    return 64 * (k // GRID) * width + 64 * (k % GRID)
+def make_4_patches(B):
+    """4 zero-copy views of B[N,C,256,256], row-major 2x2 grid of 128x128 patches (reference order B1..B4, 4P:468-471)."""
+    assert B.shape[-1] == 256 and B.shape[-2] == 256, "the reference hard-codes the offset 128 (256x256 images only)"
+    return tuple(B[:, :, 128 * (k // 2):128 * (k // 2) + 128, 128 * (k % 2):128 * (k % 2) + 128] for k in range(4))
+
+
+def patch_first_flat_index(k, width=256, grid=GRID):
+    """flat NCHW offset (within one channel plane) of the first element of patch k of a grid x grid patch grid:
+    grid 4: 0,64,128,192,16384,...; grid 2: 0,128,32768,32896"""
+    p = width // grid
+    return p * (k // grid) * width + p * (k % grid)
 
 
 class _Triplet16Fn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, fake, real, neg_idx):
-        loss, dfake = ops.patch16_triplet(fake.detach(), real.detach(), neg_idx, want_grad=fake.requires_grad)
+        loss, dfake = ops.patch_triplet(fake.detach(), real.detach(), neg_idx, want_grad=fake.requires_grad)
         ctx.save_for_backward(dfake) if dfake is not None else None
         ctx.has = dfake is not None
         ctx.in_dtype = fake.dtype
@@ -47,43 +61,49 @@ class _Triplet16Fn(torch.autograd.Function):
 
 
 def patch_triplet_loss(fake_B, real_B, neg_idx):
-    """(1/16) * sum_k TripletMarginLoss(fake patch k, real patch k, real patch neg_idx[k]) -- one fused kernel."""
+    """(1/P) * sum_k TripletMarginLoss(fake patch k, real patch k, real patch neg_idx[k]) -- one fused kernel; P = len(neg_idx) = 16 (4x4 grid of
+    64x64 patches) or 4 (2x2 grid of 128x128 patches, 4P:468-481)."""
     return _Triplet16Fn.apply(fake_B, real_B, [int(i) for i in neg_idx])
 
 
 class ContrastiveLoss(nn.Module):
-    """The 16-patch triplet head. Two call forms:
-         loss(fake_B, real_B, neg_idx=None)          whole images [N,C,256,256]; neg_idx: 16 ints (drawn with
-                                                     np.random.randint(16) per patch like the reference when None)
-         loss(anchor, positive, negative)            three [N,C,64,64] patch tensors = nn.TripletMarginLoss(margin=1, p=2)
+    """The patch triplet head (patches = 16, or 4 for the 2x2 grid of the 4-patch scripts). Two call forms:
+         loss(fake_B, real_B, neg_idx=None)          whole images [N,C,256,256]; neg_idx: 16 (or 4) ints (drawn with
+                                                     np.random.randint(patches) per patch like the reference when None)
+         loss(anchor, positive, negative)            three [N,C,64,64] (or [N,C,128,128]) patch tensors = nn.TripletMarginLoss(margin=1, p=2)
                                                      on one patch (composed from the same kernel by embedding the patch)."""
 
-    def __init__(self, margin=1.0, p=2):
+    def __init__(self, margin=1.0, p=2, patches=16):
         super().__init__()
         assert margin == 1.0 and p == 2, "the reference uses margin=1.0, p=2 (:75)"
+        assert patches in (4, 16)
+        self.patches = patches
 
     def forward(self, a, b, c=None):
         if torch.is_tensor(c):
             return _single_patch_triplet(a, b, c)
         if c is None:
-            c = [int(np.random.randint(16, size=1).item()) for _ in range(16)]
+            c = [int(np.random.randint(self.patches, size=1).item()) for _ in range(self.patches)]
         return patch_triplet_loss(a, b, c)
 
 
 def _single_patch_triplet(anchor, positive, negative):
     """nn.TripletMarginLoss on one 64x64 patch through the 16-patch kernel: put anchor / positive in patch 0 and the negative
-    in patch 1 of zero images; patches 1..15 use themselves as negatives and contribute exactly 1.0 each."""
+    in patch 1 of zero images; patches 1..15 use themselves as negatives and contribute exactly 1.0 each. (128x128 patches: the 4-patch
+    kernel, patches 1..3.) The embedding copy stays in the autograd graph, so the gradient reaches `anchor`."""
     N, C = anchor.shape[:2]
+    P = anchor.shape[-1]                                          # 64: the 16-patch kernel; 128: the 4-patch kernel (total * 4 - 3)
+    assert P in (64, 128) and anchor.shape[-2] == P
+    npatch = (256 // P) ** 2
     dev = anchor.device
     fake = torch.zeros((N, C, 256, 256), dtype=torch.float32, device=dev)
     real = torch.zeros_like(fake)
-    fake[:, :, :64, :64] = anchor.float()
-    real[:, :, :64, :64] = positive.detach().float()
-    real[:, :, :64, 64:128] = negative.detach().float()
-    fake = fake.detach().requires_grad_(anchor.requires_grad)
-    neg = [1] + list(range(1, 16))
+    fake[:, :, :P, :P] = anchor.float()
+    real[:, :, :P, :P] = positive.detach().float()
+    real[:, :, :P, P:2 * P] = negative.detach().float()
+    neg = [1] + list(range(1, npatch))
     total = patch_triplet_loss(fake, real, neg)
-    return total * 16.0 - 15.0
+    return total * float(npatch) - float(npatch - 1)
 
 
 class FFT_Components(object):
@@ -107,7 +127,7 @@ class FFT_Components(object):
         return amp[0], pha[0]
 
     def make_spectra(self):
-        """reference :284-289: log|fftshift(fft2(image))|, the full S x S magnitude spectrum (S = 64 or 256), fp32 on the GPU."""
+        """reference :284-289: log|fftshift(fft2(image))|, the full S x S magnitude spectrum (S = 64, 128 or 256), fp32 on the GPU."""
         t = self._as_tensor().cuda()
         S = t.shape[-1]
         return _full_log_spectrum(t[None].expand(1, 3 if t.shape[0] == 3 else 1, S, S).contiguous(), S)[0]
@@ -126,30 +146,33 @@ def _full_log_spectrum(img, S):
 
 
 def sample_spectra(thermal_tensor):
-    """reference :378-388: thermal_tensor [N,3,S,S] in [-1,1] -> log-magnitude spectra [N,1,S,S] fp32 (S = 64 or 256) for the sample grids."""
+    """reference :378-388: thermal_tensor [N,3,S,S] in [-1,1] -> log-magnitude spectra [N,1,S,S] fp32 (S = 64, 128 or 256) for the sample grids."""
     S = thermal_tensor.shape[-1]
-    assert thermal_tensor.shape[-2] == S and S in (64, 256)
+    assert thermal_tensor.shape[-2] == S and S in (64, 128, 256)
     return _full_log_spectrum(thermal_tensor.detach(), S)[:, None]
 
 
 def fft_components(thermal_tensor, patch=True):
     """reference :293-319. thermal_tensor [N,3,S,S] in [-1,1] -> (AMP, PHA) each [N,1,S,S//2+1] fp32, fftshifted.
-    patch=True: S=64 (aspect 33); patch=False: S=256 (129)."""
-    S = 64 if patch else 256
-    assert thermal_tensor.shape[-1] == S and thermal_tensor.shape[-2] == S
+    patch=True: S taken from the tensor, 64 (33 columns, P16) or 128 (65 columns, 4P:280-281); patch=False: S=256 (129)."""
+    S = thermal_tensor.shape[-1] if patch else 256
+    assert S in ((64, 128) if patch else (256,)) and thermal_tensor.shape[-1] == S and thermal_tensor.shape[-2] == S
     N = thermal_tensor.shape[0]
     amp, pha = ops.fft_spectrum(thermal_tensor, S, 1, 1, shift=True)
     return amp.reshape(N, 1, S, S // 2 + 1), pha.reshape(N, 1, S, S // 2 + 1)
 
 
-def patch_fft_loss(fake_B, real_B):
-    """loss_FFT of calculate_ffts on whole images: 0.5 * (mean_k L1(amp) + mean_k L1(phase)) over the 16 patches.
-    Carries no gradient, exactly like the reference (tensor -> PIL -> numpy round trip, :300-302)."""
+def patch_fft_loss(fake_B, real_B, patches=16):
+    """loss_FFT of calculate_ffts on whole images: 0.5 * (mean_k L1(amp) + mean_k L1(phase)) over the 16 patches (patches=4: the four
+    128 x 128 patches with 128 x 65 spectra, 4P:499-511). Carries no gradient, exactly like the reference (tensor -> PIL -> numpy round trip,
+    :300-302)."""
+    assert patches in (4, 16)
     N = fake_B.shape[0]
-    af, pf = ops.fft_spectrum(fake_B.detach(), 64, 4, 4, shift=False)
-    ar, pr = ops.fft_spectrum(real_B.detach(), 64, 4, 4, shift=False)
+    S, g = (64, 4) if patches == 16 else (128, 2)
+    af, pf = ops.fft_spectrum(fake_B.detach(), S, g, g, shift=False)
+    ar, pr = ops.fft_spectrum(real_B.detach(), S, g, g, shift=False)
     out = torch.zeros(3, dtype=torch.float32, device=fake_B.device)
-    scale = 1.0 / (16.0 * N * 64 * 33)
+    scale = 1.0 / (float(patches) * N * S * (S // 2 + 1))
     ops.l1_sum(af, ar, scale, out[0:1])
     ops.l1_sum(pf, pr, scale, out[1:2])
     return 0.5 * (out[0] + out[1]), out[0], out[1]
@@ -168,15 +191,18 @@ def global_fft_loss(fake_B, real_B):
 
 
 def calculate_ffts(*patches):
-    """reference :323-375: calculate_ffts(fake_B1..fake_B16, B1..B16) -> loss_FFT (scalar, no gradient)."""
-    assert len(patches) == 32, "expects 16 fake patches followed by 16 real patches"
+    """reference :323-375: calculate_ffts(fake_B1..fake_B16, B1..B16) -> loss_FFT (scalar, no gradient). With 8 tensors (fake_B1..4, B1..4 of
+    128 x 128): the inline form of the 4-patch script (4P:499-511)."""
+    assert len(patches) in (8, 32), "expects 16 (or 4) fake patches followed by as many real patches"
+    P = len(patches) // 2
+    S = 64 if P == 16 else 128
     dev = patches[0].device
     N = patches[0].shape[0]
     out = torch.zeros(2, dtype=torch.float32, device=dev)
-    scale = 1.0 / (16.0 * N * 64 * 33)
-    for k in range(16):
-        af, pf = ops.fft_spectrum(patches[k].detach(), 64, 1, 1, shift=True)
-        ar, pr = ops.fft_spectrum(patches[16 + k].detach(), 64, 1, 1, shift=True)
+    scale = 1.0 / (float(P) * N * S * (S // 2 + 1))
+    for k in range(P):
+        af, pf = ops.fft_spectrum(patches[k].detach(), S, 1, 1, shift=True)
+        ar, pr = ops.fft_spectrum(patches[P + k].detach(), S, 1, 1, shift=True)
         ops.l1_sum(af, ar, scale, out[0:1])
         ops.l1_sum(pf, pr, scale, out[1:2])
     return 0.5 * (out[0] + out[1])

@@ -442,6 +442,24 @@ def patch16_triplet(fake, real, neg_idx, want_grad=True, gscale=1.0):
     return loss, dfake
 
 
+def patch_triplet(fake, real, neg_idx, want_grad=True, gscale=1.0):
+    """The triplet head on a 2x2 or 4x4 patch grid, inferred from len(neg_idx) (4: PATCH-4 / GLO-4, reference TFCGAN_multigpu_patchFFT.py:468-481;
+    16: patch16_triplet, same bits). fake/real: fp32 NCHW [N,C,256,256]. Returns (loss[1], dfake or None)."""
+    n = len(neg_idx)
+    if n not in (4, 16):
+        raise _lib.TfcError(f"patch_triplet: {n} negative indices (the patch grid has 4 or 16 patches)")
+    require_gpu(fake, real)
+    assert fake.shape == real.shape and fake.shape[2:] == (256, 256), "the reference hard-codes the patch offsets of 256x256 images"
+    fake = fake.contiguous().float()
+    real = real.contiguous().float()
+    N, C = fake.shape[:2]
+    loss = torch.empty(1, dtype=torch.float32, device=fake.device)
+    dfake = torch.empty_like(fake) if want_grad else None
+    idx = (ctypes.c_int * n)(*[int(i) for i in neg_idx])
+    check(lib().tfc_patch_triplet(stream_ptr(), _p(fake), _p(real), idx, 2 if n == 4 else 4, N, C, _p(loss), _p(dfake), gscale), "tfc_patch_triplet")
+    return loss, dfake
+
+
 _FFT_WS = {}
 
 

@@ -163,11 +163,13 @@ def broadcast_tensors(tensors, src=0, group=None):
             dist.broadcast(t, src=src, group=group)
 
 
-def shared_neg_idx(step, seed=1234):
-    """The 16 negative-patch indices of one step (reference: np.random.randint(16) per patch, unseeded, :565-580):
-    a deterministic function of (seed, step), hence identical on every rank without communication."""
+def shared_neg_idx(step, seed=1234, patches=16):
+    """The negative-patch indices of one step (reference: np.random.randint(16) per patch, unseeded, :565-580; randint(4) per patch in the
+    4-patch scripts, TFCGAN_multigpu_patchFFT.py:477-480): a deterministic function of (seed, step), hence identical on every rank without
+    communication."""
     import numpy as np
-    return [int(v) for v in np.random.default_rng([seed, step]).integers(16, size=16)]
+    assert patches in (4, 16)
+    return [int(v) for v in np.random.default_rng([seed, step]).integers(patches, size=patches)]
 
 
 def shard_slice(global_batch, r=None, ws=None):
