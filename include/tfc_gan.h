@@ -191,6 +191,20 @@ int tfc_fft_spectrum(void* stream, const float* img, long long batch_stride, lon
 /* ws: tfc_fft_spectrum_ws_bytes(S, N * wins_x * wins_y) bytes of scratch (row-transformed half spectra) -> radix-4 FFT in LDS (rows, then
  * columns; S = 128 = 4^3 * 2 adds one radix-2 pass); ws == NULL -> direct DFT (S^2 work per output row: fine for one 64 x 64 window, 1 ms per call for 32 whole 256 x 256 images). */
 size_t tfc_fft_spectrum_ws_bytes(int S, int nwin);
+/* the same spectra of RECTANGULAR windows of H rows x 256 columns, H in 2 .. 256 (the regional FFT loss of TFCGAN_multigpu_patchFFT_withregion_FFT.py:353-401
+ * uses H = 100): wins_per_img windows per image, window k starting at image row row0 + k * row_step, column 0. img: fp32 [N][C][img_h][row_stride] with
+ * img_w >= 256 valid columns; amp/pha: [N*wins_per_img][H][129] fp32; shift != 0: ky -> (ky + H/2) % H, kx -> (kx + 64) % 129 (np.fft.fftshift, even and odd H).
+ * Rows: the 256-point LDS FFT; columns: a direct H-point DFT with the column mean taken out. Im = +0 at kx in {0,128} x (ky = 0, ky = H/2 for even H).
+ * ws: tfc_fft_spectrum_rect_ws_bytes(H, N * wins_per_img) bytes of scratch (16-byte aligned; 0 for an H outside 2 .. 256).
+ * Refused (non-zero, tfc_last_error): H outside 2 .. 256, row0 + (wins_per_img - 1) * row_step + H > img_h, img_w < 256. */
+int tfc_fft_spectrum_rect(void* stream, const float* img, long long batch_stride, long long chan_stride, int row_stride, int C, int img_h, int img_w,
+                          int H, int row0, int row_step, int wins_per_img, int N, float* amp, float* pha, int shift, void* ws);
+size_t tfc_fft_spectrum_rect_ws_bytes(int H, int nwin);
+/* KL form of the regional loss (..._withregion_FFT_KL.py:400-418): log_softmax over the BATCH, KLDivLoss(reduction="mean", log_target=True). af, pf, ar:
+ * fp32 [N][M] (fake amplitude, fake phase, REAL AMPLITUDE: the reference takes the target of the phase term from the real amplitudes too, :401, :404).
+ * out[0] += scale * sum exp(t)(t - xa), out[1] += scale * sum exp(t)(t - xp), t = log_softmax_n(ar), xa = log_softmax_n(af), xp = log_softmax_n(pf).
+ * A logged scalar (no gradient); N >= 1. Side stream only when two streams are in use, like tfc_l1_sum and the triplet heads. */
+int tfc_batch_kl_sum(void* stream, const float* af, const float* pf, const float* ar, int N, long long M, float scale, float* out);
 /* evaluation metric of TFC-GAN-FFT/Devcom_MagMSE.py:91-118 (mse_spec): per window MSE(log|fft2(a)|, log|fft2(b)|) over the FULL S x S
  * spectrum, computed from the half spectra amp_a / amp_b [nwin][S][S/2+1] of tfc_fft_spectrum (S in {64,128,256}); out[nwin] */
 int tfc_logmag_mse(void* stream, const float* amp_a, const float* amp_b, int S, int nwin, float* out);

@@ -76,8 +76,10 @@ def _build_locked(verbose):
 # instead of silently producing wrong convolutions.
 # The 4-patch loss heads (tfc_triplet4_kernel with four float2 rows in flight, the 128-point FFT kernels) ride the same check: they were sized to run
 # without scratch, and a spill there would be a silent slowdown of every PATCH-4 / GLO-4 step.
+# So do the kernels of the rectangular-window spectra (the regional FFT loss): the rows kernel is the 256-point FFT with a run-time row count, the columns
+# kernel a 100 x 100 inner loop per output that was written to live in registers.
 GUARDED_KERNELS = ("tfc_igemm2_kernel", "tfc_wgrad", "tfc_triplet4_kernel", "tfc_fft_rows_kernelILi128E", "tfc_fft_cols_kernelILi128E",
-                   "tfc_spectrum_kernelILi128E")
+                   "tfc_spectrum_kernelILi128E", "tfc_fft_rect_rows_kernel", "tfc_dft_rect_cols_kernel")
 
 
 def check_no_spills(remarks):
@@ -136,6 +138,9 @@ PROTOTYPES = {
     "tfc_patch_triplet": (_i, [_vp, _vp, _vp, _c.POINTER(_i), _i, _i, _i, _vp, _vp, _f]),
     "tfc_fft_spectrum": (_i, [_vp, _vp, _ll, _ll, _i, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp]),
     "tfc_fft_spectrum_ws_bytes": (_sz, [_i, _i]),
+    "tfc_fft_spectrum_rect": (_i, [_vp, _vp, _ll, _ll, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp]),
+    "tfc_fft_spectrum_rect_ws_bytes": (_sz, [_i, _i]),
+    "tfc_batch_kl_sum": (_i, [_vp, _vp, _vp, _vp, _i, _ll, _f, _vp]),
     "tfc_logmag_mse": (_i, [_vp, _vp, _vp, _i, _i, _vp]),
     "tfc_logmag_mae": (_i, [_vp, _vp, _vp, _i, _i, _vp]),
     "tfc_pair_moments_ws_bytes": (_sz, [_i, _ll]),

@@ -69,6 +69,9 @@ hipError_t tfc_launch_triplet4(const float* fake, const float* real, const int* 
 hipError_t tfc_launch_spectrum(const float* img, long long bs, long long cs, int rs, int C, int S, int wins_x, int wins_per_img, int nwin, float* amp, float* pha, int shift, void* ws, hipStream_t st);
 size_t tfc_fft_ws_bytes(int S, int nwin);
 hipError_t tfc_launch_l1_sum(const float* a, const float* b, long long n, float scale, float* out, hipStream_t st);
+hipError_t tfc_launch_spectrum_rect(const float* img, long long bs, long long cs, int rs, int C, int H, int row0, int row_step, int wins_per_img, int nwin, float* amp, float* pha, int shift, void* ws, hipStream_t st);
+size_t tfc_fft_rect_ws_bytes(int H, int nwin);
+hipError_t tfc_launch_batch_kl(const float* af, const float* pf, const float* ar, int N, long long M, float scale, float* out, hipStream_t st);
 hipError_t tfc_launch_probe(float* out, hipStream_t st);
 hipError_t tfc_launch_logmag_mse(const float* a, const float* b, int S, int nwin, float* out, int absolute, hipStream_t st);
 // metrics.hip
@@ -862,6 +865,24 @@ extern "C" int tfc_fft_spectrum(void* stream, const float* img, long long batch_
   REQUIRE(img && amp && pha && (S == 64 || S == 128 || S == 256) && (C == 1 || C == 3) && wins_x > 0 && wins_y > 0 && N > 0, "bad args");
   if (ws) { if (int e = check_ptr16(ws, "ws")) return e; }
   CHECK_HIP(tfc_launch_spectrum(img, batch_stride, chan_stride, row_stride, C, S, wins_x, wins_x * wins_y, N * wins_x * wins_y, amp, pha, shift, ws, (hipStream_t)stream), "tfc_fft_spectrum");
+  return 0;
+}
+extern "C" size_t tfc_fft_spectrum_rect_ws_bytes(int H, int nwin) { return H >= 2 && H <= 256 && nwin > 0 ? tfc_fft_rect_ws_bytes(H, nwin) : 0; }
+extern "C" int tfc_fft_spectrum_rect(void* stream, const float* img, long long batch_stride, long long chan_stride, int row_stride, int C, int img_h,
+                                     int img_w, int H, int row0, int row_step, int wins_per_img, int N, float* amp, float* pha, int shift, void* ws) {
+  REQUIRE(H >= 2 && H <= 256, "H=%d: a rectangular window has 2 .. 256 rows", H);
+  REQUIRE(img_w >= 256, "image width %d: a rectangular window is 256 columns wide", img_w);
+  REQUIRE(img && amp && pha && (C == 1 || C == 3) && wins_per_img > 0 && N > 0 && row0 >= 0 && row_step >= 0 && row_stride >= img_w, "bad args");
+  REQUIRE((long long)row0 + (long long)(wins_per_img - 1) * row_step + H <= img_h, "windows of %d rows from row %d every %d rows (%d per image) pass the image height %d",
+          H, row0, row_step, wins_per_img, img_h);
+  if (int e = check_ptr16(ws, "ws")) return e;
+  CHECK_HIP(tfc_launch_spectrum_rect(img, batch_stride, chan_stride, row_stride, C, H, row0, row_step, wins_per_img, N * wins_per_img, amp, pha, shift, ws,
+                                     (hipStream_t)stream), "tfc_fft_spectrum_rect");
+  return 0;
+}
+extern "C" int tfc_batch_kl_sum(void* stream, const float* af, const float* pf, const float* ar, int N, long long M, float scale, float* out) {
+  REQUIRE(af && pf && ar && out && N > 0 && M > 0, "bad args");
+  CHECK_HIP(tfc_launch_batch_kl(af, pf, ar, N, M, scale, out, (hipStream_t)stream), "tfc_batch_kl_sum");
   return 0;
 }
 extern "C" int tfc_logmag_mse(void* stream, const float* amp_a, const float* amp_b, int S, int nwin, float* out) {

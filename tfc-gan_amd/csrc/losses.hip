@@ -545,3 +545,204 @@ hipError_t tfc_launch_l1_sum(const float* a, const float* b, long long n, float 
   hipLaunchKernelGGL(tfc_l1_sum_kernel, dim3((int)nb), dim3(256), 0, st, a, b, n, scale, out);
   return hipGetLastError();
 }
+
+// ---------------------------------------------------------------------------------------------------
+// Rectangular windows: H rows x 256 columns, H a run-time value in 2 .. 256 (the regional FFT loss of TFCGAN_multigpu_patchFFT_withregion_FFT.py:353-401
+// and ..._withregion_FFT_KL.py:357-420 takes the spectra of rows 0..99 and 100..199, 100 x 129 bins each).  Window k of image n starts at image
+// row row0 + k * row_step, column 0.  Same luma, same rfft2, same amp / atan2 as above; amp / pha: [windows][H][129].
+//   pass 1 (rows)   : tfc_fft_rows_kernel<256> with a run-time row count: a workgroup owns 32 consecutive rows, a wave one pair of real rows per
+//                     256-point transform; pairs past the last row are skipped, the second row of the last pair of an odd H is zeros.  The half spectra
+//                     go to the scratch T[window][kx][y] with y < H.
+//   pass 2 (columns): H = 100 = 4 * 5 * 5 is no 4^m or 2 * 4^m, so each of the 129 columns takes a DIRECT H-point DFT from an exact table
+//                     exp(-2 pi i m / H), m < H (sincospi in double, rounded once), indexed by the integer (ky * y) mod H that is carried along
+//                     as t += ky.  A workgroup owns RECT_CB = 13 columns of one window (129 = 9 * 13 + 12), staged in LDS as col[y][column]; a lane
+//                     owns one (ky, column) output, so per y the lanes of a wave read 13 consecutive float2 of col (conflict-free) and up to six
+//                     table entries (64 consecutive outputs span five or six ky), whose banks are not controlled.
+//                     The column MEAN is taken out before the sum and comes back at ky = 0 (sum_y exp(-2 pi i ky y / H) = 0 for every other ky):
+//                     F[0] = sum_y R[y],  F[ky] = sum_y (R[y] - F[0] / H) exp(-2 pi i ky y / H).  Column kx = 0 holds the row sums, about 32 000 each
+//                     for a mid-grey image, whose direct sum would carry partial sums near 1e6 (ulp 0.06) into bins of a few thousand; without the
+//                     mean the terms are as small as the bins they make.
+//   Im is forced to +0 at the self-conjugate bins kx in {0, 128} x (ky = 0, and ky = H/2 for even H).
+//   fftshift on store: ky -> (ky + H/2) % H (numpy's shift for even and odd H), kx -> (kx + 64) % 129.
+// ---------------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(256)
+tfc_fft_rect_rows_kernel(const float* __restrict__ img, long long bs, long long cs, int rs, int C, int H, int row0, int row_step, int wins_per_img,
+                         float2* __restrict__ T) {
+  constexpr int S = 256, NB = S / 2 + 1, G = S / 4, RPB = 32;     // one transform per wave (G = 64 lanes)
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  float2* tw = reinterpret_cast<float2*>(smem);                   // [S]
+  float2* wbuf = tw + S;                                          // [4 waves][2][S]
+  float2* tile = wbuf + 4 * 2 * S;                                // [NB][RPB]
+  const int tid = threadIdx.x, j = tid & 63, wave = tid >> 6;
+  const int nrb = (H + RPB - 1) / RPB;                            // row blocks per window; the last one is ragged when H % 32 != 0
+  const int w = blockIdx.x / nrb, y0 = (blockIdx.x % nrb) * RPB;
+  const int n = w / wins_per_img, kw = w % wins_per_img;
+  const float* base = img + (size_t)n * bs + (size_t)(row0 + kw * row_step) * rs;
+  for (int i = tid; i < S; i += 256) {
+    float sn, cn;
+    sincospif(2.f * (float)i / (float)S, &sn, &cn);
+    tw[i] = make_float2(cn, -sn);
+  }
+  __syncthreads();
+  float2* b0 = wbuf + (wave * 2 + 0) * S;
+  float2* b1 = wbuf + (wave * 2 + 1) * S;
+  auto luma = [&](int y, int x) -> float {
+    int q[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      const float v = base[(size_t)(C == 1 ? 0 : c) * cs + (size_t)y * rs + x] * 255.f;
+      q[c] = ((int)v) & 255;
+    }
+    return (float)((19595 * q[0] + 38470 * q[1] + 7471 * q[2] + 32768) >> 16);
+  };
+  for (int it = 0; it < RPB / 2 / 4; ++it) {
+    const int pr = it * 4 + wave;                                 // row pair of this workgroup (0 .. 15)
+    const int ya = y0 + 2 * pr;
+    if (ya >= H) continue;                                        // wave-uniform: the whole transform lies past the window
+    const bool two = ya + 1 < H;                                  // odd H: the last row is paired with zeros
+#pragma unroll
+    for (int r = 0; r < 4; ++r) b0[j + r * G] = make_float2(luma(ya, j + r * G), two ? luma(ya + 1, j + r * G) : 0.f);
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    const float2* Z = tfc_fft_r4<S>(b0, b1, tw, j);
+    for (int k = j; k < NB; k += G) {
+      const float2 a = Z[k], b = Z[(S - k) & (S - 1)];
+      tile[k * RPB + 2 * pr] = make_float2(0.5f * (a.x + b.x), 0.5f * (a.y - b.y));
+      tile[k * RPB + 2 * pr + 1] = make_float2(0.5f * (a.y + b.y), 0.5f * (b.x - a.x));
+    }
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+  }
+  __syncthreads();
+  float2* Tw = T + (size_t)w * NB * H;
+  for (int i = tid; i < NB * RPB; i += 256) {
+    const int kx = i / RPB, y = y0 + i % RPB;
+    if (y < H) Tw[(size_t)kx * H + y] = tile[i];                  // tile rows past H were never written and are not read
+  }
+}
+
+constexpr int RECT_CB = 13;
+
+__global__ void __launch_bounds__(256)
+tfc_dft_rect_cols_kernel(const float2* __restrict__ T, int H, float* __restrict__ amp, float* __restrict__ pha, int shift) {
+  constexpr int NB = 129, CB = RECT_CB, NCB = (NB + CB - 1) / CB;
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  float2* tw = reinterpret_cast<float2*>(smem);                   // [H]      exp(-2 pi i m / H)
+  float2* col = tw + H;                                           // [H][CB]  the columns, mean removed
+  float2* csum = col + H * CB;                                    // [CB]     sum_y R[y] = F[0]
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int w = blockIdx.x / NCB, c0 = (blockIdx.x % NCB) * CB;
+  const int ncol = NB - c0 < CB ? NB - c0 : CB;
+  for (int i = tid; i < H; i += 256) {
+    double sn, cn;
+    sincospi(2.0 * (double)i / (double)H, &sn, &cn);
+    tw[i] = make_float2((float)cn, (float)-sn);
+  }
+  const float2* src = T + ((size_t)w * NB + c0) * H;              // ncol columns of H values, contiguous
+  for (int o = tid; o < ncol * H; o += 256) {
+    const int ci = o / H, y = o - ci * H;
+    col[y * CB + ci] = src[o];
+  }
+  __syncthreads();
+  for (int ci = wave; ci < ncol; ci += 4) {                       // fixed order: lane-strided partial sums, then the xor tree
+    float sx = 0.f, sy = 0.f;
+    for (int y = lane; y < H; y += 64) { const float2 v = col[y * CB + ci]; sx += v.x; sy += v.y; }
+    sx = wave_sum(sx); sy = wave_sum(sy);
+    if (lane == 0) csum[ci] = make_float2(sx, sy);
+  }
+  __syncthreads();
+  const float inv_h = 1.f / (float)H;
+  for (int o = tid; o < H * CB; o += 256) {
+    const int ci = o % CB;
+    if (ci < ncol) { col[o].x -= csum[ci].x * inv_h; col[o].y -= csum[ci].y * inv_h; }
+  }
+  __syncthreads();
+  for (int o = tid; o < H * CB; o += 256) {
+    const int ky = o / CB, ci = o - ky * CB, c = c0 + ci;
+    if (ci >= ncol) continue;
+    float re = 0.f, im = 0.f;
+    int t = 0;                                                    // (ky * y) mod H
+    for (int y = 0; y < H; ++y) {
+      const float2 v = col[y * CB + ci], e = tw[t];
+      re += v.x * e.x - v.y * e.y;
+      im += v.x * e.y + v.y * e.x;
+      t += ky;
+      if (t >= H) t -= H;
+    }
+    if (ky == 0) { re = csum[ci].x; im = csum[ci].y; }
+    if ((c == 0 || c == NB - 1) && (ky == 0 || 2 * ky == H)) im = 0.f;
+    int oy = ky, ox = c;
+    if (shift) { oy = (ky + H / 2) % H; ox = (c + NB / 2) % NB; }
+    const size_t oi = ((size_t)w * H + oy) * NB + ox;
+    amp[oi] = sqrtf(re * re + im * im);
+    pha[oi] = atan2f(im, re);
+  }
+}
+
+size_t tfc_fft_rect_ws_bytes(int H, int nwin) { return (size_t)nwin * 129 * H * sizeof(float2); }
+hipError_t tfc_launch_spectrum_rect(const float* img, long long bs, long long cs, int rs, int C, int H, int row0, int row_step, int wins_per_img,
+                                    int nwin, float* amp, float* pha, int shift, void* ws, hipStream_t st) {
+  constexpr int NB = 129;
+  const size_t lds_r = (size_t)(256 + 4 * 2 * 256 + NB * 32) * sizeof(float2);
+  const size_t lds_c = (size_t)(H + H * RECT_CB + RECT_CB) * sizeof(float2);          // 28 776 B at H = 256
+  hipLaunchKernelGGL(tfc_fft_rect_rows_kernel, dim3(nwin * ((H + 31) / 32)), dim3(256), lds_r, st, img, bs, cs, rs, C, H, row0, row_step, wins_per_img,
+                     (float2*)ws);
+  hipLaunchKernelGGL(tfc_dft_rect_cols_kernel, dim3(nwin * ((NB + RECT_CB - 1) / RECT_CB)), dim3(256), lds_c, st, (const float2*)ws, H, amp, pha, shift);
+  return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------------------
+// KL form of the regional loss (TFCGAN_multigpu_patchFFT_withregion_FFT_KL.py:400-418): every spectrum goes through F.log_softmax(., dim=0) -- over
+// the BATCH -- and nn.KLDivLoss(reduction="mean", log_target=True), the mean over all elements of exp(t) (t - x).  af, pf, ar: [N][M] (fake amplitude,
+// fake phase, real amplitude); the reference takes the real PHASE target from the real amplitudes as well (:401, :404), so ar is the target of both:
+//   t = ar_n - lse_n(ar),  xa = af_n - lse_n(af),  xp = pf_n - lse_n(pf);   out[0] += scale * sum exp(t) (t - xa),  out[1] += scale * sum exp(t) (t - xp).
+// One lane owns one bin and walks the N batch entries twice (the bin index is the fastest one: coalesced): an online max / sum exp(x - max), then the
+// terms.  The log-softmax is max-subtracted in fp32, (x - max) - log(sum exp(x - max)) -- amplitudes reach 3.3e6.  exp(t) = 0 contributes nothing,
+// whatever t - x is.  At N = 1 every term is exp(0) * (0 - 0).  Slots of this kernel's own (logged scalars, tfc_block_commit); like the triplet and L1 heads it runs on the SIDE stream only
+// (engine.step: pixel_losses).
+// ---------------------------------------------------------------------------------------------------
+static __device__ TfcRedSlot g_kl_amp_slot, g_kl_pha_slot;
+
+// one step of the online log-sum-exp: afterwards m = max(m, x) and z = sum exp(. - m) over the entries seen so far (m = -inf, z = 0 before the first:
+// 0 * exp(-inf) + 1 = 1)
+static __device__ __forceinline__ void kl_online(float x, float& m, float& z) {
+  if (x > m) { z = z * expf(m - x) + 1.f; m = x; }
+  else z += expf(x - m);
+}
+
+__global__ void __launch_bounds__(256)
+tfc_batch_kl_kernel(const float* __restrict__ af, const float* __restrict__ pf, const float* __restrict__ ar, int N, long long M, float scale,
+                    float* out) {
+  __shared__ float red[2][4];
+  float sa = 0.f, sp = 0.f;
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < M; i += (long long)gridDim.x * 256) {
+    float ma = -INFINITY, mp = -INFINITY, mr = -INFINITY, za = 0.f, zp = 0.f, zr = 0.f;
+    for (int n = 0; n < N; ++n) {                                 // first walk: running max m and z = sum exp(x - m), re-based when the max moves
+      const size_t o = (size_t)n * M + i;
+      kl_online(af[o], ma, za); kl_online(pf[o], mp, zp); kl_online(ar[o], mr, zr);
+    }
+    const float la = logf(za), lp = logf(zp), lr = logf(zr);
+    for (int n = 0; n < N; ++n) {
+      const size_t o = (size_t)n * M + i;
+      const float t = (ar[o] - mr) - lr;
+      const float e = expf(t);
+      if (e > 0.f) {                                              // exp(t) = 0: no term (never 0 * inf)
+        sa += e * (t - ((af[o] - ma) - la));
+        sp += e * (t - ((pf[o] - mp) - lp));
+      }
+    }
+  }
+  sa = wave_sum(sa); sp = wave_sum(sp);
+  if ((threadIdx.x & 63) == 0) { red[0][threadIdx.x >> 6] = sa; red[1][threadIdx.x >> 6] = sp; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    tfc_block_commit(&g_kl_amp_slot, ((double)red[0][0] + (double)red[0][1] + (double)red[0][2] + (double)red[0][3]) * (double)scale, out);
+    tfc_block_commit(&g_kl_pha_slot, ((double)red[1][0] + (double)red[1][1] + (double)red[1][2] + (double)red[1][3]) * (double)scale, out + 1);
+  }
+}
+hipError_t tfc_launch_batch_kl(const float* af, const float* pf, const float* ar, int N, long long M, float scale, float* out, hipStream_t st) {
+  long long nb = (M + 255) / 256;
+  if (nb > 512) nb = 512;
+  hipLaunchKernelGGL(tfc_batch_kl_kernel, dim3((int)nb), dim3(256), 0, st, af, pf, ar, N, M, scale, out);
+  return hipGetLastError();
+}

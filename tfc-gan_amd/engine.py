@@ -11,6 +11,10 @@ Scope notes: LPIPS (:598) needs VGG weights that cannot be
 plug it in.  The temperature head (:587-595, zero gradient) is computed when the caller passes `T_B` (and the augmented
 negatives `B_tf`): it adds 0.5 * loss_temp_g to the logged loss_G exactly as :607 does.  The FFT term carries no gradient in the reference (tensor -> PIL -> numpy, :300-302) and none here.  bf16 needs no
 GradScaler (:518); the reference's wasted D weight-gradients during the G step (:619 zeroes them) are simply not computed.
+
+`patches=4, region_fft="l1" | "kl"` adds the regional FFT loss of TFCGAN_multigpu_patchFFT_withregion_FFT.py ("4R", L1 form) /
+..._withregion_FFT_KL.py ("4K", KL form over the batch): lambda_region * regional_fft_loss(fake, B) joins the logged loss_G (4R:606-620, 4K:623-636;
+losses.region_weights gives each script's weights). It carries no gradient in the reference and none here; the discriminator step is PATCH-4's.
 """
 import math
 import os
@@ -18,18 +22,23 @@ import os
 import torch
 
 from . import nets, ops, parallel
-from .losses import global_fft_loss, patch_fft_loss, temperature_triplet_loss
+from .losses import global_fft_loss, patch_fft_loss, regional_fft_loss, temperature_triplet_loss
 from .ops import DT_BF16
 
 
 class TrainStep:
     def __init__(self, generator, discriminator, lr=2e-4, b1=0.5, b2=0.999, eps=1e-8, compute_dtype=torch.bfloat16,
                  fft_mode="patch", seed=0, bucket_bytes=16 << 20, lambda_gan=0.5, lambda_fft=0.01, lambda_trip=1.0, d_bucket_bytes=4 << 20,
-                 batch_invariant=None, patches=16):
+                 batch_invariant=None, patches=16, region_fft=None, lambda_region=0.5e-4):
         dev = next(generator.parameters()).device
         if patches not in (4, 16):
             raise ops._lib.TfcError(f"TrainStep: patches={patches} (16: the 4x4 grid of 64x64 patches, 4: the 2x2 grid of 128x128 patches)")
         self.patches = patches
+        if region_fft not in (None, "l1", "kl"):
+            raise ops._lib.TfcError(f"TrainStep: region_fft={region_fft!r} (None, 'l1': the L1 regional FFT loss, 'kl': its batch-softmax KL form)")
+        if region_fft is not None and patches != 4:
+            raise ops._lib.TfcError("TrainStep: region_fft belongs to the 4-patch scripts (patches=4); no reference script combines it with 16 patches")
+        self.region_fft, self.lambda_region = region_fft, lambda_region
         if dev.type != "cuda":
             raise ops._lib.TfcError("TrainStep needs the modules on a CUDA/HIP device (no CPU fallback)")
         self.dev, self.dt = dev, ops.dt_of(compute_dtype)
@@ -112,7 +121,9 @@ class TrainStep:
             lt, gt = ops.patch_triplet(fake, real_B, neg_idx, want_grad=True, gscale=self.lambda_trip)
             lf = patch_fft_loss(fake, real_B, self.patches) if self.fft_mode == "patch" else global_fft_loss(fake, real_B)
             ex = extra_loss_G(fake, real_B) if extra_loss_G is not None else None     # optional pluggable term (LPIPS, P16:598): (loss, dfake), already weighted
-            return lt, gt, lf, ex
+            # forward-only head: beside the other pixel losses, on their stream; (loss_FFT_reg, loss_Amp_reg, loss_Pha_reg) or None
+            reg = regional_fft_loss(fake, real_B, self.region_fft) if self.region_fft is not None else None
+            return lt, gt, lf, ex, reg
         if nets.side_stream_on() and os.environ.get("TFC_NO_GSTEP_OVERLAP", "0") in ("", "0"):
             # Two-stream form of the same program (nets.py: side stream). Both power iterations of this step's two discriminator calls come first, in
             # call order (they read the weights only); the chain of the SECOND call (real pair, no gradient) then runs beside the generator forward,
@@ -122,14 +133,14 @@ class TrainStep:
             pr = nets.on_side(self.dev, lambda: self.D.chain(real_B, real_A, snap_r, save=False), snap_r[2][0])[0]
             pr_ready = nets.side_mark(self.dev)
             fake, gctx = self.G.forward(real_A, seed=drop_seed, train=train)
-            loss_trip, g_trip, (loss_fft, loss_amp, loss_pha), extra_pair = nets.on_side(self.dev, pixel_losses)
+            loss_trip, g_trip, (loss_fft, loss_amp, loss_pha), extra_pair, region = nets.on_side(self.dev, pixel_losses)
             pf, dctx_f = self.D.chain(fake, real_A, snap_f, save=True)
             nets.wait_mark(self.dev, pr_ready)                    # the logits of the real pair; the pixel losses (LPIPS: 6 ms) run on, D.backward below joins
         else:
             fake, gctx = self.G.forward(real_A, seed=drop_seed, train=train)
             pf, dctx_f = self.D.forward(fake, real_A, power_iter=True, save=True)
             pr, _ = self.D.forward(real_B, real_A, power_iter=True, save=False)
-            loss_trip, g_trip, (loss_fft, loss_amp, loss_pha), extra_pair = pixel_losses()
+            loss_trip, g_trip, (loss_fft, loss_amp, loss_pha), extra_pair, region = pixel_losses()
         g_pf = self._gl(pf)
         loss_gan = ops.bce_relativistic(dt, pf, pr, 0, 0.9, da=ops.View(g_pf.t, 1, 0), gscale=self.lambda_gan)
         g_fake = self.D.backward(dctx_f, g_pf, grads=None, need_input_grad=True)
@@ -172,7 +183,13 @@ class TrainStep:
             self.last["loss_temp_g"] = loss_temp
         if extra is not None:
             self.last["loss_extra_g"] = extra.reshape(())
-        if parallel.collectives_active():                          # every logged loss is a batch mean: mean over ranks = the global-batch value
+        if region is not None:
+            loss_reg, loss_amp_reg, loss_pha_reg = region
+            self.last["loss_G"] = self.last["loss_G"] + self.lambda_region * loss_reg
+            self.last.update(loss_FFT_reg=loss_reg, loss_Amp_reg=loss_amp_reg, loss_Pha_reg=loss_pha_reg)
+        # Every logged loss but the KL regional term is a batch mean, so the mean over ranks is the global-batch value. With region_fft="kl" the
+        # softmax runs over each rank's shard: loss_FFT_reg, loss_Amp_reg, loss_Pha_reg and their share of loss_G are the mean of per-shard values.
+        if parallel.collectives_active():
             keys = [k for k in self.last if k != "fake_B"]
             packed = torch.stack([self.last[k].reshape(()).float() for k in keys])
             parallel.all_reduce_mean(packed)

@@ -11,6 +11,10 @@ and the 4-patch family (TFCGAN_multigpu_patchFFT.py = "4P", TFCGAN_multigpu_glob
   patch_triplet_loss with 4 indices      4P:474-481   0.25 * sum of 4 nn.TripletMarginLoss
   fft_components on 128x128 patches      4P:263-288   128 x 65 spectra;  patch_fft_loss(patches=4)  4P:499-511
 
+and the regional FFT loss of the two 4-patch scripts that carry one (TFCGAN_multigpu_patchFFT_withregion_FFT.py = "4R", ..._withregion_FFT_KL.py = "4K")
+
+  regional_fft_components / regional_fft_loss   4R:353-401 (L1 form), 4K:357-420 (KL form over the batch)   100 x 129 spectra of rows 0..99, 100..199
+
 The reference has no class called ContrastiveLoss: the "16-patch contrastive head" named by the project brief IS the
 16-fold triplet mean above; `ContrastiveLoss` here is defined as exactly that.
 """
@@ -188,6 +192,57 @@ def global_fft_loss(fake_B, real_B):
     ops.l1_sum(af, ar, scale, out[0:1])
     ops.l1_sum(pf, pr, scale, out[1:2])
     return 0.5 * (out[0] + out[1]), out[0], out[1]
+
+
+# ---- regional FFT loss (4R:353-401, 4K:357-420) -------------------------------------------------------------------------------
+REGIONS = {"hair": (0, 100), "eyes": (100, 100)}      # (first row, rows): fake_B[:, :, 0:100, :] and fake_B[:, :, 100:img_width-56, :] (4R:375-376); rows 200..255 unused
+
+
+def regional_fft_components(thermal_tensor, region):
+    """The nested reg_fft of regional_fft_loss (4R:358-371) on one region of whole images: thermal_tensor [N,3,256,256] in [-1,1]; region "hair" (rows
+    0..99), "eyes" (rows 100..199) or an explicit (row0, H) with H in 2 .. 256. Per sample ToPILImage -> convert("L") -> np.fft.rfft2 (H x 129) ->
+    fftshift of both axes -> abs, arctan2. Returns (AMP, PHA), each [N,1,H,129] fp32. N comes from the tensor (the reference loops opt.batch_size)."""
+    row0, H = REGIONS[region] if isinstance(region, str) else (int(region[0]), int(region[1]))
+    N = thermal_tensor.shape[0]
+    amp, pha = ops.fft_spectrum_rect(thermal_tensor.detach(), H, row0, 0, 1, shift=True)
+    return amp.reshape(N, 1, H, 129), pha.reshape(N, 1, H, 129)
+
+
+def regional_fft_loss(fake_B, real_B, kind="l1"):
+    """regional_fft_loss of 4R (kind="l1", 4R:353-401) or 4K (kind="kl", 4K:357-420) -> (loss_FFT_reg, loss_Amp_reg, loss_Pha_reg), device scalars
+    without gradient (the reference goes tensor -> PIL -> numpy) and without a host synchronisation.
+      l1: loss_Amp_reg = L1mean(Ah_F, Ah_R) + L1mean(Ae_F, Ae_R) -- a SUM over the two regions --, loss_Pha_reg the same of the phases (4R:391-398).
+      kl: every spectrum through F.log_softmax(., dim=0), i.e. over the BATCH, then nn.KLDivLoss(reduction="mean", log_target=True) = mean of
+          exp(t)(t - x), summed over the two regions (4K:400-417). The reference builds the real PHASE target from the real AMPLITUDES (4K:401, :404);
+          that is reproduced literally: the target of the phase term is the target of the amplitude term. At N = 1 the loss is exactly 0.
+    loss_FFT_reg = 1/2 (loss_Amp_reg + loss_Pha_reg) in both. The spectra are taken unshifted: every term is a sum over all bins."""
+    if kind not in ("l1", "kl"):
+        raise ops._lib.TfcError(f"regional_fft_loss: kind={kind!r} ('l1': ..._withregion_FFT.py, 'kl': ..._withregion_FFT_KL.py)")
+    ops.require_gpu(fake_B, real_B)
+    N = fake_B.shape[0]
+    (_, H), step = REGIONS["hair"], REGIONS["eyes"][0]
+    af, pf = ops.fft_spectrum_rect(fake_B.detach(), H, 0, step, 2, shift=False)      # [N*2][100][129]: sample n = windows 2n (hair), 2n+1 (eyes)
+    ar, pr = ops.fft_spectrum_rect(real_B.detach(), H, 0, step, 2, shift=False)
+    out = torch.zeros(2, dtype=torch.float32, device=fake_B.device)
+    scale = 1.0 / (N * H * 129)                                    # the mean of one region; the two regions add
+    if kind == "l1":
+        ops.l1_sum(af, ar, scale, out[0:1])
+        ops.l1_sum(pf, pr, scale, out[1:2])
+    else:
+        ops.batch_kl_sum(af.reshape(N, -1), pf.reshape(N, -1), ar.reshape(N, -1), scale, out)
+    return 0.5 * (out[0] + out[1]), out[0], out[1]
+
+
+def region_weights(kind):
+    """TrainStep keyword values that reproduce loss_G of 4R (kind="l1", 4R:603-620) / 4K (kind="kl", 4K:617-636) without the LPIPS and temperature terms:
+      4R: loss_G = 1/2 (GAN + 1e-4 * fft_loss + 1e-4 * regional + patch + ..);  fft_loss is the SUM over the four patches (4R:315-317) and
+          patch_fft_loss returns their mean, hence the factor 4 in lambda_fft.
+      4K: loss_G = 1/2 (GAN + 1e-4 * (0.01 * regional) + patch + ..);  the patch FFT loss is logged only."""
+    if kind == "l1":
+        return {"lambda_gan": 0.5, "lambda_trip": 0.5, "lambda_fft": 0.5 * 1e-4 * 4, "lambda_region": 0.5e-4}
+    if kind == "kl":
+        return {"lambda_gan": 0.5, "lambda_trip": 0.5, "lambda_fft": 0.0, "lambda_region": 0.5e-6}
+    raise ops._lib.TfcError(f"region_weights: kind={kind!r} ('l1' or 'kl')")
 
 
 def calculate_ffts(*patches):

@@ -488,6 +488,42 @@ def fft_spectrum(img, S, wins_x, wins_y, shift=True, direct=False):
     return amp, pha
 
 
+def fft_spectrum_rect(img, H, row0=0, row_step=0, wins=1, shift=True):
+    """Spectra of `wins` windows of H rows x 256 columns per image, window k starting at image row row0 + k * row_step (H in 2 .. 256; the regional
+    FFT loss uses H = 100, rows 0 and 100). img: fp32 [N,C,h,w >= 256] (any strides on N/C/H, unit stride on W). Returns amp, pha [N*wins, H, 129]."""
+    require_gpu(img)
+    if img.dtype != torch.float32:
+        img = img.float()
+    if img.stride(3) != 1:
+        img = img.contiguous()
+    N, C, h, w = img.shape
+    nwin = N * wins
+    need = lib().tfc_fft_spectrum_rect_ws_bytes(H, nwin)          # 0 for a refused H: the call below says why
+    amp = torch.empty((nwin, max(H, 0), 129), dtype=torch.float32, device=img.device)
+    pha = torch.empty_like(amp)
+    key = (img.device, torch.cuda.current_stream().cuda_stream)   # the scratch of fft_spectrum: calls on a stream are ordered
+    ws = _FFT_WS.get(key)
+    if ws is None or ws.numel() < max(need, 16):
+        ws = _FFT_WS[key] = torch.empty(max(need, 16), dtype=torch.uint8, device=img.device)
+    check(lib().tfc_fft_spectrum_rect(stream_ptr(), _p(img), img.stride(0), img.stride(1), img.stride(2), C, h, w, H, row0, row_step, wins, N,
+                                      _p(amp), _p(pha), 1 if shift else 0, _p(ws)), "tfc_fft_spectrum_rect")
+    return amp, pha
+
+
+def batch_kl_sum(af, pf, ar, scale, out):
+    """out[0] += scale * sum exp(t)(t - xa), out[1] += scale * sum exp(t)(t - xp) with t / xa / xp = log_softmax over dim 0 of ar / af / pf
+    (contiguous fp32 [N, ...] of one shape; ar is the target of both terms, as in the reference's KL regional loss)."""
+    require_gpu(af, pf, ar, out)
+    for name, v in (("af", af), ("pf", pf), ("ar", ar)):
+        if v.dtype != torch.float32 or not v.is_contiguous() or v.shape != af.shape or v.dim() < 1 or v.shape[0] < 1:
+            raise _lib.TfcError(f"batch_kl_sum: {name} is {v.dtype} {tuple(v.shape)}, contiguous={v.is_contiguous()} "
+                                f"(three contiguous fp32 tensors of one shape [N >= 1, ...])")
+    if out.dtype != torch.float32 or not out.is_contiguous() or out.numel() < 2:
+        raise _lib.TfcError(f"batch_kl_sum: out is {out.dtype} with {out.numel()} elements (contiguous fp32, at least 2)")
+    N = af.shape[0]
+    check(lib().tfc_batch_kl_sum(stream_ptr(), _p(af), _p(pf), _p(ar), N, af.numel() // N, scale, _p(out)), "tfc_batch_kl_sum")
+
+
 def logmag_mse(amp_a, amp_b, absolute=False):
     """per window mean squared (or absolute) difference of the log-magnitude spectra over the FULL S x S spectrum"""
     nwin, S = amp_a.shape[0], amp_a.shape[1]
