@@ -180,7 +180,7 @@ int tfc_patch16_triplet(void* stream, const float* fake, const float* real, cons
                         float* loss, float* dfake, float gscale);
 /* the same head on a grid x grid patch grid (patches of 256/grid pixels): grid 4 IS tfc_patch16_triplet (same bits); grid 2 = the four 128 x 128
  * patches of TFCGAN_multigpu_patchFFT.py:468-481, loss[0] = (1/4) sum_k mean(...).  neg_idx_host: grid*grid ints in [0, grid*grid).
- * dfake (nullable) is written for every pixel (zero where the hinge is inactive). */
+ * dfake (nullable) is written for every pixel (zero where the hinge is inactive).  One kernel for both grids (tfc_patch_triplet_kernel<grid>). */
 int tfc_patch_triplet(void* stream, const float* fake, const float* real, const int* neg_idx_host, int grid, int N, int C,
                       float* loss, float* dfake, float gscale);
 /* spectra: ToPILImage -> convert("L") -> np.fft.rfft2 -> fftshift -> abs / arctan2, P16:271-319.
@@ -194,7 +194,7 @@ size_t tfc_fft_spectrum_ws_bytes(int S, int nwin);
 /* the same spectra of RECTANGULAR windows of H rows x 256 columns, H in 2 .. 256 (the regional FFT loss of TFCGAN_multigpu_patchFFT_withregion_FFT.py:353-401
  * uses H = 100): wins_per_img windows per image, window k starting at image row row0 + k * row_step, column 0. img: fp32 [N][C][img_h][row_stride] with
  * img_w >= 256 valid columns; amp/pha: [N*wins_per_img][H][129] fp32; shift != 0: ky -> (ky + H/2) % H, kx -> (kx + 64) % 129 (np.fft.fftshift, even and odd H).
- * Rows: the 256-point LDS FFT; columns: a direct H-point DFT with the column mean taken out. Im = +0 at kx in {0,128} x (ky = 0, ky = H/2 for even H).
+ * Rows: the row pass of tfc_fft_spectrum at S = 256 with H rows (tfc_fft_rows_kernel<256, true>); columns: a direct H-point DFT with the column mean taken out. Im = +0 at kx in {0,128} x (ky = 0, ky = H/2 for even H).
  * ws: tfc_fft_spectrum_rect_ws_bytes(H, N * wins_per_img) bytes of scratch (16-byte aligned; 0 for an H outside 2 .. 256).
  * Refused (non-zero, tfc_last_error): H outside 2 .. 256, row0 + (wins_per_img - 1) * row_step + H > img_h, img_w < 256. */
 int tfc_fft_spectrum_rect(void* stream, const float* img, long long batch_stride, long long chan_stride, int row_stride, int C, int img_h, int img_w,

@@ -735,6 +735,44 @@ def test_triplet16_vs_oracle_and_golden(golden):
     assert torch.allclose(f2.grad.cpu(), fk.grad, atol=1e-9, rtol=1e-4)
 
 
+def test_triplet16_second_ragged_trip_vs_oracle(golden):
+    """N = 3, C = 3: 9216 patch rows against the 8192 row slots of one trip of the grid-stride loop (512 workgroups x 4 waves x 4 rows in flight) --
+    the smallest batch with a second trip, and that trip is ragged (1024 of its 8192 slots hold a row). The loop tail is shared by both patch
+    grids. Tolerances of test_triplet16_vs_oracle_and_golden."""
+    fk, rl = O.synthetic_pairs(3, seed=31)
+    assert fk.shape == (3, 3, 256, 256)
+    fk = torch.tanh(fk * 1.5).requires_grad_(True)
+    neg = golden("triplet16")["neg_idx"].tolist()
+    want = O.patch_triplet_loss(fk, rl, neg)
+    want.backward()
+    loss, dfake = ops.patch16_triplet(fk.detach().to(DEV), rl.to(DEV), neg)
+    err = (dfake.cpu() - fk.grad).abs().max().item()
+    print(f"loss {loss.item():.8f} vs {want.item():.8f}; gradient error {err:.3e}, max |grad| {fk.grad.abs().max().item():.3e}")
+    assert abs(loss.item() - want.item()) < 2e-6
+    assert err < 1e-9 + 1e-5 * fk.grad.abs().max().item()
+
+
+def test_patch16_triplet_c_entry_point(golden):
+    """tfc_patch16_triplet of the C ABI, called directly (ops.patch16_triplet goes through tfc_patch_triplet(grid=4)): the same gradient bits as the
+    grid entry point, and its own argument checks with their texts."""
+    lib = _lib.load()
+    fk, rl = O.synthetic_pairs(1, seed=31)
+    fk, rl = torch.tanh(fk * 1.5).to(DEV), rl.to(DEV)
+    neg = golden("triplet16")["neg_idx"].tolist()
+    want_loss, want = ops.patch_triplet(fk, rl, neg, gscale=0.5)
+    loss, dfake = torch.empty(1, device=DEV), torch.empty_like(fk)
+
+    def call(idx, fake=fk):
+        return lib.tfc_patch16_triplet(ops.stream_ptr(), fake.data_ptr() if fake is not None else None, rl.data_ptr(), (ctypes.c_int * 16)(*idx),
+                                       1, 3, loss.data_ptr(), dfake.data_ptr(), 0.5)
+    assert call(neg) == 0
+    assert torch.equal(dfake, want) and abs(loss.item() - want_loss.item()) < 2e-6
+    assert call(neg[:15] + [16]) != 0 and lib.tfc_last_error() == b"neg_idx[15]=16 out of range"
+    assert call([-1] + neg[1:]) != 0 and lib.tfc_last_error() == b"neg_idx[0]=-1 out of range"
+    assert call(neg, fake=None) != 0 and lib.tfc_last_error() == b"bad args"
+    assert torch.equal(dfake, want)                                  # a refused call launches nothing
+
+
 def test_fft_spectrum_vs_oracle_and_golden(golden):
     gp, gg = golden("fft_patch"), golden("fft_global")
     ff, rr = O.synthetic_pairs(1, seed=41)

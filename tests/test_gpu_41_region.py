@@ -108,6 +108,32 @@ def test_rect_spectrum_at_256_rows_matches_the_square_fft(shift):
     assert dp[big_bins].max().item() <= 2e-3
 
 
+@pytest.mark.parametrize("shift", [True, False])
+@pytest.mark.parametrize("S,wx,wy", [(64, 2, 3), (128, 2, 1)])
+def test_square_spectrum_every_window_vs_numpy_float64(S, wx, wy, shift):
+    """tfc_fft_spectrum, EVERY window of a non-square window grid on the non-contiguous view (row stride 512, offset origin), against numpy float64
+    rfft2 of the window's uint8 luma: the FFT and the direct-DFT kernels share the luma and the window origin, so comparing them with each other
+    cannot see a geometry slip (x and y swapped, a wrong step). Amplitude within 4e-6 * max(amp), the bound of the numpy comparisons above -- a
+    wrong origin shows there; the phase of the four self-conjugate bins is exactly 0 or pi."""
+    x, big = spectrum_images()
+    img = big.to(DEV)[:2, :, 16:, 100:356]
+    assert not img.is_contiguous() and img.stride(2) == 512
+    amp, pha = ops.fft_spectrum(img, S, wx, wy, shift=shift)
+    nb = S // 2 + 1
+    assert amp.shape == pha.shape == (2 * wx * wy, S, nb)
+    f = np.stack([np.fft.rfft2(R4.luma_of(x[n, :, (k // wx) * S:(k // wx) * S + S, (k % wx) * S:(k % wx) * S + S])) for n in range(2) for k in range(wx * wy)])
+    a_ref = t(np.abs(np.fft.fftshift(f, axes=(-2, -1)) if shift else f))
+    scale = a_ref.max().item()
+    a_err = (amp.cpu().double() - a_ref).abs().flatten(1).max(dim=1).values
+    print(f"S={S} {wx}x{wy} shift={shift}: amp error per window / max ({scale:.4g}): {(a_err / scale).tolist()}")
+    assert a_err.max().item() <= 4e-6 * scale
+    kys, kxs = [0, S // 2], [0, S // 2]
+    if shift:
+        kys, kxs = [(k + S // 2) % S for k in kys], [(k + nb // 2) % nb for k in kxs]
+    corner = pha[:, kys][:, :, kxs]
+    assert bool(((corner == 0.0) | (corner == PI32)).all())
+
+
 # ---- 3. against the reference's own values --------------------------------------------------------------------------------------------------
 def test_regional_components_vs_reference_golden(golden):
     """regional_fft_components(.., "eyes") against the lifted reg_fft: the forms of the S = 128 fixture test (amplitude 2e-6 * max + 2e-2,

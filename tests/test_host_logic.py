@@ -44,6 +44,19 @@ def test_build_refuses_spilling_hand_scheduled_kernels():
     assert len(got) == 2 and all("tfc_igemm2_kernel" in g for g in got), got
 
 
+def test_build_refuses_a_guard_that_names_no_kernel():
+    """GUARDED_KERNELS matches by substring: an entry that matches no `Function Name:` remark of the build (a renamed kernel) guards nothing, and
+    the build has to say which one"""
+    def remark(name):
+        return (f"a.hip:1:1: remark: Function Name: _Z9{name}v [-Rpass-analysis=kernel-resource-usage]\n"
+                "a.hip:1:1: remark:     ScratchSize [bytes/lane]: 0 [-Rpass-analysis=kernel-resource-usage]\n")
+    every = "".join(remark(g) for g in _lib.GUARDED_KERNELS) + remark("tfc_adam_kernelPf")
+    assert _lib.unmatched_guards(every) == []
+    gone = _lib.GUARDED_KERNELS[2]
+    assert _lib.unmatched_guards("".join(remark(g) for g in _lib.GUARDED_KERNELS if g != gone)) == [gone]
+    assert _lib.unmatched_guards("a.hip:1:1: warning: " + gone + "\n") == list(_lib.GUARDED_KERNELS)      # only Function Name remarks count
+
+
 def test_errors_are_loud():
     lib = _lib.load()
     rc = lib.tfc_conv_fwd(None, 7, 0, None, 0, 1, 8, 8, 8, 8, None, None, 0, None, None, None, None, 0, None)

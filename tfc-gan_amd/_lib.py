@@ -63,6 +63,9 @@ def _build_locked(verbose):
     res = subprocess.run(cmd, stderr=subprocess.PIPE, text=True)
     if res.returncode != 0:
         raise RuntimeError("hipcc failed:\n" + "\n".join(l for l in res.stderr.splitlines() if "remark:" not in l)[-8000:])
+    unmatched = unmatched_guards(res.stderr)
+    if unmatched:
+        raise RuntimeError("GUARDED_KERNELS entries that match no compiled kernel (renamed or removed? they guard nothing): " + ", ".join(unmatched))
     bad = check_no_spills(res.stderr)
     if bad:
         raise RuntimeError("hand-scheduled kernels must not spill (their asm loads carry hand-counted waits the compiler cannot see): " + "; ".join(bad))
@@ -74,12 +77,13 @@ def _build_locked(verbose):
 # while hipcc keeps their destination registers in place (no scratch, no VGPR spill) between the load and the wait. The compiler's resource remarks
 # (-Rpass-analysis=kernel-resource-usage) are checked at every build, so a toolchain or flag change that makes one of them spill fails loudly here
 # instead of silently producing wrong convolutions.
-# The 4-patch loss heads (tfc_triplet4_kernel with four float2 rows in flight, the 128-point FFT kernels) ride the same check: they were sized to run
-# without scratch, and a spill there would be a silent slowdown of every PATCH-4 / GLO-4 step.
-# So do the kernels of the rectangular-window spectra (the regional FFT loss): the rows kernel is the 256-point FFT with a run-time row count, the columns
-# kernel a 100 x 100 inner loop per output that was written to live in registers.
-GUARDED_KERNELS = ("tfc_igemm2_kernel", "tfc_wgrad", "tfc_triplet4_kernel", "tfc_fft_rows_kernelILi128E", "tfc_fft_cols_kernelILi128E",
-                   "tfc_spectrum_kernelILi128E", "tfc_fft_rect_rows_kernel", "tfc_dft_rect_cols_kernel")
+# The 4-patch loss heads (tfc_patch_triplet_kernel<2> with four float2 rows in flight, the 128-point FFT kernels) ride the same check: they were sized
+# to run without scratch, and a spill there would be a silent slowdown of every PATCH-4 / GLO-4 step.
+# So do the kernels of the rectangular-window spectra (the regional FFT loss): the rows kernel is tfc_fft_rows_kernel<256, true> (the row FFT of
+# the square spectra with the checks of a ragged row count compiled in; "ILi256E" matches both 256-point instantiations), the columns kernel a 100 x 100 inner loop per output that was written to live in registers.
+# Entries are substrings of the MANGLED names in the remarks; one that matches no compiled kernel fails the build (unmatched_guards).
+GUARDED_KERNELS = ("tfc_igemm2_kernel", "tfc_wgrad", "tfc_patch_triplet_kernelILi2E", "tfc_fft_rows_kernelILi128E", "tfc_fft_rows_kernelILi256E",
+                   "tfc_fft_cols_kernelILi128E", "tfc_spectrum_kernelILi128E", "tfc_dft_rect_cols_kernel")
 
 
 def check_no_spills(remarks):
@@ -95,6 +99,13 @@ def check_no_spills(remarks):
                     if val != 0:
                         bad.append(f"{name[:80]}: {key} {val}")
     return bad
+
+
+def unmatched_guards(remarks):
+    """remarks: hipcc stderr of a WHOLE build. Returns the GUARDED_KERNELS entries that occur in no `Function Name:` remark: a guard that names
+    no kernel (after a rename, say) would check nothing and tell nobody."""
+    names = [line.split("Function Name:")[1] for line in remarks.splitlines() if "Function Name:" in line]
+    return [g for g in GUARDED_KERNELS if not any(g in n for n in names)]
 
 
 _c = ctypes

@@ -64,13 +64,10 @@ hipError_t tfc_launch_adam(float* p, const float* g, float* m, float* v, long lo
 hipError_t tfc_launch_axpby(float* out, const float* x, const float* y, long long n, float a, float b, hipStream_t st);
 hipError_t tfc_launch_dropout_mask(unsigned char* out, long long n, unsigned seed, unsigned thresh24, hipStream_t st);
 hipError_t tfc_launch_cast(int dt, int to_f32, const void* x, void* y, long long n, hipStream_t st);
-hipError_t tfc_launch_triplet16(const float* fake, const float* real, const int* neg_idx, int N, int C, float margin, float eps, float* loss, float* dfake, float gscale, hipStream_t st);
-hipError_t tfc_launch_triplet4(const float* fake, const float* real, const int* neg_idx, int N, int C, float margin, float eps, float* loss, float* dfake, float gscale, hipStream_t st);
-hipError_t tfc_launch_spectrum(const float* img, long long bs, long long cs, int rs, int C, int S, int wins_x, int wins_per_img, int nwin, float* amp, float* pha, int shift, void* ws, hipStream_t st);
-size_t tfc_fft_ws_bytes(int S, int nwin);
+hipError_t tfc_launch_patch_triplet(int grid, const float* fake, const float* real, const int* neg_idx, int N, int C, float margin, float eps, float* loss, float* dfake, float gscale, hipStream_t st);
+hipError_t tfc_launch_spectrum(const float* img, const TfcWinGrid& g, int S, int H, bool rect, int nwin, float* amp, float* pha, int shift, void* ws, hipStream_t st);
+size_t tfc_fft_ws_bytes(int S, int H, int nwin);
 hipError_t tfc_launch_l1_sum(const float* a, const float* b, long long n, float scale, float* out, hipStream_t st);
-hipError_t tfc_launch_spectrum_rect(const float* img, long long bs, long long cs, int rs, int C, int H, int row0, int row_step, int wins_per_img, int nwin, float* amp, float* pha, int shift, void* ws, hipStream_t st);
-size_t tfc_fft_rect_ws_bytes(int H, int nwin);
 hipError_t tfc_launch_batch_kl(const float* af, const float* pf, const float* ar, int N, long long M, float scale, float* out, hipStream_t st);
 hipError_t tfc_launch_probe(float* out, hipStream_t st);
 hipError_t tfc_launch_logmag_mse(const float* a, const float* b, int S, int nwin, float* out, int absolute, hipStream_t st);
@@ -842,32 +839,34 @@ extern "C" int tfc_spectral_norm_bwd(void* stream, const float* G, const float* 
   return 0;
 }
 
-extern "C" int tfc_patch16_triplet(void* stream, const float* fake, const float* real, const int* neg_idx_host, int N, int C,
-                                   float* loss, float* dfake, float gscale) {
+// the patch triplet head on a grid x grid patch grid (grid 4 IS tfc_patch16_triplet, whichever entry point it came through)
+static int patch_triplet(void* stream, const float* fake, const float* real, const int* neg_idx_host, int grid, int N, int C, float* loss, float* dfake,
+                         float gscale) {
   REQUIRE(fake && real && neg_idx_host && loss && N > 0 && C > 0, "bad args");
-  for (int i = 0; i < 16; ++i) REQUIRE(neg_idx_host[i] >= 0 && neg_idx_host[i] < 16, "neg_idx[%d]=%d out of range", i, neg_idx_host[i]);
-  CHECK_HIP(tfc_launch_triplet16(fake, real, neg_idx_host, N, C, 1.0f, 1e-6f, loss, dfake, gscale, (hipStream_t)stream), "tfc_patch16_triplet");
+  if (grid == 2)
+    REQUIRE(((uintptr_t)fake & 7) == 0 && ((uintptr_t)real & 7) == 0 && ((uintptr_t)dfake & 7) == 0, "fake / real / dfake must be 8-byte aligned (pixel pairs)");
+  for (int i = 0; i < grid * grid; ++i) REQUIRE(neg_idx_host[i] >= 0 && neg_idx_host[i] < grid * grid, "neg_idx[%d]=%d out of range", i, neg_idx_host[i]);
+  CHECK_HIP(tfc_launch_patch_triplet(grid, fake, real, neg_idx_host, N, C, 1.0f, 1e-6f, loss, dfake, gscale, (hipStream_t)stream),
+            grid == 4 ? "tfc_patch16_triplet" : "tfc_patch_triplet");
   return 0;
 }
-extern "C" int tfc_patch_triplet(void* stream, const float* fake, const float* real, const int* neg_idx_host, int grid, int N, int C,
-                                 float* loss, float* dfake, float gscale) {
+extern "C" int tfc_patch16_triplet(void* stream, const float* fake, const float* real, const int* neg_idx_host, int N, int C, float* loss, float* dfake, float gscale) {
+  return patch_triplet(stream, fake, real, neg_idx_host, 4, N, C, loss, dfake, gscale);
+}
+extern "C" int tfc_patch_triplet(void* stream, const float* fake, const float* real, const int* neg_idx_host, int grid, int N, int C, float* loss, float* dfake, float gscale) {
   REQUIRE(grid == 2 || grid == 4, "grid=%d: the patch grid is 2 (four 128 x 128 patches) or 4 (sixteen 64 x 64 patches)", grid);
-  if (grid == 4) return tfc_patch16_triplet(stream, fake, real, neg_idx_host, N, C, loss, dfake, gscale);
-  REQUIRE(fake && real && neg_idx_host && loss && N > 0 && C > 0, "bad args");
-  REQUIRE(((uintptr_t)fake & 7) == 0 && ((uintptr_t)real & 7) == 0 && ((uintptr_t)dfake & 7) == 0, "fake / real / dfake must be 8-byte aligned (pixel pairs)");
-  for (int i = 0; i < 4; ++i) REQUIRE(neg_idx_host[i] >= 0 && neg_idx_host[i] < 4, "neg_idx[%d]=%d out of range", i, neg_idx_host[i]);
-  CHECK_HIP(tfc_launch_triplet4(fake, real, neg_idx_host, N, C, 1.0f, 1e-6f, loss, dfake, gscale, (hipStream_t)stream), "tfc_patch_triplet");
-  return 0;
+  return patch_triplet(stream, fake, real, neg_idx_host, grid, N, C, loss, dfake, gscale);
 }
-extern "C" size_t tfc_fft_spectrum_ws_bytes(int S, int nwin) { return (S == 64 || S == 128 || S == 256) && nwin > 0 ? tfc_fft_ws_bytes(S, nwin) : 0; }
+extern "C" size_t tfc_fft_spectrum_ws_bytes(int S, int nwin) { return (S == 64 || S == 128 || S == 256) && nwin > 0 ? tfc_fft_ws_bytes(S, S, nwin) : 0; }
 extern "C" int tfc_fft_spectrum(void* stream, const float* img, long long batch_stride, long long chan_stride, int row_stride, int C, int S,
                                 int wins_x, int wins_y, int N, float* amp, float* pha, int shift, void* ws) {
   REQUIRE(img && amp && pha && (S == 64 || S == 128 || S == 256) && (C == 1 || C == 3) && wins_x > 0 && wins_y > 0 && N > 0, "bad args");
   if (ws) { if (int e = check_ptr16(ws, "ws")) return e; }
-  CHECK_HIP(tfc_launch_spectrum(img, batch_stride, chan_stride, row_stride, C, S, wins_x, wins_x * wins_y, N * wins_x * wins_y, amp, pha, shift, ws, (hipStream_t)stream), "tfc_fft_spectrum");
+  const TfcWinGrid g = {batch_stride, chan_stride, row_stride, C, 0, S, S, wins_x, wins_x * wins_y};
+  CHECK_HIP(tfc_launch_spectrum(img, g, S, S, false, N * wins_x * wins_y, amp, pha, shift, ws, (hipStream_t)stream), "tfc_fft_spectrum");
   return 0;
 }
-extern "C" size_t tfc_fft_spectrum_rect_ws_bytes(int H, int nwin) { return H >= 2 && H <= 256 && nwin > 0 ? tfc_fft_rect_ws_bytes(H, nwin) : 0; }
+extern "C" size_t tfc_fft_spectrum_rect_ws_bytes(int H, int nwin) { return H >= 2 && H <= 256 && nwin > 0 ? tfc_fft_ws_bytes(256, H, nwin) : 0; }
 extern "C" int tfc_fft_spectrum_rect(void* stream, const float* img, long long batch_stride, long long chan_stride, int row_stride, int C, int img_h,
                                      int img_w, int H, int row0, int row_step, int wins_per_img, int N, float* amp, float* pha, int shift, void* ws) {
   REQUIRE(H >= 2 && H <= 256, "H=%d: a rectangular window has 2 .. 256 rows", H);
@@ -876,8 +875,8 @@ extern "C" int tfc_fft_spectrum_rect(void* stream, const float* img, long long b
   REQUIRE((long long)row0 + (long long)(wins_per_img - 1) * row_step + H <= img_h, "windows of %d rows from row %d every %d rows (%d per image) pass the image height %d",
           H, row0, row_step, wins_per_img, img_h);
   if (int e = check_ptr16(ws, "ws")) return e;
-  CHECK_HIP(tfc_launch_spectrum_rect(img, batch_stride, chan_stride, row_stride, C, H, row0, row_step, wins_per_img, N * wins_per_img, amp, pha, shift, ws,
-                                     (hipStream_t)stream), "tfc_fft_spectrum_rect");
+  const TfcWinGrid g = {batch_stride, chan_stride, row_stride, C, row0, row_step, 0, 1, wins_per_img};
+  CHECK_HIP(tfc_launch_spectrum(img, g, 256, H, true, N * wins_per_img, amp, pha, shift, ws, (hipStream_t)stream), "tfc_fft_spectrum_rect");
   return 0;
 }
 extern "C" int tfc_batch_kl_sum(void* stream, const float* af, const float* pf, const float* ar, int N, long long M, float scale, float* out) {

@@ -105,6 +105,15 @@ __device__ __forceinline__ float wave_sum(float v) {
   return v;
 }
 
+// The four wave partials of a 256-thread workgroup to one double, for thread 0 (the others get 0).  `v` is the wave's partial as its lane 0 holds it
+// (after wave_sum, or a value every lane agrees on); `red`: four floats of LDS.  Every thread calls it (one __syncthreads).  The sum is red[0] + red[1] +
+// red[2] + red[3] in doubles, in that order, and NO factor: whether a caller divides by a count or multiplies by a scale is part of its bits.
+__device__ __forceinline__ double tfc_block_sum4(float v, float* red) {
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return threadIdx.x == 0 ? (double)red[0] + (double)red[1] + (double)red[2] + (double)red[3] : 0.0;
+}
+
 // counter-based dropout RNG: keep-mask bit for element `idx` of stream `seed` (murmur3 finaliser of a 64-bit key)
 __host__ __device__ __forceinline__ uint32_t tfc_hash32(uint32_t seed, uint32_t idx) {
   uint32_t x = idx * 0x9E3779B1u + seed;

@@ -1093,10 +1093,8 @@ tfc_bce_rel_kernel(const T* __restrict__ a, const T* __restrict__ b, int n, int 
     if (da) put(da + (size_t)i * stride, gx * gscale);
     if (db) put(db + (size_t)i * stride, -gx * gscale);
   }
-  l = wave_sum(l);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = l;
-  __syncthreads();
-  if (threadIdx.x == 0) tfc_block_commit(&g_bce_slot, ((double)red[0] + (double)red[1] + (double)red[2] + (double)red[3]) / (double)n, loss, true);
+  const double tot = tfc_block_sum4(wave_sum(l), red);
+  if (threadIdx.x == 0) tfc_block_commit(&g_bce_slot, tot / (double)n, loss, true);
 }
 
 // Adam (torch.optim.Adam defaults: no weight decay, no amsgrad; reference :461-462)

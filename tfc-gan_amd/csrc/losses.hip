@@ -1,34 +1,54 @@
 // Loss heads of the PATCH-16 training step (gfx950).
-//   triplet16 : the 16-patch "contrastive" head  (reference TFCGAN_multigpu_patchFFT_16P.py:75, :558-583)
+//   triplet   : the 16-patch "contrastive" head  (reference TFCGAN_multigpu_patchFFT_16P.py:75, :558-583) and its 4-patch form
 //   spectrum  : ToPILImage -> convert("L") -> np.fft.rfft2 -> fftshift -> |.|, atan2  (reference :271-319)
 //   l1 mean   : nn.L1Loss over amplitude / phase arrays (reference :323-375)
 #include "common.h"
 
 // ---------------------------------------------------------------------------------------------------
-// 16-patch triplet.  Patch k (0-based) = rows 64*(k/4).., cols 64*(k%4)..  (make_16_patches, reference :227-253;
-// first flat NCHW index of patch k = 64*(k%4) + 16384*(k/4)).  F.triplet_margin_loss(margin 1, p 2, eps 1e-6):
-//   d(x,y) = || x - y + eps ||_2 over the LAST dim (one 64-pixel patch row); loss_k = mean_{n,c,row} max(1 + d_ap - d_an, 0)
-//   total = (1/16) sum_k loss_k.  One wave per patch row: lane = pixel, wave-shuffle reductions.
-// grad wrt anchor (fake):  [hinge>0] * ((a-p+eps)/d_ap - (a-n+eps)/d_an) * scale
+// Patch triplet on a GRID x GRID grid of P x P patches, P = 256 / GRID: GRID = 4 is the 16-patch head of PATCH-16 (make_16_patches, reference :227-253),
+// GRID = 2 the 4-patch head of PATCH-4 / GLO-4 (reference TFCGAN_multigpu_patchFFT.py:468-481).  Patch k (0-based) = rows P*(k/GRID).., cols P*(k%GRID)..
+// (first flat NCHW index of patch k = P*(k%GRID) + 256*P*(k/GRID)).  F.triplet_margin_loss(margin 1, p 2, eps 1e-6):
+//   d(x,y) = || x - y + eps ||_2 over the LAST dim (one P-pixel patch row); loss_k = mean_{n,c,row} max(1 + d_ap - d_an, 0)
+//   total = (1/GRID^2) sum_k loss_k.  One wave per patch row, P / 64 adjacent pixels per lane (one 8-byte access at GRID = 2), wave-shuffle reductions.
+//   Row id = ((n*C + c)*256 + y)*GRID + kx.
+// grad wrt anchor (fake):  [hinge>0] * ((a-p+eps)/d_ap - (a-n+eps)/d_an) * factor.  The factor is rounded as each head has always rounded it
+// (tfc_launch_patch_triplet): the 16-patch head multiplies by coef = 1 / (16 N C 64) and then by gscale; the 4-patch head multiplies ONCE, by
+// coef = gscale / (4 N C 128) rounded on the host, so that a sample's gradient at batch N with gscale = N is the same bits as that sample alone with
+// gscale = 1 (everything else in a row's arithmetic is per sample); its kernel does not read gscale.
+// A slot per grid: the 4-patch head may run beside a 16-patch call of another stream.
 // ---------------------------------------------------------------------------------------------------
-struct NegIdx { int r[16]; };
-static __device__ TfcRedSlot g_trip_slot, g_l1_slot;
+template <int GRID> struct NegIdx { int r[GRID * GRID]; };
+static __device__ TfcRedSlot g_trip_slot, g_trip4_slot, g_l1_slot;
 
+// sum of squares of a lane's pixels, in the expression shapes the two grids have always had (device code contracts a*b + c*d into one fma)
+template <int PPL> __device__ __forceinline__ float tfc_sq_sum(const float* d) {
+  if constexpr (PPL == 1) return d[0] * d[0];
+  else return d[0] * d[0] + d[1] * d[1];
+}
+
+// a lane's PPL adjacent pixels: one float, or one float2 (a single 8-byte access)
+template <int PPL> struct TfcPix;
+template <> struct TfcPix<1> { float v; __device__ __forceinline__ float& operator[](int) { return v; } };
+template <> struct TfcPix<2> { float2 v; __device__ __forceinline__ float& operator[](int i) { return i ? v.y : v.x; } };
+
+template <int GRID>
 __global__ void __launch_bounds__(256)
-tfc_triplet16_kernel(const float* __restrict__ fake, const float* __restrict__ real, const NegIdx neg, int N, int C,
-                     float margin, float eps, float* loss, float* dfake, float gscale) {
+tfc_patch_triplet_kernel(const float* __restrict__ fake, const float* __restrict__ real, const NegIdx<GRID> neg, int N, int C,
+                         float margin, float eps, float* loss, float* dfake, float coef, float gscale) {
+  static_assert(GRID == 2 || GRID == 4, "2 x 2 patches of 128 pixels or 4 x 4 patches of 64");
+  constexpr int LG = GRID == 4 ? 2 : 1, P = 256 / GRID, PPL = P / 64;          // log2 GRID, patch side, pixels per lane
+  typedef TfcPix<PPL> vec_t;
   __shared__ float red[4];
   const int lane = threadIdx.x & 63;
   const int w = threadIdx.x >> 6;
-  const long long nrows = (long long)N * C * 256 * 4;
-  const float scale = 1.f / (16.f * (float)N * (float)C * 64.f);
+  const long long nrows = (long long)N * C * 256 * GRID;
   float lsum = 0.f;
   // four rows per iteration: their loads are issued together (one dependent load -> reduce -> store chain per row leaves the
   // memory pipeline idle most of the time)
   constexpr int R = 4;
   const long long stride = (long long)gridDim.x * 4;
   for (long long row0 = (long long)blockIdx.x * 4 + w; row0 < nrows; row0 += stride * R) {
-    float a[R], p[R], ng[R];
+    vec_t a[R], p[R], ng[R];
     size_t ia[R];
     bool ok[R];
 #pragma unroll
@@ -36,104 +56,42 @@ tfc_triplet16_kernel(const float* __restrict__ fake, const float* __restrict__ r
       const long long row = row0 + r * stride;
       ok[r] = row < nrows;
       const long long rw = ok[r] ? row : row0;
-      const int kx = (int)(rw & 3);
-      const long long r2 = rw >> 2;
+      const int kx = (int)(rw & (GRID - 1));
+      const long long r2 = rw >> LG;
       const int y = (int)(r2 & 255);
       const long long nc = r2 >> 8;                              // n*C + c
-      const int k = (y >> 6) * 4 + kx;
+      const int k = (y / P) * GRID + kx;
       const int rk = neg.r[k];
       const size_t plane = (size_t)nc * 65536;
-      ia[r] = plane + (size_t)y * 256 + kx * 64 + lane;
-      const size_t in_ = plane + (size_t)((rk >> 2) * 64 + (y & 63)) * 256 + (rk & 3) * 64 + lane;
-      a[r] = fake[ia[r]]; p[r] = real[ia[r]]; ng[r] = real[in_];
+      ia[r] = plane + (size_t)y * 256 + kx * P + PPL * lane;
+      const size_t in_ = plane + (size_t)((rk >> LG) * P + (y & (P - 1))) * 256 + (rk & (GRID - 1)) * P + PPL * lane;
+      a[r] = *reinterpret_cast<const vec_t*>(fake + ia[r]);
+      p[r] = *reinterpret_cast<const vec_t*>(real + ia[r]);
+      ng[r] = *reinterpret_cast<const vec_t*>(real + in_);
     }
 #pragma unroll
     for (int r = 0; r < R; ++r) {
       if (!ok[r]) continue;                                      // wave-uniform
-      const float dp = a[r] - p[r] + eps, dn = a[r] - ng[r] + eps;
-      const float sp = wave_sum(dp * dp), sn = wave_sum(dn * dn);
+      float dp[PPL], dn[PPL];
+#pragma unroll
+      for (int i = 0; i < PPL; ++i) { dp[i] = a[r][i] - p[r][i] + eps; dn[i] = a[r][i] - ng[r][i] + eps; }
+      const float sp = wave_sum(tfc_sq_sum<PPL>(dp)), sn = wave_sum(tfc_sq_sum<PPL>(dn));
       const float dap = sqrtf(sp), dan = sqrtf(sn);
       const float hinge = margin + dap - dan;
+      vec_t g = {};
       if (hinge > 0.f) {
         lsum += hinge;                                           // identical on all lanes
-        if (dfake) {
-          const float g = (dap > 0.f ? dp / dap : 0.f) - (dan > 0.f ? dn / dan : 0.f);
-          dfake[ia[r]] = g * scale * gscale;
+#pragma unroll
+        for (int i = 0; i < PPL; ++i) {
+          g[i] = ((dap > 0.f ? dp[i] / dap : 0.f) - (dan > 0.f ? dn[i] / dan : 0.f)) * coef;
+          if constexpr (GRID == 4) g[i] *= gscale;
         }
-      } else if (dfake) {
-        dfake[ia[r]] = 0.f;
       }
+      if (dfake) *reinterpret_cast<vec_t*>(dfake + ia[r]) = g;
     }
   }
-  if (lane == 0) red[w] = lsum;
-  __syncthreads();
-  if (threadIdx.x == 0)
-    tfc_block_commit(&g_trip_slot, ((double)red[0] + (double)red[1] + (double)red[2] + (double)red[3]) / (16.0 * N * C * 64.0), loss, true);
-}
-
-// ---------------------------------------------------------------------------------------------------
-// 4-patch triplet (PATCH-4 / GLO-4, reference TFCGAN_multigpu_patchFFT.py:468-481).  Patch k = rows 128*(k/2).., cols 128*(k%2)..; first flat
-// index of patch k = 128*(k%2) + 32768*(k/2).  Same head as above with 128-pixel patch rows: one wave per row, two adjacent pixels per lane
-// (float2), total = (1/4) sum_k loss_k.  Row id = ((n*C + c)*256 + y)*2 + kx.  A slot of its own: the head may run beside a 16-patch call
-// of another stream.  The gradient's factor coef = gscale / (4 N C 128) is rounded ONCE, on the host: a sample's gradient at batch N with
-// gscale = N is then the same bits as that sample alone with gscale = 1 (everything else in a row's arithmetic is per sample).
-// ---------------------------------------------------------------------------------------------------
-struct NegIdx4 { int r[4]; };
-static __device__ TfcRedSlot g_trip4_slot;
-
-__global__ void __launch_bounds__(256)
-tfc_triplet4_kernel(const float* __restrict__ fake, const float* __restrict__ real, const NegIdx4 neg, int N, int C,
-                    float margin, float eps, float* loss, float* dfake, float coef) {
-  __shared__ float red[4];
-  const int lane = threadIdx.x & 63;
-  const int w = threadIdx.x >> 6;
-  const long long nrows = (long long)N * C * 256 * 2;
-  float lsum = 0.f;
-  constexpr int R = 4;                                           // rows in flight, as in the 16-patch kernel
-  const long long stride = (long long)gridDim.x * 4;
-  for (long long row0 = (long long)blockIdx.x * 4 + w; row0 < nrows; row0 += stride * R) {
-    float2 a[R], p[R], ng[R];
-    size_t ia[R];
-    bool ok[R];
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-      const long long row = row0 + r * stride;
-      ok[r] = row < nrows;
-      const long long rw = ok[r] ? row : row0;
-      const int kx = (int)(rw & 1);
-      const long long r2 = rw >> 1;
-      const int y = (int)(r2 & 255);
-      const long long nc = r2 >> 8;                              // n*C + c
-      const int k = (y >> 7) * 2 + kx;
-      const int rk = neg.r[k];
-      const size_t plane = (size_t)nc * 65536;
-      ia[r] = plane + (size_t)y * 256 + kx * 128 + 2 * lane;
-      const size_t in_ = plane + (size_t)((rk >> 1) * 128 + (y & 127)) * 256 + (rk & 1) * 128 + 2 * lane;
-      a[r] = *reinterpret_cast<const float2*>(fake + ia[r]);
-      p[r] = *reinterpret_cast<const float2*>(real + ia[r]);
-      ng[r] = *reinterpret_cast<const float2*>(real + in_);
-    }
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-      if (!ok[r]) continue;                                      // wave-uniform
-      const float dpx = a[r].x - p[r].x + eps, dpy = a[r].y - p[r].y + eps;
-      const float dnx = a[r].x - ng[r].x + eps, dny = a[r].y - ng[r].y + eps;
-      const float sp = wave_sum(dpx * dpx + dpy * dpy), sn = wave_sum(dnx * dnx + dny * dny);
-      const float dap = sqrtf(sp), dan = sqrtf(sn);
-      const float hinge = margin + dap - dan;
-      float2 g = make_float2(0.f, 0.f);
-      if (hinge > 0.f) {
-        lsum += hinge;                                           // identical on all lanes
-        g.x = ((dap > 0.f ? dpx / dap : 0.f) - (dan > 0.f ? dnx / dan : 0.f)) * coef;
-        g.y = ((dap > 0.f ? dpy / dap : 0.f) - (dan > 0.f ? dny / dan : 0.f)) * coef;
-      }
-      if (dfake) *reinterpret_cast<float2*>(dfake + ia[r]) = g;
-    }
-  }
-  if (lane == 0) red[w] = lsum;
-  __syncthreads();
-  if (threadIdx.x == 0)
-    tfc_block_commit(&g_trip4_slot, ((double)red[0] + (double)red[1] + (double)red[2] + (double)red[3]) / (4.0 * N * C * 128.0), loss, true);
+  const double tot = tfc_block_sum4(lsum, red);
+  if (threadIdx.x == 0) tfc_block_commit(GRID == 4 ? &g_trip_slot : &g_trip4_slot, tot / ((double)(GRID * GRID) * N * C * (double)P), loss, true);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -143,12 +101,27 @@ tfc_triplet4_kernel(const float* __restrict__ fake, const float* __restrict__ re
 // Direct DFT in LDS with an exact sincospi twiddle table: rows (real input) then columns. A workgroup owns one window
 // and a group of KG output columns, so S=256 (GLO-16) fits LDS as well as S=64 (PATCH-16) and S=128 (PATCH-4).
 // The four self-conjugate bins have Im forced to +0 (numpy's pocketfft yields exact zeros there).
-// window w -> (n = w / wins_per_img, k = w % wins_per_img), origin row (k / wins_x)*S, col (k % wins_x)*S.
+// The windows lie on a TfcWinGrid (tfc_desc.h); the luma and the window origin are shared with the FFT row pass below.
 // ---------------------------------------------------------------------------------------------------
+// first pixel (channel 0) of window w
+__device__ __forceinline__ const float* tfc_window_origin(const float* img, const TfcWinGrid& g, int w) {
+  const int n = w / g.wins_per_img, kw = w % g.wins_per_img;
+  return img + (size_t)n * g.bs + (size_t)(g.row0 + (kw / g.wins_x) * g.row_step) * g.rs + (kw % g.wins_x) * g.col_step;
+}
+// uint8 luma of the pixel whose channel-0 value is px[0] (channel stride cs; C = 1: the one channel three times)
+__device__ __forceinline__ int tfc_luma_u8(const float* px, long long cs, int C) {
+  int q[3];
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    const float v = px[(size_t)(C == 1 ? 0 : c) * cs] * 255.f;
+    q[c] = ((int)v) & 255;
+  }
+  return (19595 * q[0] + 38470 * q[1] + 7471 * q[2] + 32768) >> 16;
+}
+
 template <int S, int KG>
 __global__ void __launch_bounds__(256)
-tfc_spectrum_kernel(const float* __restrict__ img, long long bs, long long cs, int rs, int C, int wins_x, int wins_per_img,
-                    float* __restrict__ amp, float* __restrict__ pha, int shift) {
+tfc_spectrum_kernel(const float* __restrict__ img, const TfcWinGrid g, float* __restrict__ amp, float* __restrict__ pha, int shift) {
   constexpr int NB = S / 2 + 1;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   unsigned char* lum = smem;                                     // S*S bytes
@@ -156,17 +129,10 @@ tfc_spectrum_kernel(const float* __restrict__ img, long long bs, long long cs, i
   float* R = tw + 2 * S;                                         // S*KG*2 floats
   const int w = blockIdx.x;
   const int kx0 = blockIdx.y * KG;
-  const int n = w / wins_per_img, k = w % wins_per_img;
-  const int y0 = (k / wins_x) * S, x0 = (k % wins_x) * S;
-  const float* base = img + (size_t)n * bs + (size_t)y0 * rs + x0;
+  const float* base = tfc_window_origin(img, g, w);
   for (int i = threadIdx.x; i < S * S; i += 256) {
     const int y = i / S, x = i % S;
-    int q[3];
-    for (int c = 0; c < 3; ++c) {
-      const float v = base[(size_t)(C == 1 ? 0 : c) * cs + (size_t)y * rs + x] * 255.f;
-      q[c] = ((int)v) & 255;
-    }
-    lum[i] = (unsigned char)((19595 * q[0] + 38470 * q[1] + 7471 * q[2] + 32768) >> 16);
+    lum[i] = (unsigned char)tfc_luma_u8(base + (size_t)y * g.rs + x, g.cs, g.C);
   }
   for (int i = threadIdx.x; i < S; i += 256) {
     float sn, cn;
@@ -216,10 +182,8 @@ tfc_l1_sum_kernel(const float* __restrict__ a, const float* __restrict__ b, long
   __shared__ float red[4];
   float s = 0.f;
   for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) s += fabsf(a[i] - b[i]);
-  s = wave_sum(s);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) tfc_block_commit(&g_l1_slot, ((double)red[0] + (double)red[1] + (double)red[2] + (double)red[3]) * (double)scale, out);
+  const double tot = tfc_block_sum4(wave_sum(s), red);
+  if (threadIdx.x == 0) tfc_block_commit(&g_l1_slot, tot * (double)scale, out);
 }
 
 // Full-spectrum log-magnitude MSE of the evaluation scripts (Devcom_MagMSE.py:91-118: mean_squared_error(log|fftshift(fft2(a))|,
@@ -292,10 +256,8 @@ tfc_row_triplet_kernel(const float* __restrict__ a, const float* __restrict__ p,
     const float hinge = margin + sqrtf(sp) - sqrtf(sn);
     if (hinge > 0.f) lsum += hinge;
   }
-  if (lane == 0) red[w] = lsum;
-  __syncthreads();
-  if (threadIdx.x == 0)
-    tfc_block_commit(&g_rowtrip_slot, ((double)red[0] + (double)red[1] + (double)red[2] + (double)red[3]) / (double)rows, loss, true);
+  const double tot = tfc_block_sum4(lsum, red);
+  if (threadIdx.x == 0) tfc_block_commit(&g_rowtrip_slot, tot / (double)rows, loss, true);
 }
 hipError_t tfc_launch_vectorize_temps(const float* x, long long bs, int rs, int N, int H, int W, const float* lut, float* out, hipStream_t st) {
   const long long total = (long long)N * H * W;
@@ -313,29 +275,22 @@ hipError_t tfc_launch_row_triplet(const float* a, const float* p, const float* n
 }
 
 // ---------------------------------------------------------------------------------------------------
-hipError_t tfc_launch_triplet16(const float* fake, const float* real, const int* neg_idx, int N, int C, float margin, float eps,
-                                float* loss, float* dfake, float gscale, hipStream_t st) {
-  NegIdx ni;
-  for (int i = 0; i < 16; ++i) ni.r[i] = neg_idx[i];
-  long long nrows = (long long)N * C * 1024;
-  long long nb = (nrows + 3) / 4;
+template <int GRID>
+static void launch_patch_triplet(const float* fake, const float* real, const int* neg_idx, int N, int C, float margin, float eps, float* loss, float* dfake,
+                                 float coef, float gscale, hipStream_t st) {
+  NegIdx<GRID> ni;
+  for (int i = 0; i < GRID * GRID; ++i) ni.r[i] = neg_idx[i];
+  long long nb = ((long long)N * C * 256 * GRID + 3) / 4;        // rows / 4
   if (nb > 512) nb = 512;                                        // one double atomic + one ticket per workgroup on a single address
-  hipLaunchKernelGGL(tfc_triplet16_kernel, dim3((int)nb), dim3(256), 0, st, fake, real, ni, N, C, margin, eps, loss, dfake, gscale);
+  hipLaunchKernelGGL(tfc_patch_triplet_kernel<GRID>, dim3((int)nb), dim3(256), 0, st, fake, real, ni, N, C, margin, eps, loss, dfake, coef, gscale);
+}
+hipError_t tfc_launch_patch_triplet(int grid, const float* fake, const float* real, const int* neg_idx, int N, int C, float margin, float eps,
+                                    float* loss, float* dfake, float gscale, hipStream_t st) {
+  // the gradient's factor: see the kernel's header
+  if (grid == 4) launch_patch_triplet<4>(fake, real, neg_idx, N, C, margin, eps, loss, dfake, 1.f / (16.f * (float)N * (float)C * 64.f), gscale, st);
+  else launch_patch_triplet<2>(fake, real, neg_idx, N, C, margin, eps, loss, dfake, (float)((double)gscale / (4.0 * N * C * 128.0)), gscale, st);
   return hipGetLastError();
 }
-hipError_t tfc_launch_triplet4(const float* fake, const float* real, const int* neg_idx, int N, int C, float margin, float eps,
-                               float* loss, float* dfake, float gscale, hipStream_t st) {
-  NegIdx4 ni;
-  for (int i = 0; i < 4; ++i) ni.r[i] = neg_idx[i];
-  long long nrows = (long long)N * C * 512;
-  long long nb = (nrows + 3) / 4;
-  if (nb > 512) nb = 512;                                        // as above
-  const float coef = (float)((double)gscale / (4.0 * N * C * 128.0));
-  hipLaunchKernelGGL(tfc_triplet4_kernel, dim3((int)nb), dim3(256), 0, st, fake, real, ni, N, C, margin, eps, loss, dfake, coef);
-  return hipGetLastError();
-}
-
-// S in {64, 128, 256}; windows = N * wins_per_img; amp/pha: [windows][S][S/2+1]
 
 // ---------------------------------------------------------------------------------------------------
 // The same spectra by FFT (S = 64 or 256 = 4^3 / 4^4, or S = 128 = 4^3 * 2 for the 2x2 patch grid of PATCH-4): radix-4 Stockham autosort passes
@@ -343,7 +298,9 @@ hipError_t tfc_launch_triplet4(const float* fake, const float* real, const int* 
 // The direct DFT above costs S^2 MACs per output row; at S = 256 (GLO-16, G16:294-313) that was 1.04 ms per call = 15 % of the GLO-16 step.
 //   pass 1 (rows)   : a workgroup owns 32 consecutive rows of one window; two REAL rows are packed into one complex transform
 //                     (z = row0 + i row1;  R0[k] = (Z[k] + conj Z[S-k]) / 2,  R1[k] = (Z[k] - conj Z[S-k]) / 2i); the half spectra go through an
-//                     LDS tile to the scratch  T[window][kx][y]  (transposed, so that pass 2 reads whole columns as contiguous runs);
+//                     LDS tile to the scratch  T[window][kx][y], y < H  (transposed, so that pass 2 reads whole columns as contiguous runs).
+//                     The window has H rows, a run-time value: H = S for the square spectra; at S = 256 any H in 2 .. 256 (the rectangular
+//                     windows below), where row pairs past the last row are skipped and the second row of the last pair of an odd H is zeros;
 //   pass 2 (columns): complex transforms of CB columns per workgroup; amp = |F|, pha = atan2(Im, Re) (Im forced to +0 at the four self-conjugate
 //                     bins, as the direct kernel does), staged in LDS and stored with the optional fftshift of both axes.
 // One transform is carried by S/4 lanes (one radix-4 butterfly each per pass): a wave runs one 256-point, two 128-point or four 64-point transforms
@@ -391,41 +348,45 @@ __device__ __forceinline__ float2* tfc_fft_r4(float2* b0, float2* b1, const floa
   return b0;
 }
 
+// tw[i] = exp(-2 pi i * i / S), i < S, from the exact sincospi; every thread of the workgroup calls it, the caller synchronises
 template <int S>
+__device__ __forceinline__ void tfc_fill_twiddles(float2* tw) {
+  for (int i = threadIdx.x; i < S; i += 256) {
+    float sn, cn;
+    sincospif(2.f * (float)i / (float)S, &sn, &cn);
+    tw[i] = make_float2(cn, -sn);
+  }
+}
+
+template <int S, bool RAGGED>
 __global__ void __launch_bounds__(256)
-tfc_fft_rows_kernel(const float* __restrict__ img, long long bs, long long cs, int rs, int C, int wins_x, int wins_per_img, float2* __restrict__ T) {
+tfc_fft_rows_kernel(const float* __restrict__ img, const TfcWinGrid g, int H, float2* __restrict__ T) {
   constexpr int NB = S / 2 + 1, G = S / 4, FPW = 64 / G, RPB = 32;          // lanes per transform, transforms per wave at a time, rows per workgroup
+  // RAGGED = false: PRECONDITION H even and a multiple of 32 (the square windows, H = S: tfc_launch_spectrum passes nothing else); every row pair of
+  // every row block is read and transformed without a check.  RAGGED = true: any H; row pairs past H are skipped.  A skip jumps over the wave barriers
+  // of tfc_fft_r4, so it must be wave-uniform: ONE transform per wave, S = 256 only (the other sizes carry 4 or 2 transforms per wave).
+  static_assert(!RAGGED || FPW == 1, "a ragged row count needs one transform per wave");
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   float2* tw = reinterpret_cast<float2*>(smem);                   // [S]
   float2* wbuf = tw + S;                                          // [4 waves][2][FPW][S]
   float2* tile = wbuf + 4 * 2 * FPW * S;                          // [NB][RPB]
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int f = lane / G, j = lane % G;
-  const int w = blockIdx.x / (S / RPB), y0 = (blockIdx.x % (S / RPB)) * RPB;
-  const int n = w / wins_per_img, kw = w % wins_per_img;
-  const float* base = img + (size_t)n * bs + (size_t)((kw / wins_x) * S) * rs + (kw % wins_x) * S;
-  for (int i = tid; i < S; i += 256) {
-    float sn, cn;
-    sincospif(2.f * (float)i / (float)S, &sn, &cn);
-    tw[i] = make_float2(cn, -sn);
-  }
+  const int nrb = (H + RPB - 1) / RPB;                            // row blocks per window; the last one is ragged when H % 32 != 0
+  const int w = blockIdx.x / nrb, y0 = (blockIdx.x % nrb) * RPB;
+  const float* base = tfc_window_origin(img, g, w);
+  tfc_fill_twiddles<S>(tw);
   __syncthreads();
   float2* b0 = wbuf + ((wave * 2 + 0) * FPW + f) * S;
   float2* b1 = wbuf + ((wave * 2 + 1) * FPW + f) * S;
-  auto luma = [&](int y, int x) -> float {
-    int q[3];
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      const float v = base[(size_t)(C == 1 ? 0 : c) * cs + (size_t)y * rs + x] * 255.f;
-      q[c] = ((int)v) & 255;
-    }
-    return (float)((19595 * q[0] + 38470 * q[1] + 7471 * q[2] + 32768) >> 16);
-  };
+  auto luma = [&](int y, int x) -> float { return (float)tfc_luma_u8(base + (size_t)y * g.rs + x, g.cs, g.C); };
   for (int it = 0; it < RPB / 2 / (4 * FPW); ++it) {
     const int pr = (it * 4 + wave) * FPW + f;                     // row pair of this workgroup (0 .. 15)
     const int ya = y0 + 2 * pr;
+    if (RAGGED && ya >= H) continue;                              // wave-uniform: the whole transform lies past the window
+    const bool two = !RAGGED || ya + 1 < H;                       // odd H: the last row is paired with zeros
 #pragma unroll
-    for (int r = 0; r < 4; ++r) b0[j + r * G] = make_float2(luma(ya, j + r * G), luma(ya + 1, j + r * G));
+    for (int r = 0; r < 4; ++r) b0[j + r * G] = make_float2(luma(ya, j + r * G), two ? luma(ya + 1, j + r * G) : 0.f);
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     __builtin_amdgcn_wave_barrier();
     const float2* Z = tfc_fft_r4<S>(b0, b1, tw, j);
@@ -438,10 +399,10 @@ tfc_fft_rows_kernel(const float* __restrict__ img, long long bs, long long cs, i
     __builtin_amdgcn_wave_barrier();
   }
   __syncthreads();
-  float2* Tw = T + (size_t)w * NB * S;
+  float2* Tw = T + (size_t)w * NB * H;
   for (int i = tid; i < NB * RPB; i += 256) {
-    const int kx = i / RPB, yy = i % RPB;
-    Tw[(size_t)kx * S + y0 + yy] = tile[i];
+    const int kx = i / RPB, y = y0 + i % RPB;
+    if (!RAGGED || y < H) Tw[(size_t)kx * H + y] = tile[i];       // ragged: tile rows past H were never written and are not read
   }
 }
 
@@ -458,11 +419,7 @@ tfc_fft_cols_kernel(const float2* __restrict__ T, float* __restrict__ amp, float
   const int f = lane / G, j = lane % G;
   constexpr int NCB = (NB + CB - 1) / CB;
   const int w = blockIdx.x / NCB, c0 = (blockIdx.x % NCB) * CB;
-  for (int i = tid; i < S; i += 256) {
-    float sn, cn;
-    sincospif(2.f * (float)i / (float)S, &sn, &cn);
-    tw[i] = make_float2(cn, -sn);
-  }
+  tfc_fill_twiddles<S>(tw);
   __syncthreads();
   float2* b0 = wbuf + ((wave * 2 + 0) * FPW + f) * S;
   float2* b1 = wbuf + ((wave * 2 + 1) * FPW + f) * S;
@@ -499,46 +456,6 @@ tfc_fft_cols_kernel(const float2* __restrict__ T, float* __restrict__ amp, float
   }
 }
 
-size_t tfc_fft_ws_bytes(int S, int nwin) { return (size_t)nwin * (S / 2 + 1) * S * sizeof(float2); }
-template <int S, int CB>
-static hipError_t launch_fft_t(const float* img, long long bs, long long cs, int rs, int C, int wins_x, int wins_per_img, int nwin, float* amp,
-                               float* pha, int shift, void* ws, hipStream_t st) {
-  constexpr int NB = S / 2 + 1, FPW = 64 / (S / 4);
-  static_assert(CB % (4 * FPW) == 0, "a workgroup's four waves transform 4 * FPW columns at a time");
-  const size_t lds_r = (size_t)(S + 4 * 2 * FPW * S + NB * 32) * sizeof(float2);
-  const size_t lds_c = (size_t)(S + 4 * 2 * FPW * S) * sizeof(float2) + (size_t)2 * S * CB * sizeof(float);
-  hipLaunchKernelGGL((tfc_fft_rows_kernel<S>), dim3(nwin * (S / 32)), dim3(256), lds_r, st, img, bs, cs, rs, C, wins_x, wins_per_img, (float2*)ws);
-  hipLaunchKernelGGL((tfc_fft_cols_kernel<S, CB>), dim3(nwin * ((NB + CB - 1) / CB)), dim3(256), lds_c, st, (const float2*)ws, amp, pha, shift);
-  return hipGetLastError();
-}
-hipError_t tfc_launch_spectrum(const float* img, long long bs, long long cs, int rs, int C, int S, int wins_x, int wins_per_img,
-                               int nwin, float* amp, float* pha, int shift, void* ws, hipStream_t st) {
-  if (ws && S == 64) return launch_fft_t<64, 16>(img, bs, cs, rs, C, wins_x, wins_per_img, nwin, amp, pha, shift, ws, st);
-  if (ws && S == 128) return launch_fft_t<128, 8>(img, bs, cs, rs, C, wins_x, wins_per_img, nwin, amp, pha, shift, ws, st);
-  if (ws && S == 256) return launch_fft_t<256, 8>(img, bs, cs, rs, C, wins_x, wins_per_img, nwin, amp, pha, shift, ws, st);
-  if (S == 64) {                                                  // no scratch given: direct DFT (also the independent cross-check of the FFT path)
-    constexpr int KG = 33;
-    const size_t lds = 64 * 64 + 2 * 64 * 4 + 64 * KG * 2 * 4;
-    hipLaunchKernelGGL((tfc_spectrum_kernel<64, KG>), dim3(nwin, 1), dim3(256), lds, st, img, bs, cs, rs, C, wins_x, wins_per_img, amp, pha, shift);
-  } else if (S == 128) {                                          // two column groups (33 + 32 of the 65 columns); 51 200 B of LDS
-    constexpr int KG = 33;
-    const size_t lds = 128 * 128 + 2 * 128 * 4 + 128 * KG * 2 * 4;
-    hipLaunchKernelGGL((tfc_spectrum_kernel<128, KG>), dim3(nwin, (65 + KG - 1) / KG), dim3(256), lds, st, img, bs, cs, rs, C, wins_x, wins_per_img, amp, pha, shift);
-  } else if (S == 256) {
-    constexpr int KG = 16;
-    const size_t lds = 256 * 256 + 2 * 256 * 4 + 256 * KG * 2 * 4;
-    static bool attr_set = false;                                 // > 64 KiB of dynamic LDS needs an explicit opt-in (once)
-    if (!attr_set) {
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&tfc_spectrum_kernel<256, KG>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      if (e != hipSuccess) return e;
-      attr_set = true;
-    }
-    hipLaunchKernelGGL((tfc_spectrum_kernel<256, KG>), dim3(nwin, (129 + KG - 1) / KG), dim3(256), lds, st, img, bs, cs, rs, C, wins_x, wins_per_img, amp, pha, shift);
-  } else {
-    return hipErrorInvalidValue;
-  }
-  return hipGetLastError();
-}
 hipError_t tfc_launch_l1_sum(const float* a, const float* b, long long n, float scale, float* out, hipStream_t st) {
   long long nb = (n + 255) / 256;
   if (nb > 512) nb = 512;
@@ -550,9 +467,8 @@ hipError_t tfc_launch_l1_sum(const float* a, const float* b, long long n, float 
 // Rectangular windows: H rows x 256 columns, H a run-time value in 2 .. 256 (the regional FFT loss of TFCGAN_multigpu_patchFFT_withregion_FFT.py:353-401
 // and ..._withregion_FFT_KL.py:357-420 takes the spectra of rows 0..99 and 100..199, 100 x 129 bins each).  Window k of image n starts at image
 // row row0 + k * row_step, column 0.  Same luma, same rfft2, same amp / atan2 as above; amp / pha: [windows][H][129].
-//   pass 1 (rows)   : tfc_fft_rows_kernel<256> with a run-time row count: a workgroup owns 32 consecutive rows, a wave one pair of real rows per
-//                     256-point transform; pairs past the last row are skipped, the second row of the last pair of an odd H is zeros.  The half spectra
-//                     go to the scratch T[window][kx][y] with y < H.
+//   pass 1 (rows)   : tfc_fft_rows_kernel<256> with H rows: a workgroup owns 32 consecutive rows, a wave one pair of real rows per 256-point
+//                     transform.  The half spectra go to the scratch T[window][kx][y] with y < H.
 //   pass 2 (columns): H = 100 = 4 * 5 * 5 is no 4^m or 2 * 4^m, so each of the 129 columns takes a DIRECT H-point DFT from an exact table
 //                     exp(-2 pi i m / H), m < H (sincospi in double, rounded once), indexed by the integer (ky * y) mod H that is carried along
 //                     as t += ky.  A workgroup owns RECT_CB = 13 columns of one window (129 = 9 * 13 + 12), staged in LDS as col[y][column]; a lane
@@ -565,62 +481,6 @@ hipError_t tfc_launch_l1_sum(const float* a, const float* b, long long n, float 
 //   Im is forced to +0 at the self-conjugate bins kx in {0, 128} x (ky = 0, and ky = H/2 for even H).
 //   fftshift on store: ky -> (ky + H/2) % H (numpy's shift for even and odd H), kx -> (kx + 64) % 129.
 // ---------------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(256)
-tfc_fft_rect_rows_kernel(const float* __restrict__ img, long long bs, long long cs, int rs, int C, int H, int row0, int row_step, int wins_per_img,
-                         float2* __restrict__ T) {
-  constexpr int S = 256, NB = S / 2 + 1, G = S / 4, RPB = 32;     // one transform per wave (G = 64 lanes)
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  float2* tw = reinterpret_cast<float2*>(smem);                   // [S]
-  float2* wbuf = tw + S;                                          // [4 waves][2][S]
-  float2* tile = wbuf + 4 * 2 * S;                                // [NB][RPB]
-  const int tid = threadIdx.x, j = tid & 63, wave = tid >> 6;
-  const int nrb = (H + RPB - 1) / RPB;                            // row blocks per window; the last one is ragged when H % 32 != 0
-  const int w = blockIdx.x / nrb, y0 = (blockIdx.x % nrb) * RPB;
-  const int n = w / wins_per_img, kw = w % wins_per_img;
-  const float* base = img + (size_t)n * bs + (size_t)(row0 + kw * row_step) * rs;
-  for (int i = tid; i < S; i += 256) {
-    float sn, cn;
-    sincospif(2.f * (float)i / (float)S, &sn, &cn);
-    tw[i] = make_float2(cn, -sn);
-  }
-  __syncthreads();
-  float2* b0 = wbuf + (wave * 2 + 0) * S;
-  float2* b1 = wbuf + (wave * 2 + 1) * S;
-  auto luma = [&](int y, int x) -> float {
-    int q[3];
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      const float v = base[(size_t)(C == 1 ? 0 : c) * cs + (size_t)y * rs + x] * 255.f;
-      q[c] = ((int)v) & 255;
-    }
-    return (float)((19595 * q[0] + 38470 * q[1] + 7471 * q[2] + 32768) >> 16);
-  };
-  for (int it = 0; it < RPB / 2 / 4; ++it) {
-    const int pr = it * 4 + wave;                                 // row pair of this workgroup (0 .. 15)
-    const int ya = y0 + 2 * pr;
-    if (ya >= H) continue;                                        // wave-uniform: the whole transform lies past the window
-    const bool two = ya + 1 < H;                                  // odd H: the last row is paired with zeros
-#pragma unroll
-    for (int r = 0; r < 4; ++r) b0[j + r * G] = make_float2(luma(ya, j + r * G), two ? luma(ya + 1, j + r * G) : 0.f);
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    const float2* Z = tfc_fft_r4<S>(b0, b1, tw, j);
-    for (int k = j; k < NB; k += G) {
-      const float2 a = Z[k], b = Z[(S - k) & (S - 1)];
-      tile[k * RPB + 2 * pr] = make_float2(0.5f * (a.x + b.x), 0.5f * (a.y - b.y));
-      tile[k * RPB + 2 * pr + 1] = make_float2(0.5f * (a.y + b.y), 0.5f * (b.x - a.x));
-    }
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-  }
-  __syncthreads();
-  float2* Tw = T + (size_t)w * NB * H;
-  for (int i = tid; i < NB * RPB; i += 256) {
-    const int kx = i / RPB, y = y0 + i % RPB;
-    if (y < H) Tw[(size_t)kx * H + y] = tile[i];                  // tile rows past H were never written and are not read
-  }
-}
-
 constexpr int RECT_CB = 13;
 
 __global__ void __launch_bounds__(256)
@@ -679,15 +539,59 @@ tfc_dft_rect_cols_kernel(const float2* __restrict__ T, int H, float* __restrict_
   }
 }
 
-size_t tfc_fft_rect_ws_bytes(int H, int nwin) { return (size_t)nwin * 129 * H * sizeof(float2); }
-hipError_t tfc_launch_spectrum_rect(const float* img, long long bs, long long cs, int rs, int C, int H, int row0, int row_step, int wins_per_img,
-                                    int nwin, float* amp, float* pha, int shift, void* ws, hipStream_t st) {
-  constexpr int NB = 129;
-  const size_t lds_r = (size_t)(256 + 4 * 2 * 256 + NB * 32) * sizeof(float2);
-  const size_t lds_c = (size_t)(H + H * RECT_CB + RECT_CB) * sizeof(float2);          // 28 776 B at H = 256
-  hipLaunchKernelGGL(tfc_fft_rect_rows_kernel, dim3(nwin * ((H + 31) / 32)), dim3(256), lds_r, st, img, bs, cs, rs, C, H, row0, row_step, wins_per_img,
-                     (float2*)ws);
-  hipLaunchKernelGGL(tfc_dft_rect_cols_kernel, dim3(nwin * ((NB + RECT_CB - 1) / RECT_CB)), dim3(256), lds_c, st, (const float2*)ws, H, amp, pha, shift);
+// ---------------------------------------------------------------------------------------------------
+// Spectra of nwin windows of H rows x S columns on the grid g; amp / pha: [nwin][H][S/2+1].  S in {64, 128, 256}.
+//   rect = false: square windows (H = S): row FFT + column FFT through the scratch ws, or, with no scratch, the direct DFT;
+//   rect = true : S = 256, H in 2 .. 256: row FFT + direct H-point column DFT through ws.
+// ws holds T[nwin][S/2+1][H] (tfc_fft_ws_bytes).
+// ---------------------------------------------------------------------------------------------------
+size_t tfc_fft_ws_bytes(int S, int H, int nwin) { return (size_t)nwin * (S / 2 + 1) * H * sizeof(float2); }
+template <int S, bool RAGGED>
+static void launch_fft_rows(const float* img, const TfcWinGrid& g, int H, int nwin, void* ws, hipStream_t st) {
+  constexpr int NB = S / 2 + 1, FPW = 64 / (S / 4);
+  const size_t lds = (size_t)(S + 4 * 2 * FPW * S + NB * 32) * sizeof(float2);
+  hipLaunchKernelGGL((tfc_fft_rows_kernel<S, RAGGED>), dim3(nwin * ((H + 31) / 32)), dim3(256), lds, st, img, g, H, (float2*)ws);
+}
+template <int S, int CB>
+static void launch_fft_cols(int nwin, float* amp, float* pha, int shift, void* ws, hipStream_t st) {
+  constexpr int NB = S / 2 + 1, FPW = 64 / (S / 4);
+  static_assert(CB % (4 * FPW) == 0, "a workgroup's four waves transform 4 * FPW columns at a time");
+  const size_t lds = (size_t)(S + 4 * 2 * FPW * S) * sizeof(float2) + (size_t)2 * S * CB * sizeof(float);
+  hipLaunchKernelGGL((tfc_fft_cols_kernel<S, CB>), dim3(nwin * ((NB + CB - 1) / CB)), dim3(256), lds, st, (const float2*)ws, amp, pha, shift);
+}
+template <int S, int KG>
+static hipError_t launch_direct(const float* img, const TfcWinGrid& g, int nwin, float* amp, float* pha, int shift, hipStream_t st) {
+  constexpr int NB = S / 2 + 1;
+  constexpr size_t lds = S * S + 2 * S * 4 + S * KG * 2 * 4;     // 51 200 B at <128, 33>
+  if constexpr (lds > 65536) {                                   // > 64 KiB of dynamic LDS needs an explicit opt-in (once)
+    static bool attr_set = false;
+    if (!attr_set) {
+      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&tfc_spectrum_kernel<S, KG>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+      if (e != hipSuccess) return e;
+      attr_set = true;
+    }
+  }
+  hipLaunchKernelGGL((tfc_spectrum_kernel<S, KG>), dim3(nwin, (NB + KG - 1) / KG), dim3(256), lds, st, img, g, amp, pha, shift);
+  return hipSuccess;
+}
+hipError_t tfc_launch_spectrum(const float* img, const TfcWinGrid& g, int S, int H, bool rect, int nwin, float* amp, float* pha, int shift, void* ws,
+                               hipStream_t st) {
+  if (rect ? (S != 256 || !ws) : (H != S)) return hipErrorInvalidValue;
+  if (rect) {
+    const size_t lds_c = (size_t)(H + H * RECT_CB + RECT_CB) * sizeof(float2);          // 28 776 B at H = 256
+    launch_fft_rows<256, true>(img, g, H, nwin, ws, st);
+    hipLaunchKernelGGL(tfc_dft_rect_cols_kernel, dim3(nwin * ((129 + RECT_CB - 1) / RECT_CB)), dim3(256), lds_c, st, (const float2*)ws, H, amp, pha, shift);
+  } else if (ws) {
+    if (S == 64) { launch_fft_rows<64, false>(img, g, H, nwin, ws, st); launch_fft_cols<64, 16>(nwin, amp, pha, shift, ws, st); }
+    else if (S == 128) { launch_fft_rows<128, false>(img, g, H, nwin, ws, st); launch_fft_cols<128, 8>(nwin, amp, pha, shift, ws, st); }
+    else if (S == 256) { launch_fft_rows<256, false>(img, g, H, nwin, ws, st); launch_fft_cols<256, 8>(nwin, amp, pha, shift, ws, st); }
+    else return hipErrorInvalidValue;
+  } else {                                                        // no scratch given: direct DFT (also the independent cross-check of the FFT path)
+    hipError_t e = S == 64 ? launch_direct<64, 33>(img, g, nwin, amp, pha, shift, st)
+                 : S == 128 ? launch_direct<128, 33>(img, g, nwin, amp, pha, shift, st)      // two column groups (33 + 32 of the 65 columns)
+                 : S == 256 ? launch_direct<256, 16>(img, g, nwin, amp, pha, shift, st) : hipErrorInvalidValue;
+    if (e != hipSuccess) return e;
+  }
   return hipGetLastError();
 }
 
@@ -732,7 +636,7 @@ tfc_batch_kl_kernel(const float* __restrict__ af, const float* __restrict__ pf, 
       }
     }
   }
-  sa = wave_sum(sa); sp = wave_sum(sp);
+  sa = wave_sum(sa); sp = wave_sum(sp);                           // two sums behind ONE barrier: tfc_block_sum4 would cost a second one
   if ((threadIdx.x & 63) == 0) { red[0][threadIdx.x >> 6] = sa; red[1][threadIdx.x >> 6] = sp; }
   __syncthreads();
   if (threadIdx.x == 0) {

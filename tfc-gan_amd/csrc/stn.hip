@@ -190,9 +190,8 @@ tfc_row_triplet_grad_kernel(const float* __restrict__ a, const float* __restrict
       }
     }
   }
-  if (lane == 0) red[wv] = lsum;
-  __syncthreads();
-  if (threadIdx.x == 0) tfc_block_commit(&g_rowtrip2_slot, ((double)red[0] + (double)red[1] + (double)red[2] + (double)red[3]) / (double)rows, loss);
+  const double tot = tfc_block_sum4(lsum, red);
+  if (threadIdx.x == 0) tfc_block_commit(&g_rowtrip2_slot, tot / (double)rows, loss);
 }
 
 hipError_t tfc_launch_affine_warp_fwd(const float* src, const float* theta, float* out, int N, int C, int H, int W, hipStream_t st) {

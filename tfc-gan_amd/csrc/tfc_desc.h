@@ -123,6 +123,10 @@ hipError_t tfc_launch_part_reduce(const float* part, float* out, int G, int npar
 // (tfc_wgrad_reduce_fin_kernel) it sets `done` and the caller skips the separate finish pass
 struct TfcWgradFin { float* grad; long long sn, sc; int accumulate; bool done; };
 
+// Spectrum windows (losses.hip): the strides of an NCHW fp32 image (unit stride on W, C = 1 or 3) and the window grid on it. Window w is window
+// kw = w % wins_per_img of image w / wins_per_img; its first pixel is row row0 + (kw / wins_x) * row_step, column (kw % wins_x) * col_step.
+struct TfcWinGrid { long long bs, cs; int rs, C; int row0, row_step, col_step, wins_x, wins_per_img; };
+
 // ---- input pipeline (input.hip): resampling plan of one (H, W) file geometry -> 2 x (out x out). The plan buffer starts with this header,
 // followed by the int tables the offsets (in ints from the start of the buffer) point at: bounds[out][2] = {first source index, tap count},
 // coef[out][ksize] = taps in 22-bit fixed point.

@@ -166,6 +166,18 @@ def fft_components(thermal_tensor, patch=True):
     return amp.reshape(N, 1, S, S // 2 + 1), pha.reshape(N, 1, S, S // 2 + 1)
 
 
+def _spectral_l1(spectrum, fake, real, scale, out=None):
+    """The spectral L1 loss on one window grid: `spectrum(img)` -> (amp, pha) of every window of a batch. Adds scale * sum |amp_fake - amp_real| to
+    out[0] and the same of the phases to out[1] (`out`: two zeros unless given) and returns out."""
+    af, pf = spectrum(fake.detach())
+    ar, pr = spectrum(real.detach())
+    if out is None:
+        out = torch.zeros(2, dtype=torch.float32, device=fake.device)
+    ops.l1_sum(af, ar, scale, out[0:1])
+    ops.l1_sum(pf, pr, scale, out[1:2])
+    return out
+
+
 def patch_fft_loss(fake_B, real_B, patches=16):
     """loss_FFT of calculate_ffts on whole images: 0.5 * (mean_k L1(amp) + mean_k L1(phase)) over the 16 patches (patches=4: the four
     128 x 128 patches with 128 x 65 spectra, 4P:499-511). Carries no gradient, exactly like the reference (tensor -> PIL -> numpy round trip,
@@ -173,24 +185,15 @@ def patch_fft_loss(fake_B, real_B, patches=16):
     assert patches in (4, 16)
     N = fake_B.shape[0]
     S, g = (64, 4) if patches == 16 else (128, 2)
-    af, pf = ops.fft_spectrum(fake_B.detach(), S, g, g, shift=False)
-    ar, pr = ops.fft_spectrum(real_B.detach(), S, g, g, shift=False)
-    out = torch.zeros(3, dtype=torch.float32, device=fake_B.device)
     scale = 1.0 / (float(patches) * N * S * (S // 2 + 1))
-    ops.l1_sum(af, ar, scale, out[0:1])
-    ops.l1_sum(pf, pr, scale, out[1:2])
+    out = _spectral_l1(lambda img: ops.fft_spectrum(img, S, g, g, shift=False), fake_B, real_B, scale)
     return 0.5 * (out[0] + out[1]), out[0], out[1]
 
 
 def global_fft_loss(fake_B, real_B):
     """GLO-16 variant (TFCGAN_multigpu_globalFFT_16P.py:294-313, :524-529): rfft2 of the whole 256x256 image."""
     N = fake_B.shape[0]
-    af, pf = ops.fft_spectrum(fake_B.detach(), 256, 1, 1, shift=False)
-    ar, pr = ops.fft_spectrum(real_B.detach(), 256, 1, 1, shift=False)
-    out = torch.zeros(2, dtype=torch.float32, device=fake_B.device)
-    scale = 1.0 / (N * 256 * 129)
-    ops.l1_sum(af, ar, scale, out[0:1])
-    ops.l1_sum(pf, pr, scale, out[1:2])
+    out = _spectral_l1(lambda img: ops.fft_spectrum(img, 256, 1, 1, shift=False), fake_B, real_B, 1.0 / (N * 256 * 129))
     return 0.5 * (out[0] + out[1]), out[0], out[1]
 
 
@@ -221,14 +224,13 @@ def regional_fft_loss(fake_B, real_B, kind="l1"):
     ops.require_gpu(fake_B, real_B)
     N = fake_B.shape[0]
     (_, H), step = REGIONS["hair"], REGIONS["eyes"][0]
-    af, pf = ops.fft_spectrum_rect(fake_B.detach(), H, 0, step, 2, shift=False)      # [N*2][100][129]: sample n = windows 2n (hair), 2n+1 (eyes)
-    ar, pr = ops.fft_spectrum_rect(real_B.detach(), H, 0, step, 2, shift=False)
-    out = torch.zeros(2, dtype=torch.float32, device=fake_B.device)
+    spectrum = lambda img: ops.fft_spectrum_rect(img, H, 0, step, 2, shift=False)    # noqa: E731  [N*2][100][129]: sample n = windows 2n (hair), 2n+1 (eyes)
     scale = 1.0 / (N * H * 129)                                    # the mean of one region; the two regions add
     if kind == "l1":
-        ops.l1_sum(af, ar, scale, out[0:1])
-        ops.l1_sum(pf, pr, scale, out[1:2])
+        out = _spectral_l1(spectrum, fake_B, real_B, scale)
     else:
+        (af, pf), (ar, _) = spectrum(fake_B.detach()), spectrum(real_B.detach())
+        out = torch.zeros(2, dtype=torch.float32, device=fake_B.device)
         ops.batch_kl_sum(af.reshape(N, -1), pf.reshape(N, -1), ar.reshape(N, -1), scale, out)
     return 0.5 * (out[0] + out[1]), out[0], out[1]
 
@@ -256,10 +258,7 @@ def calculate_ffts(*patches):
     out = torch.zeros(2, dtype=torch.float32, device=dev)
     scale = 1.0 / (float(P) * N * S * (S // 2 + 1))
     for k in range(P):
-        af, pf = ops.fft_spectrum(patches[k].detach(), S, 1, 1, shift=True)
-        ar, pr = ops.fft_spectrum(patches[P + k].detach(), S, 1, 1, shift=True)
-        ops.l1_sum(af, ar, scale, out[0:1])
-        ops.l1_sum(pf, pr, scale, out[1:2])
+        _spectral_l1(lambda img: ops.fft_spectrum(img, S, 1, 1, shift=True), patches[k], patches[P + k], scale, out)
     return 0.5 * (out[0] + out[1])
 
 

@@ -429,22 +429,14 @@ def spectral_norm_bwd(G, W, u, v, sigma2, gout, accumulate=False):
 
 # ---- loss heads -----------------------------------------------------------------------------------------------
 def patch16_triplet(fake, real, neg_idx, want_grad=True, gscale=1.0):
-    """fake/real: fp32 NCHW [N,C,256,256]; neg_idx: 16 ints. Returns (loss[1], dfake or None)."""
-    require_gpu(fake, real)
-    assert fake.shape == real.shape and fake.shape[2:] == (256, 256), "make_16_patches hard-codes 256x256 (reference :233-251)"
-    fake = fake.contiguous().float()
-    real = real.contiguous().float()
-    N, C = fake.shape[:2]
-    loss = torch.empty(1, dtype=torch.float32, device=fake.device)
-    dfake = torch.empty_like(fake) if want_grad else None
-    idx = (ctypes.c_int * 16)(*[int(i) for i in neg_idx])
-    check(lib().tfc_patch16_triplet(stream_ptr(), _p(fake), _p(real), idx, N, C, _p(loss), _p(dfake), gscale), "tfc_patch16_triplet")
-    return loss, dfake
+    """fake/real: fp32 NCHW [N,C,256,256]; neg_idx: 16 ints. Returns (loss[1], dfake or None). The 4x4 grid of patch_triplet."""
+    assert len(neg_idx) == 16, "make_16_patches: 16 negative indices (reference :233-251)"
+    return patch_triplet(fake, real, neg_idx, want_grad, gscale)
 
 
 def patch_triplet(fake, real, neg_idx, want_grad=True, gscale=1.0):
     """The triplet head on a 2x2 or 4x4 patch grid, inferred from len(neg_idx) (4: PATCH-4 / GLO-4, reference TFCGAN_multigpu_patchFFT.py:468-481;
-    16: patch16_triplet, same bits). fake/real: fp32 NCHW [N,C,256,256]. Returns (loss[1], dfake or None)."""
+    16: PATCH-16, reference TFCGAN_multigpu_patchFFT_16P.py:558-583). fake/real: fp32 NCHW [N,C,256,256]. Returns (loss[1], dfake or None)."""
     n = len(neg_idx)
     if n not in (4, 16):
         raise _lib.TfcError(f"patch_triplet: {n} negative indices (the patch grid has 4 or 16 patches)")
@@ -463,26 +455,35 @@ def patch_triplet(fake, real, neg_idx, want_grad=True, gscale=1.0):
 _FFT_WS = {}
 
 
-def fft_spectrum(img, S, wins_x, wins_y, shift=True, direct=False):
-    """img: fp32 [N,C,H,W] (any strides on N/C/H, unit stride on W). Returns amp, pha [N*wins_x*wins_y, S, S//2+1].
-    direct=True: the direct-DFT kernel (no scratch) instead of the LDS radix-4 FFT -- the tests cross-check the two."""
+def _image_f32(img):
+    """the image as the spectrum / temperature kernels read it: fp32, unit stride on W (any strides on N/C/H)"""
     require_gpu(img)
     if img.dtype != torch.float32:
         img = img.float()
     if img.stride(3) != 1:
         img = img.contiguous()
+    return img
+
+
+def _fft_scratch(device, need):
+    """at least `need` bytes of row-pass scratch, one buffer per (device, stream): calls on a stream are ordered"""
+    key = (device, torch.cuda.current_stream().cuda_stream)
+    ws = _FFT_WS.get(key)
+    if ws is None or ws.numel() < need:
+        ws = _FFT_WS[key] = torch.empty(need, dtype=torch.uint8, device=device)
+    return ws
+
+
+def fft_spectrum(img, S, wins_x, wins_y, shift=True, direct=False):
+    """img: fp32 [N,C,H,W] (any strides on N/C/H, unit stride on W). Returns amp, pha [N*wins_x*wins_y, S, S//2+1].
+    direct=True: the direct-DFT kernel (no scratch) instead of the LDS radix-4 FFT -- the tests cross-check the two."""
+    img = _image_f32(img)
     N, C = img.shape[:2]
     assert img.shape[2] >= wins_y * S and img.shape[3] >= wins_x * S
     nwin = N * wins_x * wins_y
     amp = torch.empty((nwin, S, S // 2 + 1), dtype=torch.float32, device=img.device)
     pha = torch.empty_like(amp)
-    ws = None
-    if not direct:
-        need = lib().tfc_fft_spectrum_ws_bytes(S, nwin)
-        key = (img.device, torch.cuda.current_stream().cuda_stream)   # one scratch per (device, stream): calls on a stream are ordered
-        ws = _FFT_WS.get(key)
-        if ws is None or ws.numel() < need:
-            ws = _FFT_WS[key] = torch.empty(need, dtype=torch.uint8, device=img.device)
+    ws = None if direct else _fft_scratch(img.device, lib().tfc_fft_spectrum_ws_bytes(S, nwin))
     check(lib().tfc_fft_spectrum(stream_ptr(), _p(img), img.stride(0), img.stride(1), img.stride(2), C, S, wins_x, wins_y, N,
                                  _p(amp), _p(pha), 1 if shift else 0, _p(ws)), "tfc_fft_spectrum")
     return amp, pha
@@ -491,20 +492,12 @@ def fft_spectrum(img, S, wins_x, wins_y, shift=True, direct=False):
 def fft_spectrum_rect(img, H, row0=0, row_step=0, wins=1, shift=True):
     """Spectra of `wins` windows of H rows x 256 columns per image, window k starting at image row row0 + k * row_step (H in 2 .. 256; the regional
     FFT loss uses H = 100, rows 0 and 100). img: fp32 [N,C,h,w >= 256] (any strides on N/C/H, unit stride on W). Returns amp, pha [N*wins, H, 129]."""
-    require_gpu(img)
-    if img.dtype != torch.float32:
-        img = img.float()
-    if img.stride(3) != 1:
-        img = img.contiguous()
+    img = _image_f32(img)
     N, C, h, w = img.shape
     nwin = N * wins
-    need = lib().tfc_fft_spectrum_rect_ws_bytes(H, nwin)          # 0 for a refused H: the call below says why
     amp = torch.empty((nwin, max(H, 0), 129), dtype=torch.float32, device=img.device)
     pha = torch.empty_like(amp)
-    key = (img.device, torch.cuda.current_stream().cuda_stream)   # the scratch of fft_spectrum: calls on a stream are ordered
-    ws = _FFT_WS.get(key)
-    if ws is None or ws.numel() < max(need, 16):
-        ws = _FFT_WS[key] = torch.empty(max(need, 16), dtype=torch.uint8, device=img.device)
+    ws = _fft_scratch(img.device, max(lib().tfc_fft_spectrum_rect_ws_bytes(H, nwin), 16))    # 0 bytes for a refused H: the call below says why
     check(lib().tfc_fft_spectrum_rect(stream_ptr(), _p(img), img.stride(0), img.stride(1), img.stride(2), C, h, w, H, row0, row_step, wins, N,
                                       _p(amp), _p(pha), 1 if shift else 0, _p(ws)), "tfc_fft_spectrum_rect")
     return amp, pha
@@ -535,11 +528,7 @@ def logmag_mse(amp_a, amp_b, absolute=False):
 
 def vectorize_temps(img, lut):
     """img: fp32 [N,C,H,W] (unit stride on W); lut: fp32 [256] on the device. Returns [N,H,W] fp32 (channel 0 -> uint8 -> lut)."""
-    require_gpu(img)
-    if img.dtype != torch.float32:
-        img = img.float()
-    if img.stride(3) != 1:
-        img = img.contiguous()
+    img = _image_f32(img)
     N, _, H, W = img.shape
     out = torch.empty((N, H, W), dtype=torch.float32, device=img.device)
     check(lib().tfc_vectorize_temps(stream_ptr(), _p(img), img.stride(0), img.stride(2), N, H, W, _p(lut), _p(out)), "tfc_vectorize_temps")
