@@ -65,7 +65,8 @@ def ref_morph_gradient(x):
 
 
 def test_morph_gradient_and_triplet_vs_torch_restatement_unpinned():
-    """forward, backward (arg-max / arg-min routing) and the whole morph_triplet loss of STN:444-459; continuous random images have no ties"""
+    """forward, backward (arg-max / arg-min routing) and the whole morph_triplet loss of STN:444-459 on continuous random images; tied data
+    (plateaus, the warp's replicated border) and the first-maximum rule are in test_gpu_42_stn21_edges.py::test_morph_gradient_on_ties_and_thin_planes"""
     x = rnd((2, 3, 40, 56), 5).requires_grad_(True)
     want = ref_morph_gradient(x)
     go = rnd(tuple(want.shape), 6)

@@ -282,6 +282,24 @@ __device__ __forceinline__ float wave_max(float v) {
 }
 constexpr int AP = 65;                                             // LDS row pitch of the [T][64] / [T][T] tiles
 
+// x . y over the head dim as an unevaluated sum hi + lo, about twice fp32's precision (Ogita / Rump / Oishi Dot2: the product's error by fma, the
+// sum's by TwoSum; no contraction, or the error terms are not the errors). A logit kept in ONE fp32 is known to ulp(|logit|) only: at logits of
+// +-100 that is 4e-6 absolute, it is the RELATIVE error of every small probability of a row, and the query / key gradients of a nearly one-hot
+// row are made of exactly those: 1e-6 rel-L2 on the probabilities and up to 3e-5 on dqkv against fp64, whatever the order of an fp32 sum
+// (test_attention_fp32_large_logits; with hi + lo: 2e-8 and 3e-7).
+__device__ __forceinline__ void dot64_2(const float* x, const float* y, float& hi, float& lo) {
+#pragma clang fp contract(off)
+  float s = 0.f, c = 0.f;
+  for (int d = 0; d < 64; ++d) {
+    const float a = x[d], b = y[d];
+    const float p = a * b, pe = fmaf(a, b, -p);
+    const float t = s + p, z = t - s, se = (s - (t - z)) + (p - z);
+    s = t;
+    c += pe + se;
+  }
+  hi = s; lo = c;
+}
+
 template <int DT>
 __global__ void __launch_bounds__(256)
 tfc_vit_attn_fwd_kernel(const float* __restrict__ qkv, float* __restrict__ out, float* __restrict__ probs, int T, int H, float scale) {
@@ -297,14 +315,12 @@ tfc_vit_attn_fwd_kernel(const float* __restrict__ qkv, float* __restrict__ out, 
   __syncthreads();
   for (int i = w; i < T; i += 4) {
     const int j = lane;
-    float s = -INFINITY;
-    if (j < T) {
-      float a = 0.f;
-      for (int d = 0; d < 64; ++d) a = fmaf(q[i * AP + d], k[j * AP + d], a);
-      s = a * scale;
-    }
-    const float mx = wave_max(s);
-    const float e = j < T ? expf(s - mx) : 0.f;
+    float hi = -INFINITY, lo = 0.f;
+    if (j < T) { dot64_2(q + i * AP, k + j * AP, hi, lo); if (scale < 0.f) { hi = -hi; lo = -lo; } }   // the maximum of the SCALED logits
+    // the maximum is subtracted from hi + lo, so the rounding to one fp32 happens on the DIFFERENCE: the entries that carry weight have a small one
+    const float mh = wave_max(hi);
+    const float ml = wave_max(hi == mh ? lo : -INFINITY);
+    const float e = j < T ? expf(((hi - mh) + (lo - ml)) * fabsf(scale)) : 0.f;
     const float pij = e / wave_sum(e);
     if (j < T) { probs[(((size_t)n * H + h) * T + i) * T + j] = pij; p[i * AP + j] = op(pij); }
   }
