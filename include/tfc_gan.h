@@ -438,6 +438,33 @@ int tfc_conv_plan_query(int dt, int op, int pass, int N, int H, int W, int Cin, 
 /* device probe of the MFMA / transposing-read lane maps the kernels rely on (writes 3*64*16 floats) */
 int tfc_probe_mfma(void* stream, float* out);
 
+/* ---- label-conditioned ("debiased") 4-patch scripts: label plane of the generator, auxiliary classifier heads of the discriminator ------------
+ * Reference TFC-GAN-FFT/TFCGAN_multigpu_patchFFT_debiased.py (DB1) :146-151, :171-174 (fc + 4th input channel), :216-233 (three Linear + Softmax
+ * heads on the flattened 6 x H x W discriminator input), :522 / :603-606 (CrossEntropyLoss on the softmax output). All pointers are device pointers
+ * unless named *_host; image-sized pointers 16-byte aligned; H * W a multiple of 4. The heads are given as three weight pointers (torch layout
+ * [C_h][6*H*W] fp32), three bias pointers and three class counts (each >= 1, at most 16 in all); outputs order the classes head after head. */
+/* out [N][H][W][8] in the compute dtype: channels 0..2 = img [N][3][H][W] fp32, channel 3 = fc(labels) (labels [N][3], fc_w [H*W][3], fc_b [H*W],
+ * fp32 fmas, rounded once), channels 4..7 = 0 */
+int tfc_pack_nhwc8_labels(void* stream, int dt, const float* img, const float* labels, const float* fc_w, const float* fc_b, void* out, int N, int H, int W);
+/* g: fp32 NCHW gradient [N][gC][H][W] whose channel `ch` is the plane's: d_fc_w[p][k] (+)= sum_n g[n][ch][p] labels[n][k], d_fc_b[p] (+)= sum_n g[n][ch][p]
+ * (n ascending inside one thread) */
+int tfc_label_plane_bwd(void* stream, const float* g, int gC, int ch, const float* labels, float* d_fc_w, float* d_fc_b, int N, int H, int W, int accumulate);
+/* x: the packed discriminator input [N][H][W][8] (x_pitch must be 8; channels 0..2 img_A, 3..5 img_B; column c*H*W + p of a weight row).
+ * logits [N][sum C_h] fp32 = bias + x . W^T: fp32 sums, per-wave partials in fixed part_ws slots. Every weight element is read once per launch. */
+int tfc_aux_heads_fwd(void* stream, int dt, const void* x, int x_pitch, int N, int H, int W, const float* const* w3, const float* const* b3,
+                      const int* nclass3_host, float* logits, float* part_ws);
+/* probs [N][sum C_h] = per-head softmax(logits); losses[0..2] = mean_n(logsumexp(probs_h) - probs_h[y]) (the reference's double softmax),
+ * losses[3] = scale * sum_h w3_host[h] * losses[h]; dlogits (nullable) = d losses[3] / d logits. targets: int32 [N][3] on the device;
+ * targets_host (nullable): the same values on the host, refused when one lies outside [0, C_h). One workgroup, fixed-order sums. */
+int tfc_softmax_ce_heads(void* stream, const float* logits, const int* targets, const int* targets_host, const int* nclass3_host,
+                         const float* w3_host, float scale, int N, float* probs, float* losses4, float* dlogits);
+/* g [N][gC][H][W] fp32 (gC >= 3): g[n][c][p] += sum_o dlogits[n][o] W[o][c*H*W + p] for c < 3 (the img_A half of the input) */
+int tfc_aux_heads_dgrad(void* stream, float* g, int gC, int N, int H, int W, const float* const* w3, const int* nclass3_host, const float* dlogits);
+/* dw3[h][o][c*H*W + p] (+)= sum_n dl_r[n][o] x_r[n][p][c] + sum_n dl_f[n][o] x_f[n][p][c], db3[h][o] (+)= sum_n dl_r[n][o] + sum_n dl_f[n][o]
+ * (real pair first, n ascending inside one thread; x_f / dl_f nullable together), written into the torch-layout gradients directly */
+int tfc_aux_heads_wgrad(void* stream, int dt, const void* x_r, const float* dl_r, const void* x_f, const float* dl_f, int x_pitch, int N, int H, int W,
+                        float* const* dw3, float* const* db3, const int* nclass3_host, int accumulate);
+
 #ifdef __cplusplus
 }
 #endif

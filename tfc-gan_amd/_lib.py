@@ -12,7 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _ROOT = os.path.dirname(_HERE)
 CSRC = os.path.join(_HERE, "csrc")
 SO_PATH = os.path.join(_HERE, "libtfcgan_hip.so")
-SOURCES = ["api.hip", "igemm.hip", "elementwise.hip", "losses.hip", "stn.hip", "lpips.hip", "input.hip", "probe.hip", "vit.hip", "metrics.hip"]
+SOURCES = ["api.hip", "igemm.hip", "elementwise.hip", "losses.hip", "stn.hip", "lpips.hip", "input.hip", "probe.hip", "vit.hip", "metrics.hip", "debias.hip"]
 HEADERS = ["common.h", "tfc_desc.h", "pack_math.h"]
 PUBLIC_HEADER = os.path.join(_ROOT, "include", "tfc_gan.h")
 
@@ -83,7 +83,10 @@ def _build_locked(verbose):
 # the square spectra with the checks of a ragged row count compiled in; "ILi256E" matches both 256-point instantiations), the columns kernel a 100 x 100 inner loop per output that was written to live in registers.
 # Entries are substrings of the MANGLED names in the remarks; one that matches no compiled kernel fails the build (unmatched_guards).
 GUARDED_KERNELS = ("tfc_igemm2_kernel", "tfc_wgrad", "tfc_patch_triplet_kernelILi2E", "tfc_fft_rows_kernelILi128E", "tfc_fft_rows_kernelILi256E",
-                   "tfc_fft_cols_kernelILi128E", "tfc_spectrum_kernelILi128E", "tfc_dft_rect_cols_kernel")
+                   "tfc_fft_cols_kernelILi128E", "tfc_spectrum_kernelILi128E", "tfc_dft_rect_cols_kernel",
+                   # the label plane and the auxiliary heads (debias.hip): up to 96 weights or sums per thread, sized to stay in registers
+                   "tfc_pack_labels_kernel", "tfc_label_plane_bwd_kernel", "tfc_aux_heads_fwd_kernel", "tfc_aux_heads_dgrad_kernel",
+                   "tfc_aux_heads_wgrad_kernel", "tfc_softmax_ce_heads_kernel")
 
 
 def check_no_spills(remarks):
@@ -203,6 +206,12 @@ PROTOTYPES = {
     "tfc_get_batch_invariant": (_i, []),
     "tfc_conv_plan_query": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _c.POINTER(_i), _i]),
     "tfc_probe_mfma": (_i, [_vp, _vp]),
+    "tfc_pack_nhwc8_labels": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i]),
+    "tfc_label_plane_bwd": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _i, _i, _i, _i]),
+    "tfc_aux_heads_fwd": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _c.POINTER(_vp), _c.POINTER(_vp), _c.POINTER(_i), _vp, _vp]),
+    "tfc_softmax_ce_heads": (_i, [_vp, _vp, _vp, _c.POINTER(_i), _c.POINTER(_i), _c.POINTER(_f), _f, _i, _vp, _vp, _vp]),
+    "tfc_aux_heads_dgrad": (_i, [_vp, _vp, _i, _i, _i, _i, _c.POINTER(_vp), _c.POINTER(_i), _vp]),
+    "tfc_aux_heads_wgrad": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _c.POINTER(_vp), _c.POINTER(_vp), _c.POINTER(_i), _i]),
 }
 
 

@@ -1287,6 +1287,128 @@ extern "C" int tfc_conv_plan_query(int dt, int op, int pass, int N, int H, int W
   for (int i = 0; i < n && i < 8; ++i) out[i] = rec[i];
   return 8;
 }
+// ---- label plane + auxiliary classifier heads (debias.hip) -----------------------------------------------------------------------------------
+struct TfcAuxRows { const float* w[16]; const float* b[16]; };
+struct TfcAuxGradRows { float* w[16]; float* b[16]; };
+struct TfcCeHeads { int nc[3]; int off[3]; float w[3]; float scale; };
+hipError_t tfc_launch_pack_labels(int dt, const float* img, const float* labels, const float* fw, const float* fb, void* out, int N, int HW, hipStream_t st);
+hipError_t tfc_launch_label_plane_bwd(const float* g, long long gs, const float* labels, float* dw, float* db, int N, int HW, int accumulate, hipStream_t st);
+hipError_t tfc_launch_aux_heads_fwd(int dt, const void* x, const TfcAuxRows& rows, int ct, float* logits, float* part_ws, int N, int HW, hipStream_t st);
+hipError_t tfc_launch_aux_heads_dgrad(float* g, long long gs, const TfcAuxRows& rows, int ct, const float* dl, int N, int HW, hipStream_t st);
+hipError_t tfc_launch_aux_heads_wgrad(int dt, const void* xr, const float* dlr, const void* xf, const float* dlf, const TfcAuxGradRows& rows, int ct,
+                                      int N, int HW, int accumulate, hipStream_t st);
+hipError_t tfc_launch_softmax_ce_heads(const float* logits, const int* targets, const TfcCeHeads& a, int ct, int N, float* probs, float* losses,
+                                       float* dlogits, hipStream_t st);
+int tfc_aux_fwd_nparts(int HW);
+
+static inline bool al16(const void* p) { return p != nullptr && (((uintptr_t)p) & 15) == 0; }
+#define REQUIRE_IMAGE(N, H, W) do { \
+    REQUIRE(N > 0 && N <= 65535 && H > 0 && W > 0, "bad dims N=%d H=%d W=%d (1 <= N <= 65535)", N, H, W); \
+    REQUIRE((long long)H * W < (1LL << 24) && ((long long)H * W) % 4 == 0, "H*W=%lld must be a multiple of 4 below 2^24 (16-byte units of a plane)", (long long)H * W); \
+  } while (0)
+// class counts of the three heads -> total (<= 16), or a refusal
+static int aux_classes(const int* nc, int* total) {
+  REQUIRE(nc != nullptr, "nclass3 is null");
+  int ct = 0;
+  for (int h = 0; h < 3; ++h) {
+    REQUIRE(nc[h] >= 1 && nc[h] <= 16, "head %d has %d classes (1 .. 16)", h, nc[h]);
+    ct += nc[h];
+  }
+  REQUIRE(ct <= 16, "%d classes in all: the head kernels hold at most 16 rows", ct);
+  *total = ct;
+  return 0;
+}
+
+extern "C" int tfc_pack_nhwc8_labels(void* stream, int dt, const float* img, const float* labels, const float* fc_w, const float* fc_b, void* out,
+                                     int N, int H, int W) {
+  REQUIRE(dt == TFC_DT_BF16 || dt == TFC_DT_F32 || dt == TFC_DT_BF16X3, "bad dtype %d", dt);
+  REQUIRE_IMAGE(N, H, W);
+  REQUIRE(labels != nullptr, "labels is null");
+  REQUIRE(al16(img) && al16(fc_w) && al16(fc_b) && al16(out), "img / fc_w / fc_b / out must be 16-byte aligned device pointers");
+  CHECK_HIP(tfc_launch_pack_labels(dt, img, labels, fc_w, fc_b, out, N, H * W, (hipStream_t)stream), "tfc_pack_nhwc8_labels");
+  return 0;
+}
+
+extern "C" int tfc_label_plane_bwd(void* stream, const float* g, int gC, int ch, const float* labels, float* d_fc_w, float* d_fc_b, int N, int H, int W,
+                                   int accumulate) {
+  REQUIRE_IMAGE(N, H, W);
+  REQUIRE(gC >= 1 && gC <= 8 && ch >= 0 && ch < gC, "channel %d of a %d-channel gradient", ch, gC);
+  REQUIRE(labels != nullptr, "labels is null");
+  REQUIRE(al16(g) && al16(d_fc_w) && al16(d_fc_b), "g / d_fc_w / d_fc_b must be 16-byte aligned device pointers");
+  const long long HW = (long long)H * W;
+  CHECK_HIP(tfc_launch_label_plane_bwd(g + (size_t)ch * HW, (long long)gC * HW, labels, d_fc_w, d_fc_b, N, (int)HW, accumulate ? 1 : 0, (hipStream_t)stream),
+            "tfc_label_plane_bwd");
+  return 0;
+}
+
+extern "C" int tfc_aux_heads_fwd(void* stream, int dt, const void* x, int x_pitch, int N, int H, int W, const float* const* w3, const float* const* b3,
+                                 const int* nclass3_host, float* logits, float* part_ws) {
+  REQUIRE(dt == TFC_DT_BF16 || dt == TFC_DT_F32 || dt == TFC_DT_BF16X3, "bad dtype %d", dt);
+  REQUIRE_IMAGE(N, H, W);
+  REQUIRE(x_pitch == 8, "x pitch %d: the heads read the packed 8-channel discriminator input", x_pitch);
+  int ct = 0;
+  if (int rc = aux_classes(nclass3_host, &ct)) return rc;
+  REQUIRE(w3 && b3 && logits && part_ws && al16(x), "null argument (x must be 16-byte aligned)");
+  REQUIRE((long long)N * tfc_aux_fwd_nparts(H * W) * ct <= (long long)TFC_PART_WS_FLOATS, "N=%d x H*W=%d: the partial sums pass part_ws", N, H * W);
+  TfcAuxRows rows = {};
+  for (int h = 0, o = 0; h < 3; ++h) {
+    REQUIRE(al16(w3[h]) && b3[h], "head %d: weight must be a 16-byte aligned device pointer, bias non-null", h);
+    for (int r = 0; r < nclass3_host[h]; ++r, ++o) { rows.w[o] = w3[h] + (size_t)r * 6 * H * W; rows.b[o] = b3[h] + r; }
+  }
+  CHECK_HIP(tfc_launch_aux_heads_fwd(dt, x, rows, ct, logits, part_ws, N, H * W, (hipStream_t)stream), "tfc_aux_heads_fwd");
+  return 0;
+}
+
+extern "C" int tfc_softmax_ce_heads(void* stream, const float* logits, const int* targets, const int* targets_host, const int* nclass3_host,
+                                    const float* w3_host, float scale, int N, float* probs, float* losses4, float* dlogits) {
+  REQUIRE(N > 0 && N <= (1 << 20), "bad N=%d", N);
+  int ct = 0;
+  if (int rc = aux_classes(nclass3_host, &ct)) return rc;
+  REQUIRE(logits && targets && w3_host && probs && losses4, "null argument");
+  TfcCeHeads a;
+  for (int h = 0, off = 0; h < 3; ++h) { a.nc[h] = nclass3_host[h]; a.off[h] = off; a.w[h] = w3_host[h]; off += nclass3_host[h]; }
+  a.scale = scale;
+  if (targets_host)
+    for (int n = 0; n < N; ++n)
+      for (int h = 0; h < 3; ++h)
+        REQUIRE(targets_host[n * 3 + h] >= 0 && targets_host[n * 3 + h] < a.nc[h], "target %d of sample %d, head %d: outside [0, %d)", targets_host[n * 3 + h], n, h, a.nc[h]);
+  CHECK_HIP(tfc_launch_softmax_ce_heads(logits, targets, a, ct, N, probs, losses4, dlogits, (hipStream_t)stream), "tfc_softmax_ce_heads");
+  return 0;
+}
+
+extern "C" int tfc_aux_heads_dgrad(void* stream, float* g, int gC, int N, int H, int W, const float* const* w3, const int* nclass3_host, const float* dlogits) {
+  REQUIRE_IMAGE(N, H, W);
+  REQUIRE(gC >= 3 && gC <= 8, "gradient of %d channels (3 .. 8: the first three are img_A's)", gC);
+  int ct = 0;
+  if (int rc = aux_classes(nclass3_host, &ct)) return rc;
+  REQUIRE(w3 && dlogits && al16(g), "null argument (g must be 16-byte aligned)");
+  TfcAuxRows rows = {};
+  for (int h = 0, o = 0; h < 3; ++h) {
+    REQUIRE(al16(w3[h]), "head %d: weight must be a 16-byte aligned device pointer", h);
+    for (int r = 0; r < nclass3_host[h]; ++r, ++o) rows.w[o] = w3[h] + (size_t)r * 6 * H * W;
+  }
+  CHECK_HIP(tfc_launch_aux_heads_dgrad(g, (long long)gC * H * W, rows, ct, dlogits, N, H * W, (hipStream_t)stream), "tfc_aux_heads_dgrad");
+  return 0;
+}
+
+extern "C" int tfc_aux_heads_wgrad(void* stream, int dt, const void* x_r, const float* dl_r, const void* x_f, const float* dl_f, int x_pitch, int N, int H,
+                                   int W, float* const* dw3, float* const* db3, const int* nclass3_host, int accumulate) {
+  REQUIRE(dt == TFC_DT_BF16 || dt == TFC_DT_F32 || dt == TFC_DT_BF16X3, "bad dtype %d", dt);
+  REQUIRE_IMAGE(N, H, W);
+  REQUIRE(x_pitch == 8, "x pitch %d: the heads read the packed 8-channel discriminator input", x_pitch);
+  int ct = 0;
+  if (int rc = aux_classes(nclass3_host, &ct)) return rc;
+  REQUIRE(al16(x_r) && dl_r && dw3 && db3, "null argument (x_r must be 16-byte aligned)");
+  REQUIRE((x_f == nullptr) == (dl_f == nullptr) && (!x_f || al16(x_f)), "x_f and dl_f come together (x_f 16-byte aligned)");
+  TfcAuxGradRows rows = {};
+  for (int h = 0, o = 0; h < 3; ++h) {
+    REQUIRE(al16(dw3[h]) && db3[h], "head %d: weight gradient must be a 16-byte aligned device pointer, bias gradient non-null", h);
+    for (int r = 0; r < nclass3_host[h]; ++r, ++o) { rows.w[o] = dw3[h] + (size_t)r * 6 * H * W; rows.b[o] = db3[h] + r; }
+  }
+  CHECK_HIP(tfc_launch_aux_heads_wgrad(dt, x_r, dl_r, x_f, dl_f, rows, ct, N, H * W, accumulate ? 1 : 0, (hipStream_t)stream), "tfc_aux_heads_wgrad");
+  return 0;
+}
+
 extern "C" int tfc_probe_mfma(void* stream, float* out) {
   REQUIRE(out, "out is null");
   CHECK_HIP(tfc_launch_probe(out, (hipStream_t)stream), "tfc_probe_mfma");

@@ -121,9 +121,31 @@ class TestImageDataset(ImageDataset):
         super().__init__(root, transforms_, mode)
 
 
+class LabelledImageDataset(ImageDataset):
+    """ImageDataset of the label-conditioned scripts (datasets_temp_Debias.py:46-150): the files and their labels come from an annotations CSV with a
+    header row (pd.read_csv there, the stdlib csv here) -- column 0 the file name under root/mode, columns 2, 3, 4 gender, ethnicity, age. Items are the
+    decoded files as in ImageDataset; `labels` holds the float [len, 3] table and DeviceLoader adds the batch's rows as "LAB" (float [N, 3], kept on the
+    host: TrainStep checks the class ranges there)."""
+
+    def __init__(self, annots_csv, root, transforms_=None, mode="train"):
+        import csv
+        super().__init__(root, transforms_, mode)
+        with open(annots_csv, newline="") as f:
+            rows = [r for r in csv.reader(f) if r]
+        if len(rows) < 1 or len(rows[0]) < 5:
+            raise TfcError(f"{annots_csv}: expected a header row and at least 5 columns (file, _, gender, ethnicity, age)")
+        rows = rows[1:]                                           # pd.read_csv takes the first row as the header
+        self.image_dir = os.path.join(root, mode)
+        self.files = [os.path.join(self.image_dir, r[0]) for r in rows]
+        try:
+            self.labels = np.array([[float(r[2]), float(r[3]), float(r[4])] for r in rows], dtype=np.float32).reshape(len(rows), 3)
+        except (ValueError, IndexError) as e:
+            raise TfcError(f"{annots_csv}: columns 2, 3, 4 must hold the numeric gender / ethnicity / age classes ({e})") from None
+
+
 class DeviceLoader:
     """DataLoader(ImageDataset(...), batch_size, shuffle, num_workers) of P16:484-490 with the batch assembled on the GPU. Yields dicts with the
-    reference's keys: A, B, B1..B4, T_B (TestImageDataset: A, B). Files of one batch must share their geometry (the reference's datasets do);
+    reference's keys: A, B, B1..B4, T_B (TestImageDataset: A, B; LabelledImageDataset: + LAB). Files of one batch must share their geometry (the reference's datasets do);
     a batch with mixed sizes is processed per geometry group and concatenated in order."""
 
     def __init__(self, dataset, batch_size=1, shuffle=False, drop_last=False, num_workers=8, device="cuda:0", seed=0, out=256):
@@ -186,4 +208,7 @@ class DeviceLoader:
         for bi, idx in enumerate(batches):
             cur = nxt if nxt is not None else [self.pool.submit(self.ds.__getitem__, i) for i in idx]
             nxt = [self.pool.submit(self.ds.__getitem__, i) for i in batches[bi + 1]] if bi + 1 < len(batches) else None   # decode ahead
-            yield self._assemble([f.result() for f in cur])
+            batch = self._assemble([f.result() for f in cur])
+            if hasattr(self.ds, "labels"):                        # LabelledImageDataset: "LAB" as the reference's batch carries it
+                batch["LAB"] = torch.from_numpy(np.ascontiguousarray(self.ds.labels[[i % len(self.ds) for i in idx]]))
+            yield batch

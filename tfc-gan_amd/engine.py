@@ -15,6 +15,17 @@ GradScaler (:518); the reference's wasted D weight-gradients during the G step (
 `patches=4, region_fft="l1" | "kl"` adds the regional FFT loss of TFCGAN_multigpu_patchFFT_withregion_FFT.py ("4R", L1 form) /
 ..._withregion_FFT_KL.py ("4K", KL form over the batch): lambda_region * regional_fft_loss(fake, B) joins the logged loss_G (4R:606-620, 4K:623-636;
 losses.region_weights gives each script's weights). It carries no gradient in the reference and none here; the discriminator step is PATCH-4's.
+
+`patches=4, labels="generated" | "real"` runs the label-conditioned ("debiased") scripts TFCGAN_multigpu_patchFFT_debiased.py (DB1), ..._V2.py (DB2) and
+..._V3.py (DB3) on GeneratorUNet(labels=3) / Discriminator1(aux_classes=(2, 4, 3)); losses.debias_weights gives each script's keywords.
+    G step : fake = G(A, gl), gl = the drawn labels ("generated", DB1:504-508) or the real ones ("real", DB2:512)
+             loss_G += loss_label = sum_h label_weights[h] * CE(head_h(fake, A), gl[:, h])                              (DB1:522, DB3:531)
+             its gradient reaches fake through the heads' input gradient, and fc through the input gradient of down1
+    D step : loss_D = 0.5 * ((loss_real + real_loss_label) + (loss_fake + fake_loss_label))                           (DB1:609)
+             real_loss_label = d_label_scale * sum_h CE(head_h(B, A), labels[:, h]); fake_loss_label the same on (fake, A) against the DRAWN labels
+             in every variant (DB1:603-606, DB3:612-618)
+CE is the reference's nn.CrossEntropyLoss applied to the heads' Softmax output (two softmaxes), kept as it is. V4..V7 of the family (two frozen
+pretrained ResNet18 classifiers) are not covered, and the labelled step is tested on one rank only.
 """
 import math
 import os
@@ -26,10 +37,19 @@ from .losses import global_fft_loss, patch_fft_loss, regional_fft_loss, temperat
 from .ops import DT_BF16
 
 
+def draw_gen_labels(N, seed, step, rank=0, classes=ops.AUX_CLASSES):
+    """the generator's labels of one step, int64 numpy [N,3] -- np.random.randint(0, 2 | 4 | 3, (batch, 1)) per column in the reference (DB1:504-506), here
+    a deterministic function of (seed, step, rank): reproducible, and different on every rank (each rank draws for its own shard)"""
+    import numpy as np
+    rng = np.random.default_rng([int(seed), int(step), int(rank), 0xDEB1A5])
+    return np.stack([rng.integers(0, c, size=N) for c in classes], 1)
+
+
 class TrainStep:
     def __init__(self, generator, discriminator, lr=2e-4, b1=0.5, b2=0.999, eps=1e-8, compute_dtype=torch.bfloat16,
                  fft_mode="patch", seed=0, bucket_bytes=16 << 20, lambda_gan=0.5, lambda_fft=0.01, lambda_trip=1.0, d_bucket_bytes=4 << 20,
-                 batch_invariant=None, patches=16, region_fft=None, lambda_region=0.5e-4):
+                 batch_invariant=None, patches=16, region_fft=None, lambda_region=0.5e-4, labels=None, label_weights=(1.0, 1.0, 1.0),
+                 d_label_scale=1.0):
         dev = next(generator.parameters()).device
         if patches not in (4, 16):
             raise ops._lib.TfcError(f"TrainStep: patches={patches} (16: the 4x4 grid of 64x64 patches, 4: the 2x2 grid of 128x128 patches)")
@@ -39,6 +59,19 @@ class TrainStep:
         if region_fft is not None and patches != 4:
             raise ops._lib.TfcError("TrainStep: region_fft belongs to the 4-patch scripts (patches=4); no reference script combines it with 16 patches")
         self.region_fft, self.lambda_region = region_fft, lambda_region
+        if labels not in (None, "generated", "real"):
+            raise ops._lib.TfcError(f"TrainStep: labels={labels!r} (None, 'generated': G is fed the drawn labels, 'real': the batch's own)")
+        if labels is not None:
+            if patches != 4:
+                raise ops._lib.TfcError("TrainStep: labels= belongs to the label-conditioned 4-patch scripts (patches=4); no reference script combines it "
+                                        "with 16 patches")
+            if not getattr(generator, "labels", 0) or not getattr(discriminator, "aux_classes", None):
+                raise ops._lib.TfcError("TrainStep(labels=...) needs GeneratorUNet(img_shape, labels=3) and Discriminator1(img_shape, aux_classes=(2, 4, 3))")
+            if len(label_weights) != 3:
+                raise ops._lib.TfcError(f"TrainStep: label_weights={label_weights!r} (three weights: gender, ethnicity, age)")
+        elif getattr(generator, "labels", 0) or getattr(discriminator, "aux_classes", None):
+            raise ops._lib.TfcError("TrainStep: a label-conditioned generator / discriminator needs labels='generated' or 'real' (losses.debias_weights)")
+        self.labels, self.label_weights, self.d_label_scale = labels, tuple(float(w) for w in label_weights), float(d_label_scale)
         if dev.type != "cuda":
             raise ops._lib.TfcError("TrainStep needs the modules on a CUDA/HIP device (no CPU fallback)")
         self.dev, self.dt = dev, ops.dt_of(compute_dtype)
@@ -68,9 +101,9 @@ class TrainStep:
         # the discriminator's 11 MB of gradients: its largest layer (model.9, 8.4 MB) is final first, so a 4 MiB cut lets that part of the exchange
         # run under the rest of the D backward; only the last ~2.6 MB (model.6, .3, .0) are exposed
         self.d_reduce = parallel.BucketReducer(self.dflat, min(bucket_bytes, d_bucket_bytes))
-        self.G = nets.GeneratorCore(self.dt, generator.channels)
+        self.G = nets.GeneratorCore(self.dt, generator.channels, getattr(generator, "labels", 0))
         self.G.set_params(self.gflat.views)
-        self.D = nets.DiscriminatorCore(self.dt, discriminator.channels)
+        self.D = nets.DiscriminatorCore(self.dt, discriminator.channels, getattr(discriminator, "aux_classes", None))
         self.D.set_params(self.dflat.views, self.dbufs)
         self.G.repack()
         self.D.repack()
@@ -91,11 +124,27 @@ class TrainStep:
     def _gl(self, like):
         return ops.new_act(like.N, like.H, like.W, 8, self.dt, self.dev)      # tfc_bce_relativistic writes whole 8-channel pixels (logit gradient, 7 zeros)
 
-    def step(self, real_A, real_B, neg_idx=None, extra_loss_G=None, T_B=None, B_tf=None):
+    def step(self, real_A, real_B, neg_idx=None, extra_loss_G=None, T_B=None, B_tf=None, labels=None, gen_labels=None):
         with ops.batch_invariant_scope(self.batch_invariant):     # both streams of the step launch from this thread: one setting for all of it
-            return self._step(real_A, real_B, neg_idx, extra_loss_G, T_B, B_tf)
+            return self._step(real_A, real_B, neg_idx, extra_loss_G, T_B, B_tf, labels, gen_labels)
 
-    def _step(self, real_A, real_B, neg_idx=None, extra_loss_G=None, T_B=None, B_tf=None):
+    def _label_tensors(self, labels, gen_labels, N, t):
+        """the step's two label sets as (fp32 [N,3] device, int32 [N,3] device, int32 numpy) each; checked on the host. gen_labels=None draws them as
+        the reference does per step (DB1:504-506), from (seed, step, rank)."""
+        if labels is None:
+            raise ops._lib.TfcError("TrainStep(labels=...).step needs labels= (float or integer [N,3]: gender, ethnicity, age; batch['LAB'])")
+        if gen_labels is None:
+            gen_labels = draw_gen_labels(N, self.seed, t, parallel.rank(), self.D.aux_classes)
+        out = []
+        for v in (labels, gen_labels):
+            host = ops.check_targets(v, self.D.aux_classes)
+            if host.shape[0] != N:
+                raise ops._lib.TfcError(f"TrainStep: {host.shape[0]} label rows for a batch of {N}")
+            ti = torch.from_numpy(host).to(self.dev, non_blocking=True)
+            out.append((ti.float(), ti, host))
+        return out
+
+    def _step(self, real_A, real_B, neg_idx=None, extra_loss_G=None, T_B=None, B_tf=None, labels=None, gen_labels=None):
         """real_A, real_B: fp32 NCHW [N,3,256,256] in [-1,1] on the GPU (this rank's shard). Returns a dict of device scalars.
         T_B [N,256,256] + B_tf [N,3,256,256] (augmented real_B) switch the gradient-free temperature term on.
         extra_loss_G(fake, real_B) -> (loss, dfake) runs on the SIDE stream beside the discriminator chain (with the triplet / FFT heads): it may use any
@@ -109,6 +158,13 @@ class TrainStep:
             raise ops._lib.TfcError(f"TrainStep(patches={self.patches}): neg_idx has {len(neg_idx)} entries")
         drop_seed = (self.seed * 7919 + t * 104729 + parallel.rank() * 1299709) & 0x3FFFFFF
         train = self.G_mod.training
+        lab = None
+        if self.labels is not None:
+            lab_real, lab_gen = self._label_tensors(labels, gen_labels, real_A.shape[0], t)
+            lab = lab_gen if self.labels == "generated" else lab_real          # what G is fed and what its loss_label is taken against
+        elif labels is not None or gen_labels is not None:
+            raise ops._lib.TfcError("TrainStep.step: labels / gen_labels belong to TrainStep(labels='generated' | 'real')")
+        g_labels = None if lab is None else lab[0]
         pv = self._param_versions()
         if pv != self._pversions:                                 # weights written from outside since the last step (load_state_dict): re-pack
             self.G.repack()
@@ -132,12 +188,12 @@ class TrainStep:
             snap_r = self.D.sn_snapshot(self.dev, True, False)
             pr = nets.on_side(self.dev, lambda: self.D.chain(real_B, real_A, snap_r, save=False), snap_r[2][0])[0]
             pr_ready = nets.side_mark(self.dev)
-            fake, gctx = self.G.forward(real_A, seed=drop_seed, train=train)
+            fake, gctx = self.G.forward(real_A, seed=drop_seed, train=train, labels=g_labels)
             loss_trip, g_trip, (loss_fft, loss_amp, loss_pha), extra_pair, region = nets.on_side(self.dev, pixel_losses)
             pf, dctx_f = self.D.chain(fake, real_A, snap_f, save=True)
             nets.wait_mark(self.dev, pr_ready)                    # the logits of the real pair; the pixel losses (LPIPS: 6 ms) run on, D.backward below joins
         else:
-            fake, gctx = self.G.forward(real_A, seed=drop_seed, train=train)
+            fake, gctx = self.G.forward(real_A, seed=drop_seed, train=train, labels=g_labels)
             pf, dctx_f = self.D.forward(fake, real_A, power_iter=True, save=True)
             pr, _ = self.D.forward(real_B, real_A, power_iter=True, save=False)
             loss_trip, g_trip, (loss_fft, loss_amp, loss_pha), extra_pair, region = pixel_losses()
@@ -145,6 +201,13 @@ class TrainStep:
         loss_gan = ops.bce_relativistic(dt, pf, pr, 0, 0.9, da=ops.View(g_pf.t, 1, 0), gscale=self.lambda_gan)
         g_fake = self.D.backward(dctx_f, g_pf, grads=None, need_input_grad=True)
         ops.axpby(g_fake, g_fake, g_trip, 1.0, 1.0)
+        label_out = None
+        if lab is not None:
+            # the heads of the fake pair, on the caller's stream on both forms of the step (same launches, same order: same bits)
+            probs_g, ll_g, dl_g = ops.softmax_ce_heads(self.D.heads(dctx_f.ins[0]), lab[1], self.label_weights, 1.0, classes=self.D.aux_classes,
+                                                       targets_host=lab[2])
+            self.D.heads_input_grad(g_fake, dl_g)
+            label_out = {"loss_label": ll_g[3], "fake_probs": probs_g}
         extra = None
         if extra_pair is not None:
             extra, g_extra = extra_pair
@@ -162,6 +225,17 @@ class TrainStep:
         (pr2, dctx_r), (pf2, dctx_f2) = self.D.forward_pair(real_B, real_A, fake, real_A, power_iter=True, save=True)
         g_pr, g_pf2 = self._gl(pr2), self._gl(pf2)
         loss_d = ops.bce_relativistic(dt, pr2, pf2, 1, 0.9, 0.0, da=ops.View(g_pr.t, 1, 0), db=ops.View(g_pf2.t, 1, 0))
+        if lab is not None:
+            # real pair against the real labels, fake pair against the drawn ones; 0.5 * d_label_scale is each sum's factor in loss_D (DB1:609), so the
+            # kernel's total is half the logged term (a power of two: 2 * total is the same float as the sum scaled by d_label_scale alone)
+            hs = 0.5 * self.d_label_scale
+            ones = (1.0, 1.0, 1.0)
+            probs_r, ll_r, dl_r = ops.softmax_ce_heads(self.D.heads(dctx_r.ins[0]), lab_real[1], ones, hs, classes=self.D.aux_classes, targets_host=lab_real[2])
+            probs_f, ll_f, dl_f = ops.softmax_ce_heads(self.D.heads(dctx_f2.ins[0]), lab_gen[1], ones, hs, classes=self.D.aux_classes, targets_host=lab_gen[2])
+            # the heads' gradients first: they need nothing from the convolution backward, and their 14 MB bucket is the first in D's order
+            self.D.heads_wgrad(dctx_r.ins[0], dl_r, dctx_f2.ins[0], dl_f, self.dflat.grad_views, accumulate=False, hook=self.d_reduce.ready)
+            label_out.update(real_loss_label=2.0 * ll_r[3], fake_loss_label=2.0 * ll_f[3], d_real_probs=probs_r, d_fake_probs=probs_f)
+            loss_d = loss_d + (ll_r[3] + ll_f[3])
         self.D.backward(dctx_r, g_pr, grads=self.dflat.grad_views, need_input_grad=False, accumulate=False)
         self.D.backward(dctx_f2, g_pf2, grads=self.dflat.grad_views, need_input_grad=False, accumulate=True, hook=self.d_reduce.ready)
         dscale = self.d_reduce.finish()
@@ -170,6 +244,8 @@ class TrainStep:
         ops.arena_end(self.dev)
         self._invalidate_module_cores()
         loss_g = self.lambda_gan * loss_gan + self.lambda_trip * loss_trip + self.lambda_fft * loss_fft
+        if label_out is not None:
+            loss_g = loss_g + label_out["loss_label"]
         if extra is not None:
             loss_g = loss_g + extra.reshape(loss_g.shape).to(loss_g.dtype)
         loss_temp = None
@@ -183,6 +259,8 @@ class TrainStep:
             self.last["loss_temp_g"] = loss_temp
         if extra is not None:
             self.last["loss_extra_g"] = extra.reshape(())
+        if label_out is not None:                                 # loss_label / real_loss_label / fake_loss_label, and the heads' probabilities [N,9]
+            self.last.update({k: (v.reshape(()) if v.numel() == 1 else v) for k, v in label_out.items()})
         if region is not None:
             loss_reg, loss_amp_reg, loss_pha_reg = region
             self.last["loss_G"] = self.last["loss_G"] + self.lambda_region * loss_reg
@@ -190,7 +268,7 @@ class TrainStep:
         # Every logged loss but the KL regional term is a batch mean, so the mean over ranks is the global-batch value. With region_fft="kl" the
         # softmax runs over each rank's shard: loss_FFT_reg, loss_Amp_reg, loss_Pha_reg and their share of loss_G are the mean of per-shard values.
         if parallel.collectives_active():
-            keys = [k for k in self.last if k != "fake_B"]
+            keys = [k for k in self.last if self.last[k].numel() == 1]      # the scalars (not fake_B, not the heads' probabilities)
             packed = torch.stack([self.last[k].reshape(()).float() for k in keys])
             parallel.all_reduce_mean(packed)
             for i, k in enumerate(keys):

@@ -247,6 +247,21 @@ def region_weights(kind):
     raise ops._lib.TfcError(f"region_weights: kind={kind!r} ('l1' or 'kl')")
 
 
+def debias_weights(kind):
+    """TrainStep keyword values of the label-conditioned 4-patch scripts (TFCGAN_multigpu_patchFFT_debiased.py "DB1", ..._V2.py, ..._V3.py) without their
+    LPIPS and temperature terms; use with patches=4:
+      v1 (DB1:572): loss_G = GAN + triplet + label + 0.001 FFT; G is fed the drawn labels, loss_label is taken against them (DB1:508, :522)
+      v2 (DB2:582): loss_G = GAN + label + 0.001 FFT; G is fed the real labels (DB2:512, :530); the discriminator's label sums carry 1/3 (DB2:611, :617)
+      v3 (DB3:583): v2 with the ethnicity term of loss_label weighted 10 (DB3:531); the discriminator's label sums stay unweighted (DB3:612, :618)"""
+    if kind == "v1":
+        return {"lambda_gan": 1.0, "lambda_fft": 0.001, "lambda_trip": 1.0, "labels": "generated", "label_weights": (1.0, 1.0, 1.0), "d_label_scale": 1.0}
+    if kind == "v2":
+        return {"lambda_gan": 1.0, "lambda_fft": 0.001, "lambda_trip": 0.0, "labels": "real", "label_weights": (1.0, 1.0, 1.0), "d_label_scale": 1.0 / 3.0}
+    if kind == "v3":
+        return {"lambda_gan": 1.0, "lambda_fft": 0.001, "lambda_trip": 0.0, "labels": "real", "label_weights": (1.0, 10.0, 1.0), "d_label_scale": 1.0 / 3.0}
+    raise ops._lib.TfcError(f"debias_weights: kind={kind!r} ('v1', 'v2' or 'v3')")
+
+
 def calculate_ffts(*patches):
     """reference :323-375: calculate_ffts(fake_B1..fake_B16, B1..B16) -> loss_FFT (scalar, no gradient). With 8 tensors (fake_B1..4, B1..4 of
     128 x 128): the inline form of the 4-patch script (4P:499-511)."""

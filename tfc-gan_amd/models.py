@@ -243,13 +243,29 @@ class _GeneratorFn(torch.autograd.Function):
         return (None, gx, None) + tuple(grads[k] for k in names)
 
 
-class GeneratorUNet(nn.Module):
-    """reference :136-174. forward(x[N,3,S,S]) -> fake_B in (-1,1), fp32 NCHW (the reference casts to HalfTensor, :173)."""
+def _refuse_autograd(module, tensors):
+    """the label-conditioned forms train through TrainStep only: their modules' own forward carries no autograd graph, so it refuses to run where one
+    is expected instead of leaving None gradients behind"""
+    if torch.is_grad_enabled() and (any(p.requires_grad for p in module.parameters()) or any(torch.is_tensor(t) and t.requires_grad for t in tensors)):
+        raise ops._lib.TfcError(f"{type(module).__name__}: the label-conditioned forward (label plane / auxiliary heads) has no autograd backward. Train with "
+                                "tfc_gan_amd.TrainStep(G, D, **tfc_gan_amd.debias_weights(kind), patches=4), which runs its hand-written backward; "
+                                "call the module itself under torch.no_grad() (sample_images, inference).")
 
-    def __init__(self, img_shape):
+
+class GeneratorUNet(nn.Module):
+    """reference :136-174. forward(x[N,3,S,S]) -> fake_B in (-1,1), fp32 NCHW (the reference casts to HalfTensor, :173).
+    labels=3: the label-conditioned generator of TFCGAN_multigpu_patchFFT_debiased.py:142-186 -- fc = nn.Linear(3, h*w) of the labels, reshaped to a
+    plane, is the 4th input channel of down1; forward(x, labels[N,3])."""
+
+    def __init__(self, img_shape, labels=0):
         super().__init__()
         channels, self.h, self.w = img_shape
-        self.down1 = UNetDown(channels, 64, normalize=False)
+        if labels not in (0, 3):
+            raise ops._lib.TfcError(f"GeneratorUNet: labels={labels} (0: the plain generator, 3: gender / ethnicity / age through fc)")
+        self.labels = labels
+        if labels:
+            self.fc = nn.Linear(labels, self.h * self.w)        # first, as in the reference: state_dict() lists fc.* ahead of down1
+        self.down1 = UNetDown(channels + (1 if labels else 0), 64, normalize=False)
         self.down2 = UNetDown(64, 128)
         self.down3 = UNetDown(128, 256, dropout=0.5)
         self.down4 = UNetDown(256, 512, dropout=0.5)
@@ -269,14 +285,14 @@ class GeneratorUNet(nn.Module):
 
     def named_core_params(self):
         sd = dict(self.named_parameters())
-        return {k: sd[k] for k in nets.g_param_names()}
+        return {k: sd[k] for k in nets.g_param_names(self.labels)}
 
     def _core_for(self, device):
         dt = ops.dt_of(self.compute_dtype or get_compute_dtype())
         params = self.named_core_params()
         key = (dt, str(device), self._weights_gen) + tuple((p.data_ptr(), p._version) for p in params.values())
         if self._core is None or self._core.dt != dt:
-            self._core = nets.GeneratorCore(dt, self.channels)
+            self._core = nets.GeneratorCore(dt, self.channels, self.labels)
         if key != self._core_key:
             for k, p in params.items():
                 if p.dtype != torch.float32 or not p.is_cuda:
@@ -286,8 +302,16 @@ class GeneratorUNet(nn.Module):
             self._core_key = key
         return self._core
 
-    def forward(self, x):
+    def forward(self, x, labels=None):
         _refuse_replica(self)
+        if (labels is not None) != bool(self.labels):
+            raise ops._lib.TfcError("GeneratorUNet: forward(x, labels) belongs to GeneratorUNet(img_shape, labels=3), forward(x) to the plain generator")
+        if self.labels:
+            _refuse_autograd(self, (x, labels))
+            core = self._core_for(x.device)
+            fake, _ = core.forward(x.detach().float().contiguous(), seed=_next_seed(self), train=self.training, save=False,
+                                   labels=labels.detach().to(x.device).float())
+            return fake
         params = self.named_core_params()
         return _GeneratorFn.apply(self, x, _next_seed(self), *params.values())
 
@@ -319,9 +343,11 @@ class _DiscriminatorFn(torch.autograd.Function):
 
 
 class Discriminator1(nn.Module):
-    """reference :182-211 (spectral-norm PatchGAN). forward(img_A, img_B) -> logits [N,1,S/16,S/16] fp32."""
+    """reference :182-211 (spectral-norm PatchGAN). forward(img_A, img_B) -> logits [N,1,S/16,S/16] fp32.
+    aux_classes=(2, 4, 3): the label-conditioned discriminator of TFCGAN_multigpu_patchFFT_debiased.py:194-233 -- aux_gender / aux_ethn / aux_age, each
+    nn.Sequential(nn.Linear(6*h*w, C), nn.Softmax()) on the flattened input; forward then returns (logits, gender_hat, ethn_hat, age_hat)."""
 
-    def __init__(self, img_shape):
+    def __init__(self, img_shape, aux_classes=None):
         super().__init__()
         channels, self.h, self.w = img_shape
 
@@ -332,6 +358,12 @@ class Discriminator1(nn.Module):
         self.model = nn.Sequential(*discriminator_block(channels * 2, 64), *discriminator_block(64, 128),
                                    *discriminator_block(128, 256), *discriminator_block(256, 512),
                                    nn.ZeroPad2d((1, 0, 1, 0)), nn.Conv2d(512, 1, 4, padding=1, bias=False))
+        self.aux_classes = tuple(aux_classes) if aux_classes else None
+        if self.aux_classes:
+            if self.aux_classes != tuple(c for _, c in nets.D_AUX):
+                raise ops._lib.TfcError(f"Discriminator1: aux_classes={aux_classes} (None, or (2, 4, 3): gender, ethnicity, age as in the reference)")
+            for name, c in nets.D_AUX:
+                setattr(self, name, nn.Sequential(nn.Linear(channels * 2 * self.h * self.w, c), nn.Softmax(dim=1)))
         self.channels = channels
         self.compute_dtype = None
         self._core = None
@@ -340,7 +372,7 @@ class Discriminator1(nn.Module):
 
     def named_core_params(self):
         sd = dict(self.named_parameters())
-        return {k: sd[k] for k in nets.d_param_names()}
+        return {k: sd[k] for k in nets.d_param_names(bool(self.aux_classes))}
 
     def named_core_buffers(self):
         sd = dict(self.named_buffers())
@@ -356,7 +388,7 @@ class Discriminator1(nn.Module):
         params, bufs = self.named_core_params(), self.named_core_buffers()
         key = (dt, str(device), self._weights_gen) + tuple((p.data_ptr(), p._version) for p in params.values()) + tuple(b.data_ptr() for b in bufs.values())
         if self._core is None or self._core.dt != dt:
-            self._core = nets.DiscriminatorCore(dt, self.channels)
+            self._core = nets.DiscriminatorCore(dt, self.channels, self.aux_classes)
         if key != self._core_key:
             for k, p in list(params.items()) + list(bufs.items()):
                 if p.dtype != torch.float32 or not p.is_cuda:
@@ -368,6 +400,16 @@ class Discriminator1(nn.Module):
 
     def forward(self, img_A, img_B):
         _refuse_replica(self)
+        if self.aux_classes:
+            _refuse_autograd(self, (img_A, img_B))
+            core = self._core_for(img_A.device)
+            x8 = ops.pack_nhwc8(core.dt, img_A.detach().float(), img_B.detach().float())
+            logits, _ = core.forward(img_A.detach().float().contiguous(), img_B.detach().float().contiguous(), power_iter=self.training, save=False)
+            N = x8.N
+            probs, _, _ = ops.softmax_ce_heads(core.heads(x8), torch.zeros((N, 3), dtype=torch.int32, device=img_A.device), want_grad=False,
+                                               classes=self.aux_classes)
+            hats = torch.split(probs, list(self.aux_classes), dim=1)
+            return (logits.t[..., 0].reshape(N, 1, logits.H, logits.W).float(),) + tuple(h.contiguous() for h in hats)
         params = self.named_core_params()
         return _DiscriminatorFn.apply(self, img_A, img_B, *params.values())
 

@@ -105,26 +105,41 @@ def down_weight_key(name):
     return f"{name}.model.0.weight"
 
 
-def g_param_names():
+G_FC = ["fc.weight", "fc.bias"]         # the label plane of the label-conditioned generator (TFCGAN_multigpu_patchFFT_debiased.py:149)
+# the auxiliary classifier heads of the label-conditioned discriminator (..._debiased.py:218-220): (child name, classes)
+D_AUX = [("aux_gender", 2), ("aux_ethn", 4), ("aux_age", 3)]
+
+
+def g_param_names(labels=0):
     names = [down_weight_key(n) for n, *_ in G_DOWN] + [f"{n}.model.0.weight" for n, *_ in G_UP]
-    return names + ["final.2.weight", "final.2.bias"]
+    return names + ["final.2.weight", "final.2.bias"] + (G_FC if labels else [])
 
 
 def g_backward_order():
-    """Parameter names in the order their gradients become final during backward (bucket order for DDP)."""
+    """Parameter names in the order their gradients become final during backward (bucket order for DDP). fc.* (label-conditioned generator only) come
+    last: they hang off the input gradient of down1."""
     return (["final.2.weight", "final.2.bias"] + [f"{n}.model.0.weight" for n, *_ in reversed(G_UP)]
-            + [down_weight_key(n) for n, *_ in reversed(G_DOWN)])
+            + [down_weight_key(n) for n, *_ in reversed(G_DOWN)] + G_FC)
 
 
-def d_param_names():
+def d_aux_names():
+    out = []
+    for n, _ in D_AUX:
+        out += [f"{n}.0.weight", f"{n}.0.bias"]
+    return out
+
+
+def d_param_names(aux=False):
     out = []
     for i, _, _ in D_BLOCKS:
         out += [f"model.{i}.bias", f"model.{i}.parametrizations.weight.original"]
-    return out + ["model.13.weight"]
+    return out + ["model.13.weight"] + (d_aux_names() if aux else [])
 
 
 def d_backward_order():
-    out = ["model.13.weight"]
+    """the heads' parameters (label-conditioned discriminator only) come first: their gradients need nothing from the convolution backward, so their
+    14 MB bucket can leave before it starts"""
+    out = d_aux_names() + ["model.13.weight"]
     for i, _, _ in reversed(D_BLOCKS):
         out += [f"model.{i}.parametrizations.weight.original", f"model.{i}.bias"]
     return out
@@ -139,9 +154,12 @@ class _Ctx:
 
 
 class GeneratorCore:
-    def __init__(self, dt=DT_BF16, channels=3):
+    def __init__(self, dt=DT_BF16, channels=3, labels=0):
         self.dt = dt
         self.channels = channels
+        self.labels = int(labels)                                 # 3: fc(labels) is down1's extra input channel (label-conditioned generator)
+        self.in_channels = channels + (1 if self.labels else 0)
+        self.down = [(G_DOWN[0][0], self.in_channels) + G_DOWN[0][2:]] + G_DOWN[1:]
         self.params = None
         self.packed = {}
         self._ws = None
@@ -157,7 +175,7 @@ class GeneratorCore:
         """re-pack every operand stream (fwd + dgrad) from the current weights: ONE launch over a device-resident plan"""
         if getattr(self, "_plan", None) is None:
             P, jobs, slots = self.params, [], []
-            for name, cin, cout, _, _ in G_DOWN:
+            for name, cin, cout, _, _ in self.down:
                 jobs.append((OP_CONV, 0, P[down_weight_key(name)], cin, cout)); slots.append((name, "fwd"))
                 if name != "down1":
                     jobs.append((OP_CONV, 1, P[down_weight_key(name)], cin, cout)); slots.append((name, "dgrad"))
@@ -172,10 +190,13 @@ class GeneratorCore:
         self._plan.run()
 
     # ---- forward ----
-    def forward(self, x, seed=0, train=True, save=True):
+    def forward(self, x, seed=0, train=True, save=True, labels=None):
         """x: fp32 NCHW [N,3,S,S] (S multiple of 64, >= 128). Returns (fake fp32 NCHW in (-1,1), ctx). down1 runs as ONE kernel (conv + LeakyReLU +
-        BlurPool, ops.first_block_fwd): its 266 MB conv output is never written, the backward needs its signs only and gets them as sign words."""
-        ops.require_gpu(x)
+        BlurPool, ops.first_block_fwd): its 266 MB conv output is never written, the backward needs its signs only and gets them as sign words.
+        labels: fp32 [N,3] on the device, for a label-conditioned core (its fc plane is written as input channel 3 by the packing kernel)."""
+        ops.require_gpu(x, labels)
+        if (labels is not None) != bool(self.labels):
+            raise ops._lib.TfcError("GeneratorCore: labels go with a label-conditioned generator (labels=3) and only with it")
         if not self.packed:
             self.repack()
         dt, dev = self.dt, x.device
@@ -183,7 +204,14 @@ class GeneratorCore:
         assert C == self.channels and S == S2 and S % 64 == 0 and S >= 128, "GeneratorUNet needs square inputs, S % 64 == 0, S >= 128"
         ctx = _Ctx()
         ctx.N, ctx.S, ctx.seed, ctx.train = N, S, seed, train
-        x8 = ops.pack_nhwc8(dt, x)
+        if self.labels:
+            if tuple(labels.shape) != (N, self.labels):
+                raise ops._lib.TfcError(f"GeneratorCore: labels {tuple(labels.shape)} for a batch of {N} (expected [N, {self.labels}])")
+            labels = labels.contiguous().float()
+            x8 = ops.pack_nhwc8_labels(dt, x, labels, self.params["fc.weight"], self.params["fc.bias"])
+        else:
+            x8 = ops.pack_nhwc8(dt, x)
+        ctx.labels = labels
         # concat buffers: cat[k] = (up_k output | skip) at the resolution of the skip
         sizes = [S >> (i + 1) for i in range(6)]                 # pooled sizes of down1..down6: 128,64,32,16,8,4
         cat = {}
@@ -195,7 +223,7 @@ class GeneratorCore:
         ctx.x8, ctx.cat, ctx.d6 = x8, cat, d6
         ctx.raw, ctx.stats, ctx.dins = [], [], []
         cur = x8
-        for i, (name, cin, cout, normalize, drop) in enumerate(G_DOWN):
+        for i, (name, cin, cout, normalize, drop) in enumerate(self.down):
             h = cur.H
             if i < 5:
                 up = skip_of[i]
@@ -266,6 +294,7 @@ class GeneratorCore:
         dt, N = self.dt, ctx.N
         dev = g_fake.device
         ch = self.channels
+        want_gx, need_input_grad = need_input_grad, need_input_grad or bool(self.labels)   # fc trains through down1's input gradient (channel 3)
         gb = grads["final.2.bias"]
         if not accumulate:
             gb.zero_()
@@ -315,7 +344,7 @@ class GeneratorCore:
             g_cat = g_in                                          # gradient of the next concat buffer (or of d6 when j == 0)
         g_cur = g_cat                                             # = gradient of d6
         for i in range(5, -1, -1):
-            name, cin, cout, normalize, drop = G_DOWN[i]
+            name, cin, cout, normalize, drop = self.down[i]
             raw, stats, din = ctx.raw[i], ctx.stats[i], ctx.dins[i]
             Hc = din.H - 1
             dp = drop if ctx.train else 0.0
@@ -356,18 +385,30 @@ class GeneratorCore:
                 g_cur = tgt
             elif need_input_grad:
                 w1 = self.params[key]
-                if dt == DT_BF16 and cout == 64 and self.channels <= 4:
-                    return ops.conv_dgrad_image(dt, d_raw, N, din.H, din.W, cin, w1, None, self.channels)   # rows-packed kernel, fp32 NCHW out
-                gx8 = new_act(N, din.H, din.W, din.pitch, dt, dev)
-                ops.conv_dgrad(dt, OP_CONV, d_raw, N, din.H, din.W, cin, cout, ops.pack_weight(dt, OP_CONV, 1, w1.contiguous(), cin, cout), gx8)
-                return ops.unpack_nchw(dt, gx8, self.channels, c0=0)
+                if dt == DT_BF16 and cout == 64 and cin <= 4:
+                    gx = ops.conv_dgrad_image(dt, d_raw, N, din.H, din.W, cin, w1, None, cin)   # rows-packed kernel, fp32 NCHW out
+                else:
+                    gx8 = new_act(N, din.H, din.W, din.pitch, dt, dev)
+                    ops.conv_dgrad(dt, OP_CONV, d_raw, N, din.H, din.W, cin, cout, ops.pack_weight(dt, OP_CONV, 1, w1.contiguous(), cin, cout), gx8)
+                    gx = ops.unpack_nchw(dt, gx8, cin, c0=0)
+                if not self.labels:
+                    return gx
+                # channel 3 is the gradient of the label plane: d fc.weight / d fc.bias, the last gradients of the generator
+                def _fc_grad(gx=gx):                              # with the other parameter gradients and their hooks: on the side stream
+                    ops.label_plane_bwd(gx, ctx.labels, grads["fc.weight"], grads["fc.bias"], ch=self.channels, accumulate=accumulate)
+                    if hook:
+                        hook("fc.weight")
+                        hook("fc.bias")
+                _on_side(dev, _fc_grad, gx)
+                return gx[:, :self.channels].contiguous() if want_gx else None
         return None
 
 
 class DiscriminatorCore:
-    def __init__(self, dt=DT_BF16, channels=3):
+    def __init__(self, dt=DT_BF16, channels=3, aux_classes=None):
         self.dt = dt
         self.channels = channels
+        self.aux_classes = tuple(aux_classes) if aux_classes else None      # (2, 4, 3): the three auxiliary classifier heads on the raw input
         self.params = None
         self.buffers = None
         self.head_packed = {}
@@ -474,6 +515,34 @@ class DiscriminatorCore:
         ops.patchgan_head_fwd(dt, cur, self.params["model.13.weight"], View(logits.t, 1, 0))
         ctx.p4 = cur
         return View(logits.t, 1, 0), (ctx if save else None)
+
+    # ---- auxiliary classifier heads (label-conditioned discriminator): three Linear on the flattened 6 x S x S input ----
+    def aux_params(self, src=None):
+        src = self.params if src is None else src
+        return [src[f"{n}.0.weight"] for n, _ in D_AUX], [src[f"{n}.0.bias"] for n, _ in D_AUX]
+
+    def heads(self, x8):
+        """x8: the packed input of a call (ctx.ins[0] of chain()). Returns the heads' logits [N, sum classes] fp32 (the Softmax of the modules and the
+        reference's cross entropy on top of it live in ops.softmax_ce_heads)."""
+        if not self.aux_classes:
+            raise ops._lib.TfcError("DiscriminatorCore.heads: this discriminator has no auxiliary heads (aux_classes=None)")
+        ws, bs = self.aux_params()
+        return ops.aux_heads_fwd(self.dt, x8, ws, bs, self.aux_classes)
+
+    def heads_input_grad(self, g_img, dlogits):
+        """g_img (fp32 NCHW gradient of img_A, in place) += the heads' share"""
+        return ops.aux_heads_dgrad(g_img, self.aux_params()[0], dlogits, self.aux_classes)
+
+    def heads_wgrad(self, x_r, dl_r, x_f, dl_f, grads, accumulate=False, hook=None):
+        """gradients of the six head parameters from the real pair and the fake pair, straight into the torch-layout views `grads`"""
+        dws, dbs = self.aux_params(grads)
+
+        def _heads_wgrad():                                       # like every parameter gradient: on the side stream, hooks behind it; backward() joins
+            ops.aux_heads_wgrad(self.dt, x_r, dl_r, x_f, dl_f, dws, dbs, accumulate, self.aux_classes)
+            if hook:
+                for k in d_aux_names():
+                    hook(k)
+        _on_side(x_r.t.device, _heads_wgrad, dl_r, *([dl_f] if dl_f is not None else []))
 
     def forward_pair(self, a1, b1, a2, b2, power_iter=True, save=True):
         """forward(a1, b1) then forward(a2, b2), same results as the two calls in that order (the second power iteration follows the first). With the

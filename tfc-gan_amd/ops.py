@@ -562,6 +562,110 @@ def adam_step(p, g, m, v, lr, b1, b2, eps, step, gscale=1.0):
     check(lib().tfc_adam_step(stream_ptr(), _p(p), _p(g), _p(m), _p(v), p.numel(), lr, b1, b2, eps, step, gscale), "tfc_adam_step")
 
 
+# ---- label plane + auxiliary classifier heads (csrc/debias.hip; the label-conditioned 4-patch scripts) ---------------------------------------------
+AUX_CLASSES = (2, 4, 3)             # gender, ethnicity, age: reference TFCGAN_multigpu_patchFFT_debiased.py:218-220
+
+
+def _ptr3(ts):
+    return (ctypes.c_void_p * 3)(*[t.data_ptr() for t in ts])
+
+
+def _int3(v):
+    return (ctypes.c_int * 3)(*[int(i) for i in v])
+
+
+def _f32c(t, what):
+    if t.dtype != torch.float32 or not t.is_contiguous():
+        raise _lib.TfcError(f"{what} must be a contiguous fp32 tensor (got {t.dtype}, contiguous={t.is_contiguous()})")
+    return t
+
+
+def pack_nhwc8_labels(dt, img, labels, fc_w, fc_b):
+    """torch.cat((img, fc(labels).view(N,1,H,W)), 1) as the NHWC8 activation of the compute dtype: channels 0..2 img, 3 the label plane, 4..7 zero"""
+    require_gpu(img, labels, fc_w, fc_b)
+    img = img.contiguous().float()
+    labels = labels.contiguous().float()
+    N, C, H, W = img.shape
+    if C != 3 or tuple(labels.shape) != (N, 3) or tuple(fc_w.shape) != (H * W, 3) or tuple(fc_b.shape) != (H * W,):
+        raise _lib.TfcError(f"pack_nhwc8_labels: img {tuple(img.shape)}, labels {tuple(labels.shape)}, fc.weight {tuple(fc_w.shape)}, fc.bias "
+                            f"{tuple(fc_b.shape)} (expected [N,3,H,W], [N,3], [H*W,3], [H*W])")
+    out = new_act(N, H, W, 8, dt, img.device)
+    check(lib().tfc_pack_nhwc8_labels(stream_ptr(), dt, _p(img), _p(labels), _p(_f32c(fc_w, "fc.weight")), _p(_f32c(fc_b, "fc.bias")), out.ptr, N, H, W),
+          "tfc_pack_nhwc8_labels")
+    return out
+
+
+def label_plane_bwd(g, labels, d_fc_w, d_fc_b, ch=3, accumulate=False):
+    """g: fp32 NCHW input gradient [N,C,H,W] whose channel `ch` is the label plane's -> d fc.weight [H*W,3], d fc.bias [H*W] (written or accumulated)"""
+    require_gpu(g, labels, d_fc_w, d_fc_b)
+    N, C, H, W = g.shape
+    labels = labels.contiguous().float()
+    check(lib().tfc_label_plane_bwd(stream_ptr(), _p(_f32c(g, "g")), C, ch, _p(labels), _p(_f32c(d_fc_w, "d fc.weight")), _p(_f32c(d_fc_b, "d fc.bias")),
+                                    N, H, W, 1 if accumulate else 0), "tfc_label_plane_bwd")
+
+
+def aux_heads_fwd(dt, x: View, ws, bs, classes=AUX_CLASSES):
+    """x: the packed discriminator input [N,H,W,8]; ws / bs: the three heads' weights [C_h, 6*H*W] and biases [C_h] (fp32) -> logits [N, sum C_h]"""
+    require_gpu(x.t, *ws, *bs)
+    logits = torch.empty((x.N, sum(classes)), dtype=torch.float32, device=x.t.device)
+    check(lib().tfc_aux_heads_fwd(stream_ptr(), dt, x.ptr, x.pitch, x.N, x.H, x.W, _ptr3([_f32c(w, "head weight") for w in ws]),
+                                  _ptr3([_f32c(b, "head bias") for b in bs]), _int3(classes), _p(logits), part_ws(x.t.device)), "tfc_aux_heads_fwd")
+    return logits
+
+
+def check_targets(targets, classes=AUX_CLASSES):
+    """targets: anything that np.asarray turns into [N,3] whole numbers (host values) -> int32 numpy [N,3]; refuses values outside [0, C_h)"""
+    import numpy as np
+    a = np.asarray(targets.detach().cpu() if isinstance(targets, torch.Tensor) else targets)
+    if a.ndim != 2 or a.shape[1] != 3:
+        raise _lib.TfcError(f"labels: shape {a.shape} (expected [N,3]: gender, ethnicity, age)")
+    r = np.rint(a.astype(np.float64))
+    if not np.array_equal(r, a.astype(np.float64)):
+        raise _lib.TfcError("labels: class indices must be whole numbers")
+    for h, c in enumerate(classes):
+        if r.shape[0] and (r[:, h].min() < 0 or r[:, h].max() >= c):
+            raise _lib.TfcError(f"labels: column {h} has a class outside [0, {c}) (values {r[:, h].min():g} .. {r[:, h].max():g})")
+    return np.ascontiguousarray(r.astype(np.int32))
+
+
+def softmax_ce_heads(logits, targets, weights=(1.0, 1.0, 1.0), scale=1.0, want_grad=True, classes=AUX_CLASSES, targets_host=None):
+    """logits [N, sum C_h] fp32, targets int32 [N,3] on the device (targets_host: the same as int32 numpy, validated by the library when given).
+    Returns (probs [N, sum C_h], losses [4] = three head losses + scale * weighted sum, dlogits or None)."""
+    require_gpu(logits, targets)
+    N = logits.shape[0]
+    assert targets.dtype == torch.int32 and targets.is_contiguous() and tuple(targets.shape) == (N, 3)
+    probs = torch.empty_like(logits)
+    losses = torch.empty(4, dtype=torch.float32, device=logits.device)
+    dl = torch.empty_like(logits) if want_grad else None
+    th = None
+    if targets_host is not None:
+        assert targets_host.dtype.name == "int32" and targets_host.shape == (N, 3) and targets_host.flags["C_CONTIGUOUS"]
+        th = targets_host.ctypes.data_as(ctypes.POINTER(ctypes.c_int))
+    check(lib().tfc_softmax_ce_heads(stream_ptr(), _p(_f32c(logits, "logits")), _p(targets), th, _int3(classes),
+                                     (ctypes.c_float * 3)(*[float(w) for w in weights]), float(scale), N, _p(probs), _p(losses), _p(dl)),
+          "tfc_softmax_ce_heads")
+    return probs, losses, dl
+
+
+def aux_heads_dgrad(g, ws, dlogits, classes=AUX_CLASSES):
+    """g [N,C>=3,H,W] fp32 (in place): g[:, :3] += the heads' gradient w.r.t. the img_A half of their input"""
+    require_gpu(g, dlogits, *ws)
+    N, C, H, W = g.shape
+    check(lib().tfc_aux_heads_dgrad(stream_ptr(), _p(_f32c(g, "g")), C, N, H, W, _ptr3([_f32c(w, "head weight") for w in ws]), _int3(classes),
+                                    _p(_f32c(dlogits, "dlogits"))), "tfc_aux_heads_dgrad")
+    return g
+
+
+def aux_heads_wgrad(dt, x_r: View, dl_r, x_f: View, dl_f, dws, dbs, accumulate=False, classes=AUX_CLASSES):
+    """weight / bias gradients of the three heads from the real pair (x_r, dl_r) and, when given, the fake pair, into the torch-layout gradients"""
+    require_gpu(x_r.t, dl_r, *dws, *dbs)
+    assert x_f is None or (x_f.t.shape == x_r.t.shape and x_f.pitch == x_r.pitch)
+    check(lib().tfc_aux_heads_wgrad(stream_ptr(), dt, x_r.ptr, _p(_f32c(dl_r, "dlogits")), None if x_f is None else x_f.ptr,
+                                    None if dl_f is None else _p(_f32c(dl_f, "dlogits")), x_r.pitch, x_r.N, x_r.H, x_r.W,
+                                    _ptr3([_f32c(w, "head weight gradient") for w in dws]), _ptr3([_f32c(b, "head bias gradient") for b in dbs]),
+                                    _int3(classes), 1 if accumulate else 0), "tfc_aux_heads_wgrad")
+
+
 # ---- STN21 localiser (vit.hip) ---------------------------------------------------------------------------------
 VIT_A_ROWS, VIT_A_TRANS, VIT_A_UNFOLD = 0, 1, 2
 VIT_B_WEIGHT, VIT_B_ROWS, VIT_B_UNFOLD = 0, 1, 2
