@@ -465,6 +465,27 @@ int tfc_aux_heads_dgrad(void* stream, float* g, int gC, int N, int H, int W, con
 int tfc_aux_heads_wgrad(void* stream, int dt, const void* x_r, const float* dl_r, const void* x_f, const float* dl_f, int x_pitch, int N, int H, int W,
                         float* const* dw3, float* const* db3, const int* nclass3_host, int accumulate);
 
+/* ---- edge mask of the MASK-4 script (TFC-GAN-FFT/TFCGAN_multigpu_patchFFT_experiment.py "4X" :385-390), forward and exact backward -----------
+ * g = 0.299 R + 0.587 G + 0.114 B; lap = (S49(g) - 49 g) / 96 (7x7 box sum, reflect padding 3); L = |lap|; mn, mx = min, max of L over the whole
+ * batch; Mn = (L - mn) / (mx - mn); Bl = gauss9(Mn) (sigma 1.6, reflect padding 4); M = max Bl over the batch; mask = Bl / M. fp32 throughout.
+ * Any H, W >= 8 (N*H*W < 2^31); a constant image (mx == mn) gives NaN as in the reference. All pointers are 16-byte aligned device pointers.
+ * ws: tfc_mask_ws_bytes(N, H, W) bytes that belong to ONE forward: the extrema, their tie counts and the backward's global sums live there between
+ * launches (floats 0..9: mn, mx, ties(mn), ties(mx), M, ties(M), dM per tie, L1 loss, dmx per tie, dmn per tie); nothing returns to the host. */
+size_t tfc_mask_ws_bytes(int N, int H, int W);
+/* img [N][3][H][W] -> lap [N][H][W] (signed), bl [N][H][W] (= Bl), ws */
+int tfc_mask_fwd(void* stream, const float* img, float* lap, float* bl, void* ws, int N, int H, int W);
+/* mask [N][H][W] = bl / M */
+int tfc_mask_scale(void* stream, const float* bl, const void* ws, float* mask, int N, int H, int W);
+/* dimg [N][3][H][W] = d/d img of sum(dout * mask) (dout [N][H][W] given, ref null), or of scale * mean|mask - ref| (ref [N][H][W] given, dout null;
+ * the loss is left in float 7 of ws and its gradient w.r.t. the mask in dout_buf). Exact: d/dM, d/dmx, d/dmn go to every position that attains the
+ * extremum, split evenly; sign(0) = 0 through the abs; both filters run as the true adjoints of their reflect-padded forms. dmn: N*H*W floats of
+ * scratch. dimg null (with ref): the loss alone. */
+int tfc_mask_bwd(void* stream, const float* lap, const float* bl, void* ws, const float* dout, const float* ref, float scale, float* dout_buf,
+                 float* dmn, float* dimg, int N, int H, int W);
+/* out [N][H][W][8] in the compute dtype: channels 0..2 = img [N][3][H][W] fp32, channel 3 = plane [N][H][W] fp32 (divided by *plane_div, a device
+ * float, when it is not null: Bl with its M), channels 4..7 = 0. H * W a multiple of 4. */
+int tfc_pack_nhwc8_plane(void* stream, int dt, const float* img, const float* plane, const float* plane_div, void* out, int N, int H, int W);
+
 #ifdef __cplusplus
 }
 #endif

@@ -8,6 +8,7 @@ Discriminator1 (alias Discriminator), weights_init_normal, make_16_patches, the 
 make_4_patches and the 4-patch heads of TFCGAN_multigpu_patchFFT.py / TFCGAN_multigpu_globalFFT.py (patches=4),
 the regional FFT loss of the ..._withregion_FFT(.py|_KL.py) scripts (TrainStep(region_fft=...)),
 the label-conditioned step of ..._debiased(.py|_V2.py|_V3.py) (TrainStep(labels=...), GeneratorUNet(labels=3), Discriminator1(aux_classes=(2, 4, 3))),
+the edge-mask step of ..._experiment.py (TrainStep(mask=True), GeneratorUNet(mask=True), mask_maker, mask_l1_loss),
 FFT_Components / fft_components / calculate_ffts, and the fused TrainStep + data-parallel layer.
 """
 import os as _os
@@ -29,7 +30,7 @@ from .stn import Warp, affine_warp, morph_gradient, morph_triplet, triplet_margi
 from .synthetic import synthetic_pairs, synthetic_temperatures  # noqa: F401
 from .inference import global_grid, load_clean_state, save_checkpoint, stitch_16_patches, stitch_patches  # noqa: F401
 from .losses import (ContrastiveLoss, FFT_Components, calculate_ffts, color_jitter_params, color_jitter_thermal, debias_weights,  # noqa: F401
-                     fft_components, global_fft_loss, make_4_patches, make_16_patches, mse_spec, other_spec, patch_fft_loss, patch_first_flat_index,
+                     fft_components, global_fft_loss, make_4_patches, make_16_patches, mask_l1_loss, mask_maker, mask_weights, mse_spec, other_spec, patch_fft_loss, patch_first_flat_index,
                      patch_triplet_loss, region_weights, regional_fft_components, regional_fft_loss, sample_spectra, temperature_triplet_loss,
                      vectorize_temps)
 from .metrics import EvalAccumulator, bhattacharyya, mutual_information, ncc, psnr, ssim, to_gray, to_uint8  # noqa: F401
@@ -38,6 +39,6 @@ from .models import (BlurPool, Discriminator, Discriminator1, GeneratorUNet, UNe
 
 __all__ = ["UNetDown", "UNetUp", "GeneratorUNet", "Discriminator1", "Discriminator", "BlurPool", "weights_init_normal",
            "make_16_patches", "make_4_patches", "patch_first_flat_index", "stitch_patches", "ContrastiveLoss", "patch_triplet_loss", "FFT_Components", "fft_components", "calculate_ffts",
-           "patch_fft_loss", "global_fft_loss", "regional_fft_components", "regional_fft_loss", "region_weights", "debias_weights", "mse_spec", "other_spec", "psnr", "ssim", "bhattacharyya", "ncc", "mutual_information", "to_uint8", "to_gray",
+           "patch_fft_loss", "global_fft_loss", "regional_fft_components", "regional_fft_loss", "region_weights", "debias_weights", "mask_weights", "mask_maker", "mask_l1_loss", "mse_spec", "other_spec", "psnr", "ssim", "bhattacharyya", "ncc", "mutual_information", "to_uint8", "to_gray",
            "EvalAccumulator", "sample_spectra", "vectorize_temps", "temperature_triplet_loss", "color_jitter_thermal",
            "color_jitter_params", "synthetic_pairs", "synthetic_temperatures", "load_clean_state", "save_checkpoint", "stitch_16_patches", "global_grid", "TrainStep", "STN21Step", "LPIPS", "ImageDataset", "LabelledImageDataset", "TestImageDataset", "DeviceLoader", "pair_resize_normalize", "Warp", "affine_warp", "morph_gradient", "morph_triplet", "triplet_margin_rows", "set_compute_dtype", "get_compute_dtype", "set_batch_invariant", "get_batch_invariant", "build", "TfcError"]

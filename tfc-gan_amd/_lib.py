@@ -12,7 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _ROOT = os.path.dirname(_HERE)
 CSRC = os.path.join(_HERE, "csrc")
 SO_PATH = os.path.join(_HERE, "libtfcgan_hip.so")
-SOURCES = ["api.hip", "igemm.hip", "elementwise.hip", "losses.hip", "stn.hip", "lpips.hip", "input.hip", "probe.hip", "vit.hip", "metrics.hip", "debias.hip"]
+SOURCES = ["api.hip", "igemm.hip", "elementwise.hip", "losses.hip", "stn.hip", "lpips.hip", "input.hip", "probe.hip", "vit.hip", "metrics.hip", "debias.hip", "mask.hip"]
 HEADERS = ["common.h", "tfc_desc.h", "pack_math.h"]
 PUBLIC_HEADER = os.path.join(_ROOT, "include", "tfc_gan.h")
 
@@ -86,7 +86,10 @@ GUARDED_KERNELS = ("tfc_igemm2_kernel", "tfc_wgrad", "tfc_patch_triplet_kernelIL
                    "tfc_fft_cols_kernelILi128E", "tfc_spectrum_kernelILi128E", "tfc_dft_rect_cols_kernel",
                    # the label plane and the auxiliary heads (debias.hip): up to 96 weights or sums per thread, sized to stay in registers
                    "tfc_pack_labels_kernel", "tfc_label_plane_bwd_kernel", "tfc_aux_heads_fwd_kernel", "tfc_aux_heads_dgrad_kernel",
-                   "tfc_aux_heads_wgrad_kernel", "tfc_softmax_ce_heads_kernel")
+                   "tfc_aux_heads_wgrad_kernel", "tfc_softmax_ce_heads_kernel",
+                   # the edge mask (mask.hip): tile kernels with their taps and four outputs per thread in registers
+                   "tfc_mask_lap_kernel", "tfc_mask_blur_kernel", "tfc_mask_blur_bwd_kernel", "tfc_mask_lap_bwd_kernel", "tfc_mask_dot_kernel",
+                   "tfc_mask_final_extrema_kernel", "tfc_mask_final_sums_kernel", "tfc_mask_scale_kernel", "tfc_pack_plane_kernel")
 
 
 def check_no_spills(remarks):
@@ -212,6 +215,11 @@ PROTOTYPES = {
     "tfc_softmax_ce_heads": (_i, [_vp, _vp, _vp, _c.POINTER(_i), _c.POINTER(_i), _c.POINTER(_f), _f, _i, _vp, _vp, _vp]),
     "tfc_aux_heads_dgrad": (_i, [_vp, _vp, _i, _i, _i, _i, _c.POINTER(_vp), _c.POINTER(_i), _vp]),
     "tfc_aux_heads_wgrad": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _c.POINTER(_vp), _c.POINTER(_vp), _c.POINTER(_i), _i]),
+    "tfc_mask_ws_bytes": (_sz, [_i, _i, _i]),
+    "tfc_mask_fwd": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i]),
+    "tfc_mask_scale": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i]),
+    "tfc_mask_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _i, _i, _i]),
+    "tfc_pack_nhwc8_plane": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i]),
 }
 
 

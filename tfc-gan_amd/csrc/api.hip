@@ -1409,6 +1409,61 @@ extern "C" int tfc_aux_heads_wgrad(void* stream, int dt, const void* x_r, const 
   return 0;
 }
 
+// ---- edge mask of the MASK-4 script (mask.hip) -------------------------------------------------------------------------------------------------
+long long tfc_mask_nblk(int N, int H, int W);
+int tfc_mask_stats_floats(void);
+hipError_t tfc_launch_mask_fwd(const float* img, float* lap, float* bl, void* ws, int N, int H, int W, hipStream_t st);
+hipError_t tfc_launch_mask_scale(const float* bl, const void* ws, float* mask, long long total, hipStream_t st);
+hipError_t tfc_launch_mask_bwd(const float* lap, const float* bl, void* ws, const float* dout, const float* ref, float scale, float* dout_buf,
+                               float* dmn, float* dimg, int N, int H, int W, hipStream_t st);
+hipError_t tfc_launch_pack_plane(int dt, const float* img, const float* plane, const float* Mdev, void* out, int N, int HW, hipStream_t st);
+
+// both filters reflect once (padding 3 and 4): a side below 8 would need a second reflection for the blur of an 8 x 8 tile's halo
+#define REQUIRE_MASK_IMAGE(N, H, W) do { \
+    REQUIRE(N > 0 && N <= 65535 && H >= 8 && W >= 8 && H <= (1 << 20) && W <= (1 << 20), "bad dims N=%d H=%d W=%d (1 <= N <= 65535; H, W >= 8)", N, H, W); \
+    REQUIRE((long long)N * H * W < (1LL << 31), "N*H*W=%lld must stay below 2^31", (long long)N * H * W); \
+  } while (0)
+
+extern "C" size_t tfc_mask_ws_bytes(int N, int H, int W) {
+  if (N <= 0 || H < 8 || W < 8) return 0;
+  return (size_t)tfc_mask_stats_floats() * sizeof(float) + (size_t)tfc_mask_nblk(N, H, W) * 16;
+}
+
+extern "C" int tfc_mask_fwd(void* stream, const float* img, float* lap, float* bl, void* ws, int N, int H, int W) {
+  REQUIRE_MASK_IMAGE(N, H, W);
+  REQUIRE(al16(img) && al16(lap) && al16(bl) && al16(ws), "img / lap / bl / ws must be 16-byte aligned device pointers");
+  CHECK_HIP(tfc_launch_mask_fwd(img, lap, bl, ws, N, H, W, (hipStream_t)stream), "tfc_mask_fwd");
+  return 0;
+}
+
+extern "C" int tfc_mask_scale(void* stream, const float* bl, const void* ws, float* mask, int N, int H, int W) {
+  REQUIRE_MASK_IMAGE(N, H, W);
+  REQUIRE(al16(bl) && al16(ws) && al16(mask), "bl / ws / mask must be 16-byte aligned device pointers");
+  CHECK_HIP(tfc_launch_mask_scale(bl, ws, mask, (long long)N * H * W, (hipStream_t)stream), "tfc_mask_scale");
+  return 0;
+}
+
+extern "C" int tfc_mask_bwd(void* stream, const float* lap, const float* bl, void* ws, const float* dout, const float* ref, float scale, float* dout_buf,
+                            float* dmn, float* dimg, int N, int H, int W) {
+  REQUIRE_MASK_IMAGE(N, H, W);
+  REQUIRE(al16(lap) && al16(bl) && al16(ws), "lap / bl / ws must be 16-byte aligned device pointers");
+  REQUIRE((dout != nullptr) != (ref != nullptr), "exactly one of dout (an upstream gradient) and ref (the L1 loss against it) is given");
+  REQUIRE(al16(dout ? dout : ref), "dout / ref must be a 16-byte aligned device pointer");
+  REQUIRE(!ref || al16(dout_buf), "with ref, dout_buf (N*H*W floats, 16-byte aligned) receives the loss's gradient w.r.t. the mask");
+  REQUIRE(dimg == nullptr || (al16(dimg) && al16(dmn)), "dimg and dmn (N*H*W floats) must be 16-byte aligned device pointers");
+  REQUIRE(dimg != nullptr || ref != nullptr, "without dimg only the L1 loss (ref) is left to compute");
+  CHECK_HIP(tfc_launch_mask_bwd(lap, bl, ws, dout, ref, scale, dout_buf, dmn, dimg, N, H, W, (hipStream_t)stream), "tfc_mask_bwd");
+  return 0;
+}
+
+extern "C" int tfc_pack_nhwc8_plane(void* stream, int dt, const float* img, const float* plane, const float* plane_div, void* out, int N, int H, int W) {
+  REQUIRE(dt == TFC_DT_BF16 || dt == TFC_DT_F32 || dt == TFC_DT_BF16X3, "bad dtype %d", dt);
+  REQUIRE_IMAGE(N, H, W);
+  REQUIRE(al16(img) && al16(plane) && al16(out), "img / plane / out must be 16-byte aligned device pointers");
+  CHECK_HIP(tfc_launch_pack_plane(dt, img, plane, plane_div, out, N, H * W, (hipStream_t)stream), "tfc_pack_nhwc8_plane");
+  return 0;
+}
+
 extern "C" int tfc_probe_mfma(void* stream, float* out) {
   REQUIRE(out, "out is null");
   CHECK_HIP(tfc_launch_probe(out, (hipStream_t)stream), "tfc_probe_mfma");

@@ -26,6 +26,15 @@ losses.region_weights gives each script's weights). It carries no gradient in th
              in every variant (DB1:603-606, DB3:612-618)
 CE is the reference's nn.CrossEntropyLoss applied to the heads' Softmax output (two softmaxes), kept as it is. V4..V7 of the family (two frozen
 pretrained ResNet18 classifiers) are not covered, and the labelled step is tested on one rank only.
+
+`patches=4, mask=True` runs the edge-mask script TFCGAN_multigpu_patchFFT_experiment.py ("4X") on GeneratorUNet(mask=True); losses.mask_weights gives
+its keywords.
+    G step : mask_A = mask_maker(real_A) (data, no gradient); fake = G(real_A, mask_A)                                   (4X:548, :563)
+             loss_G += lambda_mask * loss_mask, loss_mask = L1(mask_maker(fake), mask_maker(real_B))                      (4X:584-587)
+             its exact gradient (csrc/mask.hip: batch extrema with ties, adjoints of the reflect-padded filters) joins the gradient of fake
+    D step : PATCH-4's.
+The mask normalises by extrema of the WHOLE batch, so the samples of a batch are coupled by definition: an explicit batch_invariant=True is refused, and
+with several ranks each rank normalises its own shard (the reference's DataParallel normalises the gathered batch): multi-rank MASK-4 is not covered.
 """
 import math
 import os
@@ -33,7 +42,7 @@ import os
 import torch
 
 from . import nets, ops, parallel
-from .losses import global_fft_loss, patch_fft_loss, regional_fft_loss, temperature_triplet_loss
+from .losses import global_fft_loss, mask_l1_loss, patch_fft_loss, regional_fft_loss, temperature_triplet_loss
 from .ops import DT_BF16
 
 
@@ -49,7 +58,7 @@ class TrainStep:
     def __init__(self, generator, discriminator, lr=2e-4, b1=0.5, b2=0.999, eps=1e-8, compute_dtype=torch.bfloat16,
                  fft_mode="patch", seed=0, bucket_bytes=16 << 20, lambda_gan=0.5, lambda_fft=0.01, lambda_trip=1.0, d_bucket_bytes=4 << 20,
                  batch_invariant=None, patches=16, region_fft=None, lambda_region=0.5e-4, labels=None, label_weights=(1.0, 1.0, 1.0),
-                 d_label_scale=1.0):
+                 d_label_scale=1.0, mask=False, lambda_mask=0.5):
         dev = next(generator.parameters()).device
         if patches not in (4, 16):
             raise ops._lib.TfcError(f"TrainStep: patches={patches} (16: the 4x4 grid of 64x64 patches, 4: the 2x2 grid of 128x128 patches)")
@@ -72,6 +81,20 @@ class TrainStep:
         elif getattr(generator, "labels", 0) or getattr(discriminator, "aux_classes", None):
             raise ops._lib.TfcError("TrainStep: a label-conditioned generator / discriminator needs labels='generated' or 'real' (losses.debias_weights)")
         self.labels, self.label_weights, self.d_label_scale = labels, tuple(float(w) for w in label_weights), float(d_label_scale)
+        if mask:
+            if patches != 4:
+                raise ops._lib.TfcError("TrainStep: mask=True belongs to the edge-mask 4-patch script (patches=4); no reference script combines it with "
+                                        "16 patches")
+            if labels is not None:
+                raise ops._lib.TfcError("TrainStep: mask=True and labels= are two different scripts (each feeds its own 4th input channel to G)")
+            if not getattr(generator, "mask", False):
+                raise ops._lib.TfcError("TrainStep(mask=True) needs GeneratorUNet(img_shape, mask=True)")
+            if batch_invariant:
+                raise ops._lib.TfcError("TrainStep(mask=True, batch_invariant=True): the mask is normalised by the extrema of the whole batch, so the "
+                                        "samples of a batch are coupled by definition; there is no batch-invariant form of this step")
+        elif getattr(generator, "mask", False):
+            raise ops._lib.TfcError("TrainStep: a generator built with mask=True needs TrainStep(..., patches=4, mask=True) (losses.mask_weights)")
+        self.mask, self.lambda_mask = bool(mask), float(lambda_mask)
         if dev.type != "cuda":
             raise ops._lib.TfcError("TrainStep needs the modules on a CUDA/HIP device (no CPU fallback)")
         self.dev, self.dt = dev, ops.dt_of(compute_dtype)
@@ -101,7 +124,7 @@ class TrainStep:
         # the discriminator's 11 MB of gradients: its largest layer (model.9, 8.4 MB) is final first, so a 4 MiB cut lets that part of the exchange
         # run under the rest of the D backward; only the last ~2.6 MB (model.6, .3, .0) are exposed
         self.d_reduce = parallel.BucketReducer(self.dflat, min(bucket_bytes, d_bucket_bytes))
-        self.G = nets.GeneratorCore(self.dt, generator.channels, getattr(generator, "labels", 0))
+        self.G = nets.GeneratorCore(self.dt, generator.channels, getattr(generator, "labels", 0), self.mask)
         self.G.set_params(self.gflat.views)
         self.D = nets.DiscriminatorCore(self.dt, discriminator.channels, getattr(discriminator, "aux_classes", None))
         self.D.set_params(self.dflat.views, self.dbufs)
@@ -179,7 +202,13 @@ class TrainStep:
             ex = extra_loss_G(fake, real_B) if extra_loss_G is not None else None     # optional pluggable term (LPIPS, P16:598): (loss, dfake), already weighted
             # forward-only head: beside the other pixel losses, on their stream; (loss_FFT_reg, loss_Amp_reg, loss_Pha_reg) or None
             reg = regional_fft_loss(fake, real_B, self.region_fft) if self.region_fft is not None else None
-            return lt, gt, lf, ex, reg
+            # the mask term: (lambda_mask * loss_mask, its gradient w.r.t. fake); mask(real_B) once per step
+            mk = mask_l1_loss(fake, real_B, scale=self.lambda_mask) if (self.mask and self.lambda_mask != 0.0) else None
+            return lt, gt, lf, ex, reg, mk
+        g_in = {"labels": g_labels}
+        if self.mask:                                             # mask_A = mask_maker(real_A): Bl and its batch maximum stay on the device, the
+            mctx = ops.mask_fwd(real_A)                           # packing kernel divides on the way into input channel 3
+            g_in = {"plane": mctx.bl, "plane_div": mctx.M}
         if nets.side_stream_on() and os.environ.get("TFC_NO_GSTEP_OVERLAP", "0") in ("", "0"):
             # Two-stream form of the same program (nets.py: side stream). Both power iterations of this step's two discriminator calls come first, in
             # call order (they read the weights only); the chain of the SECOND call (real pair, no gradient) then runs beside the generator forward,
@@ -188,19 +217,21 @@ class TrainStep:
             snap_r = self.D.sn_snapshot(self.dev, True, False)
             pr = nets.on_side(self.dev, lambda: self.D.chain(real_B, real_A, snap_r, save=False), snap_r[2][0])[0]
             pr_ready = nets.side_mark(self.dev)
-            fake, gctx = self.G.forward(real_A, seed=drop_seed, train=train, labels=g_labels)
-            loss_trip, g_trip, (loss_fft, loss_amp, loss_pha), extra_pair, region = nets.on_side(self.dev, pixel_losses)
+            fake, gctx = self.G.forward(real_A, seed=drop_seed, train=train, **g_in)
+            loss_trip, g_trip, (loss_fft, loss_amp, loss_pha), extra_pair, region, mask_pair = nets.on_side(self.dev, pixel_losses)
             pf, dctx_f = self.D.chain(fake, real_A, snap_f, save=True)
             nets.wait_mark(self.dev, pr_ready)                    # the logits of the real pair; the pixel losses (LPIPS: 6 ms) run on, D.backward below joins
         else:
-            fake, gctx = self.G.forward(real_A, seed=drop_seed, train=train, labels=g_labels)
+            fake, gctx = self.G.forward(real_A, seed=drop_seed, train=train, **g_in)
             pf, dctx_f = self.D.forward(fake, real_A, power_iter=True, save=True)
             pr, _ = self.D.forward(real_B, real_A, power_iter=True, save=False)
-            loss_trip, g_trip, (loss_fft, loss_amp, loss_pha), extra_pair, region = pixel_losses()
+            loss_trip, g_trip, (loss_fft, loss_amp, loss_pha), extra_pair, region, mask_pair = pixel_losses()
         g_pf = self._gl(pf)
         loss_gan = ops.bce_relativistic(dt, pf, pr, 0, 0.9, da=ops.View(g_pf.t, 1, 0), gscale=self.lambda_gan)
         g_fake = self.D.backward(dctx_f, g_pf, grads=None, need_input_grad=True)
         ops.axpby(g_fake, g_fake, g_trip, 1.0, 1.0)
+        if mask_pair is not None:
+            ops.axpby(g_fake, g_fake, mask_pair[1], 1.0, 1.0)
         label_out = None
         if lab is not None:
             # the heads of the fake pair, on the caller's stream on both forms of the step (same launches, same order: same bits)
@@ -246,6 +277,8 @@ class TrainStep:
         loss_g = self.lambda_gan * loss_gan + self.lambda_trip * loss_trip + self.lambda_fft * loss_fft
         if label_out is not None:
             loss_g = loss_g + label_out["loss_label"]
+        if mask_pair is not None:
+            loss_g = loss_g + mask_pair[0].reshape(loss_g.shape)
         if extra is not None:
             loss_g = loss_g + extra.reshape(loss_g.shape).to(loss_g.dtype)
         loss_temp = None
@@ -261,6 +294,8 @@ class TrainStep:
             self.last["loss_extra_g"] = extra.reshape(())
         if label_out is not None:                                 # loss_label / real_loss_label / fake_loss_label, and the heads' probabilities [N,9]
             self.last.update({k: (v.reshape(()) if v.numel() == 1 else v) for k, v in label_out.items()})
+        if self.mask:                                             # the script's loss_mask (unweighted); 0 when the term is switched off
+            self.last["loss_mask"] = (mask_pair[0] / self.lambda_mask).reshape(()) if mask_pair is not None else torch.zeros((), device=self.dev)
         if region is not None:
             loss_reg, loss_amp_reg, loss_pha_reg = region
             self.last["loss_G"] = self.last["loss_G"] + self.lambda_region * loss_reg

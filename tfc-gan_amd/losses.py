@@ -262,6 +262,34 @@ def debias_weights(kind):
     raise ops._lib.TfcError(f"debias_weights: kind={kind!r} ('v1', 'v2' or 'v3')")
 
 
+def mask_weights():
+    """TrainStep keyword values of the edge-mask 4-patch script (TFCGAN_multigpu_patchFFT_experiment.py "4X") without its LPIPS and temperature terms;
+    use with patches=4, mask=True. 4X:587: loss_G = 0.5 GAN + 0.5 LPIPS + 0.5 loss_triplet_patch + 0.5 temp + 0.001 FFT + 0.5 mask. 4X:335-337 SUMS
+    the amplitude and phase terms over the four patches where patch_fft_loss returns their mean, so lambda_fft is four times the script's 0.001 (the
+    way region_weights derives it). Name slip of the script: its loop assigns the patch triplet to `loss_patch` (4X:575) and :587 adds
+    `loss_triplet_patch`, a name the loop never assigns; the triplet term is what is meant and what runs here."""
+    return {"lambda_gan": 0.5, "lambda_trip": 0.5, "lambda_fft": 4 * 0.001, "lambda_mask": 0.5}
+
+
+def mask_maker(img):
+    """reference 4X:385-390: the edge mask [N,1,H,W] of img [N,3,H,W] -- |7x7 normalised Laplacian| of the grayscale image, min/max-normalised over
+    the WHOLE batch, 9x9 Gaussian blur (sigma 1.6), divided by its batch maximum (csrc/mask.hip; fp32 in every compute mode). Forward only: the exact
+    backward lives in mask_l1_loss / TrainStep(mask=True). A constant batch (max == min) gives NaN, as in the reference."""
+    if torch.is_grad_enabled() and img.requires_grad:
+        raise ops._lib.TfcError("mask_maker is forward-only (no autograd graph): call it under torch.no_grad() / on a detached image; the gradient of "
+                                "the mask loss comes from tfc_gan_amd.mask_l1_loss(fake, real) or TrainStep(mask=True)")
+    return ops.mask_scale(ops.mask_fwd(img))
+
+
+def mask_l1_loss(fake, real, scale=1.0, want_grad=True, real_mask=None):
+    """(loss, dfake): scale * mean|mask_maker(fake) - mask_maker(real)| (4X:584-585) and its exact gradient w.r.t. fake (None without want_grad),
+    through the batch extrema, their ties and both reflect-padded filters. real_mask: mask_maker(real) when the caller already has it."""
+    if real_mask is None:
+        real_mask = ops.mask_scale(ops.mask_fwd(real))
+    loss, dfake = ops.mask_bwd(ops.mask_fwd(fake), ref=real_mask, scale=scale, want_grad=want_grad)
+    return loss.reshape(()), dfake
+
+
 def calculate_ffts(*patches):
     """reference :323-375: calculate_ffts(fake_B1..fake_B16, B1..B16) -> loss_FFT (scalar, no gradient). With 8 tensors (fake_B1..4, B1..4 of
     128 x 128): the inline form of the 4-patch script (4P:499-511)."""

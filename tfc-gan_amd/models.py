@@ -246,6 +246,11 @@ class _GeneratorFn(torch.autograd.Function):
 def _refuse_autograd(module, tensors):
     """the label-conditioned forms train through TrainStep only: their modules' own forward carries no autograd graph, so it refuses to run where one
     is expected instead of leaving None gradients behind"""
+    if getattr(module, "mask", False) and torch.is_grad_enabled() and (any(p.requires_grad for p in module.parameters())
+                                                                      or any(torch.is_tensor(t) and t.requires_grad for t in tensors)):
+        raise ops._lib.TfcError(f"{type(module).__name__}: the mask-fed forward (edge mask as the 4th input channel) has no autograd backward. Train with "
+                                "tfc_gan_amd.TrainStep(G, D, patches=4, mask=True, **tfc_gan_amd.mask_weights()), which runs its hand-written backward; "
+                                "call the module itself under torch.no_grad() (sample_images, inference).")
     if torch.is_grad_enabled() and (any(p.requires_grad for p in module.parameters()) or any(torch.is_tensor(t) and t.requires_grad for t in tensors)):
         raise ops._lib.TfcError(f"{type(module).__name__}: the label-conditioned forward (label plane / auxiliary heads) has no autograd backward. Train with "
                                 "tfc_gan_amd.TrainStep(G, D, **tfc_gan_amd.debias_weights(kind), patches=4), which runs its hand-written backward; "
@@ -255,17 +260,22 @@ def _refuse_autograd(module, tensors):
 class GeneratorUNet(nn.Module):
     """reference :136-174. forward(x[N,3,S,S]) -> fake_B in (-1,1), fp32 NCHW (the reference casts to HalfTensor, :173).
     labels=3: the label-conditioned generator of TFCGAN_multigpu_patchFFT_debiased.py:142-186 -- fc = nn.Linear(3, h*w) of the labels, reshaped to a
-    plane, is the 4th input channel of down1; forward(x, labels[N,3])."""
+    plane, is the 4th input channel of down1; forward(x, labels[N,3]).
+    mask=True: the generator of TFCGAN_multigpu_patchFFT_experiment.py:141-181 -- the edge mask of img_A (tfc_gan_amd.mask_maker) is the 4th input
+    channel of down1; forward(img_A, mask_A[N,1,S,S]). One of labels= and mask= at most."""
 
-    def __init__(self, img_shape, labels=0):
+    def __init__(self, img_shape, labels=0, mask=False):
         super().__init__()
         channels, self.h, self.w = img_shape
         if labels not in (0, 3):
             raise ops._lib.TfcError(f"GeneratorUNet: labels={labels} (0: the plain generator, 3: gender / ethnicity / age through fc)")
+        if labels and mask:
+            raise ops._lib.TfcError("GeneratorUNet: labels= and mask= are mutually exclusive (each script feeds its own 4th input channel)")
         self.labels = labels
+        self.mask = bool(mask)
         if labels:
             self.fc = nn.Linear(labels, self.h * self.w)        # first, as in the reference: state_dict() lists fc.* ahead of down1
-        self.down1 = UNetDown(channels + (1 if labels else 0), 64, normalize=False)
+        self.down1 = UNetDown(channels + (1 if (labels or mask) else 0), 64, normalize=False)
         self.down2 = UNetDown(64, 128)
         self.down3 = UNetDown(128, 256, dropout=0.5)
         self.down4 = UNetDown(256, 512, dropout=0.5)
@@ -292,7 +302,7 @@ class GeneratorUNet(nn.Module):
         params = self.named_core_params()
         key = (dt, str(device), self._weights_gen) + tuple((p.data_ptr(), p._version) for p in params.values())
         if self._core is None or self._core.dt != dt:
-            self._core = nets.GeneratorCore(dt, self.channels, self.labels)
+            self._core = nets.GeneratorCore(dt, self.channels, self.labels, self.mask)
         if key != self._core_key:
             for k, p in params.items():
                 if p.dtype != torch.float32 or not p.is_cuda:
@@ -302,8 +312,20 @@ class GeneratorUNet(nn.Module):
             self._core_key = key
         return self._core
 
-    def forward(self, x, labels=None):
+    def forward(self, x, labels=None, mask_A=None):
         _refuse_replica(self)
+        if self.mask:
+            if mask_A is None:                                    # forward(img_A, mask_A): the mask is this generator's second argument
+                mask_A, labels = labels, None
+            if labels is not None or mask_A is None:
+                raise ops._lib.TfcError("GeneratorUNet(img_shape, mask=True): forward(img_A, mask_A) with mask_A [N,1,S,S] (tfc_gan_amd.mask_maker(img_A))")
+            _refuse_autograd(self, (x, mask_A))
+            core = self._core_for(x.device)
+            fake, _ = core.forward(x.detach().float().contiguous(), seed=_next_seed(self), train=self.training, save=False,
+                                   plane=mask_A.detach().to(x.device).float().contiguous())
+            return fake
+        if mask_A is not None:
+            raise ops._lib.TfcError("GeneratorUNet: forward(img_A, mask_A) belongs to GeneratorUNet(img_shape, mask=True)")
         if (labels is not None) != bool(self.labels):
             raise ops._lib.TfcError("GeneratorUNet: forward(x, labels) belongs to GeneratorUNet(img_shape, labels=3), forward(x) to the plain generator")
         if self.labels:

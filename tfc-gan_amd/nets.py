@@ -154,11 +154,14 @@ class _Ctx:
 
 
 class GeneratorCore:
-    def __init__(self, dt=DT_BF16, channels=3, labels=0):
+    def __init__(self, dt=DT_BF16, channels=3, labels=0, mask=False):
         self.dt = dt
         self.channels = channels
         self.labels = int(labels)                                 # 3: fc(labels) is down1's extra input channel (label-conditioned generator)
-        self.in_channels = channels + (1 if self.labels else 0)
+        self.mask = bool(mask)                                    # the edge mask of img_A is down1's extra input channel (MASK-4 generator); it is data
+        if self.labels and self.mask:
+            raise ops._lib.TfcError("GeneratorCore: labels= and mask= are two different scripts' fourth input channel (one of them at most)")
+        self.in_channels = channels + (1 if (self.labels or self.mask) else 0)
         self.down = [(G_DOWN[0][0], self.in_channels) + G_DOWN[0][2:]] + G_DOWN[1:]
         self.params = None
         self.packed = {}
@@ -190,13 +193,16 @@ class GeneratorCore:
         self._plan.run()
 
     # ---- forward ----
-    def forward(self, x, seed=0, train=True, save=True, labels=None):
+    def forward(self, x, seed=0, train=True, save=True, labels=None, plane=None, plane_div=None):
         """x: fp32 NCHW [N,3,S,S] (S multiple of 64, >= 128). Returns (fake fp32 NCHW in (-1,1), ctx). down1 runs as ONE kernel (conv + LeakyReLU +
         BlurPool, ops.first_block_fwd): its 266 MB conv output is never written, the backward needs its signs only and gets them as sign words.
-        labels: fp32 [N,3] on the device, for a label-conditioned core (its fc plane is written as input channel 3 by the packing kernel)."""
-        ops.require_gpu(x, labels)
+        labels: fp32 [N,3] on the device, for a label-conditioned core (its fc plane is written as input channel 3 by the packing kernel).
+        plane: fp32 [N,1,S,S] on the device, for a mask core: input channel 3 (plane_div: a device float it is divided by on the way, ops.MaskCtx.M)."""
+        ops.require_gpu(x, labels, plane)
         if (labels is not None) != bool(self.labels):
             raise ops._lib.TfcError("GeneratorCore: labels go with a label-conditioned generator (labels=3) and only with it")
+        if (plane is not None) != self.mask:
+            raise ops._lib.TfcError("GeneratorCore: the mask plane goes with a mask generator (mask=True) and only with it")
         if not self.packed:
             self.repack()
         dt, dev = self.dt, x.device
@@ -209,6 +215,8 @@ class GeneratorCore:
                 raise ops._lib.TfcError(f"GeneratorCore: labels {tuple(labels.shape)} for a batch of {N} (expected [N, {self.labels}])")
             labels = labels.contiguous().float()
             x8 = ops.pack_nhwc8_labels(dt, x, labels, self.params["fc.weight"], self.params["fc.bias"])
+        elif self.mask:
+            x8 = ops.pack_nhwc8_plane(dt, x, plane, plane_div)
         else:
             x8 = ops.pack_nhwc8(dt, x)
         ctx.labels = labels

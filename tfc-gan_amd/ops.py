@@ -666,6 +666,84 @@ def aux_heads_wgrad(dt, x_r: View, dl_r, x_f: View, dl_f, dws, dbs, accumulate=F
                                     _int3(classes), 1 if accumulate else 0), "tfc_aux_heads_wgrad")
 
 
+# ---- edge mask of the MASK-4 script (csrc/mask.hip; TFCGAN_multigpu_patchFFT_experiment.py:385-390) ---------------------------------------------------
+MASK_STATS = 16                     # floats at the head of a mask workspace: mn, mx, ties, ties, M, ties(M), dM, L1 loss, dmx, dmn (include/tfc_gan.h)
+
+
+class MaskCtx:
+    """what one forward of the mask operator leaves on the device: the signed Laplacian, the blurred plane Bl (mask = Bl / M) and the workspace that
+    holds the extrema, their tie counts and (after a backward) the global sums. Nothing of it is read by the host."""
+    __slots__ = ("N", "H", "W", "lap", "bl", "ws")
+
+    @property
+    def M(self):                    # device float: max of Bl over the batch
+        return self.ws[4:5]
+
+
+def _mask_dims(img, what):
+    if img.dim() != 4 or img.shape[1] != 3:
+        raise _lib.TfcError(f"{what}: image {tuple(img.shape)} (expected [N,3,H,W])")
+    N, _, H, W = img.shape
+    if H < 8 or W < 8:
+        raise _lib.TfcError(f"{what}: H={H}, W={W} (both filters reflect once: H, W >= 8)")
+    return N, H, W
+
+
+def mask_fwd(img):
+    """img fp32 [N,3,H,W] -> MaskCtx (lap, Bl, extrema on the device). fp32 in every compute mode."""
+    require_gpu(img)
+    N, H, W = _mask_dims(img, "mask_fwd")
+    img = img.detach().contiguous().float()
+    c = MaskCtx()
+    c.N, c.H, c.W = N, H, W
+    c.lap = torch.empty((N, 1, H, W), dtype=torch.float32, device=img.device)
+    c.bl = torch.empty_like(c.lap)
+    c.ws = torch.empty(lib().tfc_mask_ws_bytes(N, H, W) // 4, dtype=torch.float32, device=img.device)
+    check(lib().tfc_mask_fwd(stream_ptr(), _p(img), _p(c.lap), _p(c.bl), _p(c.ws), N, H, W), "tfc_mask_fwd")
+    return c
+
+
+def mask_scale(c: MaskCtx):
+    """the mask itself [N,1,H,W] = Bl / M"""
+    out = torch.empty_like(c.bl)
+    check(lib().tfc_mask_scale(stream_ptr(), _p(c.bl), _p(c.ws), _p(out), c.N, c.H, c.W), "tfc_mask_scale")
+    return out
+
+
+def mask_bwd(c: MaskCtx, dout=None, ref=None, scale=1.0, want_grad=True):
+    """exact backward of the mask operator through the context of its forward. dout [N,1,H,W]: an upstream gradient -> dimg [N,3,H,W]. ref [N,1,H,W]:
+    the L1 loss scale * mean|mask - ref| -> (loss [1], dimg or None)."""
+    if (dout is None) == (ref is None):
+        raise _lib.TfcError("mask_bwd: exactly one of dout (an upstream gradient) and ref (the L1 loss against it)")
+    u = dout if ref is None else ref
+    require_gpu(u, c.bl)
+    if tuple(u.shape) != tuple(c.bl.shape):
+        raise _lib.TfcError(f"mask_bwd: {tuple(u.shape)} against a mask of {tuple(c.bl.shape)}")
+    u = _f32c(u.detach().contiguous(), "dout / ref")
+    dev = c.bl.device
+    dimg = torch.empty((c.N, 3, c.H, c.W), dtype=torch.float32, device=dev) if (want_grad or ref is None) else None
+    dmn = torch.empty_like(c.bl) if dimg is not None else None
+    dbuf = torch.empty_like(c.bl) if ref is not None else None
+    check(lib().tfc_mask_bwd(stream_ptr(), _p(c.lap), _p(c.bl), _p(c.ws), _p(u if ref is None else None), _p(u if ref is not None else None),
+                             float(scale), _p(dbuf), _p(dmn), _p(dimg), c.N, c.H, c.W), "tfc_mask_bwd")
+    if ref is None:
+        return dimg
+    return c.ws[7:8].clone(), dimg
+
+
+def pack_nhwc8_plane(dt, x, plane, plane_div=None):
+    """torch.cat((x, plane), 1) as the NHWC8 activation of the compute dtype: channels 0..2 x, 3 the plane [N,1,H,W] (divided by the device float
+    plane_div when given: Bl of a MaskCtx with its M), 4..7 zero. The plane is data: it gets no gradient."""
+    require_gpu(x, plane)
+    x = x.contiguous().float()
+    N, C, H, W = x.shape
+    if C != 3 or tuple(plane.shape) != (N, 1, H, W):
+        raise _lib.TfcError(f"pack_nhwc8_plane: x {tuple(x.shape)}, plane {tuple(plane.shape)} (expected [N,3,H,W] and [N,1,H,W])")
+    out = new_act(N, H, W, 8, dt, x.device)
+    check(lib().tfc_pack_nhwc8_plane(stream_ptr(), dt, _p(x), _p(_f32c(plane, "plane")), _p(plane_div), out.ptr, N, H, W), "tfc_pack_nhwc8_plane")
+    return out
+
+
 # ---- STN21 localiser (vit.hip) ---------------------------------------------------------------------------------
 VIT_A_ROWS, VIT_A_TRANS, VIT_A_UNFOLD = 0, 1, 2
 VIT_B_WEIGHT, VIT_B_ROWS, VIT_B_UNFOLD = 0, 1, 2
