@@ -205,6 +205,17 @@ size_t tfc_fft_spectrum_rect_ws_bytes(int H, int nwin);
  * out[0] += scale * sum exp(t)(t - xa), out[1] += scale * sum exp(t)(t - xp), t = log_softmax_n(ar), xa = log_softmax_n(af), xp = log_softmax_n(pf).
  * A logged scalar (no gradient); N >= 1. Side stream only when two streams are in use, like tfc_l1_sum and the triplet heads. */
 int tfc_batch_kl_sum(void* stream, const float* af, const float* pf, const float* ar, int N, long long M, float scale, float* out);
+/* tfc_batch_kl_sum in phases, for a batch of world * N entries spread over `world` ranks (the softmax runs over ALL of them). Between the phases
+ * the caller gathers every rank's record in rank order; nothing returns to the host, nothing is allocated. rec / recs / glob: 8-byte aligned.
+ *   tfc_batch_kl_stats: first walk over this rank's N entries -> rec, float [3][M][2] = (max, sum exp(. - max)) per bin of af, pf, ar
+ *   tfc_batch_kl_merge: recs, float [world][3][M][2], world in 1 .. 64 -> glob, float [3][M][2] = (max, log sum) per bin over all ranks; one workgroup,
+ *                       the pairs of a bin are folded in rank order by the re-basing rule of the online log-sum-exp: the same bits on every rank
+ *   tfc_batch_kl_terms: second walk with the global pairs: out[0], out[1] += scale * (this rank's terms); the mean over ranks of the results with
+ *                       scale = 1 / (N * bins of a region) is the loss of the gathered batch. Stream rule of tfc_batch_kl_sum (same slots).
+ * With world == 1 the three calls leave the bits of tfc_batch_kl_sum. */
+int tfc_batch_kl_stats(void* stream, const float* af, const float* pf, const float* ar, int N, long long M, void* rec);
+int tfc_batch_kl_merge(void* stream, const void* recs, int world, long long M, void* glob);
+int tfc_batch_kl_terms(void* stream, const float* af, const float* pf, const float* ar, int N, long long M, const void* glob, float scale, float* out);
 /* evaluation metric of TFC-GAN-FFT/Devcom_MagMSE.py:91-118 (mse_spec): per window MSE(log|fft2(a)|, log|fft2(b)|) over the FULL S x S
  * spectrum, computed from the half spectra amp_a / amp_b [nwin][S][S/2+1] of tfc_fft_spectrum (S in {64,128,256}); out[nwin] */
 int tfc_logmag_mse(void* stream, const float* amp_a, const float* amp_b, int S, int nwin, float* out);
@@ -482,6 +493,32 @@ int tfc_mask_scale(void* stream, const float* bl, const void* ws, float* mask, i
  * scratch. dimg null (with ref): the loss alone. */
 int tfc_mask_bwd(void* stream, const float* lap, const float* bl, void* ws, const float* dout, const float* ref, float scale, float* dout_buf,
                  float* dmn, float* dimg, int N, int H, int W);
+/* tfc_mask_fwd / tfc_mask_bwd in phases, for a batch spread over `world` ranks whose extrema and sums are those of ALL ranks' samples. Each phase
+ * runs the kernels of the unsplit entry point on this rank's N samples and leaves a RECORD of TFC_MASK_RECORD_BYTES (four 64-bit words, 8-byte
+ * aligned device memory); the caller gathers the records of all ranks in rank order (raw bytes) and tfc_mask_merge -- one workgroup, fixed order,
+ * world in 1 .. 64 -- writes the stats floats of ws that the next phase reads, the same bits on every rank. Nothing returns to the host.
+ *   F1 tfc_mask_fwd_lap : lap; record {bits(mn), ties(mn), bits(mx), ties(mx)} of this rank's |lap| (fp32 bits and 64-bit counts)
+ *      merge which = 0  : floats 0..3. The smaller (larger) value wins with its count; equal values add their counts.
+ *   F2 tfc_mask_fwd_blur: bl from the merged mn / mx; record {bits(M), ties(M), 0, 0}
+ *      merge which = 1  : floats 4, 5. tfc_mask_scale and tfc_pack_nhwc8_plane then read the global M.
+ *   B0 tfc_mask_bwd_dot : arguments as tfc_mask_bwd; record of doubles {sum |mask - ref|, sum dout Bl, 0, 0} over this rank. Float 7 receives THIS
+ *                         rank's loss, scale * mean over its own samples (masks normalised globally): the mean over equal shards is the loss of
+ *                         the gathered batch. With ref, dout_buf receives scale / (N H W) * sign(mask - ref).
+ *      merge which = 2  : float 6 = d/dM per tie from the sum of `sum dout Bl` in rank order, the global M and its global tie count
+ *   B1 tfc_mask_bwd_blur: dmn (dout: the upstream gradient, dout_buf after a B0 with ref); record of doubles {sum dMn (L - mn), sum dMn (L - mx), 0, 0}
+ *      merge which = 3  : floats 8, 9 = d/dmx, d/dmn per tie from the sums over all ranks and the global tie counts
+ *   B2 tfc_mask_bwd_lap : dimg = the gradient of the SUM over ranks of the ranks' losses (or of sum dout * mask) w.r.t. this rank's images; with the
+ *                         1/world of a gradient mean the parameters receive the gradient of the gathered-batch loss.
+ * Tie counts reach the stats as floats, exact up to 2^24: the caller keeps world * N * H * W <= 2^24. With world == 1 (one record per merge) lap, bl,
+ * floats 0..9 and dimg are the bits of tfc_mask_fwd / tfc_mask_bwd. */
+#define TFC_MASK_RECORD_BYTES 32
+int tfc_mask_fwd_lap(void* stream, const float* img, float* lap, void* ws, void* rec, int N, int H, int W);
+int tfc_mask_fwd_blur(void* stream, const float* lap, float* bl, void* ws, void* rec, int N, int H, int W);
+int tfc_mask_merge(void* stream, void* ws, const void* recs, int world, int which);
+int tfc_mask_bwd_dot(void* stream, const float* bl, void* ws, const float* dout, const float* ref, float scale, float* dout_buf, void* rec, int N, int H,
+                     int W);
+int tfc_mask_bwd_blur(void* stream, const float* lap, const float* bl, void* ws, const float* dout, float* dmn, void* rec, int N, int H, int W);
+int tfc_mask_bwd_lap(void* stream, const float* lap, const void* ws, const float* dmn, float* dimg, int N, int H, int W);
 /* out [N][H][W][8] in the compute dtype: channels 0..2 = img [N][3][H][W] fp32, channel 3 = plane [N][H][W] fp32 (divided by *plane_div, a device
  * float, when it is not null: Bl with its M), channels 4..7 = 0. H * W a multiple of 4. */
 int tfc_pack_nhwc8_plane(void* stream, int dt, const float* img, const float* plane, const float* plane_div, void* out, int N, int H, int W);

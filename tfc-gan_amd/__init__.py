@@ -9,7 +9,8 @@ make_4_patches and the 4-patch heads of TFCGAN_multigpu_patchFFT.py / TFCGAN_mul
 the regional FFT loss of the ..._withregion_FFT(.py|_KL.py) scripts (TrainStep(region_fft=...)),
 the label-conditioned step of ..._debiased(.py|_V2.py|_V3.py) (TrainStep(labels=...), GeneratorUNet(labels=3), Discriminator1(aux_classes=(2, 4, 3))),
 the edge-mask step of ..._experiment.py (TrainStep(mask=True), GeneratorUNet(mask=True), mask_maker, mask_l1_loss),
-FFT_Components / fft_components / calculate_ffts, and the fused TrainStep + data-parallel layer.
+FFT_Components / fft_components / calculate_ffts, and the fused TrainStep + data-parallel layer (batch_scope="global": the batch-coupled mask and
+KL terms take their extrema / softmax over the batch of all ranks).
 """
 import os as _os
 
@@ -23,6 +24,7 @@ from . import _lib, data, engine, inference, losses, lpips, metrics, models, net
 from ._lib import TfcError, build  # noqa: F401
 from .engine import TrainStep  # noqa: F401
 from .nets import set_wgrad_stream  # noqa: F401
+from .parallel import all_gather_records  # noqa: F401
 from .data import DeviceLoader, ImageDataset, LabelledImageDataset, TestImageDataset, pair_resize_normalize  # noqa: F401
 from .lpips import LPIPS  # noqa: F401
 from .stn21 import STN21Step  # noqa: F401
@@ -41,4 +43,4 @@ __all__ = ["UNetDown", "UNetUp", "GeneratorUNet", "Discriminator1", "Discriminat
            "make_16_patches", "make_4_patches", "patch_first_flat_index", "stitch_patches", "ContrastiveLoss", "patch_triplet_loss", "FFT_Components", "fft_components", "calculate_ffts",
            "patch_fft_loss", "global_fft_loss", "regional_fft_components", "regional_fft_loss", "region_weights", "debias_weights", "mask_weights", "mask_maker", "mask_l1_loss", "mse_spec", "other_spec", "psnr", "ssim", "bhattacharyya", "ncc", "mutual_information", "to_uint8", "to_gray",
            "EvalAccumulator", "sample_spectra", "vectorize_temps", "temperature_triplet_loss", "color_jitter_thermal",
-           "color_jitter_params", "synthetic_pairs", "synthetic_temperatures", "load_clean_state", "save_checkpoint", "stitch_16_patches", "global_grid", "TrainStep", "STN21Step", "LPIPS", "ImageDataset", "LabelledImageDataset", "TestImageDataset", "DeviceLoader", "pair_resize_normalize", "Warp", "affine_warp", "morph_gradient", "morph_triplet", "triplet_margin_rows", "set_compute_dtype", "get_compute_dtype", "set_batch_invariant", "get_batch_invariant", "build", "TfcError"]
+           "color_jitter_params", "synthetic_pairs", "synthetic_temperatures", "load_clean_state", "save_checkpoint", "stitch_16_patches", "global_grid", "TrainStep", "STN21Step", "LPIPS", "ImageDataset", "LabelledImageDataset", "TestImageDataset", "DeviceLoader", "pair_resize_normalize", "Warp", "affine_warp", "morph_gradient", "morph_triplet", "triplet_margin_rows", "set_compute_dtype", "get_compute_dtype", "set_batch_invariant", "get_batch_invariant", "build", "TfcError", "all_gather_records"]

@@ -89,7 +89,10 @@ GUARDED_KERNELS = ("tfc_igemm2_kernel", "tfc_wgrad", "tfc_patch_triplet_kernelIL
                    "tfc_aux_heads_wgrad_kernel", "tfc_softmax_ce_heads_kernel",
                    # the edge mask (mask.hip): tile kernels with their taps and four outputs per thread in registers
                    "tfc_mask_lap_kernel", "tfc_mask_blur_kernel", "tfc_mask_blur_bwd_kernel", "tfc_mask_lap_bwd_kernel", "tfc_mask_dot_kernel",
-                   "tfc_mask_final_extrema_kernel", "tfc_mask_final_sums_kernel", "tfc_mask_scale_kernel", "tfc_pack_plane_kernel")
+                   "tfc_mask_final_extrema_kernel", "tfc_mask_final_sums_kernel", "tfc_mask_scale_kernel", "tfc_pack_plane_kernel",
+                   # their phase forms for a batch spread over ranks: the record and merge kernels (mask.hip), the two walks of the KL loss (losses.hip)
+                   "tfc_mask_record_extrema_kernel", "tfc_mask_record_sums_kernel", "tfc_mask_merge_kernel", "tfc_batch_kl_stats_kernel",
+                   "tfc_batch_kl_merge_kernel", "tfc_batch_kl_terms_kernel")
 
 
 def check_no_spills(remarks):
@@ -158,6 +161,9 @@ PROTOTYPES = {
     "tfc_fft_spectrum_rect": (_i, [_vp, _vp, _ll, _ll, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp]),
     "tfc_fft_spectrum_rect_ws_bytes": (_sz, [_i, _i]),
     "tfc_batch_kl_sum": (_i, [_vp, _vp, _vp, _vp, _i, _ll, _f, _vp]),
+    "tfc_batch_kl_stats": (_i, [_vp, _vp, _vp, _vp, _i, _ll, _vp]),
+    "tfc_batch_kl_merge": (_i, [_vp, _vp, _i, _ll, _vp]),
+    "tfc_batch_kl_terms": (_i, [_vp, _vp, _vp, _vp, _i, _ll, _vp, _f, _vp]),
     "tfc_logmag_mse": (_i, [_vp, _vp, _vp, _i, _i, _vp]),
     "tfc_logmag_mae": (_i, [_vp, _vp, _vp, _i, _i, _vp]),
     "tfc_pair_moments_ws_bytes": (_sz, [_i, _ll]),
@@ -219,6 +225,12 @@ PROTOTYPES = {
     "tfc_mask_fwd": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i]),
     "tfc_mask_scale": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i]),
     "tfc_mask_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _i, _i, _i]),
+    "tfc_mask_fwd_lap": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i]),
+    "tfc_mask_fwd_blur": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i]),
+    "tfc_mask_merge": (_i, [_vp, _vp, _vp, _i, _i]),
+    "tfc_mask_bwd_dot": (_i, [_vp, _vp, _vp, _vp, _vp, _f, _vp, _vp, _i, _i, _i]),
+    "tfc_mask_bwd_blur": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i]),
+    "tfc_mask_bwd_lap": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i]),
     "tfc_pack_nhwc8_plane": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i]),
 }
 

@@ -69,6 +69,10 @@ hipError_t tfc_launch_spectrum(const float* img, const TfcWinGrid& g, int S, int
 size_t tfc_fft_ws_bytes(int S, int H, int nwin);
 hipError_t tfc_launch_l1_sum(const float* a, const float* b, long long n, float scale, float* out, hipStream_t st);
 hipError_t tfc_launch_batch_kl(const float* af, const float* pf, const float* ar, int N, long long M, float scale, float* out, hipStream_t st);
+hipError_t tfc_launch_batch_kl_stats(const float* af, const float* pf, const float* ar, int N, long long M, void* rec, hipStream_t st);
+hipError_t tfc_launch_batch_kl_merge(const void* recs, int world, long long M, void* glob, hipStream_t st);
+hipError_t tfc_launch_batch_kl_terms(const float* af, const float* pf, const float* ar, int N, long long M, const void* glob, float scale, float* out,
+                                     hipStream_t st);
 hipError_t tfc_launch_probe(float* out, hipStream_t st);
 hipError_t tfc_launch_logmag_mse(const float* a, const float* b, int S, int nwin, float* out, int absolute, hipStream_t st);
 // metrics.hip
@@ -884,6 +888,29 @@ extern "C" int tfc_batch_kl_sum(void* stream, const float* af, const float* pf, 
   CHECK_HIP(tfc_launch_batch_kl(af, pf, ar, N, M, scale, out, (hipStream_t)stream), "tfc_batch_kl_sum");
   return 0;
 }
+extern "C" int tfc_batch_kl_stats(void* stream, const float* af, const float* pf, const float* ar, int N, long long M, void* rec) {
+  REQUIRE(af && pf && ar && rec, "null argument");
+  REQUIRE(N > 0 && M >= 1, "bad dims N=%d M=%lld (N >= 1, M >= 1)", N, M);
+  REQUIRE((((uintptr_t)rec) & 7) == 0, "rec must be 8-byte aligned");
+  CHECK_HIP(tfc_launch_batch_kl_stats(af, pf, ar, N, M, rec, (hipStream_t)stream), "tfc_batch_kl_stats");
+  return 0;
+}
+extern "C" int tfc_batch_kl_merge(void* stream, const void* recs, int world, long long M, void* glob) {
+  REQUIRE(recs && glob, "null argument");
+  REQUIRE(world >= 1 && world <= 64, "world=%d (1 .. 64 records)", world);
+  REQUIRE(M >= 1, "M=%lld (M >= 1)", M);
+  REQUIRE(((((uintptr_t)recs) | ((uintptr_t)glob)) & 7) == 0, "recs / glob must be 8-byte aligned");
+  CHECK_HIP(tfc_launch_batch_kl_merge(recs, world, M, glob, (hipStream_t)stream), "tfc_batch_kl_merge");
+  return 0;
+}
+extern "C" int tfc_batch_kl_terms(void* stream, const float* af, const float* pf, const float* ar, int N, long long M, const void* glob, float scale,
+                                  float* out) {
+  REQUIRE(af && pf && ar && glob && out, "null argument");
+  REQUIRE(N > 0 && M >= 1, "bad dims N=%d M=%lld (N >= 1, M >= 1)", N, M);
+  REQUIRE((((uintptr_t)glob) & 7) == 0, "glob must be 8-byte aligned");
+  CHECK_HIP(tfc_launch_batch_kl_terms(af, pf, ar, N, M, glob, scale, out, (hipStream_t)stream), "tfc_batch_kl_terms");
+  return 0;
+}
 extern "C" int tfc_logmag_mse(void* stream, const float* amp_a, const float* amp_b, int S, int nwin, float* out) {
   REQUIRE(amp_a && amp_b && out && (S == 64 || S == 128 || S == 256) && nwin > 0, "bad args");
   CHECK_HIP(tfc_launch_logmag_mse(amp_a, amp_b, S, nwin, out, 0, (hipStream_t)stream), "tfc_logmag_mse");
@@ -1416,6 +1443,13 @@ hipError_t tfc_launch_mask_fwd(const float* img, float* lap, float* bl, void* ws
 hipError_t tfc_launch_mask_scale(const float* bl, const void* ws, float* mask, long long total, hipStream_t st);
 hipError_t tfc_launch_mask_bwd(const float* lap, const float* bl, void* ws, const float* dout, const float* ref, float scale, float* dout_buf,
                                float* dmn, float* dimg, int N, int H, int W, hipStream_t st);
+hipError_t tfc_launch_mask_phase_f1(const float* img, float* lap, void* ws, void* rec, int N, int H, int W, hipStream_t st);
+hipError_t tfc_launch_mask_phase_f2(const float* lap, float* bl, void* ws, void* rec, int N, int H, int W, hipStream_t st);
+hipError_t tfc_launch_mask_merge(void* ws, const void* recs, int world, int which, hipStream_t st);
+hipError_t tfc_launch_mask_phase_b0(const float* bl, void* ws, const float* dout, const float* ref, float scale, float* dout_buf, void* rec, int N, int H,
+                                    int W, hipStream_t st);
+hipError_t tfc_launch_mask_phase_b1(const float* lap, const float* bl, void* ws, const float* dout, float* dmn, void* rec, int N, int H, int W, hipStream_t st);
+hipError_t tfc_launch_mask_phase_b2(const float* lap, const void* ws, const float* dmn, float* dimg, int N, int H, int W, hipStream_t st);
 hipError_t tfc_launch_pack_plane(int dt, const float* img, const float* plane, const float* Mdev, void* out, int N, int HW, hipStream_t st);
 
 // both filters reflect once (padding 3 and 4): a side below 8 would need a second reflection for the blur of an 8 x 8 tile's halo
@@ -1453,6 +1487,62 @@ extern "C" int tfc_mask_bwd(void* stream, const float* lap, const float* bl, voi
   REQUIRE(dimg == nullptr || (al16(dimg) && al16(dmn)), "dimg and dmn (N*H*W floats) must be 16-byte aligned device pointers");
   REQUIRE(dimg != nullptr || ref != nullptr, "without dimg only the L1 loss (ref) is left to compute");
   CHECK_HIP(tfc_launch_mask_bwd(lap, bl, ws, dout, ref, scale, dout_buf, dmn, dimg, N, H, W, (hipStream_t)stream), "tfc_mask_bwd");
+  return 0;
+}
+
+// the phases of tfc_mask_fwd / tfc_mask_bwd; records are TFC_MASK_RECORD_BYTES each
+static inline bool al8(const void* p) { return p != nullptr && (((uintptr_t)p) & 7) == 0; }
+extern "C" int tfc_mask_fwd_lap(void* stream, const float* img, float* lap, void* ws, void* rec, int N, int H, int W) {
+  REQUIRE(img && lap && ws && rec, "null argument");
+  REQUIRE_MASK_IMAGE(N, H, W);
+  REQUIRE(al16(img) && al16(lap) && al16(ws) && al8(rec), "img / lap / ws must be 16-byte aligned device pointers, rec 8-byte aligned");
+  CHECK_HIP(tfc_launch_mask_phase_f1(img, lap, ws, rec, N, H, W, (hipStream_t)stream), "tfc_mask_fwd_lap");
+  return 0;
+}
+
+extern "C" int tfc_mask_fwd_blur(void* stream, const float* lap, float* bl, void* ws, void* rec, int N, int H, int W) {
+  REQUIRE(lap && bl && ws && rec, "null argument");
+  REQUIRE_MASK_IMAGE(N, H, W);
+  REQUIRE(al16(lap) && al16(bl) && al16(ws) && al8(rec), "lap / bl / ws must be 16-byte aligned device pointers, rec 8-byte aligned");
+  CHECK_HIP(tfc_launch_mask_phase_f2(lap, bl, ws, rec, N, H, W, (hipStream_t)stream), "tfc_mask_fwd_blur");
+  return 0;
+}
+
+extern "C" int tfc_mask_merge(void* stream, void* ws, const void* recs, int world, int which) {
+  REQUIRE(ws && recs, "null argument");
+  REQUIRE(world >= 1 && world <= 64, "world=%d (1 .. 64 records)", world);
+  REQUIRE(which >= 0 && which <= 3, "which=%d (0: after F1, 1: after F2, 2: after B0, 3: after B1)", which);
+  REQUIRE(al16(ws) && al8(recs), "ws must be a 16-byte aligned device pointer, recs 8-byte aligned");
+  CHECK_HIP(tfc_launch_mask_merge(ws, recs, world, which, (hipStream_t)stream), "tfc_mask_merge");
+  return 0;
+}
+
+extern "C" int tfc_mask_bwd_dot(void* stream, const float* bl, void* ws, const float* dout, const float* ref, float scale, float* dout_buf, void* rec,
+                                int N, int H, int W) {
+  REQUIRE(bl && ws && rec, "null argument");
+  REQUIRE_MASK_IMAGE(N, H, W);
+  REQUIRE(al16(bl) && al16(ws) && al8(rec), "bl / ws must be 16-byte aligned device pointers, rec 8-byte aligned");
+  REQUIRE((dout != nullptr) != (ref != nullptr), "exactly one of dout (an upstream gradient) and ref (the L1 loss against it) is given");
+  REQUIRE(al16(dout ? dout : ref), "dout / ref must be a 16-byte aligned device pointer");
+  REQUIRE(!ref || al16(dout_buf), "with ref, dout_buf (N*H*W floats, 16-byte aligned) receives the loss's gradient w.r.t. the mask");
+  CHECK_HIP(tfc_launch_mask_phase_b0(bl, ws, dout, ref, scale, dout_buf, rec, N, H, W, (hipStream_t)stream), "tfc_mask_bwd_dot");
+  return 0;
+}
+
+extern "C" int tfc_mask_bwd_blur(void* stream, const float* lap, const float* bl, void* ws, const float* dout, float* dmn, void* rec, int N, int H, int W) {
+  REQUIRE(lap && bl && ws && dout && dmn && rec, "null argument");
+  REQUIRE_MASK_IMAGE(N, H, W);
+  REQUIRE(al16(lap) && al16(bl) && al16(ws) && al16(dout) && al16(dmn) && al8(rec),
+          "lap / bl / ws / dout / dmn must be 16-byte aligned device pointers, rec 8-byte aligned");
+  CHECK_HIP(tfc_launch_mask_phase_b1(lap, bl, ws, dout, dmn, rec, N, H, W, (hipStream_t)stream), "tfc_mask_bwd_blur");
+  return 0;
+}
+
+extern "C" int tfc_mask_bwd_lap(void* stream, const float* lap, const void* ws, const float* dmn, float* dimg, int N, int H, int W) {
+  REQUIRE(lap && ws && dmn && dimg, "null argument");
+  REQUIRE_MASK_IMAGE(N, H, W);
+  REQUIRE(al16(lap) && al16(ws) && al16(dmn) && al16(dimg), "lap / ws / dmn / dimg must be 16-byte aligned device pointers");
+  CHECK_HIP(tfc_launch_mask_phase_b2(lap, ws, dmn, dimg, N, H, W, (hipStream_t)stream), "tfc_mask_bwd_lap");
   return 0;
 }
 

@@ -650,3 +650,80 @@ hipError_t tfc_launch_batch_kl(const float* af, const float* pf, const float* ar
   hipLaunchKernelGGL(tfc_batch_kl_kernel, dim3((int)nb), dim3(256), 0, st, af, pf, ar, N, M, scale, out);
   return hipGetLastError();
 }
+
+// ---- the same loss in phases, for a batch that is spread over `world` ranks: the softmax runs over the batch, so the state of the
+// online log-sum-exp, one (max, sum) pair per bin and spectrum, is what the ranks exchange between the two walks.
+//   K1    : first walk over this rank's N entries -> rec [3][M][2] = (m, z) of af, pf, ar
+//   merge : recs [world][3][M][2] -> glob [3][M][2] = (max, log sum) over all ranks. The pairs are folded in rank order by the re-basing rule of
+//           kl_online, with a rank's z in the place of the single entry's 1: the same floats on every rank. One record gives (m, logf(z)).
+//   K2    : second walk with the global pair: this rank's terms, through the slots and the grid of tfc_batch_kl_kernel (same stream rule)
+__global__ void __launch_bounds__(256)
+tfc_batch_kl_stats_kernel(const float* __restrict__ af, const float* __restrict__ pf, const float* __restrict__ ar, int N, long long M,
+                          float2* __restrict__ rec) {
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < M; i += (long long)gridDim.x * 256) {
+    float ma = -INFINITY, mp = -INFINITY, mr = -INFINITY, za = 0.f, zp = 0.f, zr = 0.f;
+    for (int n = 0; n < N; ++n) {
+      const size_t o = (size_t)n * M + i;
+      kl_online(af[o], ma, za); kl_online(pf[o], mp, zp); kl_online(ar[o], mr, zr);
+    }
+    rec[i] = make_float2(ma, za); rec[M + i] = make_float2(mp, zp); rec[2 * M + i] = make_float2(mr, zr);
+  }
+}
+
+__global__ void __launch_bounds__(1024)
+tfc_batch_kl_merge_kernel(const float2* __restrict__ recs, int world, long long M3, float2* __restrict__ glob) {
+  for (long long i = threadIdx.x; i < M3; i += 1024) {            // one workgroup; every bin folds its `world` pairs in rank order
+    float m = -INFINITY, z = 0.f;
+    for (int r = 0; r < world; ++r) {
+      const float2 p = recs[(size_t)r * M3 + i];
+      if (p.x > m) { z = z * expf(m - p.x) + p.y; m = p.x; }
+      else z += p.y * expf(p.x - m);
+    }
+    glob[i] = make_float2(m, logf(z));
+  }
+}
+
+__global__ void __launch_bounds__(256)
+tfc_batch_kl_terms_kernel(const float* __restrict__ af, const float* __restrict__ pf, const float* __restrict__ ar, int N, long long M,
+                          const float2* __restrict__ glob, float scale, float* out) {
+  __shared__ float red[2][4];
+  float sa = 0.f, sp = 0.f;
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < M; i += (long long)gridDim.x * 256) {
+    const float2 ga = glob[i], gp = glob[M + i], gr = glob[2 * M + i];
+    const float ma = ga.x, la = ga.y, mp = gp.x, lp = gp.y, mr = gr.x, lr = gr.y;
+    for (int n = 0; n < N; ++n) {
+      const size_t o = (size_t)n * M + i;
+      const float t = (ar[o] - mr) - lr;
+      const float e = expf(t);
+      if (e > 0.f) {
+        sa += e * (t - ((af[o] - ma) - la));
+        sp += e * (t - ((pf[o] - mp) - lp));
+      }
+    }
+  }
+  sa = wave_sum(sa); sp = wave_sum(sp);
+  if ((threadIdx.x & 63) == 0) { red[0][threadIdx.x >> 6] = sa; red[1][threadIdx.x >> 6] = sp; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    tfc_block_commit(&g_kl_amp_slot, ((double)red[0][0] + (double)red[0][1] + (double)red[0][2] + (double)red[0][3]) * (double)scale, out);
+    tfc_block_commit(&g_kl_pha_slot, ((double)red[1][0] + (double)red[1][1] + (double)red[1][2] + (double)red[1][3]) * (double)scale, out + 1);
+  }
+}
+
+static int kl_grid(long long M) {
+  long long nb = (M + 255) / 256;
+  return (int)(nb > 512 ? 512 : nb);
+}
+hipError_t tfc_launch_batch_kl_stats(const float* af, const float* pf, const float* ar, int N, long long M, void* rec, hipStream_t st) {
+  hipLaunchKernelGGL(tfc_batch_kl_stats_kernel, dim3(kl_grid(M)), dim3(256), 0, st, af, pf, ar, N, M, (float2*)rec);
+  return hipGetLastError();
+}
+hipError_t tfc_launch_batch_kl_merge(const void* recs, int world, long long M, void* glob, hipStream_t st) {
+  hipLaunchKernelGGL(tfc_batch_kl_merge_kernel, dim3(1), dim3(1024), 0, st, (const float2*)recs, world, 3 * M, (float2*)glob);
+  return hipGetLastError();
+}
+hipError_t tfc_launch_batch_kl_terms(const float* af, const float* pf, const float* ar, int N, long long M, const void* glob, float scale, float* out,
+                                     hipStream_t st) {
+  hipLaunchKernelGGL(tfc_batch_kl_terms_kernel, dim3(kl_grid(M)), dim3(256), 0, st, af, pf, ar, N, M, (const float2*)glob, scale, out);
+  return hipGetLastError();
+}

@@ -376,6 +376,86 @@ tfc_mask_lap_bwd_kernel(const float* __restrict__ dmn, const float* __restrict__
   }
 }
 
+// ---- the same work in phases, for a batch that is spread over `world` ranks -------------------------------------------------------
+// Between two phases every rank leaves a RECORD of four 64-bit words, the caller gathers the records of all ranks in rank order, and a one-workgroup
+// merge kernel turns them into the stats floats the next phase reads -- the same floats on every rank, because every rank merges the same records
+// in the same order. Extrema travel as (fp32 bits, 64-bit tie count) and merge by the rule of tfc_mask_final_extrema_kernel (the smaller / larger
+// value wins with its count, equal values add their counts); sums travel as doubles and are added in rank order. With one record the stats floats
+// are the ones the unsplit finalisers write, bit for bit.
+//   after F1: {bits(mn), ties(mn), bits(mx), ties(mx)}     after F2: {bits(M), ties(M), 0, 0}
+//   after B0: {sum |mask - ref|, sum dout Bl, 0, 0}        after B1: {sum dMn (L - mn), sum dMn (L - mx), 0, 0}     (doubles)
+#define MK_REC_WORDS 4
+
+// one workgroup: the extrema partials of this rank -> its record (which 0: after F1, which 1: after F2). The reduction of tfc_mask_final_extrema_kernel.
+__global__ void __launch_bounds__(256)
+tfc_mask_record_extrema_kernel(const uint4* __restrict__ part, int nblk, unsigned long long* __restrict__ rec, int which) {
+  __shared__ float lv[256];
+  __shared__ unsigned long long lc[256];
+  float mn = __builtin_inff(), mx = -1.f;
+  unsigned long long cmn = 0, cmx = 0;
+  for (int k = threadIdx.x; k < nblk; k += 256) {
+    const uint4 p = part[k];
+    const float a = __uint_as_float(p.x), c = __uint_as_float(p.z);
+    if (a == mn) cmn += p.y; else if (a < mn) { mn = a; cmn = p.y; }
+    if (c == mx) cmx += p.w; else if (c > mx) { mx = c; cmx = p.w; }
+  }
+  mk_extremum<false>(mn, cmn, lv, lc);
+  mk_extremum<true>(mx, cmx, lv, lc);
+  if (threadIdx.x == 0) {
+    if (which == 0) { rec[0] = __float_as_uint(mn); rec[1] = cmn; rec[2] = __float_as_uint(mx); rec[3] = cmx; }
+    else { rec[0] = __float_as_uint(mx); rec[1] = cmx; rec[2] = 0ull; rec[3] = 0ull; }
+  }
+}
+
+// one workgroup: the pairs of doubles of this rank -> its record, the fixed order of tfc_mask_final_sums_kernel. With loss_out (after B0) this rank's
+// own L1 loss, scale * mean over ITS samples of |mask - ref| (masks normalised by the merged extrema), goes to the stats.
+__global__ void __launch_bounds__(256)
+tfc_mask_record_sums_kernel(const double* __restrict__ part, int nblk, double* __restrict__ rec, float* __restrict__ loss_out, float loss_scale) {
+  __shared__ double l0[256], l1[256];
+  double s0 = 0.0, s1 = 0.0;
+  for (int k = threadIdx.x; k < nblk; k += 256) { s0 += part[2 * (size_t)k]; s1 += part[2 * (size_t)k + 1]; }
+  mk_sum2(s0, s1, l0, l1);
+  if (threadIdx.x == 0) {
+    rec[0] = s0; rec[1] = s1; rec[2] = 0.0; rec[3] = 0.0;
+    if (loss_out) loss_out[0] = (float)(s0 * (double)loss_scale);
+  }
+}
+
+// one workgroup, one lane: the records of `world` ranks (rank order) -> stats. which 0: (mn, mx, ties) of |lap|; 1: (M, ties) of Bl;
+// 2: d/dM per tie from the sum of dout Bl over all ranks; 3: (d/dmx, d/dmn per tie) from the two sums of B1 over all ranks.
+__global__ void __launch_bounds__(64)
+tfc_mask_merge_kernel(const unsigned long long* __restrict__ recs, int world, float* __restrict__ stats, int which) {
+  if (threadIdx.x != 0) return;
+  if (which <= 1) {
+    float mn = __builtin_inff(), mx = -1.f;
+    unsigned long long cmn = 0, cmx = 0;
+    for (int r = 0; r < world; ++r) {
+      const unsigned long long* p = recs + (size_t)r * MK_REC_WORDS;
+      if (which == 0) {
+        const float a = __uint_as_float((unsigned)p[0]);
+        if (a == mn) cmn += p[1]; else if (a < mn) { mn = a; cmn = p[1]; }
+      }
+      const float c = __uint_as_float((unsigned)p[which == 0 ? 2 : 0]);
+      const unsigned long long cc = p[which == 0 ? 3 : 1];
+      if (c == mx) cmx += cc; else if (c > mx) { mx = c; cmx = cc; }
+    }
+    if (which == 0) { stats[MS_MN] = mn; stats[MS_MX] = mx; stats[MS_CMN] = (float)cmn; stats[MS_CMX] = (float)cmx; }
+    else { stats[MS_M] = mx; stats[MS_CM] = (float)cmx; }
+  } else {
+    const double* d = reinterpret_cast<const double*>(recs);
+    double s0 = d[0], s1 = d[1];                                  // starts from rank 0's doubles, not from +0.0: one record passes through unchanged
+    for (int r = 1; r < world; ++r) { s0 += d[(size_t)r * MK_REC_WORDS]; s1 += d[(size_t)r * MK_REC_WORDS + 1]; }
+    if (which == 2) {
+      const double M = stats[MS_M];
+      stats[MS_DM] = (float)(-(s1 / (M * M)) / (double)stats[MS_CM]);
+    } else {
+      const double D = (double)stats[MS_MX] - (double)stats[MS_MN];
+      stats[MS_DMX] = (float)(-(s0 / (D * D)) / (double)stats[MS_CMX]);
+      stats[MS_DMN] = (float)((s1 / (D * D)) / (double)stats[MS_CMN]);
+    }
+  }
+}
+
 // ---- torch.cat((img, plane), 1) -> NHWC8 of the compute dtype: channels 0..2 img, 3 the plane (divided by *Mdev when given: Bl -> mask), 4..7 zero
 template <typename T>
 __global__ void __launch_bounds__(256)
@@ -455,6 +535,52 @@ hipError_t tfc_launch_mask_bwd(const float* lap, const float* bl, void* ws, cons
     hipLaunchKernelGGL(tfc_mask_final_sums_kernel, dim3(1), dim3(256), 0, st, (const double*)part, nblk, stats, 1, 0.f);
     hipLaunchKernelGGL(tfc_mask_lap_bwd_kernel, grid, dim3(256), 0, st, (const float*)dmn, lap, dimg, (const float*)stats, H, W);
   }
+  return hipGetLastError();
+}
+
+// ---- the phases: each launcher runs the kernels of one phase of tfc_launch_mask_fwd / tfc_launch_mask_bwd, with the record kernel in the finaliser's place
+hipError_t tfc_launch_mask_phase_f1(const float* img, float* lap, void* ws, void* rec, int N, int H, int W, hipStream_t st) {
+  uint4* part = (uint4*)((float*)ws + MS_FLOATS);
+  hipLaunchKernelGGL(tfc_mask_lap_kernel, tile_grid(N, H, W), dim3(256), 0, st, img, lap, part, H, W);
+  hipLaunchKernelGGL(tfc_mask_record_extrema_kernel, dim3(1), dim3(256), 0, st, (const uint4*)part, (int)tfc_mask_nblk(N, H, W), (unsigned long long*)rec, 0);
+  return hipGetLastError();
+}
+
+hipError_t tfc_launch_mask_phase_f2(const float* lap, float* bl, void* ws, void* rec, int N, int H, int W, hipStream_t st) {
+  float* stats = (float*)ws;
+  uint4* part = (uint4*)(stats + MS_FLOATS);
+  hipLaunchKernelGGL(tfc_mask_blur_kernel, tile_grid(N, H, W), dim3(256), 0, st, lap, bl, part, (const float*)stats, gauss_taps(), H, W);
+  hipLaunchKernelGGL(tfc_mask_record_extrema_kernel, dim3(1), dim3(256), 0, st, (const uint4*)part, (int)tfc_mask_nblk(N, H, W), (unsigned long long*)rec, 1);
+  return hipGetLastError();
+}
+
+hipError_t tfc_launch_mask_merge(void* ws, const void* recs, int world, int which, hipStream_t st) {
+  hipLaunchKernelGGL(tfc_mask_merge_kernel, dim3(1), dim3(64), 0, st, (const unsigned long long*)recs, world, (float*)ws, which);
+  return hipGetLastError();
+}
+
+hipError_t tfc_launch_mask_phase_b0(const float* bl, void* ws, const float* dout, const float* ref, float scale, float* dout_buf, void* rec, int N, int H,
+                                    int W, hipStream_t st) {
+  float* stats = (float*)ws;
+  double* part = (double*)(stats + MS_FLOATS);
+  const long long total = (long long)N * H * W;
+  const int nd = (int)((total + 1023) / 1024);
+  const float gs = (float)((double)scale / (double)total);
+  hipLaunchKernelGGL(tfc_mask_dot_kernel, dim3((unsigned)nd), dim3(256), 0, st, bl, (const float*)stats, dout, ref, gs, dout_buf, part, total);
+  hipLaunchKernelGGL(tfc_mask_record_sums_kernel, dim3(1), dim3(256), 0, st, (const double*)part, nd, (double*)rec, stats + MS_LOSS, gs);
+  return hipGetLastError();
+}
+
+hipError_t tfc_launch_mask_phase_b1(const float* lap, const float* bl, void* ws, const float* dout, float* dmn, void* rec, int N, int H, int W, hipStream_t st) {
+  float* stats = (float*)ws;
+  double* part = (double*)(stats + MS_FLOATS);
+  hipLaunchKernelGGL(tfc_mask_blur_bwd_kernel, tile_grid(N, H, W), dim3(256), 0, st, dout, bl, lap, dmn, part, (const float*)stats, gauss_taps(), H, W);
+  hipLaunchKernelGGL(tfc_mask_record_sums_kernel, dim3(1), dim3(256), 0, st, (const double*)part, (int)tfc_mask_nblk(N, H, W), (double*)rec, (float*)nullptr, 0.f);
+  return hipGetLastError();
+}
+
+hipError_t tfc_launch_mask_phase_b2(const float* lap, const void* ws, const float* dmn, float* dimg, int N, int H, int W, hipStream_t st) {
+  hipLaunchKernelGGL(tfc_mask_lap_bwd_kernel, tile_grid(N, H, W), dim3(256), 0, st, dmn, lap, dimg, (const float*)ws, H, W);
   return hipGetLastError();
 }
 

@@ -25,7 +25,7 @@ losses.region_weights gives each script's weights). It carries no gradient in th
              real_loss_label = d_label_scale * sum_h CE(head_h(B, A), labels[:, h]); fake_loss_label the same on (fake, A) against the DRAWN labels
              in every variant (DB1:603-606, DB3:612-618)
 CE is the reference's nn.CrossEntropyLoss applied to the heads' Softmax output (two softmaxes), kept as it is. V4..V7 of the family (two frozen
-pretrained ResNet18 classifiers) are not covered, and the labelled step is tested on one rank only.
+pretrained ResNet18 classifiers) are not covered. Every term of the labelled step is per sample: it shards like PATCH-4 (tests/test_gpu_46_coupled_ddp.py).
 
 `patches=4, mask=True` runs the edge-mask script TFCGAN_multigpu_patchFFT_experiment.py ("4X") on GeneratorUNet(mask=True); losses.mask_weights gives
 its keywords.
@@ -33,8 +33,12 @@ its keywords.
              loss_G += lambda_mask * loss_mask, loss_mask = L1(mask_maker(fake), mask_maker(real_B))                      (4X:584-587)
              its exact gradient (csrc/mask.hip: batch extrema with ties, adjoints of the reflect-padded filters) joins the gradient of fake
     D step : PATCH-4's.
-The mask normalises by extrema of the WHOLE batch, so the samples of a batch are coupled by definition: an explicit batch_invariant=True is refused, and
-with several ranks each rank normalises its own shard (the reference's DataParallel normalises the gathered batch): multi-rank MASK-4 is not covered.
+The mask normalises by extrema of the WHOLE batch, so the samples of a batch are coupled by definition: an explicit batch_invariant=True is refused.
+
+`batch_scope="global"` (the default) keeps the two batch-coupled terms -- the mask's extrema, the KL form's softmax over the batch -- those of the
+gathered batch on several ranks, as the reference's DataParallel computes them: their kernels run in phases and the ranks exchange the state of the
+reductions in between (six small all-gathers per MASK-4 step on top of mask_A's two, one per KL step). "shard" takes them over each
+rank's own samples. Without active collectives both are the same launches.
 """
 import math
 import os
@@ -58,8 +62,10 @@ class TrainStep:
     def __init__(self, generator, discriminator, lr=2e-4, b1=0.5, b2=0.999, eps=1e-8, compute_dtype=torch.bfloat16,
                  fft_mode="patch", seed=0, bucket_bytes=16 << 20, lambda_gan=0.5, lambda_fft=0.01, lambda_trip=1.0, d_bucket_bytes=4 << 20,
                  batch_invariant=None, patches=16, region_fft=None, lambda_region=0.5e-4, labels=None, label_weights=(1.0, 1.0, 1.0),
-                 d_label_scale=1.0, mask=False, lambda_mask=0.5):
+                 d_label_scale=1.0, mask=False, lambda_mask=0.5, batch_scope="global"):
         dev = next(generator.parameters()).device
+        ops.phased_scope(batch_scope, "TrainStep")                # refuses an unknown value
+        self.batch_scope = batch_scope
         if patches not in (4, 16):
             raise ops._lib.TfcError(f"TrainStep: patches={patches} (16: the 4x4 grid of 64x64 patches, 4: the 2x2 grid of 128x128 patches)")
         self.patches = patches
@@ -201,13 +207,14 @@ class TrainStep:
             lf = patch_fft_loss(fake, real_B, self.patches) if self.fft_mode == "patch" else global_fft_loss(fake, real_B)
             ex = extra_loss_G(fake, real_B) if extra_loss_G is not None else None     # optional pluggable term (LPIPS, P16:598): (loss, dfake), already weighted
             # forward-only head: beside the other pixel losses, on their stream; (loss_FFT_reg, loss_Amp_reg, loss_Pha_reg) or None
-            reg = regional_fft_loss(fake, real_B, self.region_fft) if self.region_fft is not None else None
-            # the mask term: (lambda_mask * loss_mask, its gradient w.r.t. fake); mask(real_B) once per step
-            mk = mask_l1_loss(fake, real_B, scale=self.lambda_mask) if (self.mask and self.lambda_mask != 0.0) else None
+            reg = regional_fft_loss(fake, real_B, self.region_fft, batch_scope=self.batch_scope) if self.region_fft is not None else None
+            # the mask term: (lambda_mask * loss_mask, its gradient w.r.t. fake); mask(real_B) once per step. With batch_scope="global" on several ranks
+            # its exchanges are issued here, on the stream the pixel losses run on, in program order like every collective of the step
+            mk = mask_l1_loss(fake, real_B, scale=self.lambda_mask, batch_scope=self.batch_scope) if (self.mask and self.lambda_mask != 0.0) else None
             return lt, gt, lf, ex, reg, mk
         g_in = {"labels": g_labels}
         if self.mask:                                             # mask_A = mask_maker(real_A): Bl and its batch maximum stay on the device, the
-            mctx = ops.mask_fwd(real_A)                           # packing kernel divides on the way into input channel 3
+            mctx = ops.mask_fwd(real_A, batch_scope=self.batch_scope)     # packing kernel divides on the way into input channel 3
             g_in = {"plane": mctx.bl, "plane_div": mctx.M}
         if nets.side_stream_on() and os.environ.get("TFC_NO_GSTEP_OVERLAP", "0") in ("", "0"):
             # Two-stream form of the same program (nets.py: side stream). Both power iterations of this step's two discriminator calls come first, in
@@ -300,8 +307,9 @@ class TrainStep:
             loss_reg, loss_amp_reg, loss_pha_reg = region
             self.last["loss_G"] = self.last["loss_G"] + self.lambda_region * loss_reg
             self.last.update(loss_FFT_reg=loss_reg, loss_Amp_reg=loss_amp_reg, loss_Pha_reg=loss_pha_reg)
-        # Every logged loss but the KL regional term is a batch mean, so the mean over ranks is the global-batch value. With region_fft="kl" the
-        # softmax runs over each rank's shard: loss_FFT_reg, loss_Amp_reg, loss_Pha_reg and their share of loss_G are the mean of per-shard values.
+        # Every logged loss is a batch mean or, for the two batch-coupled terms under batch_scope="global" (loss_mask; loss_FFT_reg, loss_Amp_reg,
+        # loss_Pha_reg of region_fft="kl"), this rank's share of one: the mean over ranks is the global-batch value. Under batch_scope="shard" those
+        # terms are normalised per shard and their logged values are the mean of per-shard values, not the reference's.
         if parallel.collectives_active():
             keys = [k for k in self.last if self.last[k].numel() == 1]      # the scalars (not fake_B, not the heads' probabilities)
             packed = torch.stack([self.last[k].reshape(()).float() for k in keys])

@@ -211,16 +211,19 @@ def regional_fft_components(thermal_tensor, region):
     return amp.reshape(N, 1, H, 129), pha.reshape(N, 1, H, 129)
 
 
-def regional_fft_loss(fake_B, real_B, kind="l1"):
+def regional_fft_loss(fake_B, real_B, kind="l1", batch_scope="global"):
     """regional_fft_loss of 4R (kind="l1", 4R:353-401) or 4K (kind="kl", 4K:357-420) -> (loss_FFT_reg, loss_Amp_reg, loss_Pha_reg), device scalars
     without gradient (the reference goes tensor -> PIL -> numpy) and without a host synchronisation.
       l1: loss_Amp_reg = L1mean(Ah_F, Ah_R) + L1mean(Ae_F, Ae_R) -- a SUM over the two regions --, loss_Pha_reg the same of the phases (4R:391-398).
       kl: every spectrum through F.log_softmax(., dim=0), i.e. over the BATCH, then nn.KLDivLoss(reduction="mean", log_target=True) = mean of
           exp(t)(t - x), summed over the two regions (4K:400-417). The reference builds the real PHASE target from the real AMPLITUDES (4K:401, :404);
           that is reproduced literally: the target of the phase term is the target of the amplitude term. At N = 1 the loss is exactly 0.
-    loss_FFT_reg = 1/2 (loss_Amp_reg + loss_Pha_reg) in both. The spectra are taken unshifted: every term is a sum over all bins."""
+    loss_FFT_reg = 1/2 (loss_Amp_reg + loss_Pha_reg) in both. The spectra are taken unshifted: every term is a sum over all bins.
+    batch_scope (kind="kl" on several ranks): "global", the softmax runs over the batch of ALL ranks and each rank returns the mean of its own terms --
+    the mean over ranks is the loss of the gathered batch (ops.batch_kl_sum); "shard", over this rank's samples only. The L1 form is per sample."""
     if kind not in ("l1", "kl"):
         raise ops._lib.TfcError(f"regional_fft_loss: kind={kind!r} ('l1': ..._withregion_FFT.py, 'kl': ..._withregion_FFT_KL.py)")
+    ops.phased_scope(batch_scope, "regional_fft_loss")
     ops.require_gpu(fake_B, real_B)
     N = fake_B.shape[0]
     (_, H), step = REGIONS["hair"], REGIONS["eyes"][0]
@@ -231,7 +234,7 @@ def regional_fft_loss(fake_B, real_B, kind="l1"):
     else:
         (af, pf), (ar, _) = spectrum(fake_B.detach()), spectrum(real_B.detach())
         out = torch.zeros(2, dtype=torch.float32, device=fake_B.device)
-        ops.batch_kl_sum(af.reshape(N, -1), pf.reshape(N, -1), ar.reshape(N, -1), scale, out)
+        ops.batch_kl_sum(af.reshape(N, -1), pf.reshape(N, -1), ar.reshape(N, -1), scale, out, batch_scope=batch_scope)
     return 0.5 * (out[0] + out[1]), out[0], out[1]
 
 
@@ -271,22 +274,26 @@ def mask_weights():
     return {"lambda_gan": 0.5, "lambda_trip": 0.5, "lambda_fft": 4 * 0.001, "lambda_mask": 0.5}
 
 
-def mask_maker(img):
+def mask_maker(img, batch_scope="global"):
     """reference 4X:385-390: the edge mask [N,1,H,W] of img [N,3,H,W] -- |7x7 normalised Laplacian| of the grayscale image, min/max-normalised over
     the WHOLE batch, 9x9 Gaussian blur (sigma 1.6), divided by its batch maximum (csrc/mask.hip; fp32 in every compute mode). Forward only: the exact
-    backward lives in mask_l1_loss / TrainStep(mask=True). A constant batch (max == min) gives NaN, as in the reference."""
+    backward lives in mask_l1_loss / TrainStep(mask=True). A constant batch (max == min) gives NaN, as in the reference. On several ranks the whole
+    batch is the gathered batch of all ranks (batch_scope="global", two small exchanges: ops.mask_fwd) or this rank's samples ("shard")."""
     if torch.is_grad_enabled() and img.requires_grad:
         raise ops._lib.TfcError("mask_maker is forward-only (no autograd graph): call it under torch.no_grad() / on a detached image; the gradient of "
                                 "the mask loss comes from tfc_gan_amd.mask_l1_loss(fake, real) or TrainStep(mask=True)")
-    return ops.mask_scale(ops.mask_fwd(img))
+    return ops.mask_scale(ops.mask_fwd(img, batch_scope=batch_scope))
 
 
-def mask_l1_loss(fake, real, scale=1.0, want_grad=True, real_mask=None):
+def mask_l1_loss(fake, real, scale=1.0, want_grad=True, real_mask=None, batch_scope="global"):
     """(loss, dfake): scale * mean|mask_maker(fake) - mask_maker(real)| (4X:584-585) and its exact gradient w.r.t. fake (None without want_grad),
-    through the batch extrema, their ties and both reflect-padded filters. real_mask: mask_maker(real) when the caller already has it."""
+    through the batch extrema, their ties and both reflect-padded filters. real_mask: mask_maker(real) when the caller already has it.
+    batch_scope="global" on several ranks: both masks are normalised over the gathered batch; loss is this rank's share (the mean over ranks is the
+    loss of the gathered batch) and dfake the gradient of the sum of the shares, as a gradient MEAN over ranks expects (ops.mask_bwd)."""
+    ops.phased_scope(batch_scope, "mask_l1_loss")
     if real_mask is None:
-        real_mask = ops.mask_scale(ops.mask_fwd(real))
-    loss, dfake = ops.mask_bwd(ops.mask_fwd(fake), ref=real_mask, scale=scale, want_grad=want_grad)
+        real_mask = ops.mask_scale(ops.mask_fwd(real, batch_scope=batch_scope))
+    loss, dfake = ops.mask_bwd(ops.mask_fwd(fake, batch_scope=batch_scope), ref=real_mask, scale=scale, want_grad=want_grad, batch_scope=batch_scope)
     return loss.reshape(()), dfake
 
 

@@ -9,7 +9,7 @@ from dataclasses import dataclass
 
 import torch
 
-from . import _lib
+from . import _lib, parallel
 from ._lib import (DT_BF16, DT_BF16X3, DT_F32, EP_ACCUM, EP_BIAS, EP_LEAKY, EP_RELU, EP_STATS, EP_TANH_NCHW, OP_CONV, OP_CONV3, OP_CONVT, OP_PADCONV, OP_UPCONV,
                    check)
 
@@ -503,9 +503,23 @@ def fft_spectrum_rect(img, H, row0=0, row_step=0, wins=1, shift=True):
     return amp, pha
 
 
-def batch_kl_sum(af, pf, ar, scale, out):
+BATCH_SCOPES = ("global", "shard")
+
+
+def phased_scope(batch_scope, what):
+    """does a batch-coupled operator run in phases with an exchange between them? batch_scope "global" (the default): the batch is the gathered batch
+    of all ranks, so with active collectives (parallel.collectives_active) yes; "shard": each rank's own samples, as before the phases existed.
+    Without active collectives both values take the unsplit entry point: same launches, same bits."""
+    if batch_scope not in BATCH_SCOPES:
+        raise _lib.TfcError(f"{what}: batch_scope={batch_scope!r} ('global': the batch of all ranks, 'shard': this rank's samples)")
+    return batch_scope == "global" and parallel.collectives_active()
+
+
+def batch_kl_sum(af, pf, ar, scale, out, batch_scope="global", group=None):
     """out[0] += scale * sum exp(t)(t - xa), out[1] += scale * sum exp(t)(t - xp) with t / xa / xp = log_softmax over dim 0 of ar / af / pf
-    (contiguous fp32 [N, ...] of one shape; ar is the target of both terms, as in the reference's KL regional loss)."""
+    (contiguous fp32 [N, ...] of one shape; ar is the target of both terms, as in the reference's KL regional loss). batch_scope "global" on several
+    ranks: the softmax runs over the entries of all ranks and the sums over this rank's terms (phased_scope)."""
+    phased = phased_scope(batch_scope, "batch_kl_sum")
     require_gpu(af, pf, ar, out)
     for name, v in (("af", af), ("pf", pf), ("ar", ar)):
         if v.dtype != torch.float32 or not v.is_contiguous() or v.shape != af.shape or v.dim() < 1 or v.shape[0] < 1:
@@ -514,7 +528,16 @@ def batch_kl_sum(af, pf, ar, scale, out):
     if out.dtype != torch.float32 or not out.is_contiguous() or out.numel() < 2:
         raise _lib.TfcError(f"batch_kl_sum: out is {out.dtype} with {out.numel()} elements (contiguous fp32, at least 2)")
     N = af.shape[0]
-    check(lib().tfc_batch_kl_sum(stream_ptr(), _p(af), _p(pf), _p(ar), N, af.numel() // N, scale, _p(out)), "tfc_batch_kl_sum")
+    M = af.numel() // N
+    if not phased:
+        check(lib().tfc_batch_kl_sum(stream_ptr(), _p(af), _p(pf), _p(ar), N, M, scale, _p(out)), "tfc_batch_kl_sum")
+        return
+    # the softmax over the batch of ALL ranks: first walk, exchange of the (max, sum) pairs, merge in rank order, second walk
+    rec = torch.empty((3, M, 2), dtype=torch.float32, device=af.device)
+    check(lib().tfc_batch_kl_stats(stream_ptr(), _p(af), _p(pf), _p(ar), N, M, _p(rec)), "tfc_batch_kl_stats")
+    recs = parallel.all_gather_records(rec, group)
+    check(lib().tfc_batch_kl_merge(stream_ptr(), _p(recs), recs.shape[0], M, _p(rec)), "tfc_batch_kl_merge")      # rec is free again: the global pairs
+    check(lib().tfc_batch_kl_terms(stream_ptr(), _p(af), _p(pf), _p(ar), N, M, _p(rec), scale, _p(out)), "tfc_batch_kl_terms")
 
 
 def logmag_mse(amp_a, amp_b, absolute=False):
@@ -672,12 +695,17 @@ MASK_STATS = 16                     # floats at the head of a mask workspace: mn
 
 class MaskCtx:
     """what one forward of the mask operator leaves on the device: the signed Laplacian, the blurred plane Bl (mask = Bl / M) and the workspace that
-    holds the extrema, their tie counts and (after a backward) the global sums. Nothing of it is read by the host."""
-    __slots__ = ("N", "H", "W", "lap", "bl", "ws")
+    holds the extrema, their tie counts and (after a backward) the global sums. Nothing of it is read by the host. phased: the extrema are those of
+    all ranks' samples (mask_fwd ran in phases); the backward then runs in phases too, over `group`."""
+    __slots__ = ("N", "H", "W", "lap", "bl", "ws", "phased", "group")
 
     @property
     def M(self):                    # device float: max of Bl over the batch
         return self.ws[4:5]
+
+
+MASK_RECORD_WORDS = 4               # TFC_MASK_RECORD_BYTES / 8: what a rank leaves between two phases (include/tfc_gan.h)
+MASK_TIE_LIMIT = 1 << 24            # tie counts are kept as floats in the workspace: exact up to 2^24
 
 
 def _mask_dims(img, what):
@@ -689,17 +717,42 @@ def _mask_dims(img, what):
     return N, H, W
 
 
-def mask_fwd(img):
-    """img fp32 [N,3,H,W] -> MaskCtx (lap, Bl, extrema on the device). fp32 in every compute mode."""
+def check_mask_tie_range(world, N, H, W, what="mask_fwd"):
+    """a tie count of the gathered batch can reach world * N * H * W and is kept as a float: refuse what a float cannot count"""
+    if world * N * H * W > MASK_TIE_LIMIT:
+        raise _lib.TfcError(f"{what}: world * N * H * W = {world} * {N} * {H} * {W} = {world * N * H * W} > 2^24: the tie counts of the batch extrema "
+                            f"are kept as fp32 and would no longer be exact (use batch_scope='shard' or a smaller global batch)")
+
+
+def _mask_exchange(c, rec, which):
+    """gather this rank's record, merge the records of all ranks into the stats floats of c.ws"""
+    recs = parallel.all_gather_records(rec, c.group)
+    check(lib().tfc_mask_merge(stream_ptr(), _p(c.ws), _p(recs), recs.shape[0], which), "tfc_mask_merge")
+
+
+def mask_fwd(img, batch_scope="global", group=None):
+    """img fp32 [N,3,H,W] -> MaskCtx (lap, Bl, extrema on the device). fp32 in every compute mode. batch_scope "global" on several ranks: the extrema
+    are those of the gathered batch (two phases, two small exchanges: phased_scope)."""
+    phased = phased_scope(batch_scope, "mask_fwd")
     require_gpu(img)
     N, H, W = _mask_dims(img, "mask_fwd")
+    if phased:
+        check_mask_tie_range(parallel.dist.get_world_size(group), N, H, W)
     img = img.detach().contiguous().float()
     c = MaskCtx()
-    c.N, c.H, c.W = N, H, W
+    c.N, c.H, c.W, c.phased, c.group = N, H, W, phased, group
     c.lap = torch.empty((N, 1, H, W), dtype=torch.float32, device=img.device)
     c.bl = torch.empty_like(c.lap)
     c.ws = torch.empty(lib().tfc_mask_ws_bytes(N, H, W) // 4, dtype=torch.float32, device=img.device)
-    check(lib().tfc_mask_fwd(stream_ptr(), _p(img), _p(c.lap), _p(c.bl), _p(c.ws), N, H, W), "tfc_mask_fwd")
+    if not phased:
+        check(lib().tfc_mask_fwd(stream_ptr(), _p(img), _p(c.lap), _p(c.bl), _p(c.ws), N, H, W), "tfc_mask_fwd")
+        return c
+    rec = torch.empty(MASK_RECORD_WORDS, dtype=torch.int64, device=img.device)
+    check(lib().tfc_mask_fwd_lap(stream_ptr(), _p(img), _p(c.lap), _p(c.ws), _p(rec), N, H, W), "tfc_mask_fwd_lap")
+    _mask_exchange(c, rec, 0)
+    rec = torch.empty_like(rec)                                   # a fresh record: the gather of the first may still be reading it
+    check(lib().tfc_mask_fwd_blur(stream_ptr(), _p(c.lap), _p(c.bl), _p(c.ws), _p(rec), N, H, W), "tfc_mask_fwd_blur")
+    _mask_exchange(c, rec, 1)
     return c
 
 
@@ -710,11 +763,16 @@ def mask_scale(c: MaskCtx):
     return out
 
 
-def mask_bwd(c: MaskCtx, dout=None, ref=None, scale=1.0, want_grad=True):
+def mask_bwd(c: MaskCtx, dout=None, ref=None, scale=1.0, want_grad=True, batch_scope="global"):
     """exact backward of the mask operator through the context of its forward. dout [N,1,H,W]: an upstream gradient -> dimg [N,3,H,W]. ref [N,1,H,W]:
-    the L1 loss scale * mean|mask - ref| -> (loss [1], dimg or None)."""
+    the L1 loss scale * mean|mask - ref| -> (loss [1], dimg or None). Through a context whose forward ran in phases (batch_scope "global" on several
+    ranks) the loss is this rank's share, scale * mean over ITS samples -- the mean over ranks is the loss of the gathered batch --, and dimg is the
+    gradient of the SUM of the ranks' shares (of the ranks' sum dout * mask) w.r.t. this rank's images: after the 1/world of the gradient exchange the
+    parameters receive the gradient of the gathered-batch loss."""
     if (dout is None) == (ref is None):
         raise _lib.TfcError("mask_bwd: exactly one of dout (an upstream gradient) and ref (the L1 loss against it)")
+    if phased_scope(batch_scope, "mask_bwd") != c.phased:
+        raise _lib.TfcError(f"mask_bwd: batch_scope={batch_scope!r} through a context whose forward ran with the other scope")
     u = dout if ref is None else ref
     require_gpu(u, c.bl)
     if tuple(u.shape) != tuple(c.bl.shape):
@@ -724,8 +782,20 @@ def mask_bwd(c: MaskCtx, dout=None, ref=None, scale=1.0, want_grad=True):
     dimg = torch.empty((c.N, 3, c.H, c.W), dtype=torch.float32, device=dev) if (want_grad or ref is None) else None
     dmn = torch.empty_like(c.bl) if dimg is not None else None
     dbuf = torch.empty_like(c.bl) if ref is not None else None
-    check(lib().tfc_mask_bwd(stream_ptr(), _p(c.lap), _p(c.bl), _p(c.ws), _p(u if ref is None else None), _p(u if ref is not None else None),
-                             float(scale), _p(dbuf), _p(dmn), _p(dimg), c.N, c.H, c.W), "tfc_mask_bwd")
+    if not c.phased:
+        check(lib().tfc_mask_bwd(stream_ptr(), _p(c.lap), _p(c.bl), _p(c.ws), _p(u if ref is None else None), _p(u if ref is not None else None),
+                                 float(scale), _p(dbuf), _p(dmn), _p(dimg), c.N, c.H, c.W), "tfc_mask_bwd")
+    else:
+        rec = torch.empty(MASK_RECORD_WORDS, dtype=torch.int64, device=dev)
+        check(lib().tfc_mask_bwd_dot(stream_ptr(), _p(c.bl), _p(c.ws), _p(u if ref is None else None), _p(u if ref is not None else None),
+                                     float(scale), _p(dbuf), _p(rec), c.N, c.H, c.W), "tfc_mask_bwd_dot")
+        if dimg is not None:                                      # the loss alone needs no exchange: it is this rank's own
+            _mask_exchange(c, rec, 2)
+            rec = torch.empty_like(rec)
+            check(lib().tfc_mask_bwd_blur(stream_ptr(), _p(c.lap), _p(c.bl), _p(c.ws), _p(u if ref is None else dbuf), _p(dmn), _p(rec), c.N, c.H, c.W),
+                  "tfc_mask_bwd_blur")
+            _mask_exchange(c, rec, 3)
+            check(lib().tfc_mask_bwd_lap(stream_ptr(), _p(c.lap), _p(c.ws), _p(dmn), _p(dimg), c.N, c.H, c.W), "tfc_mask_bwd_lap")
     if ref is None:
         return dimg
     return c.ws[7:8].clone(), dimg

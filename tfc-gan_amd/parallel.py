@@ -152,6 +152,22 @@ def all_reduce_mean(t, group=None):
     return t
 
 
+def all_gather_records(t, group=None):
+    """the records of every rank, [world, *t.shape] in rank order (t: this rank's contiguous record, the same shape and dtype on every rank); t[None]
+    without active collectives. The batch-coupled terms (the edge mask's batch extrema, the KL loss's batch softmax: DESIGN 3.4) exchange the state
+    of their reductions BETWEEN two phases of kernels and combine it in merge kernels of their own, in rank order, identically on every rank. So the
+    records travel as raw bytes (a uint8 view): no backend ever adds or converts a float. Issued on the current stream like every collective here."""
+    if not collectives_active():
+        return t[None]
+    if not t.is_contiguous():
+        raise ValueError("all_gather_records: the record must be contiguous")
+    ws = dist.get_world_size(group)
+    out = torch.empty((ws,) + tuple(t.shape), dtype=t.dtype, device=t.device)
+    raw = out.view(torch.uint8).reshape(ws, -1)
+    dist.all_gather([raw[r] for r in range(ws)], t.view(torch.uint8).reshape(-1), group=group)
+    return out
+
+
 def broadcast_flat(flat: FlatParams, src=0, group=None):
     if collectives_active():
         dist.broadcast(flat.data, src=src, group=group)
