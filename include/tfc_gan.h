@@ -323,6 +323,12 @@ int tfc_row_triplet_grad(void* stream, const float* anchor, const float* positiv
  * tfc_vit_colsum: out[L] = sum over rows of v[r * ld + j] (overwritten): bias, class-token and position gradients.
  * tfc_vit_attention_fwd / _bwd: per (image, head), T <= 64 tokens, head dim 64, H heads: qkv [N][T][3][H][64] (the qkv Linear's output),
  *   out / dout [N][T][H][64], probs [N][H][T][T] (softmax(q kt * scale), written by the forward, read by the backward), dqkv like qkv.
+ * tfc_vit_attention_tiled_fwd / _bwd: the same attention for 1 <= T <= 1025 tokens, tiled over 64 query rows x 64 key rows with LDS use independent
+ *   of T and no T x T tensor in memory. stats [N][H][3][T] (written by the forward, read by the backward): the row maximum of the signed logits
+ *   as hi + lo and the sum l of exp((logit - max) |scale|); the backward recomputes P = exp(..) / l tile by tile. ws: N * H * T floats of scratch
+ *   (delta = rowsum(P dP)). Same rounding points as the pair above (bf16 mode: q, k, v, dO when loaded, the normalised P before P v and Pt dO, dS
+ *   before dS k and dSt q), all products on the matrix core (fp32 mode: the logits as a compensated hi + lo dot product on the VALU).
+ *   Deterministic and batch invariant: dK / dV are summed over the query tiles in tile order, no atomics.
  * tfc_vit_tokens_fwd: x[n][0] = cls + pos[0], x[n][t] += pos[t] (t >= 1), x [N][T][D]. ---- */
 #define TFC_VIT_A_ROWS 0
 #define TFC_VIT_A_TRANS 1
@@ -367,6 +373,9 @@ int tfc_vit_layernorm_bwd(void* stream, const float* dy, const float* x, const f
 int tfc_vit_colsum(void* stream, const float* v, long long ld, int rows, int L, float* out, float* part_ws);
 int tfc_vit_attention_fwd(void* stream, int dt, const float* qkv, float* out, float* probs, int N, int T, int H, float scale);
 int tfc_vit_attention_bwd(void* stream, int dt, const float* dout, const float* qkv, const float* probs, float* dqkv, int N, int T, int H, float scale);
+int tfc_vit_attention_tiled_fwd(void* stream, int dt, const float* qkv, float* out, float* stats, int N, int T, int H, float scale);
+int tfc_vit_attention_tiled_bwd(void* stream, int dt, const float* dout, const float* qkv, const float* stats, float* dqkv, int N, int T, int H,
+                                float scale, float* ws);
 int tfc_vit_tokens_fwd(void* stream, float* x, const float* cls, const float* pos, int N, int T, int D);
 
 /* ---- first block, backward, fused: UNetDown(channels, 64, normalize=False) (P16:133) and discriminator_block(2 * channels, 64) (P16:183-196) are

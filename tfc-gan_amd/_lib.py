@@ -92,7 +92,9 @@ GUARDED_KERNELS = ("tfc_igemm2_kernel", "tfc_wgrad", "tfc_patch_triplet_kernelIL
                    "tfc_mask_final_extrema_kernel", "tfc_mask_final_sums_kernel", "tfc_mask_scale_kernel", "tfc_pack_plane_kernel",
                    # their phase forms for a batch spread over ranks: the record and merge kernels (mask.hip), the two walks of the KL loss (losses.hip)
                    "tfc_mask_record_extrema_kernel", "tfc_mask_record_sums_kernel", "tfc_mask_merge_kernel", "tfc_batch_kl_stats_kernel",
-                   "tfc_batch_kl_merge_kernel", "tfc_batch_kl_terms_kernel")
+                   "tfc_batch_kl_merge_kernel", "tfc_batch_kl_terms_kernel",
+                   # the tiled attention (vit.hip): 16-row statistics, P, dP and the accumulators of a 32 x 32 quarter per lane, sized for registers
+                   "tfc_vit_attn_tiled_fwd_kernel", "tfc_vit_attn_tiled_dq_kernel", "tfc_vit_attn_tiled_dkv_kernel")
 
 
 def check_no_spills(remarks):
@@ -208,6 +210,8 @@ PROTOTYPES = {
     "tfc_vit_colsum": (_i, [_vp, _vp, _ll, _i, _i, _vp, _vp]),
     "tfc_vit_attention_fwd": (_i, [_vp, _i, _vp, _vp, _vp, _i, _i, _i, _f]),
     "tfc_vit_attention_bwd": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _f]),
+    "tfc_vit_attention_tiled_fwd": (_i, [_vp, _i, _vp, _vp, _vp, _i, _i, _i, _f]),
+    "tfc_vit_attention_tiled_bwd": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _vp]),
     "tfc_vit_tokens_fwd": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i]),
     "tfc_host_emulate_conv": (_i, [_i, _i, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i]),
     "tfc_debug_set_igemm_config": (_i, [_i]),

@@ -106,6 +106,9 @@ hipError_t tfc_launch_vit_ln_bwd(const float* dy, const float* x, const float* m
 hipError_t tfc_launch_vit_colsum(const float* v, long long ld, int rows, int L, const float* x_ln, const float* mean, const float* rstd, float* out,
                                  float* part_ws, hipStream_t st);
 hipError_t tfc_launch_vit_attn_fwd(int dt, const float* qkv, float* out, float* probs, int N, int T, int H, float scale, hipStream_t st);
+hipError_t tfc_launch_vit_attn_tiled_fwd(int dt, const float* qkv, float* out, float* stats, int N, int T, int H, float scale, hipStream_t st);
+hipError_t tfc_launch_vit_attn_tiled_bwd(int dt, const float* dout, const float* qkv, const float* stats, float* dqkv, float* ws, int N, int T, int H,
+                                         float scale, hipStream_t st);
 hipError_t tfc_launch_vit_attn_bwd(int dt, const float* dout, const float* qkv, const float* probs, float* dqkv, int N, int T, int H, float scale,
                                    hipStream_t st);
 hipError_t tfc_launch_vit_tokens_fwd(float* x, const float* cls, const float* pos, int N, int T, int D, hipStream_t st);
@@ -1069,6 +1072,24 @@ extern "C" int tfc_vit_attention_bwd(void* stream, int dt, const float* dout, co
   REQUIRE(dout && qkv && probs && dqkv && N > 0 && T > 0 && T <= 64 && H > 0, "bad args");
   REQUIRE(dt == TFC_DT_BF16 || dt == TFC_DT_F32, "dt %d: the ViT kernels run bf16 or fp32 only (TFC_DT_BF16X3 is not supported)", dt);
   CHECK_HIP(tfc_launch_vit_attn_bwd(dt, dout, qkv, probs, dqkv, N, T, H, scale, (hipStream_t)stream), "tfc_vit_attention_bwd");
+  return 0;
+}
+// the tiled pair: any 1 <= T <= 1025 (512 x 512 at patch 16); every refusal names its entry point
+#define REQUIRE_ATTN_TILED(name, ptrs_ok) do { \
+    REQUIRE(ptrs_ok, name ": null pointer"); \
+    REQUIRE(T >= 1 && T <= 1025, name ": T = %d tokens (1 <= T <= 1025)", T); \
+    REQUIRE(N > 0 && N <= 65535 && H > 0 && H <= 65535, name ": bad dims N=%d H=%d", N, H); \
+    REQUIRE(dt == TFC_DT_BF16 || dt == TFC_DT_F32, name ": dt %d: the ViT kernels run bf16 or fp32 only (TFC_DT_BF16X3 is not supported)", dt); \
+  } while (0)
+extern "C" int tfc_vit_attention_tiled_fwd(void* stream, int dt, const float* qkv, float* out, float* stats, int N, int T, int H, float scale) {
+  REQUIRE_ATTN_TILED("tfc_vit_attention_tiled_fwd", qkv && out && stats);
+  CHECK_HIP(tfc_launch_vit_attn_tiled_fwd(dt, qkv, out, stats, N, T, H, scale, (hipStream_t)stream), "tfc_vit_attention_tiled_fwd");
+  return 0;
+}
+extern "C" int tfc_vit_attention_tiled_bwd(void* stream, int dt, const float* dout, const float* qkv, const float* stats, float* dqkv, int N, int T, int H,
+                                           float scale, float* ws) {
+  REQUIRE_ATTN_TILED("tfc_vit_attention_tiled_bwd", dout && qkv && stats && dqkv && ws);
+  CHECK_HIP(tfc_launch_vit_attn_tiled_bwd(dt, dout, qkv, stats, dqkv, ws, N, T, H, scale, (hipStream_t)stream), "tfc_vit_attention_tiled_bwd");
   return 0;
 }
 extern "C" int tfc_vit_tokens_fwd(void* stream, float* x, const float* cls, const float* pos, int N, int T, int D) {

@@ -12,6 +12,8 @@
 //                           tfc_part_reduce_kernel.
 //   tfc_vit_attn_fwd / _bwd softmax(q kt / sqrt(d)) v per (image, head) for T <= 64 tokens, head dim 64, q / k / v read in place from the qkv GEMM's
 //                           output (the reshape(n, t, 3, heads, d) layout of _Attention); the probabilities are saved for the backward.
+//   tfc_vit_attn_tiled_*    the same attention for any T (patch 32 / 16: 65 / 257 tokens), tiled 64 x 64 on the matrix core, LDS independent of T;
+//                           per-row softmax statistics are saved instead of the probabilities (the section further down).
 //   tfc_vit_tokens_fwd      class token + positions around the patch tokens.
 //
 // BATCH INVARIANCE: every tile shape and split-K count is a function of the layer shape (N, K), never of M: a sample's rows are computed by the same
@@ -373,6 +375,335 @@ tfc_vit_attn_bwd_kernel(const float* __restrict__ dout, const float* __restrict_
   }
 }
 
+// ---- tiled attention per (image, head, tile): any T, head dim 64 -----------------------------------------------------------------------------------
+// Query rows and key rows are cut into tiles of TQ = TK = 64 (tests/test_gpu_47_localiser_patch.py runs T = 63, 64, 65 and 127, 128, 129 around
+// them). LDS holds one [64][AP] image per operand tile whatever T is, and no T x T tensor exists in memory: the forward saves three floats per
+// (image, head, query row) -- the row maximum of the signed logits as hi + lo and the sum l of exp((logit - max) |scale|) -- and the backward
+// recomputes P = exp(..) / l tile by tile. Every product runs on the matrix core through mma64 (bf16 mode: v_mfma_f32_32x32x16_bf16 on the
+// bf16-rounded operands; fp32 mode: v_mfma_f32_32x32x2_f32), except the fp32-mode logits, which stay the compensated hi + lo dot product of
+// dot64_2 on the VALU until the row maximum is subtracted. Rounding points as in the kernels above: q, k, v, dO when loaded, the NORMALISED P
+// before P v and Pt dO, dS (formed from the fp32 P) before dS k and dSt q. So each kernel walks the key tiles twice: row statistics (forward:
+// maximum and sum; backward: delta = rowsum(P dP)) first, products second; nothing unnormalised is rescaled after the fact.
+// A workgroup = 4 waves; wave (wm, wn) owns the 32 x 32 quarter of the 64 x 64 tile product and holds it in the MFMA result layout
+// (column = lane & 31, row = acc_row(register, lane >> 5)), in fp32 mode too. Tile shapes and loop orders depend on T and H only; dK / dV are
+// summed over the query tiles in tile order by the workgroup that owns the key tile; no atomics.
+constexpr int TQ = 64, TK = 64;
+
+__device__ __forceinline__ int acc_row(int i, int half) { return (i & 3) + 8 * (i >> 2) + 4 * half; }
+
+// acc += sum over k < 64 of A(m, k) B(k, n), (m, n) in the wave's 32 x 32 quarter: A(m, k) = a[m * AM + k * AK], B(k, n) = b[n * BN + k * BKS].
+// With pitch AP = 65 a read with the lane on the row (stride 65) and one with the lane on the column (stride 1) are both conflict free.
+template <int DT, int AM, int AK, int BN, int BKS>
+__device__ __forceinline__ void mma64(f32x16_t& acc, const float* a, const float* b) {
+  const int r = threadIdx.x & 31, h = (threadIdx.x >> 5) & 1;
+  if constexpr (DT == TFC_DT_BF16) {
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+      bf16x8_t fa, fb;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        fa[j] = (__bf16)a[r * AM + (16 * s + 8 * h + j) * AK];      // exact: the tiles hold bf16-rounded values
+        fb[j] = (__bf16)b[r * BN + (16 * s + 8 * h + j) * BKS];
+      }
+      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa, fb, acc, 0, 0, 0);
+    }
+  } else {
+#pragma unroll
+    for (int s = 0; s < 32; ++s)
+      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[r * AM + (2 * s + h) * AK], b[r * BN + (2 * s + h) * BKS], acc, 0, 0, 0);
+  }
+}
+
+// rows [row0, row0 + 64) of a [T][ld] matrix (64 columns from src) into a [64][AP] tile, rounded where the mode rounds; rows past T are zero
+template <int DT>
+__device__ __forceinline__ void load_tile(float* dst, const float* __restrict__ src, size_t ld, int row0, int T) {
+  const int d = threadIdx.x & 63, t0 = threadIdx.x >> 6;
+  float x[16];
+#pragma unroll
+  for (int i = 0; i < 16; ++i) {                                    // all 16 loads in flight before the first store (a row past T re-reads row T - 1)
+    const int row = row0 + t0 + 4 * i;
+    const float v = src[(size_t)min(row, T - 1) * ld + d];
+    x[i] = row < T ? v : 0.f;
+  }
+#pragma unroll
+  for (int i = 0; i < 16; ++i) dst[(t0 + 4 * i) * AP + d] = DT == TFC_DT_BF16 ? rnd_bf16(x[i]) : x[i];
+}
+
+// dot64_2 for the 16 rows of a lane at once (the key row is read once per d); qs at the wave's first query row, kr at the lane's key row
+__device__ __forceinline__ void dot64_2x16(const float* qs, const float* kr, int half, float (&hi)[16], float (&lo)[16]) {
+#pragma clang fp contract(off)
+#pragma unroll
+  for (int i = 0; i < 16; ++i) { hi[i] = 0.f; lo[i] = 0.f; }
+  for (int d = 0; d < 64; ++d) {
+    const float b = kr[d];
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+      const float a = qs[acc_row(i, half) * AP + d];
+      const float p = a * b, pe = fmaf(a, b, -p);
+      const float s = hi[i], t = s + p, z = t - s, se = (s - (t - z)) + (p - z);
+      hi[i] = t;
+      lo[i] += pe + se;
+    }
+  }
+}
+
+// signed logits of the wave's quarter as hi + lo (bf16 mode: products of bf16 values are exact in fp32 and the MFMA sum is the logit, lo = 0)
+template <int DT>
+__device__ __forceinline__ void tile_logits(const float* qs, const float* ks, float sgn, float (&hi)[16], float (&lo)[16]) {
+  const int r = threadIdx.x & 31, h = (threadIdx.x >> 5) & 1;
+  if constexpr (DT == TFC_DT_BF16) {
+    f32x16_t acc;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) acc[i] = 0.f;
+    mma64<DT, AP, 1, AP, 1>(acc, qs, ks);
+#pragma unroll
+    for (int i = 0; i < 16; ++i) { hi[i] = sgn * acc[i]; lo[i] = 0.f; }
+  } else {
+    dot64_2x16(qs, ks + r * AP, h, hi, lo);
+#pragma unroll
+    for (int i = 0; i < 16; ++i) { hi[i] *= sgn; lo[i] *= sgn; }
+  }
+}
+
+// (mh + ml, l) <- merged with (mh2 + ml2, l2): the larger maximum (hi first, then lo) stays, the other side's sum is rescaled to it. The result
+// has the same bits whichever side is "self" (the products and the sum commute), so a butterfly leaves every lane with one value.
+__device__ __forceinline__ void stat_merge(float& mh, float& ml, float& l, float mh2, float ml2, float l2, float as) {
+  if (mh2 == -INFINITY) return;                                     // the other side has seen no column
+  if (mh == -INFINITY) { mh = mh2; ml = ml2; l = l2; return; }
+  const bool other = mh2 > mh || (mh2 == mh && ml2 > ml);
+  const float e = expf((other ? (mh - mh2) + (ml - ml2) : (mh2 - mh) + (ml2 - ml)) * as);
+  l = other ? l * e + l2 : l + l2 * e;
+  if (other) { mh = mh2; ml = ml2; }
+}
+
+__device__ __forceinline__ float tile_prob(float hi, float lo, float mh, float ml, float l, float as) {
+  return expf(((hi - mh) + (lo - ml)) * as) / l;
+}
+
+// grid (query tiles, H, N). stats [N][H][3][T]: maximum hi, maximum lo, l.
+template <int DT>
+__global__ void __launch_bounds__(256)
+tfc_vit_attn_tiled_fwd_kernel(const float* __restrict__ qkv, float* __restrict__ out, float* __restrict__ stats, int T, int H, float scale) {
+  extern __shared__ float sm[];
+  float* Qs = sm; float* Ks = Qs + 64 * AP; float* Vs = Ks + 64 * AP; float* Ps = Vs + 64 * AP; float* red = Ps + 64 * AP;   // red [2][64][3]
+  const int q0 = blockIdx.x * TQ, hd = blockIdx.y, n = blockIdx.z, D = H * 64;
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, wm = w & 1, wn = w >> 1, r = lane & 31, hf = lane >> 5;
+  const size_t ld = 3 * (size_t)D;
+  const float* qb = qkv + (size_t)n * T * ld + hd * 64;
+  const float sgn = scale < 0.f ? -1.f : 1.f, as = fabsf(scale);
+  const int nkt = (T + TK - 1) / TK;
+  auto op = [](float x) { return DT == TFC_DT_BF16 ? rnd_bf16(x) : x; };
+  load_tile<DT>(Qs, qb, ld, q0, T);
+  float mh[16], ml[16], l[16], hi[16], lo[16];
+#pragma unroll
+  for (int i = 0; i < 16; ++i) { mh[i] = -INFINITY; ml[i] = 0.f; l[i] = 0.f; }
+  for (int kt = 0; kt < nkt; ++kt) {                                // walk 1: each lane folds its own column of every key tile
+    __syncthreads();
+    load_tile<DT>(Ks, qb + D, ld, kt * TK, T);
+    __syncthreads();
+    tile_logits<DT>(Qs + wm * 32 * AP, Ks + wn * 32 * AP, sgn, hi, lo);
+    if (kt * TK + wn * 32 + r < T) {
+#pragma unroll
+      for (int i = 0; i < 16; ++i) stat_merge(mh[i], ml[i], l[i], hi[i], lo[i], 1.f, as);
+    }
+  }
+#pragma unroll
+  for (int o = 16; o > 0; o >>= 1) {                                // the 32 columns of the half wave that shares the rows
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+      const float a = __shfl_xor(mh[i], o, 64), b = __shfl_xor(ml[i], o, 64), c = __shfl_xor(l[i], o, 64);
+      stat_merge(mh[i], ml[i], l[i], a, b, c, as);
+    }
+  }
+  if (r == 0) {
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+      float* d = red + (wn * 64 + wm * 32 + acc_row(i, hf)) * 3;
+      d[0] = mh[i]; d[1] = ml[i]; d[2] = l[i];
+    }
+  }
+  __syncthreads();
+#pragma unroll
+  for (int i = 0; i < 16; ++i) {                                    // the two column halves, in one order for every wave
+    const int row = wm * 32 + acc_row(i, hf);
+    const float* a = red + row * 3;
+    const float* b = red + (64 + row) * 3;
+    mh[i] = a[0]; ml[i] = a[1]; l[i] = a[2];
+    stat_merge(mh[i], ml[i], l[i], b[0], b[1], b[2], as);
+    if (wn == 0 && r == 0 && q0 + row < T) {
+      float* st = stats + ((size_t)n * H + hd) * 3 * T + q0 + row;
+      st[0] = mh[i]; st[T] = ml[i]; st[2 * (size_t)T] = l[i];
+    }
+  }
+  f32x16_t o;
+#pragma unroll
+  for (int i = 0; i < 16; ++i) o[i] = 0.f;
+  for (int kt = 0; kt < nkt; ++kt) {                                // walk 2: normalised P, rounded, times v
+    __syncthreads();
+    load_tile<DT>(Ks, qb + D, ld, kt * TK, T);
+    load_tile<DT>(Vs, qb + 2 * D, ld, kt * TK, T);
+    __syncthreads();
+    tile_logits<DT>(Qs + wm * 32 * AP, Ks + wn * 32 * AP, sgn, hi, lo);
+    const bool cv = kt * TK + wn * 32 + r < T;
+#pragma unroll
+    for (int i = 0; i < 16; ++i)
+      Ps[(wm * 32 + acc_row(i, hf)) * AP + wn * 32 + r] = cv ? op(tile_prob(hi[i], lo[i], mh[i], ml[i], l[i], as)) : 0.f;
+    __syncthreads();
+    mma64<DT, AP, 1, 1, AP>(o, Ps + wm * 32 * AP, Vs + wn * 32);
+  }
+#pragma unroll
+  for (int i = 0; i < 16; ++i) {
+    const int row = q0 + wm * 32 + acc_row(i, hf);
+    if (row < T) out[((size_t)n * T + row) * D + hd * 64 + wn * 32 + r] = o[i];
+  }
+}
+
+// the fp32 P and dP = dO vt of the wave's quarter for one (query tile, key tile); st: the rows' statistics (LDS [4][64]: mh, ml, l, delta)
+template <int DT>
+__device__ __forceinline__ void tile_p_dp(const float* Qs, const float* Ks, const float* Vs, const float* dOs, const float* st, bool cv, float sgn, float as,
+                                          float (&p)[16], f32x16_t& dp) {
+  const int w = threadIdx.x >> 6, wm = w & 1, wn = w >> 1, hf = (threadIdx.x >> 5) & 1;
+  float hi[16], lo[16];
+  tile_logits<DT>(Qs + wm * 32 * AP, Ks + wn * 32 * AP, sgn, hi, lo);
+#pragma unroll
+  for (int i = 0; i < 16; ++i) {
+    const int row = wm * 32 + acc_row(i, hf);
+    p[i] = cv && st[192 + row] != 0.f ? tile_prob(hi[i], lo[i], st[row], st[64 + row], st[128 + row], as) : 0.f;
+    dp[i] = 0.f;
+  }
+  mma64<DT, AP, 1, AP, 1>(dp, dOs + wm * 32 * AP, Vs + wn * 32 * AP);
+}
+
+// the statistics of query rows [q0, q0 + 64) into st [4][64]: mh, ml, l and 1 (a row of the sequence) or 0 (past T: its P is forced to 0)
+__device__ __forceinline__ void load_row_stats(float* st, const float* __restrict__ stats, int q0, int T) {
+  if (threadIdx.x < 64) {
+    const int row = q0 + threadIdx.x;
+    const bool v = row < T;
+    st[threadIdx.x] = v ? stats[row] : 0.f;
+    st[64 + threadIdx.x] = v ? stats[T + row] : 0.f;
+    st[128 + threadIdx.x] = v ? stats[2 * (size_t)T + row] : 1.f;
+    st[192 + threadIdx.x] = v ? 1.f : 0.f;
+  }
+}
+
+// grid (query tiles, H, N): delta[n][h][row] = sum_j P dP (walk 1), dQ = sum over key tiles of round(P (dP - delta) scale) k (walk 2)
+template <int DT>
+__global__ void __launch_bounds__(256)
+tfc_vit_attn_tiled_dq_kernel(const float* __restrict__ dout, const float* __restrict__ qkv, const float* __restrict__ stats, float* __restrict__ dqkv,
+                             float* __restrict__ delta, int T, int H, float scale) {
+  extern __shared__ float sm[];
+  float* Qs = sm; float* Ks = Qs + 64 * AP; float* Vs = Ks + 64 * AP; float* dOs = Vs + 64 * AP; float* dSs = dOs + 64 * AP;
+  float* st = dSs + 64 * AP; float* red = st + 256;                 // st [4][64], red [2][64]
+  const int q0 = blockIdx.x * TQ, hd = blockIdx.y, n = blockIdx.z, D = H * 64;
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, wm = w & 1, wn = w >> 1, r = lane & 31, hf = lane >> 5;
+  const size_t ld = 3 * (size_t)D;
+  const float* qb = qkv + (size_t)n * T * ld + hd * 64;
+  const float sgn = scale < 0.f ? -1.f : 1.f, as = fabsf(scale);
+  const int nkt = (T + TK - 1) / TK;
+  auto op = [](float x) { return DT == TFC_DT_BF16 ? rnd_bf16(x) : x; };
+  load_tile<DT>(Qs, qb, ld, q0, T);
+  load_tile<DT>(dOs, dout + (size_t)n * T * D + hd * 64, D, q0, T);
+  load_row_stats(st, stats + ((size_t)n * H + hd) * 3 * T, q0, T);
+  float p[16], dl[16];
+  f32x16_t dp;
+#pragma unroll
+  for (int i = 0; i < 16; ++i) dl[i] = 0.f;
+  for (int kt = 0; kt < nkt; ++kt) {
+    __syncthreads();
+    load_tile<DT>(Ks, qb + D, ld, kt * TK, T);
+    load_tile<DT>(Vs, qb + 2 * D, ld, kt * TK, T);
+    __syncthreads();
+    tile_p_dp<DT>(Qs, Ks, Vs, dOs, st, kt * TK + wn * 32 + r < T, sgn, as, p, dp);
+#pragma unroll
+    for (int i = 0; i < 16; ++i) dl[i] = fmaf(p[i], dp[i], dl[i]);
+  }
+#pragma unroll
+  for (int o = 16; o > 0; o >>= 1) {
+#pragma unroll
+    for (int i = 0; i < 16; ++i) dl[i] += __shfl_xor(dl[i], o, 64);
+  }
+  if (r == 0) {
+#pragma unroll
+    for (int i = 0; i < 16; ++i) red[wn * 64 + wm * 32 + acc_row(i, hf)] = dl[i];
+  }
+  __syncthreads();
+#pragma unroll
+  for (int i = 0; i < 16; ++i) {
+    const int row = wm * 32 + acc_row(i, hf);
+    dl[i] = red[row] + red[64 + row];
+    if (wn == 0 && r == 0 && q0 + row < T) delta[((size_t)n * H + hd) * T + q0 + row] = dl[i];
+  }
+  f32x16_t dq;
+#pragma unroll
+  for (int i = 0; i < 16; ++i) dq[i] = 0.f;
+  for (int kt = 0; kt < nkt; ++kt) {
+    __syncthreads();
+    load_tile<DT>(Ks, qb + D, ld, kt * TK, T);
+    load_tile<DT>(Vs, qb + 2 * D, ld, kt * TK, T);
+    __syncthreads();
+    tile_p_dp<DT>(Qs, Ks, Vs, dOs, st, kt * TK + wn * 32 + r < T, sgn, as, p, dp);
+#pragma unroll
+    for (int i = 0; i < 16; ++i) dSs[(wm * 32 + acc_row(i, hf)) * AP + wn * 32 + r] = op(p[i] * (dp[i] - dl[i]) * scale);
+    __syncthreads();
+    mma64<DT, AP, 1, 1, AP>(dq, dSs + wm * 32 * AP, Ks + wn * 32);
+  }
+#pragma unroll
+  for (int i = 0; i < 16; ++i) {
+    const int row = q0 + wm * 32 + acc_row(i, hf);
+    if (row < T) dqkv[((size_t)n * T + row) * ld + hd * 64 + wn * 32 + r] = dq[i];
+  }
+}
+
+// grid (key tiles, H, N): dV = sum_i round(P)[i][.] dO[i], dK = sum_i round(dS)[i][.] q[i], the query tiles taken in order
+template <int DT>
+__global__ void __launch_bounds__(256)
+tfc_vit_attn_tiled_dkv_kernel(const float* __restrict__ dout, const float* __restrict__ qkv, const float* __restrict__ stats, const float* __restrict__ delta,
+                              float* __restrict__ dqkv, int T, int H, float scale) {
+  extern __shared__ float sm[];
+  float* Qs = sm; float* Ks = Qs + 64 * AP; float* Vs = Ks + 64 * AP; float* dOs = Vs + 64 * AP; float* Ps = dOs + 64 * AP; float* dSs = Ps + 64 * AP;
+  float* st = dSs + 64 * AP; float* dls = st + 256;                 // st [4][64], dls [64]
+  const int k0 = blockIdx.x * TK, hd = blockIdx.y, n = blockIdx.z, D = H * 64;
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, wm = w & 1, wn = w >> 1, r = lane & 31, hf = lane >> 5;
+  const size_t ld = 3 * (size_t)D;
+  const float* qb = qkv + (size_t)n * T * ld + hd * 64;
+  const float sgn = scale < 0.f ? -1.f : 1.f, as = fabsf(scale);
+  const int nqt = (T + TQ - 1) / TQ;
+  const bool cv = k0 + wn * 32 + r < T;
+  auto op = [](float x) { return DT == TFC_DT_BF16 ? rnd_bf16(x) : x; };
+  load_tile<DT>(Ks, qb + D, ld, k0, T);
+  load_tile<DT>(Vs, qb + 2 * D, ld, k0, T);
+  float p[16];
+  f32x16_t dp, dk, dv;
+#pragma unroll
+  for (int i = 0; i < 16; ++i) { dk[i] = 0.f; dv[i] = 0.f; }
+  for (int qt = 0; qt < nqt; ++qt) {
+    __syncthreads();
+    load_tile<DT>(Qs, qb, ld, qt * TQ, T);
+    load_tile<DT>(dOs, dout + (size_t)n * T * D + hd * 64, D, qt * TQ, T);
+    load_row_stats(st, stats + ((size_t)n * H + hd) * 3 * T, qt * TQ, T);
+    if (threadIdx.x < 64) dls[threadIdx.x] = qt * TQ + threadIdx.x < T ? delta[((size_t)n * H + hd) * T + qt * TQ + threadIdx.x] : 0.f;
+    __syncthreads();
+    tile_p_dp<DT>(Qs, Ks, Vs, dOs, st, cv, sgn, as, p, dp);
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+      const int row = wm * 32 + acc_row(i, hf);
+      Ps[row * AP + wn * 32 + r] = op(p[i]);
+      dSs[row * AP + wn * 32 + r] = op(p[i] * (dp[i] - dls[row]) * scale);
+    }
+    __syncthreads();
+    mma64<DT, 1, AP, 1, AP>(dv, Ps + wm * 32, dOs + wn * 32);       // the sum runs over the query rows: both operands are read by columns
+    mma64<DT, 1, AP, 1, AP>(dk, dSs + wm * 32, Qs + wn * 32);
+  }
+#pragma unroll
+  for (int i = 0; i < 16; ++i) {
+    const int row = k0 + wm * 32 + acc_row(i, hf);
+    if (row < T) {
+      const size_t b = ((size_t)n * T + row) * ld + hd * 64 + wn * 32 + r;
+      dqkv[b + D] = dk[i]; dqkv[b + 2 * D] = dv[i];
+    }
+  }
+}
+
 // x[n][0] = cls + pos[0]; x[n][t] += pos[t] for t >= 1 (the patch GEMM wrote the patch tokens, bias included, into rows 1..T-1)
 __global__ void __launch_bounds__(256)
 tfc_vit_tokens_fwd_kernel(float* __restrict__ x, const float* __restrict__ cls, const float* __restrict__ pos, int N, int T, int D) {
@@ -429,6 +760,40 @@ hipError_t tfc_launch_vit_attn_bwd(int dt, const float* dout, const float* qkv, 
   if (e != hipSuccess) return e;
   if (dt == TFC_DT_BF16) hipLaunchKernelGGL(tfc_vit_attn_bwd_kernel<TFC_DT_BF16>, dim3(H, N), dim3(256), lds, st, dout, qkv, probs, dqkv, T, H, scale);
   else hipLaunchKernelGGL(tfc_vit_attn_bwd_kernel<TFC_DT_F32>, dim3(H, N), dim3(256), lds, st, dout, qkv, probs, dqkv, T, H, scale);
+  return hipGetLastError();
+}
+
+template <typename K>
+static hipError_t attn_tiled_lds(K* bf16_fn, K* f32_fn, int dt, size_t bytes) {
+  return attn_lds(dt == TFC_DT_BF16 ? (const void*)bf16_fn : (const void*)f32_fn, bytes);
+}
+
+hipError_t tfc_launch_vit_attn_tiled_fwd(int dt, const float* qkv, float* out, float* stats, int N, int T, int H, float scale, hipStream_t st) {
+  const size_t lds = sizeof(float) * (4 * 64 * AP + 2 * 64 * 3);
+  const hipError_t e = attn_tiled_lds(&tfc_vit_attn_tiled_fwd_kernel<TFC_DT_BF16>, &tfc_vit_attn_tiled_fwd_kernel<TFC_DT_F32>, dt, lds);
+  if (e != hipSuccess) return e;
+  const dim3 grid((T + TQ - 1) / TQ, H, N);
+  if (dt == TFC_DT_BF16) hipLaunchKernelGGL(tfc_vit_attn_tiled_fwd_kernel<TFC_DT_BF16>, grid, dim3(256), lds, st, qkv, out, stats, T, H, scale);
+  else hipLaunchKernelGGL(tfc_vit_attn_tiled_fwd_kernel<TFC_DT_F32>, grid, dim3(256), lds, st, qkv, out, stats, T, H, scale);
+  return hipGetLastError();
+}
+
+// ws: N * H * T floats (delta, written by the dQ kernel and read by the dK / dV kernel behind it on the stream)
+hipError_t tfc_launch_vit_attn_tiled_bwd(int dt, const float* dout, const float* qkv, const float* stats, float* dqkv, float* ws, int N, int T, int H,
+                                         float scale, hipStream_t st) {
+  const size_t lq = sizeof(float) * (5 * 64 * AP + 4 * 64 + 2 * 64), lk = sizeof(float) * (6 * 64 * AP + 4 * 64 + 64);
+  hipError_t e = attn_tiled_lds(&tfc_vit_attn_tiled_dq_kernel<TFC_DT_BF16>, &tfc_vit_attn_tiled_dq_kernel<TFC_DT_F32>, dt, lq);
+  if (e != hipSuccess) return e;
+  e = attn_tiled_lds(&tfc_vit_attn_tiled_dkv_kernel<TFC_DT_BF16>, &tfc_vit_attn_tiled_dkv_kernel<TFC_DT_F32>, dt, lk);
+  if (e != hipSuccess) return e;
+  const dim3 gq((T + TQ - 1) / TQ, H, N), gk((T + TK - 1) / TK, H, N);
+  if (dt == TFC_DT_BF16) {
+    hipLaunchKernelGGL(tfc_vit_attn_tiled_dq_kernel<TFC_DT_BF16>, gq, dim3(256), lq, st, dout, qkv, stats, dqkv, ws, T, H, scale);
+    hipLaunchKernelGGL(tfc_vit_attn_tiled_dkv_kernel<TFC_DT_BF16>, gk, dim3(256), lk, st, dout, qkv, stats, (const float*)ws, dqkv, T, H, scale);
+  } else {
+    hipLaunchKernelGGL(tfc_vit_attn_tiled_dq_kernel<TFC_DT_F32>, gq, dim3(256), lq, st, dout, qkv, stats, dqkv, ws, T, H, scale);
+    hipLaunchKernelGGL(tfc_vit_attn_tiled_dkv_kernel<TFC_DT_F32>, gk, dim3(256), lk, st, dout, qkv, stats, (const float*)ws, dqkv, T, H, scale);
+  }
   return hipGetLastError();
 }
 

@@ -900,6 +900,31 @@ def vit_attention_bwd(dt, dout, qkv, probs, N, T, H, scale):
     return dqkv
 
 
+VIT_ATTN_TQ = VIT_ATTN_TK = 64      # query-tile / key-tile heights of the tiled attention kernels (TQ, TK of csrc/vit.hip)
+VIT_ATTN_MAX_T = 1025               # 512 x 512 at patch 16
+
+
+def vit_attention_tiled_fwd(dt, qkv, N, T, H, scale):
+    """qkv [N*T, 3*H*64] -> (out [N*T, H*64], stats [N, H, 3, T]: per query row the maximum of the signed logits as hi + lo and the sum of
+    exp((logit - max) |scale|)). Any 1 <= T <= 1025; no [T, T] tensor is written."""
+    require_gpu(qkv)
+    out = torch.empty((N * T, H * 64), dtype=torch.float32, device=qkv.device)
+    stats = torch.empty((N, H, 3, T), dtype=torch.float32, device=qkv.device)
+    check(lib().tfc_vit_attention_tiled_fwd(stream_ptr(), dt, _p(qkv), _p(out), _p(stats), N, T, H, scale), "tfc_vit_attention_tiled_fwd")
+    return out, stats
+
+
+def vit_attention_tiled_bwd(dt, dout, qkv, out, stats, N, T, H, scale):
+    """-> dqkv like qkv. `out` (the forward's output) is accepted for the call's symmetry and not read: delta is rowsum(P dP) on the recomputed
+    fp32 P, as in the kernels for T <= 64 (rowsum(dO o O) would carry the bf16 rounding of P into every dS)."""
+    require_gpu(dout, qkv, out, stats)
+    dqkv = torch.empty_like(qkv)
+    ws = torch.empty((N, H, T), dtype=torch.float32, device=qkv.device)
+    check(lib().tfc_vit_attention_tiled_bwd(stream_ptr(), dt, _p(dout), _p(qkv), _p(stats), _p(dqkv), N, T, H, scale, _p(ws)),
+          "tfc_vit_attention_tiled_bwd")
+    return dqkv
+
+
 def vit_tokens_fwd(x, cls, pos):
     """x [N, T, D] with the patch tokens in rows 1..T-1: row 0 = cls, every row += pos (in place)"""
     require_gpu(x, cls, pos)

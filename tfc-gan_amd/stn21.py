@@ -12,7 +12,8 @@ configuration adds is
 
 Everything heavy runs on the package's HIP kernels through the modules' autograd Functions (both generators, both discriminators, the warp,
 the morphological gradient, LPIPS); the generator now returns its INPUT gradient, which is how the warp and the localiser train through
-`G2(warped_B)`. The localiser is 17 tokens x 768 channels and runs one of two ways (`Net.localiser`, default from TFC_LOCALISER): "torch"
+`G2(warped_B)`. The localiser is 17 tokens x 768 channels (patch 64; `patch_size` 32 / 16 give the 65 / 257 tokens of the reference's other STN
+scripts) and runs one of two ways (`Net.localiser`, default from TFC_LOCALISER): "torch"
 (default) as plain torch layers (library GEMMs), "hip" on the package's own kernels (vit.py: one autograd Function over csrc/vit.hip, batch
 invariant, compute dtype from `set_compute_dtype`). kornia is absent from this image, so `VisionTransformer` is restated from its published architecture (patch embedding, class token, learned positions, 12 pre-norm encoder blocks
 with 12 heads and a 4x GELU MLP, final LayerNorm) with matmul / softmax / LayerNorm only (no MIOpen convolution, no fused attention: their
@@ -96,13 +97,29 @@ class VisionTransformer(nn.Module):
         return self.norm(self.blocks(t))
 
 
-class LocalizerVIT(nn.Module):
-    """STN:150-163"""
+MAX_TOKENS = 1025                                                 # the tiled attention kernels' range: 512 x 512 at patch 16
 
-    def __init__(self, img_shape):
+
+def token_count(h, w, patch_size):
+    """tokens of an h x w image at this patch size (patches + the class token); ValueError when the patch does not divide the image or the
+    count passes MAX_TOKENS"""
+    p = int(patch_size)
+    if p <= 0 or h % p or w % p:
+        raise ValueError(f"patch_size {patch_size!r} must be a positive divisor of the image height {h} and width {w}")
+    ntok = (h // p) * (w // p) + 1
+    if ntok > MAX_TOKENS:
+        raise ValueError(f"patch_size {p} on a {h} x {w} image gives {ntok} tokens: the limit is {MAX_TOKENS} (512 x 512 at patch 16)")
+    return ntok
+
+
+class LocalizerVIT(nn.Module):
+    """STN:150-163. patch_size: 64 (STN), 32, or 16 (the DarkVisible and test scripts, the archived STN17..21 scripts)"""
+
+    def __init__(self, img_shape, patch_size=64):
         super().__init__()
         channels, self.h, self.w = img_shape
-        self.vit = nn.Sequential(VisionTransformer(image_size=self.h, patch_size=64, in_channels=channels * 2))
+        token_count(self.h, self.w, patch_size)
+        self.vit = nn.Sequential(VisionTransformer(image_size=self.h, patch_size=int(patch_size), in_channels=channels * 2))
 
     def forward(self, x):
         return self.vit(x)
@@ -126,15 +143,18 @@ class Net(nn.Module):
     """STN:170-231. forward(img_A, img_B, src): theta = identity + fc_loc(ViT(cat(img_A, img_B))), every sample of `src` warped with its own
     matrix (F.affine_grid + F.grid_sample(bicubic, border, align_corners=True), fused in tfc_affine_warp_fwd/bwd).
     localiser: "torch" (the ViT and fc_loc as torch layers), "hip" (vit.stn_phi: the package's kernels, GPU tensors only) or None (TFC_LOCALISER,
-    default "torch"); readable and settable as `net.localiser`. Both run on the same parameters."""
+    default "torch"); readable and settable as `net.localiser`. Both run on the same parameters.
+    patch_size: the ViT's patch (64 = STN; 16 = the DarkVisible and test scripts, `fc_loc[0]` = Linear(257 * 768, 1024) at 256 x 256; 32 in
+    between), readable as `net.patch_size`. It must divide the image and give at most MAX_TOKENS tokens; state_dict key names do not depend on it."""
 
-    def __init__(self, img_shape=(3, 256, 256), localiser=None):
+    def __init__(self, img_shape=(3, 256, 256), localiser=None, patch_size=64):
         super().__init__()
         self.localiser = default_localiser() if localiser is None else localiser
         channels, h, w = img_shape
-        self.localization = LocalizerVIT(img_shape)
+        ntok = token_count(h, w, patch_size)                      # 17 / 65 / 257 at 256 x 256 and patch 64 / 32 / 16
+        self.patch_size = int(patch_size)
+        self.localization = LocalizerVIT(img_shape, self.patch_size)
         self.theta_emb = nn.Linear(1, h * w)                      # declared and never used by the reference (STN:178); kept for the state_dict
-        ntok = (h // 64) * (w // 64) + 1
         self.fc_loc = nn.Sequential(nn.Linear(ntok * 768, 1024), nn.ReLU(True), nn.Linear(1024, 512), nn.ReLU(True), nn.Linear(512, 256), nn.Sigmoid(),
                                     nn.Linear(256, 3 * 2))
         self.fc_loc[2].bias.data.zero_()                          # STN:193
@@ -184,10 +204,10 @@ class STN21Step:
     post-accumulate hooks while the rest of the backward still runs (the reference wraps all five modules in nn.DataParallel, STN:536-540).
     Every loss of the step is a batch mean except LPIPS, a batch SUM in lpips_pytorch: it is scaled by the world size so that the rank-averaged
     gradient equals the reference's on the gathered batch. lpips: a module with the reference's call surface (tfc_gan_amd.LPIPS) or None.
-    localiser: "torch", "hip" or None (TFC_LOCALISER), passed to `Net`. batch_invariant: True / False, or None for the global setting."""
+    localiser: "torch", "hip" or None (TFC_LOCALISER), and patch_size (64, 32, 16, ..), passed to `Net`. batch_invariant: True / False, or None for the global setting."""
 
     def __init__(self, img_shape=(3, 256, 256), lpips=None, lr=2e-4, b1=0.5, b2=0.999, device="cuda:0", alpha2=0.01, eps=1e-8, bucket_bytes=32 << 20,
-                 seed=0, localiser=None, batch_invariant=None):
+                 seed=0, localiser=None, batch_invariant=None, patch_size=64):
         from . import ops, parallel
         _refuse_bf16x3()
         self.batch_invariant = batch_invariant                    # None: the global setting (set_batch_invariant / TFC_BATCH_INVARIANT) at each step
@@ -195,7 +215,7 @@ class STN21Step:
         self.dev = dev
         self.G1, self.G2 = GeneratorUNet(img_shape).to(dev), GeneratorUNet(img_shape).to(dev)
         self.D1, self.D2 = Discriminator1(img_shape).to(dev), Discriminator1(img_shape).to(dev)
-        self.net = Net(img_shape, localiser=localiser).to(dev)
+        self.net = Net(img_shape, localiser=localiser, patch_size=patch_size).to(dev)
         for m in (self.G1, self.G2, self.D1, self.D2, self.net):
             m.apply(weights_init_normal)                          # STN:539-543
         self.lpips, self.alpha2, self._bucket_bytes = lpips, alpha2, bucket_bytes

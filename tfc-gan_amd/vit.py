@@ -1,5 +1,7 @@
 """The STN21 localiser (reference STN:150-201: `Net.stn_phi` = kornia VisionTransformer(256, patch 64, 6 channels) + the fc_loc MLP) on the
-package's own HIP kernels (csrc/vit.hip), forward and backward, as ONE autograd Function.
+package's own HIP kernels (csrc/vit.hip), forward and backward, as ONE autograd Function. The patch size comes from the patch weight's shape:
+patch 64 (17 tokens) runs the whole-sequence attention kernels, patch 32 / 16 (65 / 257 tokens) the tiled pair, which saves per-row softmax
+statistics instead of the probabilities.
 
 Numerics: the compute dtype follows `set_compute_dtype` -- bf16 rounds every GEMM and attention-matmul operand to bf16 with
 fp32 accumulation (what `torch.autocast` does around the reference's ViT, STN:162), fp32 keeps the operands exact (f32-input MFMA); LayerNorm
@@ -69,7 +71,10 @@ class _LocaliserFn(torch.autograd.Function):
             h1, m1, r1 = ops.vit_layernorm_fwd(x, g1, be1, EPS)
             qkv = torch.empty((M, 3 * D), dtype=torch.float32, device=a.device)
             ops.vit_gemm(dt, M, 3 * D, D, h1, wqkv, qkv, bias=bqkv)
-            o, probs = ops.vit_attention_fwd(dt, qkv, N, T, heads, scale)
+            if T <= 64:                                           # the whole-sequence kernels (patch 64: the bits every existing test pins)
+                o, probs = ops.vit_attention_fwd(dt, qkv, N, T, heads, scale)
+            else:                                                 # tiled kernels: `probs` holds the row statistics [N, H, 3, T], not [N, H, T, T]
+                o, probs = ops.vit_attention_tiled_fwd(dt, qkv, N, T, heads, scale)
             xm = torch.empty_like(x)
             ops.vit_gemm(dt, M, D, D, o, wpr, xm, bias=bpr, res=x)
             h2, m2, r2 = ops.vit_layernorm_fwd(xm, g2, be2, EPS)
@@ -160,7 +165,10 @@ class _LocaliserFn(torch.autograd.Function):
             grads[o0 + 4] = wgrad(dxm, o, M, D, D)
             grads[o0 + 5] = ops.vit_colsum(dxm, M, D)
             do = dgrad(dxm, wpr, M)
-            dqkv = ops.vit_attention_bwd(dt, do, qkv, probs, N, T, heads, scale)
+            if T <= 64:
+                dqkv = ops.vit_attention_bwd(dt, do, qkv, probs, N, T, heads, scale)
+            else:
+                dqkv = ops.vit_attention_tiled_bwd(dt, do, qkv, o, probs, N, T, heads, scale)
             grads[o0 + 2] = wgrad(dqkv, h1, M, 3 * D, D)
             grads[o0 + 3] = ops.vit_colsum(dqkv, M, 3 * D)
             dh1 = dgrad(dqkv, wqkv, M)
