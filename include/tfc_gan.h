@@ -421,9 +421,12 @@ int tfc_maxpool2_fwd(void* stream, int dt, const void* x, void* y, int N, int H,
 int tfc_maxpool2_bwd(void* stream, int dt, const void* x, const void* dy, void* dx, int N, int H, int W, int C);
 /* dz = (y > 0) ? dy (+ extra, nullable) : 0 over n elements (n % 8 == 0); dz may alias dy */
 int tfc_relu_bwd(void* stream, int dt, const void* dy, const void* y, const void* extra, void* dz, long long n);
-/* one LPIPS layer: out[n] += mean_pixels sum_c w[c] (fx/(|fx|+1e-10) - fy/(|fy|+1e-10))_c^2 ; dfx (nullable) = gscale * d out[n] / d fx */
+/* one LPIPS layer: out[n] += mean_pixels sum_c w[c] (fx/(|fx|+1e-10) - fy/(|fy|+1e-10))_c^2 ; dfx (nullable) = gscale * d out[n] / d fx.
+ * At an all-zero fx pixel the norm term of the gradient is defined as 0: dfx_c = (gscale / HW) * 2 w[c] * (-ny_c) / 1e-10.
+ * out[n] and dfx[n] have the same bits in every run and in every batch the image is part of: the workgroups of an image (their number depends on
+ * H * W and C only, at most 64) leave their sums in part_ws (required; N * 64 floats at most, N <= 65535) and are added in a fixed order. */
 int tfc_lpips_head(void* stream, int dt, const void* fx, const void* fy, const float* w, float* out, void* dfx, int N, int H, int W, int C,
-                   float gscale);
+                   float gscale, float* part_ws);
 
 /* ---- measurement -------------------------------------------------------------------------------------------------- */
 /* When enabled every gather-GEMM / wgrad launch is bracketed by hipEvents on its own stream; tfc_prof_collect()

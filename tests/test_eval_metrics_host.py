@@ -89,7 +89,7 @@ def test_metric_prototypes_are_declared_on_both_sides():
     lib = _lib.load()
     for name in METRIC_SYMBOLS:
         assert hasattr(lib, name), name
-    assert lib.tfc_abi_version() == 2
+    assert lib.tfc_abi_version() == 3
 
 
 def test_metric_entry_points_refuse_bad_arguments_loudly():

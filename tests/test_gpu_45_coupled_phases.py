@@ -260,7 +260,7 @@ def test_phase_argument_checks_return_errors_without_launching():
     for t in (lap, bl, dmn, ws):
         assert bool((t == 5.0).all())
     assert bool((rec == 7).all()) and bool((krec == 9.0).all()) and not out.any() and not img.any()     # nothing ran
-    assert lib.tfc_abi_version() == 2
+    assert lib.tfc_abi_version() == 3
 
 
 # ---- 2. the KL loss -------------------------------------------------------------------------------------------------------------------------------

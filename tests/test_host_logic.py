@@ -25,7 +25,7 @@ def test_library_exports_every_declared_symbol():
     assert declared == set(_lib.PROTOTYPES), declared ^ set(_lib.PROTOTYPES)
     for name in declared:
         assert hasattr(lib, name), name
-    assert lib.tfc_abi_version() == 2
+    assert lib.tfc_abi_version() == 3
 
 
 def test_build_refuses_spilling_hand_scheduled_kernels():

@@ -41,7 +41,7 @@ def test_new_symbols_are_declared_bound_and_exported():
     for name in NEW_SYMBOLS:
         assert getattr(lib, name) is not None
     lib.tfc_abi_version.restype = ctypes.c_int
-    assert lib.tfc_abi_version() == 2
+    assert lib.tfc_abi_version() == 3
     ws = lib.tfc_fft_spectrum_rect_ws_bytes
     ws.restype, ws.argtypes = ctypes.c_size_t, [ctypes.c_int, ctypes.c_int]
     assert ws(100, 4) == 4 * 129 * 100 * 8 and ws(2, 1) == 129 * 2 * 8 and ws(256, 1) == 129 * 256 * 8

@@ -198,7 +198,7 @@ PROTOTYPES = {
     "tfc_maxpool2_fwd": (_i, [_vp, _i, _vp, _vp, _i, _i, _i, _i]),
     "tfc_maxpool2_bwd": (_i, [_vp, _i, _vp, _vp, _vp, _i, _i, _i, _i]),
     "tfc_relu_bwd": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _ll]),
-    "tfc_lpips_head": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f]),
+    "tfc_lpips_head": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _vp]),
     "tfc_bce_relativistic": (_i, [_vp, _i, _vp, _vp, _i, _i, _f, _f, _i, _vp, _vp, _vp, _f]),
     "tfc_adam_step": (_i, [_vp, _vp, _vp, _vp, _vp, _ll, _f, _f, _f, _f, _i, _f]),
     "tfc_prof_enable": (_i, [_i]),

@@ -138,7 +138,7 @@ static int hipfail(hipError_t e, const char* where) { return fail(-100 - (int)e,
 #define REQUIRE(cond, ...) do { if (!(cond)) return fail(-1, __VA_ARGS__); } while (0)
 
 extern "C" const char* tfc_last_error(void) { return g_err.c_str(); }
-extern "C" int tfc_abi_version(void) { return 2; }              // 2: deterministic reductions (part_ws arguments)
+extern "C" int tfc_abi_version(void) { return 3; }              // 2: deterministic reductions (part_ws arguments); 3: tfc_lpips_head takes part_ws too
 extern "C" size_t tfc_part_ws_floats(void) { return (size_t)TFC_PART_WS_FLOATS; }
 
 static inline int pad8(int c) { return (c + 7) / 8 * 8; }
@@ -1214,7 +1214,7 @@ hipError_t tfc_launch_lpips_input(int dt, const float* x, const float* shift, co
 hipError_t tfc_launch_lpips_input_bwd(int dt, const void* g, const float* scale, float* dx, int N, int C, long long HW, int pitch, float alpha, int accumulate, hipStream_t st);
 hipError_t tfc_launch_maxpool2(int dt, int bwd, const void* x, const void* dy, void* out, int N, int H, int W, int C, hipStream_t st);
 hipError_t tfc_launch_relu_bwd(int dt, const void* dy, const void* y, const void* extra, void* dz, long long n, hipStream_t st);
-hipError_t tfc_launch_lpips_head(int dt, const void* fx, const void* fy, const float* w, float* out, void* dfx, int N, long long HW, int C, float gscale, hipStream_t st);
+hipError_t tfc_launch_lpips_head(int dt, const void* fx, const void* fy, const float* w, float* out, void* dfx, float* part_ws, int N, long long HW, int C, float gscale, hipStream_t st);
 
 extern "C" int tfc_lpips_input_fwd(void* stream, int dt, const float* x, const float* shift, const float* scale, void* out, int N, int C, int H, int W,
                                    int pitch) {
@@ -1260,13 +1260,14 @@ extern "C" int tfc_relu_bwd(void* stream, int dt, const void* dy, const void* y,
   return 0;
 }
 extern "C" int tfc_lpips_head(void* stream, int dt, const void* fx, const void* fy, const float* w, float* out, void* dfx, int N, int H, int W, int C,
-                              float gscale) {
+                              float gscale, float* part_ws) {
   REQUIRE(fx && fy && w && out && N > 0 && H > 0 && W > 0 && C > 0 && C % 8 == 0, "bad args");
+  REQUIRE(part_ws, "tfc_lpips_head adds its workgroup partials in a fixed order: part_ws is required");
   if (int e = check_dt(dt)) return e;
   if (int e = check_ptr16(fx, "fx")) return e;
   if (int e = check_ptr16(fy, "fy")) return e;
   if (dfx) { if (int e = check_ptr16(dfx, "dfx")) return e; }
-  CHECK_HIP(tfc_launch_lpips_head(dt, fx, fy, w, out, dfx, N, (long long)H * W, C, gscale, (hipStream_t)stream), "tfc_lpips_head");
+  CHECK_HIP(tfc_launch_lpips_head(dt, fx, fy, w, out, dfx, part_ws, N, (long long)H * W, C, gscale, (hipStream_t)stream), "tfc_lpips_head");
   return 0;
 }
 extern "C" int tfc_l1_sum(void* stream, const float* a, const float* b, long long n, float scale, float* out, int zero_first) {

@@ -7,7 +7,8 @@
 //   max-pool 2x2    : forward, and backward routing the gradient to the first maximum of the window (torch's rule)
 //   ReLU backward   : dz = (y > 0) ? dy [+ extra] : 0        (extra = the gradient a tap layer receives from its LPIPS head)
 //   head            : per pixel  n = f / (||f||_2 + 1e-10) over channels for both images, d = n_x - n_y, value = sum_c w_c d_c^2;
-//                     per image  mean over pixels; forward value and d value / d f_x in ONE pass (the head's upstream gradient is a constant)
+//                     per image  mean over pixels; forward value and d value / d f_x in ONE pass (the head's upstream gradient is a constant);
+//                     workgroup partials in fixed slots of part_ws, added in a fixed order: bit-reproducible, and independent of the batch size
 // All HBM-bound; activations NHWC with pitch == C (a multiple of 8), 16-byte units.
 #include "common.h"
 
@@ -60,7 +61,7 @@ tfc_maxpool2_fwd_kernel(const T* __restrict__ x, T* __restrict__ y, int H, int W
   for (int k = 0; k < 3; ++k) {
     unpack16<T>(*reinterpret_cast<const uint4*>(p + offs[k]), a);
 #pragma unroll
-    for (int e = 0; e < UE; ++e) m[e] = fmaxf(m[e], a[e]);
+    for (int e = 0; e < UE; ++e) m[e] = a[e] > m[e] ? a[e] : m[e];   // torch's scan: a later value replaces the maximum only if greater, so of -0.0 and +0.0 the FIRST stays (fmaxf picks +0.0)
   }
   *reinterpret_cast<uint4*>(y + op * C + u * UE) = pack16<T>(m);
 }
@@ -121,44 +122,35 @@ tfc_relu_bwd_kernel(const T* __restrict__ dy, const T* __restrict__ y, const T* 
 }
 
 // LPIPS head of one tap layer. A group of GS lanes (GS = power of two >= min(C / UE, 64)) owns one pixel, so a wave handles 64 / GS pixels at
-// once and every lane holds 16-byte units u = gl, gl + GS, ... of its pixel. out[n] += (1 / HW) * sum_c w_c (nx_c - ny_c)^2 ;
-// dfx (nullable) = gscale * d out[n] / d fx.
+// once and every lane holds 16-byte units u = gl, gl + GS, ... of its pixel. part[n][workgroup] = (1 / HW) * sum over the workgroup's pixels of
+// sum_c w_c (nx_c - ny_c)^2 ; dfx (nullable) = gscale * d out[n] / d fx. At an all-zero fx pixel the norm term of the gradient is defined as 0:
+// dfx_c = (gscale / HW) * 2 w_c d_c / a with d_c = -ny_c, a = 1e-10.
+// The grid is (workgroups per image, N): workgroup b of image n owns pixels [b * chunk, (b + 1) * chunk) of that image, with chunk a function of
+// HW and C alone (the launcher), so an image's sum is made of the same partials, added in the same order (the group leaders of a wave by the
+// xor butterfly, the four waves in order, the workgroups by tfc_part_reduce_kernel), whatever the batch size and however the workgroups are
+// scheduled: no float atomic. (Round 1 added per pixel group with memory-side atomics: 8192 of them per image made this kernel 16 ms.)
 __device__ __forceinline__ float group_sum(float v, int gs) {
   for (int o = gs >> 1; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;
 }
 template <typename T>
 __global__ void __launch_bounds__(256)
-tfc_lpips_head_kernel(const T* __restrict__ fx, const T* __restrict__ fy, const float* __restrict__ w, float* out, T* __restrict__ dfx,
-                      int C, long long HW, long long npix, float gscale, int GS) {
+tfc_lpips_head_kernel(const T* __restrict__ fx, const T* __restrict__ fy, const float* __restrict__ w, float* __restrict__ part, T* __restrict__ dfx,
+                      int C, long long HW, long long chunk, float gscale, int GS) {
   constexpr int UE = ElemTraits<T>::UE;
-  // Same-address float atomics from all 8 XCDs resolve at the memory side and cost ~0.3 us EACH (measured: 8192 of them per image made this
-  // kernel 16 ms): a workgroup owns a CONTIGUOUS pixel range (so it touches few images), sums per image in LDS and issues one global atomic
-  // per image it touched.
-  constexpr int SLOTS = 64;
-  __shared__ float simg[SLOTS];
+  __shared__ float red[4];
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const int gl = lane & (GS - 1), grp = lane / GS, ppw = 64 / GS;          // lane in group, group in wave, pixels per wave
   const int units = C / UE;
-  const long long chunk = (npix + gridDim.x - 1) / gridDim.x;
-  const long long p0 = (long long)blockIdx.x * chunk, p1 = (p0 + chunk < npix) ? p0 + chunk : npix;
-  if (p0 >= npix) return;
-  const long long img0 = p0 / HW;
-  if (threadIdx.x < SLOTS) simg[threadIdx.x] = 0.f;
-  __syncthreads();
-  float local = 0.f;
-  long long img_prev = -1;
-  auto commit = [&](long long img, float v) {
-    const long long s = img - img0;
-    if (s < SLOTS) atomicAdd(&simg[s], v / (float)HW);
-    else atomicAdd(&out[img], v / (float)HW);
-  };
+  const long long img = (long long)blockIdx.y * HW;                        // first pixel of this image
+  const long long p0 = (long long)blockIdx.x * chunk, p1 = (p0 + chunk < HW) ? p0 + chunk : HW;   // p0 < HW: gridDim.x = ceil(HW / chunk)
+  float local = 0.f;                                                       // the group leader's running sum; 0 in every other lane
   const long long stride = 4 * ppw;
   // every lane of a wave runs the same number of iterations (the shuffles need all lanes): out-of-range groups compute on pixel p1-1, masked
   for (long long base = p0 + (long long)wv * ppw; base < p1; base += stride) {
     const long long pix_raw = base + grp;
     const bool live = pix_raw < p1;
-    const long long pix = live ? pix_raw : p1 - 1;
+    const long long pix = img + (live ? pix_raw : p1 - 1);
     const T* px = fx + pix * C;
     const T* py = fy + pix * C;
     float sx = 0.f, sy = 0.f;
@@ -200,19 +192,10 @@ tfc_lpips_head_kernel(const T* __restrict__ fx, const T* __restrict__ fy, const 
         *reinterpret_cast<uint4*>(dfx + pix * C + u * UE) = pack16<T>(g);
       }
     }
-    if (gl == 0 && live) {                                         // group leader: running sum, committed when the image changes
-      const long long img = pix / HW;
-      if (img_prev >= 0 && img != img_prev) { commit(img_prev, local); local = 0.f; }
-      local += val;
-      img_prev = img;
-    }
+    if (gl == 0 && live) local += val;                             // group leader: its pixels in ascending order
   }
-  if (gl == 0 && img_prev >= 0) commit(img_prev, local);
-  __syncthreads();
-  if (threadIdx.x < SLOTS && img0 + threadIdx.x <= (p1 - 1) / HW) {
-    const float v = simg[threadIdx.x];
-    if (v != 0.f) atomicAdd(&out[img0 + threadIdx.x], v);
-  }
+  const double tot = tfc_block_sum4(wave_sum(local), red);
+  if (threadIdx.x == 0) part[(size_t)blockIdx.y * gridDim.x + blockIdx.x] = (float)(tot / (double)HW);
 }
 
 #define TFC_DISPATCH_T(dt, CALL_BF16, CALL_F32) do { if ((dt) == TFC_DT_BF16) { CALL_BF16; } else { CALL_F32; } } while (0)
@@ -254,16 +237,24 @@ hipError_t tfc_launch_relu_bwd(int dt, const void* dy, const void* y, const void
                  hipLaunchKernelGGL(tfc_relu_bwd_kernel<float>, dim3((unsigned)nb), dim3(256), 0, st, (const float*)dy, (const float*)y, (const float*)extra, (float*)dz, units));
   return hipGetLastError();
 }
-hipError_t tfc_launch_lpips_head(int dt, const void* fx, const void* fy, const float* w, float* out, void* dfx, int N, long long HW, int C, float gscale,
-                                 hipStream_t st) {
-  const long long npix = (long long)N * HW;
+hipError_t tfc_launch_part_reduce(const float* part, float* out, int G, int nparts, int L, hipStream_t st);
+// workgroups per image and their pixel range for the head: functions of HW and C (and the element type) ONLY, never of N, so that an image's sum
+// has the same bits in every batch. Up to 64 workgroups per image (batch 32 fills 8 per CU), each a whole number of workgroup iterations.
+hipError_t tfc_launch_lpips_head(int dt, const void* fx, const void* fy, const float* w, float* out, void* dfx, float* part_ws, int N, long long HW, int C,
+                                 float gscale, hipStream_t st) {
   const int units = C / (dt == TFC_DT_BF16 ? 8 : 4);
   int GS = 1;
   while (GS < units && GS < 64) GS <<= 1;
   const int ppb = 4 * (64 / GS);                                    // pixels per workgroup iteration
-  long long nb = (npix + ppb - 1) / ppb;
-  if (nb > 2048) nb = 2048;                                         // 8 workgroups per CU; each owns a contiguous pixel range
-  TFC_DISPATCH_T(dt, hipLaunchKernelGGL(tfc_lpips_head_kernel<bf16_t>, dim3((unsigned)nb), dim3(256), 0, st, (const bf16_t*)fx, (const bf16_t*)fy, w, out, (bf16_t*)dfx, C, HW, npix, gscale, GS),
-                 hipLaunchKernelGGL(tfc_lpips_head_kernel<float>, dim3((unsigned)nb), dim3(256), 0, st, (const float*)fx, (const float*)fy, w, out, (float*)dfx, C, HW, npix, gscale, GS));
-  return hipGetLastError();
+  long long wpi = (HW + ppb - 1) / ppb;
+  if (wpi > 64) wpi = 64;
+  const long long chunk = ((HW + wpi - 1) / wpi + ppb - 1) / ppb * ppb;
+  wpi = (HW + chunk - 1) / chunk;                                   // no workgroup without a pixel
+  if (!part_ws || N > 65535 || (long long)N * wpi > (long long)TFC_PART_WS_FLOATS) return hipErrorInvalidValue;
+  const dim3 g((unsigned)wpi, (unsigned)N);
+  TFC_DISPATCH_T(dt, hipLaunchKernelGGL(tfc_lpips_head_kernel<bf16_t>, g, dim3(256), 0, st, (const bf16_t*)fx, (const bf16_t*)fy, w, part_ws, (bf16_t*)dfx, C, HW, chunk, gscale, GS),
+                 hipLaunchKernelGGL(tfc_lpips_head_kernel<float>, g, dim3(256), 0, st, (const float*)fx, (const float*)fy, w, part_ws, (float*)dfx, C, HW, chunk, gscale, GS));
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  return tfc_launch_part_reduce(part_ws, out, N, (int)wpi, 1, st);   // out[n] += the image's slots, in order
 }

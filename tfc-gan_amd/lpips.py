@@ -212,7 +212,7 @@ class LPIPS(nn.Module):
         for fx, fy, w in zip(taps_x, taps_y, P["heads"]):
             d = ops.new_act(N, fx.H, fx.W, fx.C, dt, dev) if want_grad else None
             check(lib.tfc_lpips_head(st, dt, fx.ptr, fy.ptr, ops._p(w), ops._p(per_img), None if d is None else d.ptr, N, fx.H, fx.W, fx.C,
-                                     float(weight)), "tfc_lpips_head")
+                                     float(weight), ops.part_ws(dev)), "tfc_lpips_head")
             dtaps.append(d)
         value = (per_img.sum() * weight).reshape(1, 1, 1, 1)
         if not want_grad:
