@@ -45,6 +45,11 @@ extern "C" {
 #define TFC_OP_UPCONV 3   /* nn.Upsample(x2)+nn.ZeroPad2d((1,0,1,0))+nn.Conv2d(k4,p1) [+Tanh]   P16:153-158 (generator head)  */
 #define TFC_OP_CONV3 4    /* nn.Conv2d(k3,s1,p1): VGG16 features of criterion_lpips (P16:70-73, :598). Weights are passed zero-padded to
                              [Cout][Cin][4][4] (filter in rows / columns 0..2); forward and input gradient only (frozen network)          */
+#define TFC_OP_CONV2 5    /* nn.Conv2d(k4,s2,p1): the pix2pix PatchGAN blocks of TFC-STN/TFCGAN_STN21_Eur_DarkVisible.py:370-423. H and W even
+                             (an odd size is refused), output H/2 x W/2, weights [Cout][Cin][4][4]; forward (four source parity planes in one gather),
+                             input gradient (four output phases in one launch), weight gradient (bf16: the transposed convolution's phase-fused
+                             launch with the two tensors exchanged; fp32 / bf16x3: one launch per parity plane into disjoint filter taps; slabs
+                             added in a fixed order, no float atomics); every compute mode                                                 */
 
 /* epilogue flags of tfc_conv_fwd / tfc_conv_dgrad */
 #define TFC_EP_BIAS 1       /* + bias[Cout]                                                                                   */
@@ -293,6 +298,12 @@ int tfc_affine_warp_fwd(void* stream, const float* src, const float* theta, floa
  * never asks for it). Both are overwritten (zeroed inside). gout: d loss / d out. */
 int tfc_affine_warp_bwd(void* stream, const float* src, const float* theta, const float* gout, float* dtheta, float* dsrc, int N, int C, int H, int W,
                         float* part_ws);
+/* The same pair with the SAMPLING convention as an argument: the grid is F.affine_grid(align_corners=True) in both; sample_align_corners != 0 samples
+ * it with align_corners=True (the bits of the pair above), 0 with align_corners=False: ix = ((gx + 1) W - 1) / 2, d ix / d gx = W / 2, taps clipped
+ * one by one as above -- the mixed form of TFC-STN/TFCGAN_STN21_Eur_DarkVisible.py:205-206. H and W may be 1 (base coordinate 0, as torch). */
+int tfc_affine_warp_mode_fwd(void* stream, const float* src, const float* theta, float* out, int N, int C, int H, int W, int sample_align_corners);
+int tfc_affine_warp_mode_bwd(void* stream, const float* src, const float* theta, const float* gout, float* dtheta, float* dsrc, int N, int C, int H, int W,
+                             int sample_align_corners, float* part_ws);
 /* morph_triplet, STN:444-449: kornia.morphology.gradient(x, [[0,1,0],[1,1,1],[0,1,0]]) = dilation - erosion with geodesic borders (neighbours
  * outside the image never win). x / out: fp32, `planes` images of H x W; arg (nullable): per pixel arg-max | arg-min << 4 for the backward. */
 int tfc_morph_grad_fwd(void* stream, const float* x, float* out, uint8_t* arg, long long planes, int H, int W);

@@ -27,7 +27,7 @@ from .nets import set_wgrad_stream  # noqa: F401
 from .parallel import all_gather_records  # noqa: F401
 from .data import DeviceLoader, ImageDataset, LabelledImageDataset, TestImageDataset, pair_resize_normalize  # noqa: F401
 from .lpips import LPIPS  # noqa: F401
-from .stn21 import STN21Step  # noqa: F401
+from .stn21 import DarkVisibleStep, STN21Step  # noqa: F401
 from .stn import Warp, affine_warp, morph_gradient, morph_triplet, triplet_margin_rows  # noqa: F401
 from .synthetic import synthetic_pairs, synthetic_temperatures  # noqa: F401
 from .inference import global_grid, load_clean_state, save_checkpoint, stitch_16_patches, stitch_patches  # noqa: F401
@@ -36,11 +36,11 @@ from .losses import (ContrastiveLoss, FFT_Components, calculate_ffts, color_jitt
                      patch_triplet_loss, region_weights, regional_fft_components, regional_fft_loss, sample_spectra, temperature_triplet_loss,
                      vectorize_temps)
 from .metrics import EvalAccumulator, bhattacharyya, mutual_information, ncc, psnr, ssim, to_gray, to_uint8  # noqa: F401
-from .models import (BlurPool, Discriminator, Discriminator1, GeneratorUNet, UNetDown, UNetUp, get_batch_invariant,  # noqa: F401
+from .models import (BlurPool, Discriminator, Discriminator1, GeneratorUNet, Pix2PixDiscriminator, UNetDown, UNetUp, get_batch_invariant,  # noqa: F401
                      get_compute_dtype, set_batch_invariant, set_compute_dtype, weights_init_normal)
 
 __all__ = ["UNetDown", "UNetUp", "GeneratorUNet", "Discriminator1", "Discriminator", "BlurPool", "weights_init_normal",
            "make_16_patches", "make_4_patches", "patch_first_flat_index", "stitch_patches", "ContrastiveLoss", "patch_triplet_loss", "FFT_Components", "fft_components", "calculate_ffts",
            "patch_fft_loss", "global_fft_loss", "regional_fft_components", "regional_fft_loss", "region_weights", "debias_weights", "mask_weights", "mask_maker", "mask_l1_loss", "mse_spec", "other_spec", "psnr", "ssim", "bhattacharyya", "ncc", "mutual_information", "to_uint8", "to_gray",
            "EvalAccumulator", "sample_spectra", "vectorize_temps", "temperature_triplet_loss", "color_jitter_thermal",
-           "color_jitter_params", "synthetic_pairs", "synthetic_temperatures", "load_clean_state", "save_checkpoint", "stitch_16_patches", "global_grid", "TrainStep", "STN21Step", "LPIPS", "ImageDataset", "LabelledImageDataset", "TestImageDataset", "DeviceLoader", "pair_resize_normalize", "Warp", "affine_warp", "morph_gradient", "morph_triplet", "triplet_margin_rows", "set_compute_dtype", "get_compute_dtype", "set_batch_invariant", "get_batch_invariant", "build", "TfcError", "all_gather_records"]
+           "color_jitter_params", "synthetic_pairs", "synthetic_temperatures", "load_clean_state", "save_checkpoint", "stitch_16_patches", "global_grid", "TrainStep", "STN21Step", "DarkVisibleStep", "Pix2PixDiscriminator", "LPIPS", "ImageDataset", "LabelledImageDataset", "TestImageDataset", "DeviceLoader", "pair_resize_normalize", "Warp", "affine_warp", "morph_gradient", "morph_triplet", "triplet_margin_rows", "set_compute_dtype", "get_compute_dtype", "set_batch_invariant", "get_batch_invariant", "build", "TfcError", "all_gather_records"]

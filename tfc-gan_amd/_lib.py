@@ -17,7 +17,7 @@ HEADERS = ["common.h", "tfc_desc.h", "pack_math.h"]
 PUBLIC_HEADER = os.path.join(_ROOT, "include", "tfc_gan.h")
 
 DT_BF16, DT_F32, DT_BF16X3 = 0, 1, 2          # DT_BF16X3: fp32 storage, convolutions as bf16 hi/lo three-term products
-OP_CONV, OP_PADCONV, OP_CONVT, OP_UPCONV, OP_CONV3 = 0, 1, 2, 3, 4
+OP_CONV, OP_PADCONV, OP_CONVT, OP_UPCONV, OP_CONV3, OP_CONV2 = 0, 1, 2, 3, 4, 5
 EP_BIAS, EP_STATS, EP_ACCUM, EP_TANH_NCHW, EP_LEAKY, EP_RELU = 1, 2, 4, 8, 16, 32
 
 _lock = threading.Lock()
@@ -182,6 +182,8 @@ PROTOTYPES = {
     "tfc_l1_sum": (_i, [_vp, _vp, _vp, _ll, _f, _vp, _i]),
     "tfc_affine_warp_fwd": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i]),
     "tfc_affine_warp_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "tfc_affine_warp_mode_fwd": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i]),
+    "tfc_affine_warp_mode_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "tfc_morph_grad_fwd": (_i, [_vp, _vp, _vp, _vp, _ll, _i, _i]),
     "tfc_morph_grad_bwd": (_i, [_vp, _vp, _vp, _vp, _ll, _i, _i]),
     "tfc_row_triplet_grad": (_i, [_vp, _vp, _vp, _vp, _ll, _i, _f, _f, _vp, _vp]),

@@ -24,6 +24,7 @@
 #undef TFC_OP_CONVT
 #undef TFC_OP_UPCONV
 #undef TFC_OP_CONV3
+#undef TFC_OP_CONV2
 #include "tfc_desc.h"
 #include "pack_math.h"
 #define TFC_OP_CONV 0
@@ -31,6 +32,7 @@
 #define TFC_OP_CONVT 2
 #define TFC_OP_UPCONV 3
 #define TFC_OP_CONV3 4
+#define TFC_OP_CONV2 5
 
 // ---- internal launchers (igemm.hip / elementwise.hip / losses.hip) ------------------------------------------
 int tfc_total_substeps(const TfcGather& d, int es);
@@ -93,8 +95,8 @@ hipError_t tfc_launch_vectorize_temps(const float* x, long long bs, int rs, int 
 hipError_t tfc_launch_row_triplet(const float* a, const float* p, const float* ng, long long rows, int W, float margin, float eps,
                                   float* loss, hipStream_t st);
 hipError_t tfc_launch_head_fwd(int dt, const void* x, int x_pitch, const float* w, void* y, int y_pitch, int N, int H, int W, int C, hipStream_t st);
-hipError_t tfc_launch_affine_warp_fwd(const float* src, const float* theta, float* out, int N, int C, int H, int W, hipStream_t st);
-hipError_t tfc_launch_affine_warp_bwd(const float* src, const float* theta, const float* gout, float* dtheta, float* dsrc, float* part_ws, int N, int C, int H, int W, hipStream_t st);
+hipError_t tfc_launch_affine_warp_fwd(const float* src, const float* theta, float* out, int N, int C, int H, int W, int sac, hipStream_t st);
+hipError_t tfc_launch_affine_warp_bwd(const float* src, const float* theta, const float* gout, float* dtheta, float* dsrc, float* part_ws, int N, int C, int H, int W, int sac, hipStream_t st);
 hipError_t tfc_launch_morph_grad_fwd(const float* x, float* out, unsigned char* arg, long long planes, int H, int W, hipStream_t st);
 hipError_t tfc_launch_morph_grad_bwd(const float* gout, const unsigned char* arg, float* dx, long long planes, int H, int W, hipStream_t st);
 hipError_t tfc_launch_row_triplet_grad(const float* a, const float* p, const float* ng, long long rows, int W, float margin, float eps, float gscale,
@@ -233,8 +235,31 @@ extern "C" int tfc_prof_records(int max_records, int* kclass, double* ms, double
 // ---------------------------------------------------------------------------------------------------------------
 struct WeightMap { int Nreal, Creal; long long sn, sc; };
 
-static int out_hw(int op, int h) { return op == TFC_OP_CONV ? h - 1 : ((op == TFC_OP_PADCONV || op == TFC_OP_CONV3) ? h : 2 * h); }
-static int num_phases(int op, int pass) { return ((op == TFC_OP_CONVT || op == TFC_OP_UPCONV) && pass != 1) ? 4 : 1; }
+static int out_hw(int op, int h) {
+  if (op == TFC_OP_CONV2) return h / 2;
+  return op == TFC_OP_CONV ? h - 1 : ((op == TFC_OP_PADCONV || op == TFC_OP_CONV3) ? h : 2 * h);
+}
+// phases = descriptors of one pass that are packed / launched one after the other: the four sub-pixel output phases of the 2x-upsampling ops (forward
+// and weight gradient) and of the stride-2 convolution's input gradient; the four source parity planes of the stride-2 convolution's weight gradient
+static int num_phases(int op, int pass) {
+  if (op == TFC_OP_CONV2) return pass == 0 ? 1 : 4;
+  return ((op == TFC_OP_CONVT || op == TFC_OP_UPCONV) && pass != 1) ? 4 : 1;
+}
+// the phases of (op, pass) have one shape and fold into the grid of ONE gather-GEMM launch (phase-0 descriptor + per-phase shifts)
+static bool fold_phases(int op, int pass) { return pass == 0 ? (op == TFC_OP_CONVT || op == TFC_OP_UPCONV) : (pass == 1 && op == TFC_OP_CONV2); }
+static void set_fold(TfcGather& d, int op) { d.ph_n = 4; d.ph_d0 = (op == TFC_OP_UPCONV) ? 0 : 1; d.ph_oo = 1; }   // convT / conv2 dgrad: dy0 = py - 1; all: OOY = py
+
+// source parity planes of a stride-2 gather (transposed-conv dgrad, stride-2 conv forward / weight gradient): source row 2 i - 1 + k of filter tap k lies in
+// parity plane 0 for k in {1, 3} (plane rows i, i + 1) and in plane 1 for k in {0, 2} (plane rows i - 1, i)
+static void set_parity_plane(TfcPlane& p, int ppy, int ppx) {
+  static const int kOf[2][2] = {{1, 3}, {0, 2}};
+  p.py = ppy; p.px = ppx; p.dy0 = ppy ? -1 : 0; p.dx0 = ppx ? -1 : 0; p.hh = 9; p.hw = 17; p.ntaps = 4;
+  for (int jy = 0; jy < 2; ++jy)
+    for (int jx = 0; jx < 2; ++jx) {
+      const int t = jy * 2 + jx;
+      p.tap_dy[t] = jy; p.tap_dx[t] = jx; p.tap_mask[t] = 1 << (kOf[ppy][jy] * 4 + kOf[ppx][jx]);
+    }
+}
 
 static void set_tiles(TfcGather& d) {
   d.tiles_y = (d.GH + TFC_TILE_H - 1) / TFC_TILE_H;
@@ -314,6 +339,19 @@ static int build_desc(int op, int pass, int phase, int N, int H, int W, int Cin,
         if (wm) *wm = {Cout, Cin, (long long)Cin * 16, 16};
         break;
       }
+      case TFC_OP_CONV2: {
+        // nn.Conv2d(k4, s2, p1): out[o] = sum_k x[2 o - 1 + k] W[k] -- a stride-2 gather over the four parity planes of x (the tap sets of the transposed
+        // convolution's dgrad) with the weight map of the plain convolution. The weight gradient (pass 2) takes the planes one by one (phase = plane):
+        // each fills its own four filter taps.
+        d.GH = OH; d.GW = OW; d.SS = 2;
+        if (pass == 2) set_parity_plane(p, py, px);
+        else {
+          d.nplanes = 4;
+          for (int q = 0; q < 4; ++q) set_parity_plane(d.plane[q], q >> 1, q & 1);
+        }
+        if (wm) *wm = {Cout, Cin, (long long)Cin * 16, 16};
+        break;
+      }
       default: return fail(-1, "unknown op %d", op);
     }
   } else {
@@ -343,18 +381,22 @@ static int build_desc(int op, int pass, int phase, int N, int H, int W, int Cin,
       case TFC_OP_CONVT: {
         // dx[i] = sum_k dy[2i-1+k] W[k]: parity plane 0 holds k in {1,3} at plane rows {i, i+1}; plane 1 holds k in {0,2} at {i-1, i}
         d.SS = 2; d.nplanes = 4;
-        static const int kOf[2][2] = {{1, 3}, {0, 2}};
-        for (int ppy = 0; ppy < 2; ++ppy)
-          for (int ppx = 0; ppx < 2; ++ppx) {
-            TfcPlane& p = d.plane[ppy * 2 + ppx];
-            p.py = ppy; p.px = ppx; p.dy0 = ppy ? -1 : 0; p.dx0 = ppx ? -1 : 0; p.hh = 9; p.hw = 17; p.ntaps = 4;
-            for (int jy = 0; jy < 2; ++jy)
-              for (int jx = 0; jx < 2; ++jx) {
-                const int t = jy * 2 + jx;
-                p.tap_dy[t] = jy; p.tap_dx[t] = jx; p.tap_mask[t] = 1 << (kOf[ppy][jy] * 4 + kOf[ppx][jx]);
-              }
-          }
+        for (int q = 0; q < 4; ++q) set_parity_plane(d.plane[q], q >> 1, q & 1);
         if (wm) *wm = {Cin, Cout, (long long)Cout * 16, 16};   // W[ci][co][k]: n = ci, c = co
+        break;
+      }
+      case TFC_OP_CONV2: {
+        // dx[2 a + py] = sum_j dy[a + py - j] W[1 - py + 2 j]: the four output phases of the transposed convolution's forward, on the Conv2d weight
+        TfcPlane& p = d.plane[0];
+        d.GH = OH; d.GW = OW; d.OS = 2; d.OOY = py; d.OOX = px;
+        p.dy0 = py - 1; p.dx0 = px - 1; p.hh = 9; p.hw = 17; p.ntaps = 4;
+        for (int jy = 0; jy < 2; ++jy)
+          for (int jx = 0; jx < 2; ++jx) {
+            const int t = jy * 2 + jx;
+            p.tap_dy[t] = 1 - jy; p.tap_dx[t] = 1 - jx;
+            p.tap_mask[t] = 1 << ((1 - py + 2 * jy) * 4 + (1 - px + 2 * jx));
+          }
+        if (wm) *wm = {Cin, Cout, 16, (long long)Cin * 16};    // Conv2d weight [Cout][Cin][4][4]: n = ci, c = co
         break;
       }
       case TFC_OP_UPCONV: {
@@ -398,8 +440,9 @@ static int check_desc(const TfcGather& d, int dt) {
 
 static int check_common(int dt, int op, int N, int H, int W, int Cin, int Cout) {
   REQUIRE(dt == TFC_DT_BF16 || dt == TFC_DT_F32 || dt == TFC_DT_BF16X3, "bad dtype %d", dt);
-  REQUIRE(op >= 0 && op <= 4, "bad op %d", op);
+  REQUIRE(op >= 0 && op <= 5, "bad op %d", op);
   REQUIRE(N > 0 && H > 1 && W > 1 && Cin > 0 && Cout > 0, "bad dims N=%d H=%d W=%d Cin=%d Cout=%d", N, H, W, Cin, Cout);
+  REQUIRE(op != TFC_OP_CONV2 || (H % 2 == 0 && W % 2 == 0), "TFC_OP_CONV2 (stride 2) needs an even H and W (H=%d W=%d)", H, W);
   REQUIRE((long long)N * (2 * H) * (2 * W) * (long long)(pad8(Cin) > pad8(Cout) ? pad8(Cin) : pad8(Cout)) < 2147483647LL,
           "tensor exceeds 2^31 elements");
   const int es = es_of(dt);
@@ -435,7 +478,7 @@ static size_t phase_packed_offset(int dt, int op, int pass, int Cin, int Cout, i
 }
 
 extern "C" size_t tfc_conv_packed_bytes(int dt, int op, int pass, int Cin, int Cout) {
-  if (pass < 0 || pass > 1 || op < 0 || op > 4) return 0;
+  if (pass < 0 || pass > 1 || op < 0 || op > 5) return 0;
   return phase_packed_offset(dt, op, pass, Cin, Cout, num_phases(op, pass));
 }
 
@@ -476,13 +519,13 @@ extern "C" int tfc_conv_fwd(void* stream, int dt, int op, const void* x, int x_p
   if (flags & TFC_EP_BIAS) REQUIRE(bias != nullptr, "bias is null");
   if (flags & TFC_EP_STATS) REQUIRE(stats != nullptr && part_ws != nullptr, "TFC_EP_STATS needs stats and part_ws");
   int nph = num_phases(op, 0);
-  const bool fold = (op == TFC_OP_CONVT || op == TFC_OP_UPCONV);   // equal-shaped phases: fold all four into the grid of one launch
+  const bool fold = fold_phases(op, 0);                           // equal-shaped phases: fold all four into the grid of one launch
   if (fold) nph = 1;
   ProfScope prof(0, conv_flop(op, N, H, W, Cin, Cout), (hipStream_t)stream, op, 0, N, H, W, Cin, Cout);
   for (int ph = 0; ph < nph; ++ph) {
     TfcGather d;
     if (int e = build_desc(op, 0, ph, N, H, W, Cin, Cout, x_pitch, y_pitch, &d, nullptr)) return e;
-    if (fold) { d.ph_n = 4; d.ph_d0 = (op == TFC_OP_CONVT) ? 1 : 0; d.ph_oo = 1; }   // phase 0 descriptor + per-phase shifts (convT: dy0 = py-1; both: OOY = py)
+    if (fold) set_fold(d, op);                                    // phase 0 descriptor + per-phase shifts (convT: dy0 = py-1; both: OOY = py)
     if (int e = check_desc(d, dt)) return e;
     CHECK_HIP(tfc_launch_igemm(dt, d, x, (const char*)packed + phase_packed_offset(dt, op, 0, Cin, Cout, ph), y, bias, stats, part_ws, out_nchw, oscale, flags, (hipStream_t)stream), "tfc_conv_fwd");
   }
@@ -569,6 +612,7 @@ extern "C" int tfc_conv_dgrad(void* stream, int dt, int op, const void* dy, int 
   REQUIRE((flags & ~TFC_EP_ACCUM) == 0, "dgrad supports only TFC_EP_ACCUM");
   TfcGather d;
   if (int e = build_desc(op, 1, 0, N, H, W, Cin, Cout, dy_pitch, dx_pitch, &d, nullptr)) return e;
+  if (fold_phases(op, 1)) set_fold(d, op);                        // stride-2 convolution: the four output phases in one launch
   if (int e = check_desc(d, dt)) return e;
   ProfScope prof(0, conv_flop(op, N, H, W, Cin, Cout), (hipStream_t)stream, op, 1, N, H, W, Cin, Cout);
   CHECK_HIP(tfc_launch_igemm(dt, d, dy, packed, dx, nullptr, nullptr, nullptr, nullptr, oscale, flags, (hipStream_t)stream), "tfc_conv_dgrad");
@@ -635,6 +679,15 @@ static size_t wgrad_acc_bytes(int Cin, int Cout) { return (((size_t)16 * Cin * C
 static const size_t kWgradSlabBytes = (size_t)512 * 4 * 8 * 4 * 64 * 16;
 extern "C" size_t tfc_conv_wgrad_ws_bytes(int op, int Cin, int Cout) { (void)op; return wgrad_acc_bytes(Cin, Cout) + kWgradSlabBytes; }
 
+// The stride-2 convolution's weight gradient dW[co][ci][k] = sum_o dy[o] x[2 o - 1 + k] IS the transposed convolution's (dW[ci][co][k] =
+// sum_a x[a] dy[2 a - 1 + k], tfc_wgradT_kernel) with the two tensors exchanged: dy plays its input (the small grid), x its output gradient (the four
+// parity planes), and the result lands as [slot][n = ci][c = co]. bf16 runs that one launch; TFC_CONV2_WGRAD_PLANES=1 (A/B knob for profiling, ignored
+// in batch-invariant mode) keeps the four per-plane launches that the other compute modes use.
+static bool conv2_wgrad_mirrored(int dt) {
+  static const bool planes_env = [] { const char* e = getenv("TFC_CONV2_WGRAD_PLANES"); return e && atoi(e) != 0; }();
+  return dt == TFC_DT_BF16 && !(planes_env && !g_tfc_batch_invariant);
+}
+
 extern "C" int tfc_conv_wgrad(void* stream, int dt, int op, const void* x, int x_pitch, const void* dy, int dy_pitch, int N, int H, int W,
                               int Cin, int Cout, void* ws, float* dw, int accumulate) {
   if (int e = check_common(dt, op, N, H, W, Cin, Cout)) return e;
@@ -647,6 +700,7 @@ extern "C" int tfc_conv_wgrad(void* stream, int dt, int op, const void* x, int x
   hipStream_t st = (hipStream_t)stream;
   WeightMap wm{};                                                // the accumulator part of ws is all-zero on entry (caller zeroes it ONCE) and again on exit
   TfcWgradFin fin{dw, 0, 0, accumulate, false};
+  int fin_n = Cout, fin_c = Cin;                                  // the accumulator the finish pass lays out is [slot][fin_n][fin_c]
   {
     ProfScope prof(1, conv_flop(op, N, H, W, Cin, Cout), st, op, 2, N, H, W, Cin, Cout);
     bool fused = false;
@@ -658,6 +712,13 @@ extern "C" int tfc_conv_wgrad(void* stream, int dt, int op, const void* x, int x
       fused = tfc_launch_wgrad_phases_fused(op == TFC_OP_UPCONV, x, N, H, W, x_pitch, pad8(Cin), dy, dy_pitch, Cout, Cin,
                                             (float*)((char*)ws + kWgradSlabBytes), ws, st, &herr, &fin);
       if (fused) CHECK_HIP(herr, "tfc_conv_wgrad (phase-fused)");
+    } else if (op == TFC_OP_CONV2 && conv2_wgrad_mirrored(dt)) {
+      wm = {Cin, Cout, 16, (long long)Cin * 16};                 // Conv2d weight [Cout][Cin][4][4] read as n = ci, c = co
+      fin.sn = wm.sn; fin.sc = wm.sc;
+      hipError_t herr = hipSuccess;
+      fused = tfc_launch_wgrad_phases_fused(0, dy, N, H / 2, W / 2, dy_pitch, pad8(Cout), x, x_pitch, Cin, Cout,
+                                            (float*)((char*)ws + kWgradSlabBytes), ws, st, &herr, &fin);
+      if (fused) { CHECK_HIP(herr, "tfc_conv_wgrad (stride 2, parity-fused)"); fin_n = Cin; fin_c = Cout; }
     }
     const int nph = num_phases(op, 2);
     for (int ph = 0; ph < nph && !fused; ++ph) {
@@ -669,7 +730,7 @@ extern "C" int tfc_conv_wgrad(void* stream, int dt, int op, const void* x, int x
   }
   if (!fin.done) {
     ProfScope prof(2, 0.0, st, op, 3, N, H, W, Cin, Cout);     // class 2: the finish pass (layout + re-zero), no algorithmic FLOP of its own
-    CHECK_HIP(tfc_launch_wgrad_finish((float*)((char*)ws + kWgradSlabBytes), dw, Cout, Cin, wm.sn, wm.sc, accumulate, st), "tfc_conv_wgrad finish");
+    CHECK_HIP(tfc_launch_wgrad_finish((float*)((char*)ws + kWgradSlabBytes), dw, fin_n, fin_c, wm.sn, wm.sc, accumulate, st), "tfc_conv_wgrad finish");
   }
   return 0;
 }
@@ -1011,13 +1072,28 @@ extern "C" int tfc_row_triplet(void* stream, const float* anchor, const float* p
 }
 extern "C" int tfc_affine_warp_fwd(void* stream, const float* src, const float* theta, float* out, int N, int C, int H, int W) {
   REQUIRE(src && theta && out && N > 0 && C > 0 && H > 1 && W > 1, "bad args");
-  CHECK_HIP(tfc_launch_affine_warp_fwd(src, theta, out, N, C, H, W, (hipStream_t)stream), "tfc_affine_warp_fwd");
+  CHECK_HIP(tfc_launch_affine_warp_fwd(src, theta, out, N, C, H, W, 1, (hipStream_t)stream), "tfc_affine_warp_fwd");
   return 0;
 }
 extern "C" int tfc_affine_warp_bwd(void* stream, const float* src, const float* theta, const float* gout, float* dtheta, float* dsrc, int N, int C,
                                    int H, int W, float* part_ws) {
   REQUIRE(src && theta && gout && dtheta && part_ws && N > 0 && C > 0 && H > 1 && W > 1, "bad args");
-  CHECK_HIP(tfc_launch_affine_warp_bwd(src, theta, gout, dtheta, dsrc, part_ws, N, C, H, W, (hipStream_t)stream), "tfc_affine_warp_bwd");
+  CHECK_HIP(tfc_launch_affine_warp_bwd(src, theta, gout, dtheta, dsrc, part_ws, N, C, H, W, 1, (hipStream_t)stream), "tfc_affine_warp_bwd");
+  return 0;
+}
+// the same pair with the sampling convention as an argument (sample_align_corners != 0: the bits of the pair above); H and W >= 1
+extern "C" int tfc_affine_warp_mode_fwd(void* stream, const float* src, const float* theta, float* out, int N, int C, int H, int W, int sample_align_corners) {
+  REQUIRE(src && theta && out && N > 0 && C > 0 && H > 0 && W > 0, "bad args");
+  REQUIRE((long long)N * C * H * W < (1LL << 40) && (long long)H * W < 2147483647LL, "image too large");
+  CHECK_HIP(tfc_launch_affine_warp_fwd(src, theta, out, N, C, H, W, sample_align_corners ? 1 : 0, (hipStream_t)stream), "tfc_affine_warp_mode_fwd");
+  return 0;
+}
+extern "C" int tfc_affine_warp_mode_bwd(void* stream, const float* src, const float* theta, const float* gout, float* dtheta, float* dsrc, int N, int C,
+                                        int H, int W, int sample_align_corners, float* part_ws) {
+  REQUIRE(src && theta && gout && dtheta && part_ws && N > 0 && N <= 65535 && C > 0 && H > 0 && W > 0, "bad args (1 <= N <= 65535)");
+  REQUIRE((long long)H * W < 2147483647LL, "image too large");
+  CHECK_HIP(tfc_launch_affine_warp_bwd(src, theta, gout, dtheta, dsrc, part_ws, N, C, H, W, sample_align_corners ? 1 : 0, (hipStream_t)stream),
+            "tfc_affine_warp_mode_bwd");
   return 0;
 }
 // ---- STN21 localiser (vit.hip) ----
@@ -1323,11 +1399,13 @@ extern "C" int tfc_conv_plan_query(int dt, int op, int pass, int N, int H, int W
     bool fused = false;
     if ((op == TFC_OP_CONVT || op == TFC_OP_UPCONV) && dt == TFC_DT_BF16)
       fused = tfc_plan_wgrad_phases(op == TFC_OP_UPCONV, N, H, W, pad8(Cin), pad8(Cin), Cout, wm.sn % 4 == 0 && wm.sc % 4 == 0, inv, &p);
+    if (op == TFC_OP_CONV2 && conv2_wgrad_mirrored(dt))           // as tfc_conv_wgrad: the transposed convolution's launch with the tensors exchanged
+      fused = tfc_plan_wgrad_phases(0, N, H / 2, W / 2, pad8(Cout), pad8(Cout), Cin, true, inv, &p);
     if (!fused) tfc_plan_wgrad(dt, d, pad8(Cout), inv, &p, 0);
   } else {
     TfcGather d;
     if (int e = build_desc(op, pass, 0, N, H, W, Cin, Cout, pass ? pad8(Cout) : pad8(Cin), pass ? pad8(Cin) : pad8(Cout), &d, nullptr)) return e;
-    if (pass == 0 && (op == TFC_OP_CONVT || op == TFC_OP_UPCONV)) { d.ph_n = 4; d.ph_d0 = (op == TFC_OP_CONVT) ? 1 : 0; d.ph_oo = 1; }   // as tfc_conv_fwd folds the phases
+    if (fold_phases(op, pass)) set_fold(d, op);                   // as tfc_conv_fwd / tfc_conv_dgrad fold the phases
     if (int e = check_desc(d, dt)) return e;
     tfc_plan_igemm(dt, d, flags & 0xffff, ncu, inv, &p);
     if (!(flags & TFC_EP_STATS)) p.nparts = 0;
@@ -1590,7 +1668,8 @@ extern "C" int tfc_probe_mfma(void* stream, float* out) {
 //   pass 2: x [N][H][W][pad8(Cin)], w_host = dy [N][OH][OW][pad8(Cout)] -> y = dw (torch layout)
 // ---------------------------------------------------------------------------------------------------------------
 extern "C" int tfc_host_emulate_conv(int op, int pass, int es, const float* x, const float* w, float* y, int N, int H, int W, int Cin, int Cout) {
-  REQUIRE(pass >= 0 && pass <= 2 && op >= 0 && op <= 4 && (es == 2 || es == 4), "bad op/pass/es");
+  REQUIRE(pass >= 0 && pass <= 2 && op >= 0 && op <= 5 && (es == 2 || es == 4), "bad op/pass/es");
+  REQUIRE(op != TFC_OP_CONV2 || (H % 2 == 0 && W % 2 == 0), "TFC_OP_CONV2 needs an even H and W");
   const int UE = 16 / es;                                        // elements per 16-byte unit in the emulated geometry
   const int OH = out_hw(op, H), OW = out_hw(op, W);
   const int inC = pass == 1 ? pad8(Cout) : pad8(Cin);

@@ -30,24 +30,34 @@ __device__ __forceinline__ void cubic_dw(float t, float (&g)[4]) {
 }
 __device__ __forceinline__ int clip_border(int v, int n) { return v < 0 ? 0 : (v > n - 1 ? n - 1 : v); }
 
-// source coordinate of output pixel (i, j) under theta (align_corners = True): base grid x_j = -1 + 2 j / (W-1), then unnormalise
+// source coordinate of output pixel (i, j) under theta: base grid x_j = -1 + 2 j / (W-1) (F.affine_grid, align_corners = True), then the
+// unnormalisation of F.grid_sample: SAC (its align_corners) true: ix = (gx + 1) (W - 1) / 2; false: ix = ((gx + 1) W - 1) / 2 -- the mixed form of
+// TFC-STN/TFCGAN_STN21_Eur_DarkVisible.py:205-206. d ix / d gx = (W - 1) / 2 or W / 2 (unnorm_scale).
+template <bool SAC>
 __device__ __forceinline__ void src_coord(const float* th, int i, int j, int H, int W, float& ix, float& iy, float& bx, float& by) {
   bx = W > 1 ? -1.f + 2.f * (float)j / (float)(W - 1) : 0.f;
   by = H > 1 ? -1.f + 2.f * (float)i / (float)(H - 1) : 0.f;
   const float gx = th[0] * bx + th[1] * by + th[2];
   const float gy = th[3] * bx + th[4] * by + th[5];
-  ix = (gx + 1.f) * 0.5f * (float)(W - 1);
-  iy = (gy + 1.f) * 0.5f * (float)(H - 1);
+  if constexpr (SAC) {
+    ix = (gx + 1.f) * 0.5f * (float)(W - 1);
+    iy = (gy + 1.f) * 0.5f * (float)(H - 1);
+  } else {
+    ix = ((gx + 1.f) * (float)W - 1.f) * 0.5f;
+    iy = ((gy + 1.f) * (float)H - 1.f) * 0.5f;
+  }
 }
+template <bool SAC> __device__ __forceinline__ float unnorm_scale(int n) { return 0.5f * (float)(SAC ? n - 1 : n); }
 }  // namespace
 
+template <bool SAC>
 __global__ void __launch_bounds__(256)
 tfc_affine_warp_fwd_kernel(const float* __restrict__ src, const float* __restrict__ theta, float* __restrict__ out, int N, int C, int H, int W) {
   const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
   if (idx >= (long long)N * H * W) return;
   const int j = (int)(idx % W), i = (int)((idx / W) % H), n = (int)(idx / ((long long)W * H));
   float ix, iy, bx, by;
-  src_coord(theta + n * 6, i, j, H, W, ix, iy, bx, by);
+  src_coord<SAC>(theta + n * 6, i, j, H, W, ix, iy, bx, by);
   const float fx = floorf(ix), fy = floorf(iy);
   float wx[4], wy[4];
   cubic_w(ix - fx, wx);
@@ -71,6 +81,7 @@ tfc_affine_warp_fwd_kernel(const float* __restrict__ src, const float* __restric
 
 // gout: d loss / d out.  dtheta = part[n][blockIdx.x][6] (one slot per workgroup, added in a fixed order by tfc_part_reduce_kernel);
 // dsrc (nullable) [N][C][H][W] += ... (a scatter through float atomics; the launcher zeroes it)
+template <bool SAC>
 __global__ void __launch_bounds__(256)
 tfc_affine_warp_bwd_kernel(const float* __restrict__ src, const float* __restrict__ theta, const float* __restrict__ gout, float* dtheta,
                            float* dsrc, int N, int C, int H, int W) {
@@ -81,7 +92,7 @@ tfc_affine_warp_bwd_kernel(const float* __restrict__ src, const float* __restric
   if (idx < (long long)H * W) {
     const int j = (int)(idx % W), i = (int)(idx / W);
     float ix, iy, bx, by;
-    src_coord(theta + n * 6, i, j, H, W, ix, iy, bx, by);
+    src_coord<SAC>(theta + n * 6, i, j, H, W, ix, iy, bx, by);
     const float fx = floorf(ix), fy = floorf(iy);
     float wx[4], wy[4], dx[4], dy[4];
     cubic_w(ix - fx, wx); cubic_w(iy - fy, wy);
@@ -104,8 +115,8 @@ tfc_affine_warp_bwd_kernel(const float* __restrict__ src, const float* __restric
           if (dsrc) atomicAdd(&dsrc[si], go * wx[b] * wy[a]);
         }
     }
-    gix *= 0.5f * (float)(W - 1);                                   // d ix / d gx (align_corners = True)
-    giy *= 0.5f * (float)(H - 1);
+    gix *= unnorm_scale<SAC>(W);                                    // d ix / d gx
+    giy *= unnorm_scale<SAC>(H);
     g6[0] = gix * bx; g6[1] = gix * by; g6[2] = gix;
     g6[3] = giy * bx; g6[4] = giy * by; g6[5] = giy;
   }
@@ -194,19 +205,23 @@ tfc_row_triplet_grad_kernel(const float* __restrict__ a, const float* __restrict
   if (threadIdx.x == 0) tfc_block_commit(&g_rowtrip2_slot, tot / (double)rows, loss);
 }
 
-hipError_t tfc_launch_affine_warp_fwd(const float* src, const float* theta, float* out, int N, int C, int H, int W, hipStream_t st) {
+// sac: align_corners of the SAMPLING (the grid is always built with align_corners = True)
+hipError_t tfc_launch_affine_warp_fwd(const float* src, const float* theta, float* out, int N, int C, int H, int W, int sac, hipStream_t st) {
   const long long tot = (long long)N * H * W;
-  hipLaunchKernelGGL(tfc_affine_warp_fwd_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, src, theta, out, N, C, H, W);
+  const dim3 grid((unsigned)((tot + 255) / 256));
+  if (sac) hipLaunchKernelGGL(tfc_affine_warp_fwd_kernel<true>, grid, dim3(256), 0, st, src, theta, out, N, C, H, W);
+  else hipLaunchKernelGGL(tfc_affine_warp_fwd_kernel<false>, grid, dim3(256), 0, st, src, theta, out, N, C, H, W);
   return hipGetLastError();
 }
 hipError_t tfc_launch_affine_warp_bwd(const float* src, const float* theta, const float* gout, float* dtheta, float* dsrc, float* part_ws, int N, int C,
-                                      int H, int W, hipStream_t st) {
+                                      int H, int W, int sac, hipStream_t st) {
   const unsigned nbx = (unsigned)(((long long)H * W + 255) / 256);
   if (!part_ws || (long long)nbx * N * 6 > (long long)TFC_PART_WS_FLOATS) return hipErrorInvalidValue;
   hipError_t e = hipMemsetAsync(dtheta, 0, sizeof(float) * 6 * N, st);
   if (e != hipSuccess) return e;
   if (dsrc && (e = hipMemsetAsync(dsrc, 0, sizeof(float) * (size_t)N * C * H * W, st)) != hipSuccess) return e;
-  hipLaunchKernelGGL(tfc_affine_warp_bwd_kernel, dim3(nbx, N), dim3(256), 0, st, src, theta, gout, part_ws, dsrc, N, C, H, W);
+  if (sac) hipLaunchKernelGGL(tfc_affine_warp_bwd_kernel<true>, dim3(nbx, N), dim3(256), 0, st, src, theta, gout, part_ws, dsrc, N, C, H, W);
+  else hipLaunchKernelGGL(tfc_affine_warp_bwd_kernel<false>, dim3(nbx, N), dim3(256), 0, st, src, theta, gout, part_ws, dsrc, N, C, H, W);
   return tfc_launch_part_reduce(part_ws, dtheta, N, (int)nbx, 6, st);
 }
 hipError_t tfc_launch_morph_grad_fwd(const float* x, float* out, unsigned char* arg, long long planes, int H, int W, hipStream_t st) {

@@ -436,6 +436,87 @@ class Discriminator1(nn.Module):
         return _DiscriminatorFn.apply(self, img_A, img_B, *params.values())
 
 
+class _Pix2PixFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, module, img_a, img_b, *params):
+        core = module._core_for(img_a.device)
+        logits, dctx = core.forward(img_a.detach().float().contiguous(), img_b.detach().float().contiguous())
+        ctx.core, ctx.dctx = core, dctx
+        ctx.need_a = img_a.requires_grad
+        ctx.need_w = any(p.requires_grad for p in params)
+        N, H, W = logits.N, logits.H, logits.W
+        return logits.t[..., 0].reshape(N, 1, H, W).float()
+
+    @staticmethod
+    def backward(ctx, g):
+        core, dctx = ctx.core, ctx.dctx
+        N, _, H, W = g.shape
+        gl = ops.new_act(N, H, W, 8, core.dt, g.device, zero=True)
+        gl.t[..., 0] = g.reshape(N, H, W).to(gl.t.dtype)
+        names = nets.p2p_param_names()
+        grads = {k: torch.empty_like(core.params[k]) for k in names} if ctx.need_w else None
+        ga = core.backward(dctx, gl, grads, need_input_grad=ctx.need_a)
+        ctx.dctx = None
+        return (None, ga, None) + (tuple(grads[k] for k in names) if grads else (None,) * len(names))
+
+
+class Pix2PixDiscriminator(nn.Module):
+    """The plain pix2pix PatchGAN of TFC-STN/TFCGAN_STN21_Eur_DarkVisible.py:370-423 (its Discriminator1 / Discriminator2, and the same block in the
+    archived STN scripts, cyclegan_og and ThermalGAN): four blocks Conv2d(k4, stride 2, p1, bias) -> [InstanceNorm2d, not the first] ->
+    LeakyReLU(0.2), then ZeroPad2d((1, 0, 1, 0)) + Conv2d(512, 1, 4, padding=1, bias=False). No spectral norm, no BlurPool.
+    forward(img_A, img_B) -> logits [N, 1, H/16, W/16] fp32 (H, W multiples of 16); state_dict keys model.{0,2,5,8}.{weight,bias}, model.12.weight.
+    Gradients: all five weights, the bias of block 1, and img_A (the generators train through it). The biases of blocks 2-4 sit in front of an
+    InstanceNorm: their gradient is mathematically zero, torch returns rounding noise there, this module returns exact zeros."""
+
+    def __init__(self, img_shape):
+        super().__init__()
+        self.channels, self.h, self.w = (int(v) for v in img_shape)
+        # the table of nets.Pix2PixCore places every module at the index the state_dict keys name: a convolution per entry, its InstanceNorm where
+        # the entry has one, LeakyReLU behind both, and the padded head at P2P_HEAD
+        mods, cin = {}, 2 * self.channels
+        for idx, cout, norm in nets.P2P_BLOCKS:
+            mods[idx] = nn.Conv2d(cin, cout, kernel_size=4, stride=2, padding=1, bias=True)
+            if norm:
+                mods[idx + 1] = nn.InstanceNorm2d(cout)
+            mods[idx + 1 + int(norm)] = nn.LeakyReLU(0.2, inplace=True)
+            cin = cout
+        mods[nets.P2P_HEAD - 1] = nn.ZeroPad2d((1, 0, 1, 0))
+        mods[nets.P2P_HEAD] = nn.Conv2d(cin, 1, kernel_size=4, padding=1, bias=False)
+        assert sorted(mods) == list(range(nets.P2P_HEAD + 1))
+        self.model = nn.Sequential(*(mods[i] for i in range(nets.P2P_HEAD + 1)))
+        self.compute_dtype = None
+        self._core = None
+        self._core_key = None
+        self._weights_gen = 0                # bumped by the step engines after each raw-pointer Adam update
+
+    def named_core_params(self):
+        sd = dict(self.named_parameters())
+        return {k: sd[k] for k in nets.p2p_param_names()}
+
+    def named_core_buffers(self):
+        return {}
+
+    def _core_for(self, device):
+        dt = ops.dt_of(self.compute_dtype or get_compute_dtype())
+        params = self.named_core_params()
+        key = (dt, str(device), self._weights_gen) + tuple((p.data_ptr(), p._version) for p in params.values())
+        if self._core is None or self._core.dt != dt:
+            self._core = nets.Pix2PixCore(dt, self.channels)
+        if key != self._core_key:
+            for k, p in params.items():
+                if p.dtype != torch.float32 or not p.is_cuda:
+                    raise ops._lib.TfcError(f"Pix2PixDiscriminator parameter {k} must be an fp32 CUDA tensor (got {p.dtype}, {p.device})")
+            self._core.set_params({k: p.detach() for k, p in params.items()})
+            self._core.repack()
+            self._core_key = key
+        return self._core
+
+    def forward(self, img_A, img_B):
+        _refuse_replica(self)
+        params = self.named_core_params()
+        return _Pix2PixFn.apply(self, img_A, img_B, *params.values())
+
+
 # The reference script names the class Discriminator1; older scripts of the same repo (TFC-STN/archive/*) call the identical
 # class Discriminator -- north_star uses that name.
 Discriminator = Discriminator1

@@ -14,7 +14,7 @@ import os
 import torch
 
 from . import ops
-from .ops import (DT_BF16, OP_CONV, OP_CONVT, OP_PADCONV, OP_UPCONV, View, new_act)
+from .ops import (DT_BF16, OP_CONV, OP_CONV2, OP_CONVT, OP_PADCONV, OP_UPCONV, View, new_act)
 
 # Weight gradients on a second HIP stream. The weight gradient of layer i needs only the gradient of its output, which the main chain (input gradient ->
 # activation backward -> next layer) has finished with, so it runs beside that chain and fills the tails of its persistent launches (same-box A/B:
@@ -142,6 +142,26 @@ def d_backward_order():
     out = d_aux_names() + ["model.13.weight"]
     for i, _, _ in reversed(D_BLOCKS):
         out += [f"model.{i}.parametrizations.weight.original", f"model.{i}.bias"]
+    return out
+
+
+# the pix2pix PatchGAN of the DarkVisible script (TFC-STN/TFCGAN_STN21_Eur_DarkVisible.py:370-423): (index in nn.Sequential, Cout, InstanceNorm);
+# the first block reads 2 * channels inputs, the head is model.12
+P2P_BLOCKS = [(0, 64, False), (2, 128, True), (5, 256, True), (8, 512, True)]
+P2P_HEAD = 12
+
+
+def p2p_param_names():
+    out = []
+    for i, _, _ in P2P_BLOCKS:
+        out += [f"model.{i}.weight", f"model.{i}.bias"]
+    return out + [f"model.{P2P_HEAD}.weight"]
+
+
+def p2p_backward_order():
+    out = [f"model.{P2P_HEAD}.weight"]
+    for i, _, _ in reversed(P2P_BLOCKS):
+        out += [f"model.{i}.weight", f"model.{i}.bias"]
     return out
 
 
@@ -645,6 +665,145 @@ class DiscriminatorCore:
             if bi > 0 or need_input_grad:
                 g_in = new_act(N, xin.H, xin.W, xin.pitch, dt, dev)
                 ops.conv_dgrad(dt, OP_CONV, d_raw, N, xin.H, xin.W, cin, cout, self.head_packed[f"d{i}"], g_in, oscale=sigma2[1:])
+                g_cur = g_in
+        self._ws = wsh[0]
+        if need_input_grad:
+            return ops.unpack_nchw(dt, g_cur, self.channels, c0=0)
+        return None
+
+
+class Pix2PixCore:
+    """The plain pix2pix PatchGAN (no spectral norm, no BlurPool): four blocks Conv2d(k4, s2, p1, bias) -> [InstanceNorm2d] -> LeakyReLU(0.2), then
+    ZeroPad2d((1, 0, 1, 0)) + Conv2d(512, 1, 4, padding=1, no bias). Block 1 is one TFC_OP_CONV2 launch with bias and LeakyReLU in its epilogue; blocks
+    2-4 are TFC_OP_CONV2 with bias and the InstanceNorm statistics in the epilogue, then the fused normalise + activate pass; the head is the PatchGAN
+    head kernel of DiscriminatorCore.
+
+    A bias in front of InstanceNorm cannot change the output, so its gradient is mathematically zero (torch leaves rounding noise there, ~1e-6 of the
+    weight gradient's size): backward() writes exact zeros for the biases of blocks 2-4."""
+
+    def __init__(self, dt=DT_BF16, channels=3):
+        self.dt = dt
+        self.channels = channels
+        self.params = None
+        self.packed = {}
+        self._plan = None
+
+    def blocks(self):
+        cin = 2 * self.channels
+        for i, cout, norm in P2P_BLOCKS:
+            yield i, cin, cout, norm
+            cin = cout
+
+    def set_params(self, params):
+        """params: dict key -> fp32 tensor: 'model.{0,2,5,8}.weight' / '.bias', 'model.12.weight'"""
+        self.params = params
+        self.packed = {}
+        self._plan = None
+
+    def repack(self):
+        """operand streams of the nine convolution passes, once per weight update (one launch)"""
+        if self._plan is None:
+            jobs, slots = [(OP_PADCONV, 1, self.params[f"model.{P2P_HEAD}.weight"], 512, 1)], ["dhead"]
+            for i, cin, cout, _ in self.blocks():
+                W = self.params[f"model.{i}.weight"]
+                jobs.append((OP_CONV2, 0, W, cin, cout)); slots.append(f"f{i}")
+                jobs.append((OP_CONV2, 1, W, cin, cout)); slots.append(f"d{i}")
+            self._plan = ops.PackPlan(self.dt, jobs)
+            for key, buf in zip(slots, self._plan.streams):
+                self.packed[key] = buf
+        self._plan.run()
+
+    def forward(self, img_a, img_b, save=True):
+        """img_a, img_b: fp32 NCHW [N, channels, H, W], H and W multiples of 16. Returns (logits View [N, H/16, W/16, pitch 8] channel 0, ctx)."""
+        ops.require_gpu(img_a, img_b)
+        dt, dev = self.dt, img_a.device
+        N, _, H, W = img_a.shape
+        if H % 16 or W % 16:
+            raise ops._lib.TfcError(f"Pix2PixDiscriminator: the four stride-2 blocks need H and W in multiples of 16 (got {H} x {W})")
+        if not self.packed:
+            self.repack()
+        ctx = _Ctx()
+        ctx.N = N
+        ctx.ins, ctx.raw, ctx.stats = [], [], []
+        cur = ops.pack_nhwc8(dt, img_a, img_b)
+        for i, cin, cout, norm in self.blocks():
+            h, w = cur.H // 2, cur.W // 2
+            bias = self.params[f"model.{i}.bias"]
+            if norm:
+                raw = new_act(N, h, w, cout, dt, dev)
+                st = torch.zeros((N, cout, 2), dtype=torch.float32, device=dev)
+                ops.conv_fwd(dt, OP_CONV2, cur, cin, cout, self.packed[f"f{i}"], raw, bias=bias, stats=st)
+                out = new_act(N, h, w, cout, dt, dev)
+                ops.act_fwd(dt, raw, out, stats=st, slope=0.2, pool=0)
+            else:
+                # `raw` holds the ACTIVATED tensor: the backward's slope test (y > 0) is the same on LeakyReLU(z) as on z
+                raw, st = new_act(N, h, w, cout, dt, dev), None
+                ops.conv_fwd(dt, OP_CONV2, cur, cin, cout, self.packed[f"f{i}"], raw, bias=bias, flags=ops.EP_LEAKY)
+                out = raw
+            ctx.ins.append(cur)
+            ctx.raw.append(raw)
+            ctx.stats.append(st)
+            cur = out
+        logits = new_act(N, cur.H, cur.W, 8, dt, dev)             # only channel 0 is ever written or read
+        ops.patchgan_head_fwd(dt, cur, self.params[f"model.{P2P_HEAD}.weight"], View(logits.t, 1, 0))
+        ctx.p4 = cur
+        return View(logits.t, 1, 0), (ctx if save else None)
+
+    def backward(self, ctx, g_logits, grads=None, need_input_grad=True, accumulate=False, hook=None):
+        try:
+            return self._backward(ctx, g_logits, grads, need_input_grad, accumulate, hook)
+        finally:
+            _join_side(g_logits.t.device)                         # the weight gradients may have run on the side stream
+
+    def _backward(self, ctx, g_logits, grads, need_input_grad, accumulate, hook):
+        """g_logits: View [N, h, w, 8] (channel 0 = gradient, channels 1..7 zero). grads: dict key -> fp32 tensor, or None (no parameter gradients: the
+        generator step). Returns the fp32 NCHW gradient of img_a, or None."""
+        dt, N = self.dt, ctx.N
+        dev = g_logits.t.device
+        wsh = [getattr(self, "_ws", None)]                        # persistent wgrad scratch (zeroed once, re-zeroed by the kernels)
+        gl = View(g_logits.t, 8, 0)
+        p4 = ctx.p4
+        hk = f"model.{P2P_HEAD}.weight"
+        if grads is not None:
+            def _head_wgrad():
+                wsh[0] = ops.conv_wgrad(dt, OP_PADCONV, p4, gl, 512, 1, grads[hk], accumulate, wsh[0])
+                if hook:
+                    hook(hk)
+            _on_side(dev, _head_wgrad)
+        g_cur = new_act(N, p4.H, p4.W, 512, dt, dev)
+        ops.conv_dgrad(dt, OP_PADCONV, gl, N, p4.H, p4.W, 512, 1, self.packed["dhead"], g_cur)
+        blocks = list(self.blocks())
+        for bi in range(len(blocks) - 1, -1, -1):
+            i, cin, cout, norm = blocks[bi]
+            xin, raw, st = ctx.ins[bi], ctx.raw[bi], ctx.stats[bi]
+            Ho, Wo = raw.H, raw.W
+            d_raw = new_act(N, Ho, Wo, cout, dt, dev)
+            gb_img = None
+            if norm:
+                rst = torch.zeros((N, cout, 2), dtype=torch.float32, device=dev)
+                ops.act_bwd(dt, 1, g_cur, raw, N, Ho, Wo, cout, None, stats=st, slope=0.2, pool=0, rstats=rst)
+                ops.act_bwd(dt, 2, g_cur, raw, N, Ho, Wo, cout, d_raw, stats=st, slope=0.2, pool=0, rstats=rst)
+            else:
+                gb_img = torch.zeros((N, cout), dtype=torch.float32, device=dev) if grads is not None else None
+                ops.act_bwd(dt, 0, g_cur, raw, N, Ho, Wo, cout, d_raw, stats=None, slope=0.2, pool=0, rstats=gb_img)   # + per-image bias gradient
+            ddbg = getattr(self, "debug", None)                   # tests: the stored gradients of every block
+            if ddbg is not None:
+                ddbg[f"b{bi}.g_out"], ddbg[f"b{bi}.d_raw"] = g_cur, d_raw
+            if grads is not None:
+                def _block_wgrad(i=i, cin=cin, cout=cout, xin=xin, d_raw=d_raw, gb_img=gb_img):
+                    gbias = grads[f"model.{i}.bias"]
+                    if not accumulate:
+                        gbias.zero_()
+                    if gb_img is not None:                        # block 1; behind InstanceNorm the bias gradient is exactly zero
+                        ops.colsum(ops.DT_F32, View(gb_img.view(N, 1, 1, cout), cout), gbias)
+                    wsh[0] = ops.conv_wgrad(dt, OP_CONV2, xin, d_raw, cin, cout, grads[f"model.{i}.weight"], accumulate, wsh[0])
+                    if hook:
+                        hook(f"model.{i}.weight")
+                        hook(f"model.{i}.bias")
+                _on_side(dev, _block_wgrad, d_raw, *([gb_img] if gb_img is not None else []))
+            if bi > 0 or need_input_grad:
+                g_in = new_act(N, xin.H, xin.W, xin.pitch, dt, dev)
+                ops.conv_dgrad(dt, OP_CONV2, d_raw, N, xin.H, xin.W, cin, cout, self.packed[f"d{i}"], g_in)
                 g_cur = g_in
         self._ws = wsh[0]
         if need_input_grad:

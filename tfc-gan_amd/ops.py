@@ -10,7 +10,7 @@ from dataclasses import dataclass
 import torch
 
 from . import _lib, parallel
-from ._lib import (DT_BF16, DT_BF16X3, DT_F32, EP_ACCUM, EP_BIAS, EP_LEAKY, EP_RELU, EP_STATS, EP_TANH_NCHW, OP_CONV, OP_CONV3, OP_CONVT, OP_PADCONV, OP_UPCONV,
+from ._lib import (DT_BF16, DT_BF16X3, DT_F32, EP_ACCUM, EP_BIAS, EP_LEAKY, EP_RELU, EP_STATS, EP_TANH_NCHW, OP_CONV, OP_CONV2, OP_CONV3, OP_CONVT, OP_PADCONV, OP_UPCONV,
                    check)
 
 
@@ -176,7 +176,8 @@ def part_ws(device):
     return ctypes.c_void_p(ws.data_ptr())
 
 
-OUT_HW = {OP_CONV: lambda h: h - 1, OP_PADCONV: lambda h: h, OP_CONVT: lambda h: 2 * h, OP_UPCONV: lambda h: 2 * h, OP_CONV3: lambda h: h}
+OUT_HW = {OP_CONV: lambda h: h - 1, OP_PADCONV: lambda h: h, OP_CONVT: lambda h: 2 * h, OP_UPCONV: lambda h: 2 * h, OP_CONV3: lambda h: h,
+          OP_CONV2: lambda h: h // 2}
 
 
 # ---- convolution family ---------------------------------------------------------------------------------------

@@ -2,6 +2,7 @@
 script that are NOT the shared GeneratorUNet / Discriminator classes, on HIP kernels with the reference's call surface.
 
   affine_warp(src, theta)            STN:220-229  per-sample F.affine_grid(align_corners=True) + F.grid_sample(bicubic, border, align_corners=True)
+                                     (sample_align_corners=False: the grid_sample(align_corners=False) of TFCGAN_STN21_Eur_DarkVisible.py:205-206)
   Warp.forward(theta_delta, src)     STN:204-231  `Net.forward` after the localiser: adds the identity, warps every sample, concatenates
   morph_gradient(x)                  STN:444-449  kornia.morphology.gradient with the 3 x 3 cross (kornia is absent here: restated from its
                                                   published algorithm -- geodesic borders -- PARITY UNPINNED; tested against a torch restatement)
@@ -25,13 +26,17 @@ def _c(t):
 
 class _AffineWarpFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, src, theta):
+    def forward(ctx, src, theta, sample_align_corners=True):
         ops.require_gpu(src, theta)
         s, th = _c(src), _c(theta).reshape(-1, 6)
         N, C, H, W = s.shape
         assert th.shape[0] == N, "one 2x3 matrix per sample"
         out = torch.empty_like(s)
-        check(ops.lib().tfc_affine_warp_fwd(ops.stream_ptr(), ops._p(s), ops._p(th), ops._p(out), N, C, H, W), "tfc_affine_warp_fwd")
+        if sample_align_corners:
+            check(ops.lib().tfc_affine_warp_fwd(ops.stream_ptr(), ops._p(s), ops._p(th), ops._p(out), N, C, H, W), "tfc_affine_warp_fwd")
+        else:
+            check(ops.lib().tfc_affine_warp_mode_fwd(ops.stream_ptr(), ops._p(s), ops._p(th), ops._p(out), N, C, H, W, 0), "tfc_affine_warp_mode_fwd")
+        ctx.sac = bool(sample_align_corners)
         ctx.save_for_backward(s, th)
         ctx.need_src = src.requires_grad
         ctx.theta_shape = theta.shape
@@ -44,23 +49,32 @@ class _AffineWarpFn(torch.autograd.Function):
         g = _c(g)
         dth = torch.empty((N, 6), dtype=torch.float32, device=s.device)
         dsrc = torch.empty_like(s) if ctx.need_src else None
-        check(ops.lib().tfc_affine_warp_bwd(ops.stream_ptr(), ops._p(s), ops._p(th), ops._p(g), ops._p(dth), ops._p(dsrc), N, C, H, W, ops.part_ws(s.device)),
-              "tfc_affine_warp_bwd")
-        return dsrc, dth.reshape(ctx.theta_shape)
+        if ctx.sac:
+            check(ops.lib().tfc_affine_warp_bwd(ops.stream_ptr(), ops._p(s), ops._p(th), ops._p(g), ops._p(dth), ops._p(dsrc), N, C, H, W, ops.part_ws(s.device)),
+                  "tfc_affine_warp_bwd")
+        else:
+            check(ops.lib().tfc_affine_warp_mode_bwd(ops.stream_ptr(), ops._p(s), ops._p(th), ops._p(g), ops._p(dth), ops._p(dsrc), N, C, H, W, 0,
+                                                     ops.part_ws(s.device)), "tfc_affine_warp_mode_bwd")
+        return dsrc, dth.reshape(ctx.theta_shape), None
 
 
-def affine_warp(src, theta):
-    """src [N,C,H,W], theta [N,2,3] -> warped [N,C,H,W] (fp32); differentiable w.r.t. theta and src."""
-    return _AffineWarpFn.apply(src, theta)
+def affine_warp(src, theta, sample_align_corners=True):
+    """src [N,C,H,W], theta [N,2,3] -> warped [N,C,H,W] (fp32); differentiable w.r.t. theta and src. The grid is F.affine_grid(align_corners=True);
+    sample_align_corners is the align_corners of F.grid_sample (True: STN:229; False: the DarkVisible script, which mixes the two conventions)."""
+    return _AffineWarpFn.apply(src, theta, sample_align_corners)
 
 
 class Warp(nn.Module):
     """The tail of the reference's `Net.forward` (STN:204-231): theta = identity + delta, every sample warped with its own matrix."""
 
+    def __init__(self, sample_align_corners=True):
+        super().__init__()
+        self.sample_align_corners = bool(sample_align_corners)
+
     def forward(self, theta_delta, src):
         ident = torch.tensor([1.0, 0.0, 0.0, 0.0, 1.0, 0.0], dtype=torch.float32, device=src.device)
         theta = theta_delta.reshape(src.shape[0], 6).float() + ident
-        return affine_warp(src, theta.reshape(-1, 2, 3))
+        return affine_warp(src, theta.reshape(-1, 2, 3), self.sample_align_corners)
 
 
 class _MorphGradFn(torch.autograd.Function):

@@ -29,7 +29,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import stn
-from .models import Discriminator1, GeneratorUNet, get_compute_dtype, weights_init_normal
+from .models import Discriminator1, GeneratorUNet, Pix2PixDiscriminator, get_compute_dtype, weights_init_normal
 
 
 class _Attention(nn.Module):
@@ -145,9 +145,10 @@ class Net(nn.Module):
     localiser: "torch" (the ViT and fc_loc as torch layers), "hip" (vit.stn_phi: the package's kernels, GPU tensors only) or None (TFC_LOCALISER,
     default "torch"); readable and settable as `net.localiser`. Both run on the same parameters.
     patch_size: the ViT's patch (64 = STN; 16 = the DarkVisible and test scripts, `fc_loc[0]` = Linear(257 * 768, 1024) at 256 x 256; 32 in
-    between), readable as `net.patch_size`. It must divide the image and give at most MAX_TOKENS tokens; state_dict key names do not depend on it."""
+    between), readable as `net.patch_size`. It must divide the image and give at most MAX_TOKENS tokens; state_dict key names do not depend on it.
+    sample_align_corners: the align_corners of the grid_sample (True = STN; False = the DarkVisible script, whose grid is still align_corners=True)."""
 
-    def __init__(self, img_shape=(3, 256, 256), localiser=None, patch_size=64):
+    def __init__(self, img_shape=(3, 256, 256), localiser=None, patch_size=64, sample_align_corners=True):
         super().__init__()
         self.localiser = default_localiser() if localiser is None else localiser
         channels, h, w = img_shape
@@ -158,7 +159,7 @@ class Net(nn.Module):
         self.fc_loc = nn.Sequential(nn.Linear(ntok * 768, 1024), nn.ReLU(True), nn.Linear(1024, 512), nn.ReLU(True), nn.Linear(512, 256), nn.Sigmoid(),
                                     nn.Linear(256, 3 * 2))
         self.fc_loc[2].bias.data.zero_()                          # STN:193
-        self.warp = stn.Warp()
+        self.warp = stn.Warp(sample_align_corners)
 
     @property
     def localiser(self):
@@ -190,9 +191,9 @@ def _bce_rel(a, b, target):
     return F.binary_cross_entropy_with_logits(x, torch.full_like(x, target))
 
 
-def _refuse_bf16x3():
+def _refuse_bf16x3(who="STN21Step"):
     if get_compute_dtype() == "bf16x3":
-        raise ValueError('STN21Step does not support the "bf16x3" compute mode (its ViT localiser kernels run bf16 or fp32 only): '
+        raise ValueError(f'{who} does not support the "bf16x3" compute mode (its ViT localiser kernels run bf16 or fp32 only): '
                          'use torch.bfloat16 or torch.float32')
 
 
@@ -209,13 +210,13 @@ class STN21Step:
     def __init__(self, img_shape=(3, 256, 256), lpips=None, lr=2e-4, b1=0.5, b2=0.999, device="cuda:0", alpha2=0.01, eps=1e-8, bucket_bytes=32 << 20,
                  seed=0, localiser=None, batch_invariant=None, patch_size=64):
         from . import ops, parallel
-        _refuse_bf16x3()
+        _refuse_bf16x3(type(self).__name__)
         self.batch_invariant = batch_invariant                    # None: the global setting (set_batch_invariant / TFC_BATCH_INVARIANT) at each step
         dev = torch.device(device)
         self.dev = dev
         self.G1, self.G2 = GeneratorUNet(img_shape).to(dev), GeneratorUNet(img_shape).to(dev)
-        self.D1, self.D2 = Discriminator1(img_shape).to(dev), Discriminator1(img_shape).to(dev)
-        self.net = Net(img_shape, localiser=localiser, patch_size=patch_size).to(dev)
+        self.D1, self.D2 = self._make_discriminator(img_shape).to(dev), self._make_discriminator(img_shape).to(dev)
+        self.net = self._make_net(img_shape, localiser, patch_size).to(dev)
         for m in (self.G1, self.G2, self.D1, self.D2, self.net):
             m.apply(weights_init_normal)                          # STN:539-543
         self.lpips, self.alpha2, self._bucket_bytes = lpips, alpha2, bucket_bytes
@@ -225,13 +226,21 @@ class STN21Step:
             object.__setattr__(m, "_drop_seed", (seed * 7919 + parallel.rank() * 1299709 + i * 104729 + 0x5EED) & 0x7FFFFFFF)
         self._flatten()
 
+    # gradient-completion order of loss_G.backward() on the generator side: fake_A2 = G2(warped_B) is the last forward and the first backward, the
+    # localiser follows, then G2's first use finishes its gradients, G1 (the first forward) comes last
+    _G_ORDER = ("net", "G2", "G1")
+
+    def _make_discriminator(self, img_shape):
+        return Discriminator1(img_shape)
+
+    def _make_net(self, img_shape, localiser, patch_size):
+        return Net(img_shape, localiser=localiser, patch_size=patch_size)
+
     def _flatten(self):
         """(re)build the flat buffers from the modules' current parameters (call again after load_state_dict on a module)"""
         from . import parallel
         gnamed, dnamed = {}, {}
-        # gradient-completion order of loss_G.backward(): fake_A2 = G2(warped_B) is the last forward and the first backward, the localiser follows,
-        # then G2's first use finishes its gradients, G1 (the first forward) comes last
-        for pre, m in (("net.", self.net), ("G2.", self.G2), ("G1.", self.G1)):
+        for pre, m in ((n + ".", getattr(self, n)) for n in self._G_ORDER):
             items = list(m.named_parameters())
             for k, p in (reversed(items) if pre == "net." else items):
                 gnamed[pre + k] = p
@@ -321,4 +330,88 @@ class STN21Step:
             out = {k: packed[i] * (world if k == "perc_loss" else 1.0) for i, k in enumerate(keys)}
             out["loss_G"] = out["loss_GAN"] + self.alpha2 * out["recon_loss"] + out["perc_loss"] + out["morph_loss"]
         out.update({"fake_B": fake_B.detach(), "fake_A2": fake_A2.detach(), "warped_B": warped_B.detach()})
+        return out
+
+
+class DarkVisibleStep(STN21Step):
+    """The batch-loop body of TFC-STN/TFCGAN_STN21_Eur_DarkVisible.py:677-735 ("DV") on the engine of STN21Step: the same two flat fp32 buffers,
+    `tfc_adam_step`, bucketed reducers from post-accumulate hooks, sharding over ranks. What differs from STN21Step:
+
+        fake_B = G1(real_A); warped_B = Net(real_A, fake_B, src=real_B); fake_A = G2(warped_B)      (no G2(real_B) pass; G1 also trains through the
+                                                                                                      localiser's input)
+        recon  = L1(warped_B, fake_B), unweighted, gradient to both sides;  no morphological triplet
+        FFT    = L1(amp) + L1(phase) of the whole-image spectra of (fake_A, real_A): through PIL and numpy in the reference, so a VALUE of loss_G only --
+                 computed on detached images (losses.global_fft_loss) and added to nothing that is differentiated
+        loss_G = GAN + recon + perc + FFT;  loss_D_k = loss_real + loss_fake;  loss_D = 0.5 (D1 + D2)
+        both discriminators are the plain pix2pix PatchGAN (Pix2PixDiscriminator); Net(patch_size=16, sample_align_corners=False); lr 1e-4
+
+    The generator side of the flat buffers is ordered by gradient completion for this wiring: G2, the localiser, G1. LPIPS is a batch sum scaled by
+    the world size, as in STN21Step. fft=False skips the FFT term (loss_FFT = 0): it changes no gradient. "bf16x3" is refused, as there."""
+
+    _G_ORDER = ("G2", "net", "G1")
+
+    def __init__(self, img_shape=(3, 256, 256), lpips=None, lr=1e-4, b1=0.5, b2=0.999, device="cuda:0", eps=1e-8, bucket_bytes=32 << 20, seed=0,
+                 localiser=None, batch_invariant=None, patch_size=16, sample_align_corners=False, fft=True):
+        self._sample_align_corners = bool(sample_align_corners)
+        self.fft = bool(fft)
+        super().__init__(img_shape, lpips=lpips, lr=lr, b1=b1, b2=b2, device=device, eps=eps, bucket_bytes=bucket_bytes, seed=seed,
+                         localiser=localiser, batch_invariant=batch_invariant, patch_size=patch_size)
+
+    def _make_discriminator(self, img_shape):
+        return Pix2PixDiscriminator(img_shape)
+
+    def _make_net(self, img_shape, localiser, patch_size):
+        return Net(img_shape, localiser=localiser, patch_size=patch_size, sample_align_corners=self._sample_align_corners)
+
+    def _step(self, real_A, real_B):
+        _refuse_bf16x3(type(self).__name__)
+        from . import losses, ops, parallel
+        valid, fake_t = 0.9, 0.0                                  # DV:670-672
+        self.step_no += 1
+        world = parallel.world_size()
+        # ---------------- generators + STN (DV:677-718) ----------------
+        self.gflat.grad.zero_()
+        self._d_requires_grad(False)
+        fake_B = self.G1(real_A)
+        warped_B = self.net(real_A, fake_B, real_B)
+        fake_A = self.G2(warped_B)
+        recon = F.l1_loss(warped_B, fake_B)
+        if self.lpips is not None:
+            perc = (self.lpips(fake_A, real_A) + self.lpips(fake_B, real_B)).mean()       # a batch SUM inside lpips_pytorch (DV:694-696)
+        else:
+            perc = fake_B.new_zeros(())
+        if self.fft:                                              # no gradient: the reference goes tensor -> PIL -> numpy (DV:551-569, :700-704)
+            _, l_amp, l_pha = losses.global_fft_loss(fake_A.detach(), real_A.detach())
+            loss_fft = (l_amp + l_pha).detach()
+        else:
+            loss_fft = fake_B.new_zeros(())
+        gan1 = _bce_rel(self.D1(fake_B, real_A), self.D1(real_B, real_A).detach(), valid)
+        gan2 = _bce_rel(self.D2(fake_A, real_B), self.D2(real_A, real_B).detach(), valid)
+        loss_gan = gan1 + gan2
+        loss_G = loss_gan + recon + perc + loss_fft
+        (loss_gan + recon + perc * world).backward()              # hooks issue the bucket all-reduces as gradients become final
+        gscale = self.g_reduce.finish()
+        ops.adam_step(self.gflat.data, self.gflat.grad, self.gm, self.gv, self.lr, self.b1, self.b2, self.eps, self.step_no, gscale)
+        # ---------------- discriminators (DV:725-734) ----------------
+        self._d_requires_grad(True)
+        self.dflat.grad.zero_()
+
+        def disc(D, real, fake_img, cond):
+            pr, pf = D(real, cond), D(fake_img.detach(), cond)
+            return _bce_rel(pr, pf, valid) + _bce_rel(pf, pr, fake_t)
+        loss_D1, loss_D2 = disc(self.D1, real_B, fake_B, real_A), disc(self.D2, real_A, fake_A, real_B)
+        loss_D = 0.5 * (loss_D1 + loss_D2)
+        loss_D.backward()
+        dscale = self.d_reduce.finish()
+        ops.adam_step(self.dflat.data, self.dflat.grad, self.dm, self.dv, self.lr, self.b1, self.b2, self.eps, self.step_no, dscale)
+        self._bump()
+        out = {"loss_G": loss_G.detach(), "loss_GAN": loss_gan.detach(), "recon_loss": recon.detach(), "perc_loss": perc.detach(),
+               "loss_FFT": loss_fft, "loss_D": loss_D.detach(), "loss_D1": loss_D1.detach(), "loss_D2": loss_D2.detach()}
+        if world > 1:                                             # batch means: the mean over ranks is the global-batch value (LPIPS: the sum)
+            keys = list(out)
+            packed = torch.stack([out[k].reshape(()).float() for k in keys])
+            parallel.all_reduce_mean(packed)
+            out = {k: packed[i] * (world if k == "perc_loss" else 1.0) for i, k in enumerate(keys)}
+            out["loss_G"] = out["loss_GAN"] + out["recon_loss"] + out["perc_loss"] + out["loss_FFT"]
+        out.update({"fake_B": fake_B.detach(), "fake_A": fake_A.detach(), "warped_B": warped_B.detach()})
         return out
