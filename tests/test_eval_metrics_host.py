@@ -1,14 +1,12 @@
 """Evaluation metrics, host side (no GPU): the numpy / scipy restatements the GPU tests are held against (tests/eval_metrics_ref.py) agree with the
 closed forms of the metrics, and the C ABI of the metric kernels is declared on both sides."""
 import os
-import re
 
 import numpy as np
 
 from tests import eval_metrics_ref as R
 from tfc_gan_amd import _lib
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 METRIC_SYMBOLS = {"tfc_pair_moments_ws_bytes", "tfc_pair_moments_u8", "tfc_ssim_ws_bytes", "tfc_ssim_u8", "tfc_hist_u8_color", "tfc_hist_u8_joint",
                   "tfc_mi_bin_lut", "tfc_bhattacharyya", "tfc_mutual_information"}
 
@@ -82,10 +80,8 @@ def test_bhattacharyya_histogram_is_the_shift_by_five():
 def test_metric_prototypes_are_declared_on_both_sides():
     assert METRIC_SYMBOLS <= set(_lib.PROTOTYPES)
     assert "metrics.hip" in _lib.SOURCES and os.path.exists(os.path.join(_lib.CSRC, "metrics.hip"))
-    header = open(os.path.join(ROOT, "include", "tfc_gan.h")).read()
-    block = header.split("/* ---- evaluation metrics ---- */")[1]
-    declared = set(re.findall(r"\b(tfc_[a-z0-9_]+)\s*\(", re.sub(r"/\*.*?\*/", "", block, flags=re.S)))
-    assert METRIC_SYMBOLS <= declared
+    block = open(_lib.PUBLIC_HEADER).read().split("/* ---- evaluation metrics ---- */")[1]
+    assert METRIC_SYMBOLS <= set(_lib.parse_header(block.split("#ifdef __cplusplus")[0])[0])     # declared in the header's metrics section
     lib = _lib.load()
     for name in METRIC_SYMBOLS:
         assert hasattr(lib, name), name

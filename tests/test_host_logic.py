@@ -4,6 +4,8 @@ convolutions for every op / pass of the path -- conv, pad+conv, transposed conv,
 import ctypes
 import os
 import re
+import shutil
+import subprocess
 
 import numpy as np
 import pytest
@@ -16,16 +18,79 @@ from tfc_gan_amd import _lib
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
+def exported_functions(so):
+    """the unmangled tfc_* functions in the dynamic symbol table of `so`, listed by the toolchain's nm (llvm-nm beside hipcc where the ROCm
+    release ships one, else the nm on PATH)"""
+    hipcc = shutil.which(_lib.hipcc())
+    assert hipcc, "no hipcc"
+    bindir = os.path.dirname(os.path.realpath(hipcc))
+    cands = [os.path.join(bindir, *rel, "llvm-nm") for rel in ((), ("..", "llvm", "bin"), ("..", "lib", "llvm", "bin"))]
+    nm = next((c for c in cands if os.path.exists(c)), None) or shutil.which("nm")
+    assert nm, "no nm to list the library's dynamic symbols with (looked for llvm-nm beside hipcc and for nm on PATH)"
+    out = subprocess.run([nm, "-D", "--defined-only", so], check=True, capture_output=True, text=True).stdout
+    rows = [line.split() for line in out.splitlines()]
+    return {r[-1] for r in rows if len(r) >= 2 and r[-2] in "TW" and re.fullmatch(r"tfc_\w+", r[-1])}
+
+
 def test_library_exports_every_declared_symbol():
-    lib = _lib.load()
-    header = open(os.path.join(ROOT, "include", "tfc_gan.h")).read()
-    header = re.sub(r"/\*.*?\*/", "", header, flags=re.S)
-    declared = set(re.findall(r"\b(tfc_[a-z0-9_]+)\s*\(", header))
+    """the header's declarations are the ctypes table by construction (_lib.parse_header); what can still drift is the built library: it exports
+    every declared function and no tfc_* function the header does not declare"""
+    declared = set(_lib.PROTOTYPES)
     assert len(declared) >= 28
-    assert declared == set(_lib.PROTOTYPES), declared ^ set(_lib.PROTOTYPES)
+    exported = exported_functions(_lib.build())
+    assert exported == declared, exported ^ declared
+    lib = _lib.load()
     for name in declared:
         assert hasattr(lib, name), name
     assert lib.tfc_abi_version() == 3
+
+
+def parse(text):
+    return _lib.parse_header(text)[0]
+
+
+def test_header_parser_on_literal_declarations():
+    vp, i, f = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
+    assert parse("int tfc_a(void* stream, /* a comment, with a comma */ int n, // and a line comment\n float s);") == {"tfc_a": (i, [vp, i, f])}
+    assert parse("int tfc_b(void* stream,\n          const float* x,\n          long long n\n         );") == {"tfc_b": (i, [vp, vp, ctypes.c_longlong])}
+    assert parse("int tfc_c(const float* const* w_host, float* const* u_host);") == {"tfc_c": (i, [vp, vp])}
+    assert parse("unsigned tfc_d(void);\nuint8_t* tfc_e(unsigned n);\nsize_t tfc_f(uint32_t seed, double x);\nconst char* tfc_g(void);\nvoid tfc_h(int);") == {
+        "tfc_d": (ctypes.c_uint, []), "tfc_e": (vp, [ctypes.c_uint]), "tfc_f": (ctypes.c_size_t, [ctypes.c_uint32, ctypes.c_double]),
+        "tfc_g": (ctypes.c_char_p, []), "tfc_h": (None, [i])}
+    assert parse("int tfc_i(int meta[3], const float rows[], uint8_t* keep);") == {"tfc_i": (i, [vp, vp, vp])}
+    protos, consts, structs = _lib.parse_header(
+        "#ifndef TFC_X_H\n#define TFC_X_H\n#define TFC_ONE 1 /* a comment that\n runs on */\n#define TFC_MASK 0x10\nextern \"C\" {\n"
+        "typedef struct TfcS { int M, N; const float* a; long long ld; } TfcS;\nint tfc_j(const TfcS* s_host, struct TfcS* t);\n}\n#endif\n")
+    assert consts == {"ONE": 1, "MASK": 16} and protos == {"tfc_j": (i, [vp, vp])}
+    assert structs == {"TfcS": [("M", i), ("N", i), ("a", vp), ("ld", ctypes.c_longlong)]}
+
+
+@pytest.mark.parametrize("text,names", [
+    ("int tfc_k(void* stream, half_t x);", "tfc_k, argument 2"),                      # an unknown type
+    ("int tfc_l(const TfcNowhere* p);", "tfc_l, argument 1"),                         # a pointer to an undeclared struct
+    ("wide_t tfc_m(int n);", "tfc_m, return type"),
+    ("int helper(int n);", "helper"),                                                 # not a tfc_* function
+    ("int tfc_n(int (*cb)(int));", "tfc_n"),                                          # a declaration it cannot split
+    ("typedef struct TfcT { int a[3]; } TfcT;", "TfcT"),
+    ("typedef struct TfcU { short a; } TfcU;", "TfcU"),
+    ("#define TFC_SIZE (8 << 20)\n", "TFC_SIZE"),
+])
+def test_header_parser_raises_on_what_it_cannot_classify(text, names):
+    with pytest.raises(ValueError, match=re.escape(names)):
+        _lib.parse_header(text)
+
+
+def test_python_constants_and_struct_come_from_the_header():
+    from tfc_gan_amd import ops
+    assert (_lib.DT_BF16, _lib.DT_F32, _lib.DT_BF16X3) == (0, 1, 2) and _lib.OP_CONV2 == 5 and _lib.EP_RELU == 32
+    for name, value in _lib.CONSTANTS.items():
+        if name.startswith(("DT_", "OP_", "EP_")):
+            assert getattr(_lib, name) == value and getattr(ops, name) == value
+        if name.startswith("VIT_"):
+            assert getattr(ops, name) == value
+    assert ops.VIT_DACT_SIGMOID == 6 and ops.VIT_B_UNFOLD == 2
+    assert ops.VitGemm._fields_ == _lib.STRUCTS["TfcVitGemm"] and len(ops.VitGemm._fields_) == 28
+    assert ctypes.sizeof(ops.VitGemm) == 176            # sizeof(TfcVitGemm) on x86-64
 
 
 def test_build_refuses_spilling_hand_scheduled_kernels():

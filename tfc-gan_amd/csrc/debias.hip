@@ -12,13 +12,7 @@
 // other class counts (10..16 rows in all: more than 64 KB of staging) take the same kernels with 4-byte weight accesses.
 #include "common.h"
 
-#define TFC_AUX_MAXC 16
 #define TFC_AUX_CHUNK 256                                        // pixels per workgroup of the head kernels = threads
-struct TfcAuxRows { const float* w[TFC_AUX_MAXC]; const float* b[TFC_AUX_MAXC]; };
-struct TfcAuxGradRows { float* w[TFC_AUX_MAXC]; float* b[TFC_AUX_MAXC]; };
-struct TfcCeHeads { int nc[3]; int off[3]; float w[3]; float scale; };
-
-hipError_t tfc_launch_part_reduce(const float* part, float* out, int G, int nparts, int L, hipStream_t st);
 
 template <typename T> __device__ __forceinline__ void load_pixel8(const T* p, float* v);
 template <> __device__ __forceinline__ void load_pixel8<bf16_t>(const bf16_t* p, float* v) { unpack16<bf16_t>(*reinterpret_cast<const uint4*>(p), v); }

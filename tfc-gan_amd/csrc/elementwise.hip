@@ -859,14 +859,6 @@ tfc_tanh_bwd_pack_kernel(const float* __restrict__ g, const float* __restrict__ 
 //   u <- normalize(W v);  v <- normalize(W^T u);  sigma = u . (W v)        W: [R][K] fp32 row-major
 // ---------------------------------------------------------------------------------------------------
 // ---- batched form: all spectral-normed layers of one Discriminator1 forward in 3 launches (blockIdx.y = layer) ----
-struct SnBatch {
-  const float* W[4];
-  float* u[4]; float* v[4]; float* sigma2[4];
-  float* us[4]; float* vs[4];                                    // per-call snapshots of u, v for the backward (nullable)
-  float* s[4]; float* t[4];                                      // scratch
-  int R[4], K[4];
-  int n;
-};
 
 __device__ __forceinline__ float block_sum_256(float a, float* red4) {
   a = wave_sum(a);

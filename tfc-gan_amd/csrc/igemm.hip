@@ -2484,16 +2484,6 @@ tfc_pack_w_kernel(const TfcGather d, const float* __restrict__ w, const float* _
   wp[idx] = pack16<T>(v);
 }
 
-// One launch packs every operand stream of a network: a device-resident plan (built once by the host for fixed geometry and
-// fixed buffers) lists the jobs; a workgroup finds its job from the prefix sums of the unit counts.
-struct TfcPackJob {
-  TfcGather d;
-  const float* w;
-  uint4* wp;
-  long long sn, sc;
-  int NB32, Nreal, Creal, units;                                  // units = 16-byte units of this job
-  int first_block, threads;                                       // first 256-thread workgroup of this job in the planned grid; its thread count
-};
 // One thread per (output channel n, 16-byte channel unit o): it reads the 16 filter taps of its UE (n, c) pairs ONCE -- 64 contiguous
 // bytes each, both torch layouts keep the taps innermost -- and emits one packed unit per gather tap (collapsed taps: the sum of
 // their filter taps). n runs fastest over the threads, so a wave's stores are 512-byte runs of the stream (lane field = n & 31).
@@ -3075,7 +3065,6 @@ static int tfc_num_cus() {
 // answer is then a function of the layer's per-image geometry alone, and at the reference batch it is the default answer.
 // ---------------------------------------------------------------------------------------------------
 thread_local int g_tfc_batch_invariant = 0;
-bool tfc_conv_c8_eligible(const TfcGather& d, int flags);
 static inline int plan_phases(const TfcGather& d) { return d.ph_n > 1 ? d.ph_n : 1; }
 static const int kFormNT[5] = {2, 1, 1, 1, 2}, kFormWM[5] = {2, 2, 4, 1, 1}, kFormWN[5] = {2, 2, 1, 4, 4};   // <2,2,2,2> <2,1,2,2> <1,1,4,1> <4,1,1,4> <4,2,1,4>
 // InstanceNorm partial slots per image: one per (tile, phase) of the persistent kernel, one per (tile, phase, M-wave) of the one-tile-per-workgroup kernel

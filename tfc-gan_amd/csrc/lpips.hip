@@ -237,7 +237,6 @@ hipError_t tfc_launch_relu_bwd(int dt, const void* dy, const void* y, const void
                  hipLaunchKernelGGL(tfc_relu_bwd_kernel<float>, dim3((unsigned)nb), dim3(256), 0, st, (const float*)dy, (const float*)y, (const float*)extra, (float*)dz, units));
   return hipGetLastError();
 }
-hipError_t tfc_launch_part_reduce(const float* part, float* out, int G, int nparts, int L, hipStream_t st);
 // workgroups per image and their pixel range for the head: functions of HW and C (and the element type) ONLY, never of N, so that an image's sum
 // has the same bits in every batch. Up to 64 workgroups per image (batch 32 fills 8 per CU), each a whole number of workgroup iterations.
 hipError_t tfc_launch_lpips_head(int dt, const void* fx, const void* fy, const float* w, float* out, void* dfx, float* part_ws, int N, long long HW, int C,

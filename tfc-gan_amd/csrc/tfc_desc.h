@@ -14,7 +14,9 @@
 // every tap, so the im2col matrix is never materialised and each source byte crosses HBM/L2 once per
 // chunk instead of once per tap.
 #pragma once
+#include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "../../include/tfc_gan.h"   // TFC_DT_*, TFC_OP_*, TFC_EP_* and TfcVitGemm: the public values are written down there and nowhere else
 
 #define TFC_TILE_H 8
 #define TFC_TILE_W 16
@@ -26,18 +28,6 @@
 #define TFC_WPAD 16           // slack k-substeps at the end of a packed weight stream (prefetch distance headroom)
 #define TFC_PART_WS_FLOATS (8 << 20)   // floats of the per-stream partial-sum scratch every reducing entry point takes (32 MiB; include/tfc_gan.h)
 #define TFC_SN_BWD_PARTS 128           // workgroup partials (doubles) of the spectral-norm backward's dot product
-
-#define TFC_DT_BF16 0
-#define TFC_DT_F32 1
-#define TFC_DT_BF16X3 2       // fp32 storage; the gather GEMMs split every operand into bf16 hi + lo and sum hi*hi + hi*lo + lo*hi
-
-// epilogue flags
-#define TFC_EP_BIAS 1
-#define TFC_EP_STATS 2        // accumulate per-(img,channel) sum / sum of squares (InstanceNorm statistics)
-#define TFC_EP_ACCUM 4        // out += result (skip-connection gradient accumulation)
-#define TFC_EP_TANH_NCHW 8    // final layer: tanh, store fp32 NCHW
-#define TFC_EP_LEAKY 16       // LeakyReLU(0.2) on the result (discriminator blocks: no normalisation between conv and activation)
-#define TFC_EP_RELU 32        // ReLU on the result (the VGG feature stack of the LPIPS term)
 
 struct TfcPlane {
   int dy0, dx0;               // halo origin relative to the tile origin, in plane coordinates
@@ -132,4 +122,154 @@ struct TfcWinGrid { long long bs, cs; int rs, C; int row0, row_step, col_step, w
 // coef[out][ksize] = taps in 22-bit fixed point.
 struct TfcResizeAxis { int ksize; int bounds_off; int coef_off; int in_size; };
 struct TfcResizePlan { TfcResizeAxis hA, hB, v; int out; int xsplit; int H; int W; };
+
+// ---- what crosses translation units: every launcher, planner and helper that one .hip defines and another calls, and every struct that is
+// passed by value between them, is declared HERE and nowhere else; api.hip and every defining file include this header, so a definition that
+// drifts from its declaration is an overload nobody defines, and the link (-z defs) refuses it.
+// igemm.hip
+// One launch packs every operand stream of a network: a device-resident plan (built once by the host for fixed geometry and
+// fixed buffers) lists the jobs; a workgroup finds its job from the prefix sums of the unit counts.
+struct TfcPackJob {
+  TfcGather d;
+  const float* w;
+  uint4* wp;
+  long long sn, sc;
+  int NB32, Nreal, Creal, units;                                  // units = 16-byte units of this job
+  int first_block, threads;                                       // first 256-thread workgroup of this job in the planned grid; its thread count
+};
+int tfc_total_substeps(const TfcGather& d, int es);
+int tfc_nb32(int nout);
+int tfc_nb32_padded(int nout);
+size_t tfc_packed_bytes(const TfcGather& d, int es);
+hipError_t tfc_launch_pack(int dt, const TfcGather& d, const float* w, const float* scale, void* wp, int Nreal, int Creal, long long sn, long long sc, hipStream_t st);
+hipError_t tfc_launch_igemm(int dt, const TfcGather& d, const void* in, const void* wp, void* out, const float* bias, float* stats, float* part_ws, float* out_nchw, const float* oscale, int flags, hipStream_t st);
+hipError_t tfc_launch_first_block_fwd(const void* in, int N, int IH, int IW, const void* wp, const float* bias, const float* oscale, float slope, int gform,
+                                      void* out, int o_pitch, unsigned char* sign_mask, hipStream_t st);
+bool tfc_conv_c8_eligible(const TfcGather& d, int flags);
+hipError_t tfc_launch_conv_c8(const TfcGather& d, const void* in, const void* wp, void* out, const float* bias, const float* oscale, int flags,
+                              unsigned char* sign_mask, hipStream_t st);
+hipError_t tfc_launch_wgrad(int dt, const TfcGather& d, const void* dO, const void* in, float* dwacc, void* slab, int Nn_pad, int Nn_real, int Cw_real, hipStream_t st, TfcWgradFin* fin);
+hipError_t tfc_launch_dgrad_rows4(const void* dy, int dy_pitch, int N, int H, int W, const float* w, int Cin, const float* oscale, int NC, float* dx, hipStream_t st);
+hipError_t tfc_launch_upconv_head(const void* x, int x_pitch, int N, int H, int W, const float* w, const float* bias, int Cout, float* out, hipStream_t st);
+bool tfc_launch_wgrad_phases_fused(int up, const void* x, int N, int IH, int IW, int x_pitch, int Cin_pad, const void* dy, int dy_pitch, int Cout,
+                                   int Cin, float* dwacc, void* slab, hipStream_t st, hipError_t* err, TfcWgradFin* fin);
+hipError_t tfc_launch_wgrad_finish(float* acc, float* grad, int Nn, int Cw, long long sn, long long sc, int accumulate, hipStream_t st);
+hipError_t tfc_launch_pack_planned(int dt, const void* plan_dev, int njobs, int nblocks, hipStream_t st);
+hipError_t tfc_launch_dgrad_head(const void* dy, int dy_pitch, int N, int H, int W, const float* w, int Cout, void* dx, int dx_pitch, hipStream_t st);
+hipError_t tfc_launch_first_block_bwd(const TfcGather& d, const void* yact, int y_pitch, const void* dyp, int dyp_pitch, int Ho, int Wo, const void* in,
+                                      void* slab, float* dwacc, float* rstats, float* part_ws, float slope, int Nn_real, int Cw_real,
+                                      const unsigned char* sign_mask, TfcWgradFin* fin, hipStream_t st);
+// elementwise.hip
+struct SnBatch {
+  const float* W[4];
+  float* u[4]; float* v[4]; float* sigma2[4];
+  float* us[4]; float* vs[4];                                    // per-call snapshots of u, v for the backward (nullable)
+  float* s[4]; float* t[4];                                      // scratch
+  int R[4], K[4];
+  int n;
+};
+hipError_t tfc_launch_sn_step_batched(const SnBatch& b, int power_iter, float eps, hipStream_t st);
+hipError_t tfc_launch_act_fwd(int dt, const ActParams& p, const void* x, const float* stats, void* out, float* stats_out, float* part_ws, hipStream_t st);
+hipError_t tfc_launch_act_bwd(int dt, int mode, const ActParams& p, const void* dout, const void* x, const float* stats, float* rstats, void* dx, int use_x, int dx_pitch, float* part_ws, hipStream_t st);
+hipError_t tfc_launch_act_pool2_bwd_signs(const ActParams& p, const void* dout, const unsigned char* sign_mask, float* rstats, void* dx, int dx_pitch, float* part_ws, hipStream_t st);
+hipError_t tfc_launch_colsum(int dt, const void* x, long long rows, int pitch, int C, float* out, float* part_ws, hipStream_t st);
+hipError_t tfc_launch_pack_nhwc8(int dt, const float* a, int Ca, const float* b, int Cb, void* out, int N, int HW, hipStream_t st);
+hipError_t tfc_launch_unpack_nchw(int dt, const void* in, int pitch, int c0, int C, float* out, int N, int HW, float alpha, float beta, hipStream_t st);
+hipError_t tfc_launch_tanh_bwd_pack(int dt, const float* g, const float* y, void* out, float* dbias, float* part_ws, int N, int C, int HW, hipStream_t st);
+hipError_t tfc_launch_sn_bwd(const float* G, const float* W, const float* u, const float* v, const float* sigma2, float* dot_ws, float* gout, int R, int K, int accumulate, hipStream_t st);
+hipError_t tfc_launch_bce_rel(int dt, const void* a, const void* b, int n, int stride, float t1, float t2, int mode, float* loss, void* da, void* db, float gscale, hipStream_t st);
+hipError_t tfc_launch_adam(float* p, const float* g, float* m, float* v, long long n, float lr, float b1, float b2, float eps, float bc1, float bc2_sqrt, float gscale, hipStream_t st);
+hipError_t tfc_launch_axpby(float* out, const float* x, const float* y, long long n, float a, float b, hipStream_t st);
+hipError_t tfc_launch_dropout_mask(unsigned char* out, long long n, unsigned seed, unsigned thresh24, hipStream_t st);
+hipError_t tfc_launch_cast(int dt, int to_f32, const void* x, void* y, long long n, hipStream_t st);
+hipError_t tfc_launch_head_fwd(int dt, const void* x, int x_pitch, const float* w, void* y, int y_pitch, int N, int H, int W, int C, hipStream_t st);
+// losses.hip
+hipError_t tfc_launch_patch_triplet(int grid, const float* fake, const float* real, const int* neg_idx, int N, int C, float margin, float eps, float* loss, float* dfake, float gscale, hipStream_t st);
+hipError_t tfc_launch_spectrum(const float* img, const TfcWinGrid& g, int S, int H, bool rect, int nwin, float* amp, float* pha, int shift, void* ws, hipStream_t st);
+size_t tfc_fft_ws_bytes(int S, int H, int nwin);
+hipError_t tfc_launch_l1_sum(const float* a, const float* b, long long n, float scale, float* out, hipStream_t st);
+hipError_t tfc_launch_batch_kl(const float* af, const float* pf, const float* ar, int N, long long M, float scale, float* out, hipStream_t st);
+hipError_t tfc_launch_batch_kl_stats(const float* af, const float* pf, const float* ar, int N, long long M, void* rec, hipStream_t st);
+hipError_t tfc_launch_batch_kl_merge(const void* recs, int world, long long M, void* glob, hipStream_t st);
+hipError_t tfc_launch_batch_kl_terms(const float* af, const float* pf, const float* ar, int N, long long M, const void* glob, float scale, float* out,
+                                     hipStream_t st);
+hipError_t tfc_launch_logmag_mse(const float* a, const float* b, int S, int nwin, float* out, int absolute, hipStream_t st);
+hipError_t tfc_launch_vectorize_temps(const float* x, long long bs, int rs, int N, int H, int W, const float* lut, float* out, hipStream_t st);
+hipError_t tfc_launch_row_triplet(const float* a, const float* p, const float* ng, long long rows, int W, float margin, float eps,
+                                  float* loss, hipStream_t st);
+// probe.hip
+hipError_t tfc_launch_probe(float* out, hipStream_t st);
+// metrics.hip
+int tfc_moments_groups(long long count);
+void tfc_ssim_tiles(int H, int W, int wy, int wx, int* tx, int* ty);
+hipError_t tfc_launch_pair_moments(const uint8_t* a, const uint8_t* b, long long a_stride, long long b_stride, long long count, int N, long long* ws,
+                                   long long* mom, double* psnr, double* ncc, hipStream_t st);
+hipError_t tfc_launch_ssim(const uint8_t* a, long long a_is, int a_rs, const uint8_t* b, long long b_is, int b_rs, int N, int H, int W, int wy, int wx,
+                           double data_range, double* ws, double* out, hipStream_t st);
+hipError_t tfc_launch_hist_color(const uint8_t* img, long long img_stride, long long pix_stride, long long chan_stride, long long npix, int N, unsigned* hist,
+                                 hipStream_t st);
+hipError_t tfc_launch_hist_joint(const uint8_t* a, const uint8_t* b, long long a_stride, long long b_stride, long long count, int N, const uint8_t* lut_a,
+                                 const uint8_t* lut_b, int nb, unsigned* hist, hipStream_t st);
+hipError_t tfc_launch_mi_lut(const long long* mom, int N, int nb, int edge_f32, uint8_t* lut_a, uint8_t* lut_b, hipStream_t st);
+hipError_t tfc_launch_bhattacharyya(const unsigned* h1, const unsigned* h2, int N, int nbins, double* out, hipStream_t st);
+hipError_t tfc_launch_mutual_information(const unsigned* hist, int N, int nb, double* out, hipStream_t st);
+// stn.hip
+hipError_t tfc_launch_affine_warp_fwd(const float* src, const float* theta, float* out, int N, int C, int H, int W, int sac, hipStream_t st);
+hipError_t tfc_launch_affine_warp_bwd(const float* src, const float* theta, const float* gout, float* dtheta, float* dsrc, float* part_ws, int N, int C, int H, int W, int sac, hipStream_t st);
+hipError_t tfc_launch_morph_grad_fwd(const float* x, float* out, unsigned char* arg, long long planes, int H, int W, hipStream_t st);
+hipError_t tfc_launch_morph_grad_bwd(const float* gout, const unsigned char* arg, float* dx, long long planes, int H, int W, hipStream_t st);
+hipError_t tfc_launch_row_triplet_grad(const float* a, const float* p, const float* ng, long long rows, int W, float margin, float eps, float gscale,
+                                       float* loss, float* da, hipStream_t st);
+// vit.hip
+hipError_t tfc_launch_vit_gemm(int dt, const TfcVitGemm& g, float* part_ws, hipStream_t st);
+hipError_t tfc_launch_vit_ln_fwd(const float* x, const float* g, const float* b, float* y, float* mean, float* rstd, int rows, int D, float eps, hipStream_t st);
+hipError_t tfc_launch_vit_ln_bwd(const float* dy, const float* x, const float* mean, const float* rstd, const float* g, const float* dres, float* dx,
+                                 float* dgb, int rows, int D, float* part_ws, hipStream_t st);
+hipError_t tfc_launch_vit_colsum(const float* v, long long ld, int rows, int L, const float* x_ln, const float* mean, const float* rstd, float* out,
+                                 float* part_ws, hipStream_t st);
+hipError_t tfc_launch_vit_attn_fwd(int dt, const float* qkv, float* out, float* probs, int N, int T, int H, float scale, hipStream_t st);
+hipError_t tfc_launch_vit_attn_tiled_fwd(int dt, const float* qkv, float* out, float* stats, int N, int T, int H, float scale, hipStream_t st);
+hipError_t tfc_launch_vit_attn_tiled_bwd(int dt, const float* dout, const float* qkv, const float* stats, float* dqkv, float* ws, int N, int T, int H,
+                                         float scale, hipStream_t st);
+hipError_t tfc_launch_vit_attn_bwd(int dt, const float* dout, const float* qkv, const float* probs, float* dqkv, int N, int T, int H, float scale,
+                                   hipStream_t st);
+hipError_t tfc_launch_vit_tokens_fwd(float* x, const float* cls, const float* pos, int N, int T, int D, hipStream_t st);
+// input.hip
+hipError_t tfc_launch_pair_resize(const uint8_t* src, long long img_stride, int row_stride, int N, const TfcResizePlan& p, const int* plan,
+                                  uint8_t* tmp, const float* lut, float* A, float* B, float* TB, uint8_t* A8, uint8_t* B8, hipStream_t st);
+// lpips.hip
+hipError_t tfc_launch_lpips_input(int dt, const float* x, const float* shift, const float* scale, void* out, int N, int C, long long HW, int pitch, hipStream_t st);
+hipError_t tfc_launch_lpips_input_bwd(int dt, const void* g, const float* scale, float* dx, int N, int C, long long HW, int pitch, float alpha, int accumulate, hipStream_t st);
+hipError_t tfc_launch_maxpool2(int dt, int bwd, const void* x, const void* dy, void* out, int N, int H, int W, int C, hipStream_t st);
+hipError_t tfc_launch_relu_bwd(int dt, const void* dy, const void* y, const void* extra, void* dz, long long n, hipStream_t st);
+hipError_t tfc_launch_lpips_head(int dt, const void* fx, const void* fy, const float* w, float* out, void* dfx, float* part_ws, int N, long long HW, int C, float gscale, hipStream_t st);
+// debias.hip: the <= TFC_AUX_MAXC head rows travel in the kernels' argument block
+#define TFC_AUX_MAXC 16
+struct TfcAuxRows { const float* w[TFC_AUX_MAXC]; const float* b[TFC_AUX_MAXC]; };
+struct TfcAuxGradRows { float* w[TFC_AUX_MAXC]; float* b[TFC_AUX_MAXC]; };
+struct TfcCeHeads { int nc[3]; int off[3]; float w[3]; float scale; };
+hipError_t tfc_launch_pack_labels(int dt, const float* img, const float* labels, const float* fw, const float* fb, void* out, int N, int HW, hipStream_t st);
+hipError_t tfc_launch_label_plane_bwd(const float* g, long long gs, const float* labels, float* dw, float* db, int N, int HW, int accumulate, hipStream_t st);
+hipError_t tfc_launch_aux_heads_fwd(int dt, const void* x, const TfcAuxRows& rows, int ct, float* logits, float* part_ws, int N, int HW, hipStream_t st);
+hipError_t tfc_launch_aux_heads_dgrad(float* g, long long gs, const TfcAuxRows& rows, int ct, const float* dl, int N, int HW, hipStream_t st);
+hipError_t tfc_launch_aux_heads_wgrad(int dt, const void* xr, const float* dlr, const void* xf, const float* dlf, const TfcAuxGradRows& rows, int ct,
+                                      int N, int HW, int accumulate, hipStream_t st);
+hipError_t tfc_launch_softmax_ce_heads(const float* logits, const int* targets, const TfcCeHeads& a, int ct, int N, float* probs, float* losses,
+                                       float* dlogits, hipStream_t st);
+int tfc_aux_fwd_nparts(int HW);
+// mask.hip
+long long tfc_mask_nblk(int N, int H, int W);
+int tfc_mask_stats_floats(void);
+hipError_t tfc_launch_mask_fwd(const float* img, float* lap, float* bl, void* ws, int N, int H, int W, hipStream_t st);
+hipError_t tfc_launch_mask_scale(const float* bl, const void* ws, float* mask, long long total, hipStream_t st);
+hipError_t tfc_launch_mask_bwd(const float* lap, const float* bl, void* ws, const float* dout, const float* ref, float scale, float* dout_buf,
+                               float* dmn, float* dimg, int N, int H, int W, hipStream_t st);
+hipError_t tfc_launch_mask_phase_f1(const float* img, float* lap, void* ws, void* rec, int N, int H, int W, hipStream_t st);
+hipError_t tfc_launch_mask_phase_f2(const float* lap, float* bl, void* ws, void* rec, int N, int H, int W, hipStream_t st);
+hipError_t tfc_launch_mask_merge(void* ws, const void* recs, int world, int which, hipStream_t st);
+hipError_t tfc_launch_mask_phase_b0(const float* bl, void* ws, const float* dout, const float* ref, float scale, float* dout_buf, void* rec, int N, int H,
+                                    int W, hipStream_t st);
+hipError_t tfc_launch_mask_phase_b1(const float* lap, const float* bl, void* ws, const float* dout, float* dmn, void* rec, int N, int H, int W, hipStream_t st);
+hipError_t tfc_launch_mask_phase_b2(const float* lap, const void* ws, const float* dmn, float* dimg, int N, int H, int W, hipStream_t st);
+hipError_t tfc_launch_pack_plane(int dt, const float* img, const float* plane, const float* Mdev, void* out, int N, int HW, hipStream_t st);
 #endif

@@ -816,20 +816,12 @@ def pack_nhwc8_plane(dt, x, plane, plane_div=None):
 
 
 # ---- STN21 localiser (vit.hip) ---------------------------------------------------------------------------------
-VIT_A_ROWS, VIT_A_TRANS, VIT_A_UNFOLD = 0, 1, 2
-VIT_B_WEIGHT, VIT_B_ROWS, VIT_B_UNFOLD = 0, 1, 2
-VIT_C_ROWS, VIT_C_UNFOLD = 0, 1
-VIT_ACT_NONE, VIT_ACT_GELU, VIT_ACT_RELU, VIT_ACT_SIGMOID, VIT_DACT_GELU, VIT_DACT_RELU, VIT_DACT_SIGMOID = range(7)
+globals().update({k: v for k, v in _lib.CONSTANTS.items() if k.startswith("VIT_")})      # VIT_A_ROWS, VIT_B_WEIGHT, VIT_C_ROWS, VIT_ACT_NONE, ...
 
 
 class VitGemm(ctypes.Structure):
-    """mirror of TfcVitGemm (include/tfc_gan.h)"""
-    _fields_ = [("M", ctypes.c_int), ("N", ctypes.c_int), ("K", ctypes.c_int), ("a_mode", ctypes.c_int), ("a_rg", ctypes.c_int),
-                ("a", ctypes.c_void_p), ("a2", ctypes.c_void_p), ("lda", ctypes.c_longlong), ("a_rso", ctypes.c_longlong),
-                ("b_mode", ctypes.c_int), ("c_mode", ctypes.c_int), ("b", ctypes.c_void_p), ("b2", ctypes.c_void_p), ("ldb", ctypes.c_longlong),
-                ("c", ctypes.c_void_p), ("c2", ctypes.c_void_p), ("ldc", ctypes.c_longlong), ("c_rso", ctypes.c_longlong),
-                ("c_rg", ctypes.c_int), ("act", ctypes.c_int), ("bias", ctypes.c_void_p), ("res", ctypes.c_void_p), ("aux", ctypes.c_void_p),
-                ("ldaux", ctypes.c_longlong), ("uc", ctypes.c_int), ("uh", ctypes.c_int), ("uw", ctypes.c_int), ("up", ctypes.c_int)]
+    """TfcVitGemm, fields as include/tfc_gan.h declares them"""
+    _fields_ = _lib.STRUCTS["TfcVitGemm"]
 
 
 def _fp(t):
