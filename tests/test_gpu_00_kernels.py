@@ -510,7 +510,8 @@ def test_upconv_tanh_nchw_head():
 @pytest.mark.parametrize("N,H,W,Cout,with_bias", [(2, 16, 16, 3, True), (1, 9, 10, 3, True), (3, 21, 40, 1, False), (5, 64, 64, 4, True)])
 def test_generator_head_kernel(N, H, W, Cout, with_bias):
     """tfc_upconv_head_fwd (phases as columns of a 16-wide MFMA tile, channel chunks over the waves, persistent) against torch and
-    against the gather-GEMM path it replaces; ragged tiles, several tiles per workgroup"""
+    against the gather-GEMM path it replaces; ragged tiles (one tile per workgroup on a 256-CU card: the walk over several tiles is
+    test_persistent_layer_kernels_walk_tiles)"""
     dt = DT_BF16
     x = q(rnd((N, 128, H, W), 5), dt)
     w = rnd((Cout, 128, 4, 4), 6, 0.02)
@@ -529,7 +530,8 @@ def test_generator_head_kernel(N, H, W, Cout, with_bias):
 @pytest.mark.parametrize("N,H,W,Cout", [(2, 16, 16, 3), (1, 9, 10, 3), (3, 21, 40, 1), (4, 128, 128, 3)])
 def test_generator_head_dgrad_kernel(N, H, W, Cout):
     """tfc_upconv_head_dgrad (collapsed 5 x 5 stride-2 window of dy, weights-stationary) against torch autograd on bf16-rounded operands and
-    against the gather-GEMM path it replaces; ragged tiles, several tiles per workgroup, a destination window of a wider buffer"""
+    against the gather-GEMM path it replaces; ragged tiles, a destination window of a wider buffer (one tile per workgroup on a 256-CU card: the
+    walk over several tiles is test_persistent_layer_kernels_walk_tiles)"""
     dt = DT_BF16
     x = q(rnd((N, 128, H, W), 5), dt).requires_grad_(True)
     w = rnd((Cout, 128, 4, 4), 6, 0.05)
@@ -549,7 +551,8 @@ def test_generator_head_dgrad_kernel(N, H, W, Cout):
 
 @pytest.mark.parametrize("N,H,W", [(2, 16, 16), (1, 37, 50), (5, 96, 64)])
 def test_first_conv_dgrad_image(N, H, W):
-    """tfc_conv_dgrad_image (four output rows packed into the columns of a 16-wide MFMA tile) against autograd on bf16-rounded operands"""
+    """tfc_conv_dgrad_image (four output rows packed into the columns of a 16-wide MFMA tile) against autograd on bf16-rounded operands (one tile
+    per workgroup on a 256-CU card: the walk over several tiles is test_persistent_layer_kernels_walk_tiles)"""
     dt, Cin, Cout, nch, osc = DT_BF16, 6, 64, 3, 0.41
     x = rnd((N, Cin, H, W), 21).requires_grad_(True)
     w = rnd((Cout, Cin, 4, 4), 22, 0.1)
@@ -561,6 +564,114 @@ def test_first_conv_dgrad_image(N, H, W):
     want = gx[:, :nch] * osc
     assert got.shape == want.shape
     assert (got - want).abs().max().item() <= tol(dt, want.abs().max().item())
+
+
+def _walk_first_conv(masked):
+    dt, N, Cin, Cout, H, W = DT_BF16, 2, 6, 64, 24, 40         # output 23 x 39: 3 x 3 tiles of 8 x 16 per image, 18 in all, ragged on both axes
+    x = q(rnd((N, Cin, H, W), 5), dt)
+    w = rnd((Cout, Cin, 4, 4), 6, 1.0 / np.sqrt(Cin * 16))
+    b = rnd((Cout,), 7, 0.5)
+    want = F.leaky_relu(F.conv2d(x, q(w, dt), padding=1) + b.view(1, -1, 1, 1), 0.2)
+    xv, bd = to_view(x, dt), b.to(DEV)
+    pk = ops.pack_weight(dt, ops.OP_CONV, 0, w.to(DEV), Cin, Cout)
+
+    def run():
+        y = View(torch.full((N, H - 1, W - 1, Cout), 7.0, dtype=torch.bfloat16, device=DEV), Cout)
+        mask = torch.full((N, H - 1, W - 1, 8), 0xA5, dtype=torch.uint8, device=DEV) if masked else None
+        ops.conv_first_fwd(dt, xv, Cin, Cout, pk, y, bias=bd, flags=ops.EP_LEAKY, sign_mask=mask)
+        return [y.t] + ([mask] if masked else [])
+
+    def check(outs):
+        got = outs[0].float().cpu().permute(0, 3, 1, 2)
+        assert (got - want).abs().max().item() <= tol(dt, want.abs().max().item())
+        if masked:
+            assert torch.equal(outs[1], X.sign_words(outs[0].permute(0, 3, 1, 2)))
+    return run, check
+
+
+def _walk_head_fwd():
+    dt, N, H, W, Cout = DT_BF16, 2, 20, 24, 3                   # 3 x 2 tiles of 8 x 16 per image, 12 in all
+    x = q(rnd((N, 128, H, W), 5), dt)
+    w = rnd((Cout, 128, 4, 4), 6, 0.02)
+    b = rnd((Cout,), 7, 0.1)
+    want = torch.tanh(ref_conv(ops.OP_UPCONV, x, w, b))
+    xv, wd, bd = to_view(x, dt), w.to(DEV), b.to(DEV)
+
+    def run():
+        out = torch.full((N, Cout, 2 * H, 2 * W), 7.0, dtype=torch.float32, device=DEV)
+        ops.upconv_head_fwd(dt, xv, wd, bd, out)
+        return [out]
+
+    def check(outs):
+        assert (outs[0].cpu() - want).abs().max().item() <= 1e-2
+    return run, check
+
+
+def _walk_dgrad_image():
+    dt, N, H, W, Cin, Cout, nch, osc = DT_BF16, 2, 20, 40, 6, 64, 3, 0.41   # 3 x 2 tiles of 8 x 32 per image, 12 in all
+    x = rnd((N, Cin, H, W), 21).requires_grad_(True)
+    w = rnd((Cout, Cin, 4, 4), 22, 0.1)
+    y = F.conv2d(x, q(w, dt), padding=1)
+    go = q(rnd(tuple(y.shape), 23), dt)
+    (gx,) = torch.autograd.grad(y, x, go)
+    want = gx[:, :nch] * osc
+    gov, wd, od = to_view(go, dt), w.to(DEV), torch.tensor([osc], device=DEV)
+
+    def run():                                                   # the entry point itself: ops.conv_dgrad_image allocates its result, which leaves no room for a sentinel
+        out = torch.full((N, nch, H, W), 7.0, dtype=torch.float32, device=DEV)
+        _lib.check(ops.lib().tfc_conv_dgrad_image(ops.stream_ptr(), dt, gov.ptr, gov.pitch, N, H, W, Cin, Cout, ops._p(wd), ops._p(od), nch, ops._p(out)),
+                   "tfc_conv_dgrad_image")
+        return [out]
+
+    def check(outs):
+        assert (outs[0].cpu() - want).abs().max().item() <= tol(dt, want.abs().max().item())
+    return run, check
+
+
+def _walk_head_dgrad():
+    dt, N, H, W, Cout = DT_BF16, 2, 20, 24, 3                   # 3 x 2 tiles of 8 x 16 per image, 12 in all
+    x = q(rnd((N, 128, H, W), 5), dt).requires_grad_(True)
+    w = rnd((Cout, 128, 4, 4), 6, 0.05)
+    y = ref_conv(ops.OP_UPCONV, x, w)
+    go = q(rnd(tuple(y.shape), 7), dt)
+    (gx,) = torch.autograd.grad(y, x, go)
+    gov, wd = to_view(go, dt), w.to(DEV)
+
+    def run():
+        buf = torch.full((N, H, W, 160), 3.0, dtype=torch.bfloat16, device=DEV)   # the destination is a 128-channel window of a wider buffer
+        ops.upconv_head_dgrad(dt, gov, N, H, W, wd, View(buf, 128, 0))
+        return [buf]
+
+    def check(outs):
+        assert (outs[0][..., 128:] == 3.0).all()
+        got = outs[0][..., :128].float().cpu().permute(0, 3, 1, 2)
+        assert (got - gx).abs().max().item() <= tol(dt, gx.abs().max().item())
+    return run, check
+
+
+WALK_CASES = {"conv_first_fwd": lambda: _walk_first_conv(False), "conv_first_fwd_sign_mask": lambda: _walk_first_conv(True),
+              "upconv_head_fwd": _walk_head_fwd, "conv_dgrad_image": _walk_dgrad_image, "upconv_head_dgrad": _walk_head_dgrad}
+
+
+@pytest.mark.parametrize("case", list(WALK_CASES))
+def test_persistent_layer_kernels_walk_tiles(case):
+    """The loop-carried half of the persistent layer kernels (tfc_conv_c8_kernel with and without sign words, tfc_upconv_head_kernel,
+    tfc_dgrad_rows4_kernel, tfc_dgrad_head_kernel), which the default grid of a 256-CU card (512 or 1024 workgroups) hides from every small shape:
+    tfc_debug_set_persistent_grid caps the grid at 5 workgroups (12 or 18 tiles: walks of unequal length, up to 3 or 4 tiles) and at 1 (one workgroup
+    walks every tile). The default grid is held to the torch reference of the kernel's own test; the capped grids must give the SAME BITS in the whole
+    destination, sentinel-filled pad channels and sign words included: a tile's sums are formed in one fixed order whichever workgroup forms them."""
+    run, check = WALK_CASES[case]()
+    lib = ops.lib()
+    try:
+        base = run()
+        check(base)
+        for workgroups in (5, 1):
+            _lib.check(lib.tfc_debug_set_persistent_grid(workgroups), "tfc_debug_set_persistent_grid")
+            outs = run()
+            for o, b in zip(outs, base):
+                assert torch.equal(o, b), f"{case}: {workgroups} workgroup(s) and the default grid differ"
+    finally:
+        _lib.check(lib.tfc_debug_set_persistent_grid(0), "tfc_debug_set_persistent_grid")
 
 
 def oracle_act(x, norm, slope, pool, mask=None, drop_p=0.0):

@@ -361,6 +361,14 @@ def test_profiling_state_is_per_thread():
     assert lib.tfc_prof_enable(0) == 0
 
 
+def test_persistent_grid_hook_refuses_negative_values():
+    """tfc_debug_set_persistent_grid: 0 = the default grid, n >= 1 = at most n workgroups; a negative value is an error and changes nothing"""
+    lib = _lib.load()
+    assert lib.tfc_debug_set_persistent_grid(3) == 0
+    assert lib.tfc_debug_set_persistent_grid(-1) != 0
+    assert lib.tfc_debug_set_persistent_grid(0) == 0
+
+
 def test_lpips_local_weight_files(tmp_path):
     """LPIPS weights come from caller-supplied local files only (weights-only loader): torchvision's `features.N.*` layout plus the original
     `lin{i}.model.1.weight` heads, or this class's own state_dict; anything partial is refused"""

@@ -98,7 +98,11 @@ GUARDED_KERNELS = ("tfc_igemm2_kernel", "tfc_wgrad", "tfc_patch_triplet_kernelIL
                    "tfc_mask_record_extrema_kernel", "tfc_mask_record_sums_kernel", "tfc_mask_merge_kernel", "tfc_batch_kl_stats_kernel",
                    "tfc_batch_kl_merge_kernel", "tfc_batch_kl_terms_kernel",
                    # the tiled attention (vit.hip): 16-row statistics, P, dP and the accumulators of a 32 x 32 quarter per lane, sized for registers
-                   "tfc_vit_attn_tiled_fwd_kernel", "tfc_vit_attn_tiled_dq_kernel", "tfc_vit_attn_tiled_dkv_kernel")
+                   "tfc_vit_attn_tiled_fwd_kernel", "tfc_vit_attn_tiled_dq_kernel", "tfc_vit_attn_tiled_dkv_kernel",
+                   # the persistent layer kernels (igemm.hip): their shared pieces pass the register-held halo (uint4 hv[NHV]) and the accumulator arrays
+                   # through helpers; one that stops being inlined or unrolled would send those arrays to scratch, and only this check would tell.
+                   # (tfc_conv_c8_kernel<true>, "ILb1E", is not listed: it spills 3 VGPRs, 16 bytes of scratch per lane; profiles/persistent_family_ab.md.)
+                   "tfc_upconv_head_kernel", "tfc_dgrad_rows4_kernel", "tfc_dgrad_head_kernel", "tfc_conv_c8_kernelILb0E")
 
 
 def check_no_spills(remarks):

@@ -1241,6 +1241,11 @@ extern "C" int tfc_debug_set_igemm_config(int cfg) {
   g_tfc_force_cfg = cfg;
   return 0;
 }
+extern "C" int tfc_debug_set_persistent_grid(int workgroups) {
+  REQUIRE(workgroups >= 0, "workgroups must be 0 (default: occupancy x compute units) or the largest grid of the persistent layer kernels");
+  g_tfc_persistent_grid = workgroups;
+  return 0;
+}
 // ---- batch-invariant mode and the launch-plan query ------------------------------------------------------------------------
 extern "C" int tfc_set_batch_invariant(int on) {                  // per thread, like the other host-side hooks
   g_tfc_batch_invariant = on ? 1 : 0;

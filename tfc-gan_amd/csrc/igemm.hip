@@ -1046,6 +1046,124 @@ tfc_igemm2_kernel(const TfcGather d, const bf16_t* __restrict__ in, const uint4*
 }
 
 // ---------------------------------------------------------------------------------------------------
+// Shared pieces of the persistent layer kernels (tfc_conv_c8_kernel, tfc_upconv_head_kernel, tfc_dgrad_rows4_kernel, tfc_dgrad_head_kernel: the thin
+// layers at the two ends of the networks). All four are weights-stationary: a wave builds its B fragments once, a workgroup walks the tiles
+// b, b + grid, ... The ONE rule they share: the halo of the next tile is requested into registers BEFORE the stores of this tile are issued (vmcnt
+// retires in order: a load issued behind stores would have to wait for them), and it reaches LDS only behind the barrier that frees the bytes it lands
+// in -- the other halo buffer (conv_c8, dgrad_head: two buffers and a staged output tile), or the one buffer whose bytes were the four waves' partial
+// sums in between (upconv_head, dgrad_rows4). The grid never exceeds the tile count (tfc_persistent_grid), so every workgroup has a first tile.
+// ---------------------------------------------------------------------------------------------------
+struct TfcTilePos { int img, a0, b0; };                          // image and first (row, column) of a tile
+// work item wk of nwork -> its TH x TW tile, neighbouring tiles on one XCD
+template <int TH, int TW>
+__device__ __forceinline__ TfcTilePos tfc_walk_decode(int wk, int nwork, int tiles_y, int tiles_x) {
+  int tile = tfc_xcd_remap(wk, nwork);
+  const int txb = tile % tiles_x; tile /= tiles_x;
+  const int tyb = tile % tiles_y;
+  return TfcTilePos{tile / tiles_y, tyb * TH, txb * TW};
+}
+// the carry of the walk: on to the tile one grid stride further, decoded when its halo was requested
+__device__ __forceinline__ void tfc_walk_step(int& wk, TfcTilePos& pos, const TfcTilePos& next) { wk += (int)gridDim.x; pos = next; }
+
+// Register-held halo of HH x HW pixels x UPP 16-byte units, unit tid + 256 i = pixel * UPP + u of the thread: loaded from the NHWC image `img` of src
+// (SH x SW pixels, `pitch` elements apart) with halo pixel (0, 0) at source pixel (y0, x0), zero outside the image; stored later as
+// buf[(hy * LP + hx) * PS + u * 16] (PS: LDS bytes per pixel, LP: LDS pixels per row).
+constexpr int tfc_halo_units(int HH, int HW, int UPP) { return (HH * HW * UPP + 255) / 256; }
+template <int HH, int HW, int UPP, int NHV>
+__device__ __forceinline__ void tfc_halo_load(uint4 (&hv)[NHV], const bf16_t* __restrict__ src, int SH, int SW, int pitch, int img,
+                                              int y0, int x0) {
+  static_assert(NHV == tfc_halo_units(HH, HW, UPP), "one register per 16-byte unit of the thread");
+#pragma unroll
+  for (int i = 0; i < NHV; ++i) {
+    const int idx = (int)threadIdx.x + i * 256;
+    const int pix = idx / UPP, u = idx % UPP;
+    const int hy = pix / HW, hx = pix - hy * HW;
+    const int y = y0 + hy, x = x0 + hx;
+    hv[i] = make_uint4(0, 0, 0, 0);
+    if (pix < HH * HW && y >= 0 && y < SH && x >= 0 && x < SW) hv[i] = *reinterpret_cast<const uint4*>(src + ((size_t)(img * SH + y) * SW + x) * pitch + u * 8);
+  }
+}
+template <int HH, int HW, int UPP, int PS, int LP, int NHV>
+__device__ __forceinline__ void tfc_halo_store(unsigned char* buf, const uint4 (&hv)[NHV]) {
+  static_assert(NHV == tfc_halo_units(HH, HW, UPP), "one register per 16-byte unit of the thread");
+#pragma unroll
+  for (int i = 0; i < NHV; ++i) {
+    const int idx = (int)threadIdx.x + i * 256;
+    const int pix = idx / UPP, u = idx % UPP;
+    const int hy = pix / HW, hx = pix - hy * HW;
+    if (pix < HH * HW) *reinterpret_cast<uint4*>(buf + (hy * LP + hx) * PS + u * 16) = hv[i];
+  }
+}
+
+// Partial sums of the four waves, part[wave][S subtiles][16 rows][16 columns] of floats over the consumed halo's bytes. D layout of the 16 x 16 MFMA:
+// column = lane & 15 (col), row = 4 * (lane >> 4) + j (kg).
+template <int S>
+__device__ __forceinline__ void tfc_part_store(float* part, int wave, int kg, int col, const f32x4_t (&acc)[S]) {
+#pragma unroll
+  for (int st = 0; st < S; ++st)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) part[((wave * S + st) * 16 + 4 * kg + j) * 16 + col] = acc[st][j];
+}
+// ... and their sum for NV float4 of columns from c0 on in (subtile st, row): waves 0, 1, 2, 3 in this order, which is part of the result
+template <int S, int NV>
+__device__ __forceinline__ void tfc_part_sum(const float* part, int st, int row, int c0, float4 (&s)[NV]) {
+#pragma unroll
+  for (int v = 0; v < NV; ++v) s[v] = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+  for (int wv = 0; wv < 4; ++wv) {
+    const float4* pp = reinterpret_cast<const float4*>(part + ((wv * S + st) * 16 + row) * 16 + c0);
+    float4 u[NV];
+#pragma unroll
+    for (int v = 0; v < NV; ++v) u[v] = pp[v];
+#pragma unroll
+    for (int v = 0; v < NV; ++v) { s[v].x += u[v].x; s[v].y += u[v].y; s[v].z += u[v].z; s[v].w += u[v].w; }
+  }
+}
+
+// Staged tile store: the 8 x 16 pixels x U 16-byte units of the padded LDS tile (ROWP bytes per pixel) to the NHWC destination, clipped to the GH x GW
+// valid pixels from the tile origin on and to the channels below nmax; tile pixel (0, 0) of the image is destination pixel (oy, ox) of DH x DW.
+template <int U, int ROWP>
+__device__ __forceinline__ void tfc_stage_store(const unsigned char* stage, bf16_t* __restrict__ dst, int DH, int DW, int pitch, int oy, int ox, int GH, int GW,
+                                                int nmax, const TfcTilePos& t) {
+#pragma unroll
+  for (int i = 0; i < U / 2; ++i) {
+    const int idx = (int)threadIdx.x + i * 256;
+    const int pix = idx / U, u = idx % U;
+    const int a = t.a0 + (pix >> 4), b = t.b0 + (pix & 15);
+    if (a < GH && b < GW && u * 8 < nmax) {
+      const uint4 v = *reinterpret_cast<const uint4*>(stage + pix * ROWP + u * 16);
+      store_stream16(dst + ((size_t)(t.img * DH + a + oy) * DW + b + ox) * pitch + u * 8, v);
+    }
+  }
+}
+
+static int tfc_num_cus() {
+  static int ncu = 0;
+  if (!ncu) {
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || ncu <= 0) ncu = 256;
+  }
+  return ncu;
+}
+// Workgroups of a persistent layer kernel: min(nwork, occupancy x CUs). KERNEL is a template ARGUMENT, so every kernel (and every instantiation of one)
+// is asked for its own occupancy, once. Test hook (tfc_debug_set_persistent_grid, per thread): n >= 1 replaces the cap, so that a small test reaches
+// walks of several tiles and of unequal length.
+thread_local int g_tfc_persistent_grid = 0;
+template <auto KERNEL>
+static hipError_t tfc_persistent_grid(int lds_bytes, int nwork, int* grid) {
+  static int occ = 0;
+  if (!occ) {
+    int o = 0;
+    const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&o, KERNEL, 256, (size_t)lds_bytes);
+    if (e != hipSuccess) return e;
+    occ = o < 1 ? 1 : o;
+  }
+  const int cap = g_tfc_persistent_grid > 0 ? g_tfc_persistent_grid : occ * tfc_num_cus();
+  *grid = nwork < cap ? nwork : cap;
+  return hipSuccess;
+}
+
+// ---------------------------------------------------------------------------------------------------
 // First-layer convolution (8 padded input channels x 16 taps: K = 128 = 8 k-substeps; G down1 3->64 and D block 1 6->64 at
 // 256 x 256): the generic kernel spends its life in prologue / epilogue here -- per 16 KB of output it re-reads 32 KB of weight
 // fragments and pays a workgroup launch. This variant is weights-stationary and persistent: a wave keeps its eight B fragments in
@@ -1091,33 +1209,27 @@ tfc_conv_c8_kernel(const TfcGather d, const bf16_t* __restrict__ in, const uint4
   const float bv = (bias && n < d.Nout) ? bias[n] : 0.f;
   const float osc = oscale ? *oscale : 1.f;
 
-  auto decode = [&](int w, int& img, int& a0, int& b0) {
-    int tile = tfc_xcd_remap(w, nwork);
-    const int txb = tile % d.tiles_x; tile /= d.tiles_x;
-    const int tyb = tile % d.tiles_y;
-    img = tile / d.tiles_y;
-    a0 = tyb * TFC_TILE_H; b0 = txb * TFC_TILE_W;
-  };
-  const int hpix = tid;                                          // one 16-byte halo unit (= one pixel) per thread
+  auto decode = [&](int wk) { return tfc_walk_decode<TFC_TILE_H, TFC_TILE_W>(wk, nwork, d.tiles_y, d.tiles_x); };
+  // its own halo load, not tfc_halo_load: the halo size comes from the descriptor at run time, and it is one 16-byte unit (= one pixel) per thread
+  const int hpix = tid;
   const int hy = hpix / pd.hw, hx = hpix - hy * pd.hw;
   const bool hact = hpix < pd.hh * pd.hw;
   const int hoff = (hy * P + hx) * PS;
-  auto halo_load = [&](int img, int a0, int b0) -> uint4 {
+  auto halo_load = [&](const TfcTilePos& t) -> uint4 {
     uint4 v = make_uint4(0, 0, 0, 0);
-    const int y = a0 + pd.dy0 + hy, x = b0 + pd.dx0 + hx;
+    const int y = t.a0 + pd.dy0 + hy, x = t.b0 + pd.dx0 + hx;
     if (hact && y >= 0 && y < d.IH && x >= 0 && x < d.IW)
-      v = *reinterpret_cast<const uint4*>(in + ((size_t)(img * d.IH + y) * d.IW + x) * d.in_pitch);
+      v = *reinterpret_cast<const uint4*>(in + ((size_t)(t.img * d.IH + y) * d.IW + x) * d.in_pitch);
     return v;
   };
   const int laneBase = ((2 * wm * MT + (r & 1)) * P + (r >> 1)) * PS + h * PS;   // lane half h takes the odd tap of a k-substep
   constexpr int MSTRIDE = 2 * P * PS;
 
   int w = blockIdx.x;
-  int img, a0, b0, n_img = 0, n_a0 = 0, n_b0 = 0;
-  decode(w, img, a0, b0);
-  uint4 hv = halo_load(img, a0, b0);
+  TfcTilePos cur = decode(w), nxt{0, 0, 0};
+  uint4 hv = halo_load(cur);
   if (hact) *reinterpret_cast<uint4*>(smem + hoff) = hv;
-  if (w + G < nwork) { decode(w + G, n_img, n_a0, n_b0); hv = halo_load(n_img, n_a0, n_b0); }
+  if (w + G < nwork) { nxt = decode(w + G); hv = halo_load(nxt); }
   __syncthreads();
 
   for (int k = 0;; ++k) {
@@ -1162,29 +1274,21 @@ tfc_conv_c8_kernel(const TfcGather d, const bf16_t* __restrict__ in, const uint4
     }
     const bool has1 = (w + G) < nwork;
     if (has1 && hact) *reinterpret_cast<uint4*>(smem + ((k + 1) & 1) * HB + hoff) = hv;
-    int nn_img = 0, nn_a0 = 0, nn_b0 = 0;
-    if (w + 2 * G < nwork) { decode(w + 2 * G, nn_img, nn_a0, nn_b0); hv = halo_load(nn_img, nn_a0, nn_b0); }   // before the stores below
+    TfcTilePos nn{0, 0, 0};
+    if (w + 2 * G < nwork) { nn = decode(w + 2 * G); hv = halo_load(nn); }   // before the stores below
     __syncthreads();
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int idx = tid + i * 256;
-      const int pix = idx >> 3, u = idx & 7;
-      const int a = a0 + (pix >> 4), b = b0 + (pix & 15);
-      if (a < d.GH && b < d.GW && u * 8 < d.Nout) {
-        const uint4 v = *reinterpret_cast<const uint4*>(stage + pix * ROWP + u * 16);
-        store_stream16(out + ((size_t)(img * d.OH + a + d.OOY) * d.OW + b + d.OOX) * d.out_pitch + u * 8, v);
-      }
-    }
+    tfc_stage_store<8, ROWP>(stage, out, d.OH, d.OW, d.out_pitch, d.OOY, d.OOX, d.GH, d.GW, d.Nout, cur);
     if constexpr (MASK) {
       if (tid < 128) {
-        const int a = a0 + (tid >> 4), b = b0 + (tid & 15);
+        const int a = cur.a0 + (tid >> 4), b = cur.b0 + (tid & 15);
         if (a < d.GH && b < d.GW)
-          *reinterpret_cast<uint2*>(sign_mask + ((size_t)(img * d.OH + a) * d.OW + b) * 8) = *reinterpret_cast<const uint2*>(smask + tid * 2);
+          *reinterpret_cast<uint2*>(sign_mask + ((size_t)(cur.img * d.OH + a) * d.OW + b) * 8) = *reinterpret_cast<const uint2*>(smask + tid * 2);
       }
     }
     if (!has1) break;
     __syncthreads();                                             // the staged tile is free again
-    w += G; img = n_img; a0 = n_a0; b0 = n_b0; n_img = nn_img; n_a0 = nn_a0; n_b0 = nn_b0;
+    tfc_walk_step(w, cur, nxt);
+    nxt = nn;
   }
 }
 
@@ -1204,9 +1308,8 @@ tfc_conv_c8_kernel(const TfcGather d, const bf16_t* __restrict__ in, const uint4
 __global__ void __launch_bounds__(256, 2)
 tfc_upconv_head_kernel(const bf16_t* __restrict__ x, int IH, int IW, int x_pitch, const float* __restrict__ w, const float* __restrict__ bias,
                        int Cout, float* __restrict__ out, int nimg, int nwork) {
-  constexpr int HH = TFC_TILE_H + 2, HW = TFC_TILE_W + 2, NPIX = HH * HW;      // 10 x 18 halo
+  constexpr int HH = TFC_TILE_H + 2, HW = TFC_TILE_W + 2;        // 10 x 18 halo, 16 16-byte units per pixel
   constexpr int PS = 256 + 16;                                   // LDS bytes per halo pixel: 128 channels + pad (conflict-free 16-lane reads)
-  constexpr int NHV = (NPIX * 16 + 255) / 256;                   // 16-byte halo units per thread (12)
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   float* part = reinterpret_cast<float*>(smem);                  // [4 waves][8 ty][16 tx][16 cols] partial sums: reuses the halo bytes
   const int tid = threadIdx.x;
@@ -1251,33 +1354,10 @@ tfc_upconv_head_kernel(const bf16_t* __restrict__ x, int IH, int IW, int x_pitch
     for (int o = 0; o < 9; ++o) bw[o] = pack16<bf16_t>(f[o]);
   }
 
-  auto decode = [&](int wk, int& img, int& a0, int& b0) {
-    int tile = tfc_xcd_remap(wk, nwork);
-    const int txb = tile % tiles_x; tile /= tiles_x;
-    const int tyb = tile % tiles_y;
-    img = tile / tiles_y;
-    a0 = tyb * TFC_TILE_H; b0 = txb * TFC_TILE_W;
-  };
-  uint4 hv[NHV];
-  auto halo_load = [&](int img, int a0, int b0) {
-#pragma unroll
-    for (int i = 0; i < NHV; ++i) {
-      const int idx = tid + i * 256;                             // pixel * 16 + unit
-      const int pix = idx >> 4, u = idx & 15;
-      const int hy = pix / HW, hx = pix - hy * HW;
-      const int y = a0 - 1 + hy, xx = b0 - 1 + hx;
-      hv[i] = make_uint4(0, 0, 0, 0);
-      if (pix < NPIX && y >= 0 && y < IH && xx >= 0 && xx < IW)
-        hv[i] = *reinterpret_cast<const uint4*>(x + ((size_t)(img * IH + y) * IW + xx) * x_pitch + u * 8);
-    }
-  };
-  auto halo_store = [&]() {
-#pragma unroll
-    for (int i = 0; i < NHV; ++i) {
-      const int idx = tid + i * 256;
-      if (idx < NPIX * 16) *reinterpret_cast<uint4*>(smem + (idx >> 4) * PS + (idx & 15) * 16) = hv[i];
-    }
-  };
+  auto decode = [&](int wk) { return tfc_walk_decode<TFC_TILE_H, TFC_TILE_W>(wk, nwork, tiles_y, tiles_x); };
+  uint4 hv[tfc_halo_units(HH, HW, 16)];                          // 12 per thread
+  auto halo_load = [&](const TfcTilePos& t) { tfc_halo_load<HH, HW, 16>(hv, x, IH, IW, x_pitch, t.img, t.a0 - 1, t.b0 - 1); };
+  auto halo_store = [&]() { tfc_halo_store<HH, HW, 16, PS, HW>(smem, hv); };
   // reduction / store role of this thread: output pixel pair (2*rty + rh, 2*rtx .. 2*rtx+1), i.e. columns rh*8 .. rh*8+7 = phases (rh,0), (rh,1)
   const int rty = tid >> 5, rtx = (tid >> 1) & 15, rh = tid & 1;
   float bz[4];
@@ -1285,9 +1365,8 @@ tfc_upconv_head_kernel(const bf16_t* __restrict__ x, int IH, int IW, int x_pitch
   for (int c = 0; c < 4; ++c) bz[c] = (bias && c < Cout) ? bias[c] : 0.f;
 
   int wk = blockIdx.x;
-  int img, a0, b0;
-  decode(wk, img, a0, b0);
-  halo_load(img, a0, b0);
+  TfcTilePos cur = decode(wk);
+  halo_load(cur);
   halo_store();
   __syncthreads();
 
@@ -1306,28 +1385,18 @@ tfc_upconv_head_kernel(const bf16_t* __restrict__ x, int IH, int IW, int x_pitch
       }
     const bool has1 = (wk + G) < nwork;
     __syncthreads();                                             // every wave is done with this tile's halo: its bytes become the partial sums
-    int n_img = 0, n_a0 = 0, n_b0 = 0;
-    if (has1) { decode(wk + G, n_img, n_a0, n_b0); halo_load(n_img, n_a0, n_b0); }   // requested BEFORE the stores below (vmcnt is in order)
-    // D layout: col = lane & 15 = (phase, oc); row = 4 * (lane >> 4) + j = tx
-#pragma unroll
-    for (int ty = 0; ty < 8; ++ty)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) part[((wave * 8 + ty) * 16 + 4 * kg + j) * 16 + col] = acc[ty][j];
+    TfcTilePos nxt{0, 0, 0};
+    if (has1) { nxt = decode(wk + G); halo_load(nxt); }          // requested BEFORE the stores below (vmcnt is in order)
+    tfc_part_store<8>(part, wave, kg, col, acc);                 // subtile = ty, column = (phase, oc), row = tx
     __syncthreads();
     {
-      float4 s0 = make_float4(0.f, 0.f, 0.f, 0.f), s1 = s0;
-#pragma unroll
-      for (int wv = 0; wv < 4; ++wv) {
-        const float4* pp = reinterpret_cast<const float4*>(part + ((wv * 8 + rty) * 16 + rtx) * 16 + rh * 8);
-        const float4 u0 = pp[0], u1 = pp[1];
-        s0.x += u0.x; s0.y += u0.y; s0.z += u0.z; s0.w += u0.w;
-        s1.x += u1.x; s1.y += u1.y; s1.z += u1.z; s1.w += u1.w;
-      }
-      const float v0[4] = {s0.x, s0.y, s0.z, s0.w}, v1[4] = {s1.x, s1.y, s1.z, s1.w};   // px = 0 / px = 1, channel oc
-      const int oy = 2 * (a0 + rty) + rh, ox = 2 * (b0 + rtx);
+      float4 s[2];
+      tfc_part_sum<8, 2>(part, rty, rtx, rh * 8, s);
+      const float v0[4] = {s[0].x, s[0].y, s[0].z, s[0].w}, v1[4] = {s[1].x, s[1].y, s[1].z, s[1].w};   // px = 0 / px = 1, channel oc
+      const int oy = 2 * (cur.a0 + rty) + rh, ox = 2 * (cur.b0 + rtx);
       if (oy < OH && ox < OW) {
         for (int c = 0; c < Cout; ++c) {
-          float* dst = out + (((size_t)img * Cout + c) * OH + oy) * OW + ox;
+          float* dst = out + (((size_t)cur.img * Cout + c) * OH + oy) * OW + ox;
           const float e0 = tanhf(v0[c] + bz[c]), e1 = tanhf(v1[c] + bz[c]);
           if (ox + 1 < OW && (OW & 1) == 0) *reinterpret_cast<float2*>(dst) = make_float2(e0, e1);
           else { dst[0] = e0; if (ox + 1 < OW) dst[1] = e1; }
@@ -1338,7 +1407,7 @@ tfc_upconv_head_kernel(const bf16_t* __restrict__ x, int IH, int IW, int x_pitch
     __syncthreads();                                             // partial sums consumed: the bytes become the next halo
     halo_store();
     __syncthreads();
-    wk += G; img = n_img; a0 = n_a0; b0 = n_b0;
+    tfc_walk_step(wk, cur, nxt);
   }
 }
 // ---------------------------------------------------------------------------------------------------
@@ -1354,9 +1423,8 @@ tfc_upconv_head_kernel(const bf16_t* __restrict__ x, int IH, int IW, int x_pitch
 __global__ void __launch_bounds__(256, 2)
 tfc_dgrad_rows4_kernel(const bf16_t* __restrict__ dy, int OHs, int OWs, int dy_pitch, const float* __restrict__ w, int Cin, const float* __restrict__ oscale,
                        int NC, float* __restrict__ dx, int IH, int IW, int nimg, int nwork) {
-  constexpr int TR = 8, TC = 32, HH = TR + 3, HW = TC + 3, NPIX = HH * HW;      // 11 x 35 halo of dy
+  constexpr int TR = 8, TC = 32, HH = TR + 3, HW = TC + 3;       // 11 x 35 halo of dy, 8 16-byte units per pixel
   constexpr int PS = 128 + 16;                                   // LDS bytes per halo pixel: 64 co + pad (conflict-free 16-lane reads)
-  constexpr int NHV = (NPIX * 8 + 255) / 256;                    // 16-byte halo units per thread (13)
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   float* part = reinterpret_cast<float*>(smem);                  // [4 waves][4 subtiles][16 rows][16 cols]: reuses the halo bytes
   const int tid = threadIdx.x;
@@ -1384,40 +1452,16 @@ tfc_dgrad_rows4_kernel(const bf16_t* __restrict__ dy, int OHs, int OWs, int dy_p
   }
   const float osc = oscale ? *oscale : 1.f;
 
-  auto decode = [&](int wk, int& img, int& a0, int& b0) {
-    int tile = tfc_xcd_remap(wk, nwork);
-    const int txb = tile % tiles_x; tile /= tiles_x;
-    const int tyb = tile % tiles_y;
-    img = tile / tiles_y;
-    a0 = tyb * TR; b0 = txb * TC;
-  };
-  uint4 hv[NHV];
-  auto halo_load = [&](int img, int a0, int b0) {
-#pragma unroll
-    for (int i = 0; i < NHV; ++i) {
-      const int idx = tid + i * 256;                             // pixel * 8 + unit
-      const int pix = idx >> 3, u = idx & 7;
-      const int hy = pix / HW, hx = pix - hy * HW;
-      const int y = a0 - 2 + hy, xx = b0 - 2 + hx;
-      hv[i] = make_uint4(0, 0, 0, 0);
-      if (pix < NPIX && y >= 0 && y < OHs && xx >= 0 && xx < OWs)
-        hv[i] = *reinterpret_cast<const uint4*>(dy + ((size_t)(img * OHs + y) * OWs + xx) * dy_pitch + u * 8);
-    }
-  };
-  auto halo_store = [&]() {
-#pragma unroll
-    for (int i = 0; i < NHV; ++i) {
-      const int idx = tid + i * 256;
-      if (idx < NPIX * 8) *reinterpret_cast<uint4*>(smem + (idx >> 3) * PS + (idx & 7) * 16) = hv[i];
-    }
-  };
+  auto decode = [&](int wk) { return tfc_walk_decode<TR, TC>(wk, nwork, tiles_y, tiles_x); };
+  uint4 hv[tfc_halo_units(HH, HW, 8)];                           // 13 per thread
+  auto halo_load = [&](const TfcTilePos& t) { tfc_halo_load<HH, HW, 8>(hv, dy, OHs, OWs, dy_pitch, t.img, t.a0 - 2, t.b0 - 2); };
+  auto halo_store = [&]() { tfc_halo_store<HH, HW, 8, PS, HW>(smem, hv); };
   // reduction / store role: output pixel (row rrow of 8, column rcol of 32) of the tile, all NC channels
   const int rrow = tid >> 5, rcol = tid & 31;
 
   int wk = blockIdx.x;
-  int img, a0, b0;
-  decode(wk, img, a0, b0);
-  halo_load(img, a0, b0);
+  TfcTilePos cur = decode(wk);
+  halo_load(cur);
   halo_store();
   __syncthreads();
 
@@ -1438,66 +1482,42 @@ tfc_dgrad_rows4_kernel(const bf16_t* __restrict__ dy, int OHs, int OWs, int dy_p
       }
     const bool has1 = (wk + G) < nwork;
     __syncthreads();                                             // halo consumed: its bytes become the partial sums
-    int n_img = 0, n_a0 = 0, n_b0 = 0;
-    if (has1) { decode(wk + G, n_img, n_a0, n_b0); halo_load(n_img, n_a0, n_b0); }   // requested BEFORE the stores below (vmcnt is in order)
-#pragma unroll
-    for (int st = 0; st < 4; ++st)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) part[((wave * 4 + st) * 16 + 4 * kg + j) * 16 + col] = acc[st][j];
+    TfcTilePos nxt{0, 0, 0};
+    if (has1) { nxt = decode(wk + G); halo_load(nxt); }          // requested BEFORE the stores below (vmcnt is in order)
+    tfc_part_store<4>(part, wave, kg, col, acc);                 // subtile = st, column = (delta, ci), row = ix within the subtile
     __syncthreads();
     {
-      const int st = (rrow >> 2) * 2 + (rcol >> 4);
-      float4 sum = make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-      for (int wv = 0; wv < 4; ++wv) {
-        const float4 u = *reinterpret_cast<const float4*>(part + ((wv * 4 + st) * 16 + (rcol & 15)) * 16 + (rrow & 3) * 4);
-        sum.x += u.x; sum.y += u.y; sum.z += u.z; sum.w += u.w;
-      }
-      const float v[4] = {sum.x, sum.y, sum.z, sum.w};
-      const int iy = a0 + rrow, ix = b0 + rcol;
+      float4 sum[1];
+      tfc_part_sum<4, 1>(part, (rrow >> 2) * 2 + (rcol >> 4), rcol & 15, (rrow & 3) * 4, sum);
+      const float v[4] = {sum[0].x, sum[0].y, sum[0].z, sum[0].w};
+      const int iy = cur.a0 + rrow, ix = cur.b0 + rcol;
       if (iy < IH && ix < IW)
-        for (int c = 0; c < NC; ++c) dx[(((size_t)img * NC + c) * IH + iy) * IW + ix] = v[c] * osc;
+        for (int c = 0; c < NC; ++c) dx[(((size_t)cur.img * NC + c) * IH + iy) * IW + ix] = v[c] * osc;
     }
     if (!has1) break;
     __syncthreads();                                             // partial sums consumed: the bytes become the next halo
     halo_store();
     __syncthreads();
-    wk += G; img = n_img; a0 = n_a0; b0 = n_b0;
+    tfc_walk_step(wk, cur, nxt);
   }
 }
 hipError_t tfc_launch_dgrad_rows4(const void* dy, int dy_pitch, int N, int H, int W, const float* w, int Cin, const float* oscale, int NC, float* dx,
                                   hipStream_t st) {
   const int lds = 11 * 35 * (128 + 16);                          // 55,440 B >= the 16 KiB of partial sums that reuse it
-  static int grid_cap = 0;
-  if (!grid_cap) {
-    int occ = 0, dev = 0, ncu = 0;
-    hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, tfc_dgrad_rows4_kernel, 256, (size_t)lds);
-    if (e != hipSuccess) return e;
-    if ((e = hipGetDevice(&dev)) != hipSuccess) return e;
-    if ((e = hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev)) != hipSuccess) return e;
-    grid_cap = (occ < 1 ? 1 : occ) * ncu;
-  }
   const int nwork = N * ((H + 7) / 8) * ((W + 31) / 32);
-  TFC_LAUNCH(tfc_dgrad_rows4_kernel, dim3(nwork < grid_cap ? nwork : grid_cap), dim3(256), lds, st, (const bf16_t*)dy, H - 1, W - 1, dy_pitch, w,
-                     Cin, oscale, NC, dx, H, W, N, nwork);
+  int grid;
+  if (hipError_t e = tfc_persistent_grid<tfc_dgrad_rows4_kernel>(lds, nwork, &grid)) return e;
+  TFC_LAUNCH(tfc_dgrad_rows4_kernel, dim3(grid), dim3(256), lds, st, (const bf16_t*)dy, H - 1, W - 1, dy_pitch, w, Cin, oscale, NC, dx, H, W, N, nwork);
   return hipGetLastError();
 }
 
 hipError_t tfc_launch_upconv_head(const void* x, int x_pitch, int N, int H, int W, const float* w, const float* bias, int Cout, float* out,
                                   hipStream_t st) {
   const int lds = (TFC_TILE_H + 2) * (TFC_TILE_W + 2) * (256 + 16);   // 48,960 B >= the 32 KiB of partial sums that reuse it
-  static int grid_cap = 0;
-  if (!grid_cap) {
-    int occ = 0, dev = 0, ncu = 0;
-    hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, tfc_upconv_head_kernel, 256, (size_t)lds);
-    if (e != hipSuccess) return e;
-    if ((e = hipGetDevice(&dev)) != hipSuccess) return e;
-    if ((e = hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev)) != hipSuccess) return e;
-    grid_cap = (occ < 1 ? 1 : occ) * ncu;
-  }
   const int nwork = N * ((H + TFC_TILE_H - 1) / TFC_TILE_H) * ((W + TFC_TILE_W - 1) / TFC_TILE_W);
-  TFC_LAUNCH(tfc_upconv_head_kernel, dim3(nwork < grid_cap ? nwork : grid_cap), dim3(256), lds, st, (const bf16_t*)x, H, W, x_pitch, w, bias,
-                     Cout, out, N, nwork);
+  int grid;
+  if (hipError_t e = tfc_persistent_grid<tfc_upconv_head_kernel>(lds, nwork, &grid)) return e;
+  TFC_LAUNCH(tfc_upconv_head_kernel, dim3(grid), dim3(256), lds, st, (const bf16_t*)x, H, W, x_pitch, w, bias, Cout, out, N, nwork);
   return hipGetLastError();
 }
 
@@ -1557,50 +1577,23 @@ tfc_dgrad_head_kernel(const bf16_t* __restrict__ dy, int dy_pitch, const float* 
     const int o0 = ((t0 / 5) * P + t0 % 5) * 16, o1 = ((t1 / 5) * P + t1 % 5) * 16;
     offs[s] = h ? o1 : o0;
   }
-  auto decode = [&](int wk, int& img, int& a0, int& b0) {
-    int tile = tfc_xcd_remap(wk, nwork);
-    const int txb = tile % tiles_x; tile /= tiles_x;
-    const int tyb = tile % tiles_y;
-    img = tile / tiles_y;
-    a0 = tyb * TFC_TILE_H; b0 = txb * TFC_TILE_W;
-  };
-  constexpr int NHV = (HR * HC + 255) / 256;                     // halo pixels per thread (3)
-  int hoff[NHV], hy[NHV], hx[NHV];
-#pragma unroll
-  for (int i = 0; i < NHV; ++i) {
-    const int hp = tid + i * 256;
-    hy[i] = hp / HC; hx[i] = hp - hy[i] * HC;
-    hoff[i] = hp < HR * HC ? (hy[i] * P + hx[i]) * 16 : -1;
-  }
-  uint4 hv[NHV];
-  auto halo_load = [&](int img, int a0, int b0) {
-#pragma unroll
-    for (int i = 0; i < NHV; ++i) {
-      const int y = 2 * a0 - 1 + hy[i], x = 2 * b0 - 1 + hx[i];
-      hv[i] = make_uint4(0, 0, 0, 0);
-      if (hoff[i] >= 0 && y >= 0 && y < OH && x >= 0 && x < OW) hv[i] = *reinterpret_cast<const uint4*>(dy + ((size_t)(img * OH + y) * OW + x) * dy_pitch);
-    }
-  };
-  auto halo_store = [&](unsigned char* buf) {
-#pragma unroll
-    for (int i = 0; i < NHV; ++i)
-      if (hoff[i] >= 0) *reinterpret_cast<uint4*>(buf + hoff[i]) = hv[i];
-  };
+  auto decode = [&](int wk) { return tfc_walk_decode<TFC_TILE_H, TFC_TILE_W>(wk, nwork, tiles_y, tiles_x); };
+  uint4 hv[tfc_halo_units(HR, HC, 1)];                           // 3 halo pixels per thread
+  auto halo_load = [&](const TfcTilePos& t) { tfc_halo_load<HR, HC, 1>(hv, dy, OH, OW, dy_pitch, t.img, 2 * t.a0 - 1, 2 * t.b0 - 1); };
+  auto halo_store = [&](unsigned char* buf) { tfc_halo_store<HR, HC, 1, 16, P>(buf, hv); };
   // lane pixel of m-tile ms: ty = 2 * ms + (r & 1), tx = r >> 1 -> halo pixel (2 ty, 2 tx)
   const int laneBase = ((2 * (r & 1)) * P + 2 * (r >> 1)) * 16;
   constexpr int MSTRIDE = 4 * P * 16;                            // next m-tile: ty + 2 -> 4 halo rows
 
   int wk = blockIdx.x;
-  if (wk >= nwork) return;
-  int img, a0, b0;
-  decode(wk, img, a0, b0);
-  halo_load(img, a0, b0);
+  TfcTilePos cur = decode(wk);
+  halo_load(cur);
   halo_store(smem);
   __syncthreads();
   for (int k = 0;; ++k) {
     const bool more = wk + G < nwork;
-    int n_img = 0, n_a0 = 0, n_b0 = 0;
-    if (more) { decode(wk + G, n_img, n_a0, n_b0); halo_load(n_img, n_a0, n_b0); }
+    TfcTilePos nxt{0, 0, 0};
+    if (more) { nxt = decode(wk + G); halo_load(nxt); }           // requested before the K loop, so before the stores below (vmcnt is in order)
     const unsigned char* buf = smem + (k & 1) * HB + laneBase;
     f32x16_t acc[4];
 #pragma unroll
@@ -1625,34 +1618,17 @@ tfc_dgrad_head_kernel(const bf16_t* __restrict__ dy, int dy_pitch, const float* 
       }
     if (more) halo_store(smem + ((k + 1) & 1) * HB);
     __syncthreads();
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      const int idx = tid + i * 256;
-      const int pix = idx >> 4, u = idx & 15;
-      const int a = a0 + (pix >> 4), b = b0 + (pix & 15);
-      if (a < IH && b < IW) {
-        const uint4 v = *reinterpret_cast<const uint4*>(stage + pix * ROWP + u * 16);
-        store_stream16(dx + ((size_t)(img * IH + a) * IW + b) * dx_pitch + u * 8, v);
-      }
-    }
+    tfc_stage_store<16, ROWP>(stage, dx, IH, IW, dx_pitch, 0, 0, IH, IW, 128, cur);
     if (!more) break;
-    __syncthreads();
-    wk += G; img = n_img; a0 = n_a0; b0 = n_b0;
+    __syncthreads();                                             // the staged tile is free again
+    tfc_walk_step(wk, cur, nxt);
   }
 }
 hipError_t tfc_launch_dgrad_head(const void* dy, int dy_pitch, int N, int H, int W, const float* w, int Cout, void* dx, int dx_pitch, hipStream_t st) {
-  static int grid_cap = 0;
-  if (!grid_cap) {
-    int occ = 0, dev = 0, ncu = 0;
-    hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, tfc_dgrad_head_kernel, 256, 0);
-    if (e != hipSuccess) return e;
-    if ((e = hipGetDevice(&dev)) != hipSuccess) return e;
-    if ((e = hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev)) != hipSuccess) return e;
-    grid_cap = (occ < 1 ? 1 : occ) * ncu;
-  }
   const int nwork = N * ((H + TFC_TILE_H - 1) / TFC_TILE_H) * ((W + TFC_TILE_W - 1) / TFC_TILE_W);
-  TFC_LAUNCH(tfc_dgrad_head_kernel, dim3(nwork < grid_cap ? nwork : grid_cap), dim3(256), 0, st, (const bf16_t*)dy, dy_pitch, w, Cout, (bf16_t*)dx, dx_pitch, H, W, N,
-             nwork);
+  int grid;
+  if (hipError_t e = tfc_persistent_grid<tfc_dgrad_head_kernel>(0, nwork, &grid)) return e;
+  TFC_LAUNCH(tfc_dgrad_head_kernel, dim3(grid), dim3(256), 0, st, (const bf16_t*)dy, dy_pitch, w, Cout, (bf16_t*)dx, dx_pitch, H, W, N, nwork);
   return hipGetLastError();
 }
 
@@ -3050,14 +3026,6 @@ static int match_pattern(const TfcGather& d, int es) {
   return pat < 0 ? 0 : pat;
 }
 
-static int tfc_num_cus() {
-  static int ncu = 0;
-  if (!ncu) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || ncu <= 0) ncu = 256;
-  }
-  return ncu;
-}
 // ---------------------------------------------------------------------------------------------------
 // Launch plans. Every choice that shapes the arithmetic of a convolution pass -- kernel, tile form, InstanceNorm partial slots per image, split count,
 // workgroups per image -- is made HERE, by the launchers and by tfc_conv_plan_query alike. In batch-invariant mode (tfc_set_batch_invariant)
@@ -3603,21 +3571,15 @@ bool tfc_conv_c8_eligible(const TfcGather& d, int flags) {
 }
 hipError_t tfc_launch_conv_c8(const TfcGather& d, const void* in, const void* wp, void* out, const float* bias, const float* oscale, int flags,
                               unsigned char* sign_mask, hipStream_t st) {
-  static int grid_cap = 0;
-  if (!grid_cap) {
-    int occ = 0, dev = 0, ncu = 0;
-    hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, tfc_conv_c8_kernel<true>, 256, 0);
-    if (e != hipSuccess) return e;
-    if ((e = hipGetDevice(&dev)) != hipSuccess) return e;
-    if ((e = hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev)) != hipSuccess) return e;
-    grid_cap = (occ < 1 ? 1 : occ) * ncu;
-  }
   const int nwork = d.nimg * d.tiles_y * d.tiles_x;
+  int grid;
+  if (hipError_t e = sign_mask ? tfc_persistent_grid<tfc_conv_c8_kernel<true>>(0, nwork, &grid) : tfc_persistent_grid<tfc_conv_c8_kernel<false>>(0, nwork, &grid))
+    return e;
   if (sign_mask)
-    TFC_LAUNCH(tfc_conv_c8_kernel<true>, dim3(nwork < grid_cap ? nwork : grid_cap), dim3(256), 0, st, d, (const bf16_t*)in, (const uint4*)wp,
+    TFC_LAUNCH(tfc_conv_c8_kernel<true>, dim3(grid), dim3(256), 0, st, d, (const bf16_t*)in, (const uint4*)wp,
                (bf16_t*)out, (flags & TFC_EP_BIAS) ? bias : nullptr, oscale, (flags & TFC_EP_LEAKY) ? 1 : 0, tfc_nb32_padded(d.Nout), nwork, sign_mask);
   else
-    TFC_LAUNCH(tfc_conv_c8_kernel<false>, dim3(nwork < grid_cap ? nwork : grid_cap), dim3(256), 0, st, d, (const bf16_t*)in, (const uint4*)wp,
+    TFC_LAUNCH(tfc_conv_c8_kernel<false>, dim3(grid), dim3(256), 0, st, d, (const bf16_t*)in, (const uint4*)wp,
                (bf16_t*)out, (flags & TFC_EP_BIAS) ? bias : nullptr, oscale, (flags & TFC_EP_LEAKY) ? 1 : 0, tfc_nb32_padded(d.Nout), nwork, sign_mask);
   return hipGetLastError();
 }

@@ -77,6 +77,7 @@ struct ActParams {
 // Host-side hooks shared by the translation units of the library. All per-THREAD (the reference calls forward from several Python
 // threads; nothing in the library is process-global mutable state).
 extern thread_local int g_tfc_force_cfg;          // test hook (tfc_debug_set_igemm_config): -1 = heuristic tile choice
+extern thread_local int g_tfc_persistent_grid;    // test hook (tfc_debug_set_persistent_grid): 0 = occupancy x CUs, n >= 1 = at most n workgroups
 extern thread_local long long g_tfc_launch_count; // kernel launches issued by the conv-class launchers on this thread (profiling join key)
 #define TFC_LAUNCH(...) do { ++g_tfc_launch_count; hipLaunchKernelGGL(__VA_ARGS__); } while (0)
 extern thread_local int g_tfc_batch_invariant;    // tfc_set_batch_invariant: launch plans from the per-image geometry alone
