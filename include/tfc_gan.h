@@ -156,7 +156,8 @@ int tfc_pack_nhwc8(void* stream, int dt, const float* a, int Ca, const float* b,
 int tfc_unpack_nchw(void* stream, int dt, const void* in, int pitch, int c0, int C, float* out, int N, int H, int W, float alpha, float beta);
 /* nn.Tanh backward of the generator head (P16:157) + NHWC8 packing: dyraw = g * (1 - y^2); dbias (nullable, needs part_ws): float[C] += column sums */
 int tfc_tanh_bwd_pack(void* stream, int dt, const float* g, const float* y, void* dyraw, float* dbias, int N, int C, int H, int W, float* part_ws);
-/* bias gradient: out[C] += column sums of x [rows][pitch]; part_ws (nullable): lets many rows be split over workgroups */
+/* bias gradient: out[C] += column sums of x [rows][pitch]; part_ws (nullable): lets many rows be split over workgroups.
+   x 16-byte aligned, pitch >= C, C and pitch multiples of one 16-byte unit (8 bf16 / 4 fp32), as for every activation pointer */
 int tfc_colsum(void* stream, int dt, const void* x, long long rows, int pitch, int C, float* out, float* part_ws);
 int tfc_cast(void* stream, int dt, int to_f32, const void* x, void* y, long long n);
 int tfc_axpby(void* stream, float* out, const float* x, const float* y, long long n, float a, float b);

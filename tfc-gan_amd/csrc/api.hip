@@ -652,8 +652,9 @@ static int fill_act(ActParams& p, int dt, int N, int H, int W, int C, int x_pitc
                     float drop_p, uint32_t seed) {
   REQUIRE(dt == TFC_DT_BF16 || dt == TFC_DT_F32 || dt == TFC_DT_BF16X3, "bad dtype");
   const int ue = 16 / es_of(dt);
+  REQUIRE(N > 0 && H > 0 && W > 0 && C > 0, "bad dims N=%d H=%d W=%d C=%d", N, H, W, C);
   REQUIRE(C % ue == 0, "C=%d must be a multiple of %d", C, ue);
-  const int cv = C / ue;
+  const int cv = C / ue;                                          // > 0 from here on: 256 % cv below must not divide by zero
   REQUIRE(cv <= 256 && (256 % cv) == 0, "C/%d = %d must divide 256", ue, cv);
   REQUIRE(pool >= 0 && pool <= 2, "bad pool %d", pool);
   REQUIRE(pool == 0 || (H >= 3 && W >= 3), "reflect pad needs H,W >= 3");
@@ -716,7 +717,7 @@ extern "C" int tfc_dropout_mask(void* stream, uint8_t* keep, long long n, float 
 }
 
 extern "C" int tfc_pack_nhwc8(void* stream, int dt, const float* a, int Ca, const float* b, int Cb, void* out, int N, int H, int W) {
-  REQUIRE(a && out && Ca > 0 && Ca + Cb <= 8 && (Cb == 0 || b), "bad args");
+  REQUIRE(a && out && N > 0 && H > 0 && W > 0 && Ca > 0 && Cb >= 0 && Ca + Cb <= 8 && (Cb == 0 || b), "bad args");
   CHECK_HIP(tfc_launch_pack_nhwc8(dt, a, Ca, b, Cb, out, N, H * W, (hipStream_t)stream), "tfc_pack_nhwc8");
   return 0;
 }
@@ -726,14 +727,17 @@ extern "C" int tfc_unpack_nchw(void* stream, int dt, const void* in, int pitch, 
   return 0;
 }
 extern "C" int tfc_tanh_bwd_pack(void* stream, int dt, const float* g, const float* y, void* dyraw, float* dbias, int N, int C, int H, int W, float* part_ws) {
-  REQUIRE(g && y && dyraw && C > 0 && C <= 4, "bad args (C <= 4)");
+  REQUIRE(g && y && dyraw && N > 0 && H > 0 && W > 0 && C > 0 && C <= 4, "bad args (C <= 4)");
   REQUIRE(!dbias || part_ws, "dbias needs part_ws");
   CHECK_HIP(tfc_launch_tanh_bwd_pack(dt, g, y, dyraw, dbias, part_ws, N, C, H * W, (hipStream_t)stream), "tfc_tanh_bwd_pack");
   return 0;
 }
 extern "C" int tfc_colsum(void* stream, int dt, const void* x, long long rows, int pitch, int C, float* out, float* part_ws) {
+  if (int e = check_dt(dt)) return e;
   const int ue = 16 / es_of(dt);
-  REQUIRE(x && out && rows > 0 && C % ue == 0, "bad args");
+  REQUIRE(out && rows > 0 && C > 0 && C % ue == 0, "bad args");
+  if (int e = check_ptr16(x, "x")) return e;                      // the kernel reads 16-byte units at x + row * pitch + cv * ue
+  if (int e = check_pitch(dt, pitch, C, "x")) return e;
   CHECK_HIP(tfc_launch_colsum(dt, x, rows, pitch, C, out, part_ws, (hipStream_t)stream), "tfc_colsum");
   return 0;
 }
@@ -778,7 +782,7 @@ extern "C" int tfc_spectral_norm_step(void* stream, const float* W, float* u, fl
 }
 extern "C" int tfc_spectral_norm_bwd(void* stream, const float* G, const float* W, const float* u, const float* v, const float* sigma2,
                                      float* ws, float* gout, int R, int K, int accumulate) {
-  REQUIRE(G && W && u && v && sigma2 && ws && gout && (((uintptr_t)ws) & 7) == 0, "bad args (ws: 256 floats, 8-byte aligned)");
+  REQUIRE(G && W && u && v && sigma2 && ws && gout && R > 0 && K > 0 && (((uintptr_t)ws) & 7) == 0, "bad args (ws: 256 floats, 8-byte aligned)");
   CHECK_HIP(tfc_launch_sn_bwd(G, W, u, v, sigma2, ws, gout, R, K, accumulate, (hipStream_t)stream), "tfc_spectral_norm_bwd");
   return 0;
 }
