@@ -311,11 +311,8 @@ class TrainStep:
         # loss_Pha_reg of region_fft="kl"), this rank's share of one: the mean over ranks is the global-batch value. Under batch_scope="shard" those
         # terms are normalised per shard and their logged values are the mean of per-shard values, not the reference's.
         if parallel.collectives_active():
-            keys = [k for k in self.last if self.last[k].numel() == 1]      # the scalars (not fake_B, not the heads' probabilities)
-            packed = torch.stack([self.last[k].reshape(()).float() for k in keys])
-            parallel.all_reduce_mean(packed)
-            for i, k in enumerate(keys):
-                self.last[k] = packed[i]
+            # the scalars (not fake_B, not the heads' probabilities)
+            self.last.update(parallel.all_reduce_mean_scalars({k: v for k, v in self.last.items() if v.numel() == 1}))
         return self.last
 
     # algorithmic work of one step per image: conv / convT MACs x 2

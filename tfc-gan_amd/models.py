@@ -122,27 +122,18 @@ class _DownFn(torch.autograd.Function):
             xv = ops.View(t, t.shape[3])
         N, H, W, _ = xv.t.shape
         wf = w.detach().float().contiguous()
-        raw = ops.new_act(N, H - 1, W - 1, cout, dt, x.device)
-        stats = torch.zeros((N, cout, 2), dtype=torch.float32, device=x.device) if normalize else None
-        ops.conv_fwd(dt, ops.OP_CONV, xv, cin, cout, ops.pack_weight(dt, ops.OP_CONV, 0, wf, cin, cout), raw, stats=stats)
         y = ops.new_act(N, nets.pooled(H - 1), nets.pooled(W - 1), cout, dt, x.device)
-        ops.act_fwd(dt, raw, y, stats=stats, slope=0.2, pool=2, drop_p=drop_p, seed=seed)
-        ctx.saved = (xv, wf, raw, stats, normalize, drop_p, seed, dt, cin, cout)
+        raw, stats = nets.down_block_fwd(dt, xv, cin, cout, ops.pack_weight(dt, ops.OP_CONV, 0, wf, cin, cout), y, normalize, drop_p, seed)
+        ctx.saved = (xv, wf, raw, stats, drop_p, seed, dt, cin, cout)
         ctx.x_needs = x.requires_grad
         return _to_nchw(y, x)
 
     @staticmethod
     def backward(ctx, g):
-        xv, wf, raw, stats, normalize, drop_p, seed, dt, cin, cout = ctx.saved
-        N, Hc, Wc = raw.N, raw.H, raw.W
-        gv = _to_nhwc(g, dt)
-        d_raw = ops.new_act(N, Hc, Wc, cout, dt, g.device)
-        if normalize:
-            rstats = torch.zeros((N, cout, 2), dtype=torch.float32, device=g.device)
-            ops.act_bwd(dt, 1, gv, raw, N, Hc, Wc, cout, None, stats=stats, slope=0.2, pool=2, drop_p=drop_p, seed=seed, rstats=rstats)
-            ops.act_bwd(dt, 2, gv, raw, N, Hc, Wc, cout, d_raw, stats=stats, slope=0.2, pool=2, drop_p=drop_p, seed=seed, rstats=rstats)
-        else:
-            ops.act_bwd(dt, 0, gv, raw, N, Hc, Wc, cout, d_raw, stats=None, slope=0.2, pool=2, drop_p=drop_p, seed=seed)
+        xv, wf, raw, stats, drop_p, seed, dt, cin, cout = ctx.saved
+        N = raw.N
+        d_raw = ops.new_act(N, raw.H, raw.W, cout, dt, g.device)
+        nets.norm_act_bwd(dt, _to_nhwc(g, dt), raw, d_raw, stats, 0.2, 2, drop_p, seed)
         gw = torch.empty_like(wf)
         ops.conv_wgrad(dt, ops.OP_CONV, xv, d_raw, cin, cout, gw)
         gx = None
@@ -163,31 +154,19 @@ class _UpFn(torch.autograd.Function):
         xv = _to_nhwc(x, dt)
         N, H, W, _ = xv.t.shape
         wf = w.detach().float().contiguous()
-        rawT = ops.new_act(N, 2 * H, 2 * W, cout, dt, x.device)
-        ops.conv_fwd(dt, ops.OP_CONVT, xv, cin, cout, ops.pack_weight(dt, ops.OP_CONVT, 0, wf, cin, cout), rawT)
-        blur = ops.new_act(N, 2 * H, 2 * W, cout, dt, x.device)
-        bstats = torch.zeros((N, cout, 2), dtype=torch.float32, device=x.device)
-        ops.act_fwd(dt, rawT, blur, stats=None, slope=1.0, pool=1, stats_out=bstats)
         y = ops.new_act(N, 2 * H, 2 * W, cout, dt, x.device)
-        ops.act_fwd(dt, blur, y, stats=bstats, slope=0.0, pool=0, drop_p=drop_p, seed=seed)
+        blur, bstats = nets.up_block_fwd(dt, xv, cin, cout, ops.pack_weight(dt, ops.OP_CONVT, 0, wf, cin, cout), y, drop_p, seed)
         ctx.saved = (xv, wf, blur, bstats, drop_p, seed, dt, cin, cout)
         return _to_nchw(y, x)
 
     @staticmethod
     def backward(ctx, g):
         xv, wf, blur, bstats, drop_p, seed, dt, cin, cout = ctx.saved
-        N, H, W = blur.N, blur.H, blur.W
-        gv = _to_nhwc(g, dt)
-        rstats = torch.zeros((N, cout, 2), dtype=torch.float32, device=g.device)
-        ops.act_bwd(dt, 1, gv, blur, N, H, W, cout, None, stats=bstats, slope=0.0, pool=0, drop_p=drop_p, seed=seed, rstats=rstats)
-        d_blur = ops.new_act(N, H, W, cout, dt, g.device)
-        ops.act_bwd(dt, 2, gv, blur, N, H, W, cout, d_blur, stats=bstats, slope=0.0, pool=0, drop_p=drop_p, seed=seed, rstats=rstats)
-        d_rawT = ops.new_act(N, H, W, cout, dt, g.device)
-        ops.act_bwd(dt, 0, d_blur, None, N, H, W, cout, d_rawT, stats=None, slope=1.0, pool=1)
+        _, d_rawT = nets.up_block_act_bwd(dt, _to_nhwc(g, dt), blur, bstats, drop_p, seed)
         gw = torch.empty_like(wf)
         ops.conv_wgrad(dt, ops.OP_CONVT, xv, d_rawT, cin, cout, gw)
-        dx = ops.new_act(N, xv.H, xv.W, cin, dt, g.device)
-        ops.conv_dgrad(dt, ops.OP_CONVT, d_rawT, N, xv.H, xv.W, cin, cout, ops.pack_weight(dt, ops.OP_CONVT, 1, wf, cin, cout), dx)
+        dx = ops.new_act(xv.N, xv.H, xv.W, cin, dt, g.device)
+        ops.conv_dgrad(dt, ops.OP_CONVT, d_rawT, xv.N, xv.H, xv.W, cin, cout, ops.pack_weight(dt, ops.OP_CONVT, 1, wf, cin, cout), dx)
         return _to_nchw(dx, g), gw, None, None, None
 
 
@@ -225,6 +204,37 @@ class UNetUp(nn.Module):
         return torch.cat((y, skip_input.to(y.dtype)), 1)
 
 
+class _CoreModule:
+    """What the three network modules share: a core of nets.py on the module's own parameters, rebuilt when the compute dtype changes and re-packed
+    when the weights do. A module gives `_make_core(dt)` and `named_core_params()`; with `_core_buffers` its `named_core_buffers()` are the core's
+    second argument and part of the key."""
+    _core_buffers = False
+
+    def _init_core(self):
+        self.compute_dtype = None            # None -> package default
+        self._core = None
+        self._core_key = None
+        self._weights_gen = 0                # bumped by the step engines after each raw-pointer Adam update (neither data_ptr nor _version moves)
+
+    def _core_for(self, device):
+        dt = ops.dt_of(self.compute_dtype or get_compute_dtype())
+        params = self.named_core_params()
+        bufs = self.named_core_buffers() if self._core_buffers else {}
+        key = ((dt, str(device), self._weights_gen) + tuple((p.data_ptr(), p._version) for p in params.values())
+               + tuple(b.data_ptr() for b in bufs.values()))
+        if self._core is None or self._core.dt != dt:
+            self._core = self._make_core(dt)
+        if key != self._core_key:
+            for k, p in list(params.items()) + list(bufs.items()):
+                if p.dtype != torch.float32 or not p.is_cuda:
+                    raise ops._lib.TfcError(f"{type(self).__name__} {'tensor' if self._core_buffers else 'parameter'} {k} must be an fp32 CUDA tensor "
+                                            f"(got {p.dtype}, {p.device})")
+            self._core.set_params({k: p.detach() for k, p in params.items()}, *([dict(bufs)] if self._core_buffers else []))
+            self._core.repack()
+            self._core_key = key
+        return self._core
+
+
 class _GeneratorFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, module, x, seed, *params):
@@ -246,18 +256,19 @@ class _GeneratorFn(torch.autograd.Function):
 def _refuse_autograd(module, tensors):
     """the label-conditioned forms train through TrainStep only: their modules' own forward carries no autograd graph, so it refuses to run where one
     is expected instead of leaving None gradients behind"""
-    if getattr(module, "mask", False) and torch.is_grad_enabled() and (any(p.requires_grad for p in module.parameters())
-                                                                      or any(torch.is_tensor(t) and t.requires_grad for t in tensors)):
+    if not (torch.is_grad_enabled() and (any(p.requires_grad for p in module.parameters())
+                                         or any(torch.is_tensor(t) and t.requires_grad for t in tensors))):
+        return
+    if getattr(module, "mask", False):
         raise ops._lib.TfcError(f"{type(module).__name__}: the mask-fed forward (edge mask as the 4th input channel) has no autograd backward. Train with "
                                 "tfc_gan_amd.TrainStep(G, D, patches=4, mask=True, **tfc_gan_amd.mask_weights()), which runs its hand-written backward; "
                                 "call the module itself under torch.no_grad() (sample_images, inference).")
-    if torch.is_grad_enabled() and (any(p.requires_grad for p in module.parameters()) or any(torch.is_tensor(t) and t.requires_grad for t in tensors)):
-        raise ops._lib.TfcError(f"{type(module).__name__}: the label-conditioned forward (label plane / auxiliary heads) has no autograd backward. Train with "
-                                "tfc_gan_amd.TrainStep(G, D, **tfc_gan_amd.debias_weights(kind), patches=4), which runs its hand-written backward; "
-                                "call the module itself under torch.no_grad() (sample_images, inference).")
+    raise ops._lib.TfcError(f"{type(module).__name__}: the label-conditioned forward (label plane / auxiliary heads) has no autograd backward. Train with "
+                            "tfc_gan_amd.TrainStep(G, D, **tfc_gan_amd.debias_weights(kind), patches=4), which runs its hand-written backward; "
+                            "call the module itself under torch.no_grad() (sample_images, inference).")
 
 
-class GeneratorUNet(nn.Module):
+class GeneratorUNet(_CoreModule, nn.Module):
     """reference :136-174. forward(x[N,3,S,S]) -> fake_B in (-1,1), fp32 NCHW (the reference casts to HalfTensor, :173).
     labels=3: the label-conditioned generator of TFCGAN_multigpu_patchFFT_debiased.py:142-186 -- fc = nn.Linear(3, h*w) of the labels, reshaped to a
     plane, is the 4th input channel of down1; forward(x, labels[N,3]).
@@ -288,29 +299,14 @@ class GeneratorUNet(nn.Module):
         self.up5 = UNetUp(256, 64)
         self.final = nn.Sequential(nn.Upsample(scale_factor=2), nn.ZeroPad2d((1, 0, 1, 0)), nn.Conv2d(128, channels, 4, padding=1), nn.Tanh())
         self.channels = channels
-        self.compute_dtype = None            # None -> package default
-        self._core = None
-        self._core_key = None
-        self._weights_gen = 0                # bumped by TrainStep after each raw-pointer Adam update (neither data_ptr nor _version moves)
+        self._init_core()
 
     def named_core_params(self):
         sd = dict(self.named_parameters())
         return {k: sd[k] for k in nets.g_param_names(self.labels)}
 
-    def _core_for(self, device):
-        dt = ops.dt_of(self.compute_dtype or get_compute_dtype())
-        params = self.named_core_params()
-        key = (dt, str(device), self._weights_gen) + tuple((p.data_ptr(), p._version) for p in params.values())
-        if self._core is None or self._core.dt != dt:
-            self._core = nets.GeneratorCore(dt, self.channels, self.labels, self.mask)
-        if key != self._core_key:
-            for k, p in params.items():
-                if p.dtype != torch.float32 or not p.is_cuda:
-                    raise ops._lib.TfcError(f"GeneratorUNet parameter {k} must be an fp32 CUDA tensor (got {p.dtype}, {p.device})")
-            self._core.set_params({k: p.detach() for k, p in params.items()})
-            self._core.repack()
-            self._core_key = key
-        return self._core
+    def _make_core(self, dt):
+        return nets.GeneratorCore(dt, self.channels, self.labels, self.mask)
 
     def forward(self, x, labels=None, mask_A=None):
         _refuse_replica(self)
@@ -338,13 +334,15 @@ class GeneratorUNet(nn.Module):
         return _GeneratorFn.apply(self, x, _next_seed(self), *params.values())
 
 
-class _DiscriminatorFn(torch.autograd.Function):
+class _PatchGANFn(torch.autograd.Function):
+    """both discriminators: `params` are the module's named_core_params() and `names` their keys; `fwd_kw` is what its core's forward takes beside
+    the two images"""
+
     @staticmethod
-    def forward(ctx, module, img_a, img_b, *params):
+    def forward(ctx, module, names, fwd_kw, img_a, img_b, *params):
         core = module._core_for(img_a.device)
-        logits, dctx = core.forward(img_a.detach().float().contiguous(), img_b.detach().float().contiguous(),
-                                    power_iter=module.training)
-        ctx.core, ctx.dctx = core, dctx
+        logits, dctx = core.forward(img_a.detach().float().contiguous(), img_b.detach().float().contiguous(), **fwd_kw)
+        ctx.core, ctx.dctx, ctx.names = core, dctx, names
         ctx.need_a = img_a.requires_grad
         ctx.need_w = any(p.requires_grad for p in params)
         N, H, W = logits.N, logits.H, logits.W
@@ -352,22 +350,21 @@ class _DiscriminatorFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g):
-        core, dctx = ctx.core, ctx.dctx
-        dt = core.dt
+        core, dctx, names = ctx.core, ctx.dctx, ctx.names
         N, _, H, W = g.shape
-        gl = ops.new_act(N, H, W, 8, dt, g.device, zero=True)
+        gl = ops.new_act(N, H, W, 8, core.dt, g.device, zero=True)
         gl.t[..., 0] = g.reshape(N, H, W).to(gl.t.dtype)
-        names = nets.d_param_names()
         grads = {k: torch.empty_like(core.params[k]) for k in names} if ctx.need_w else None
         ga = core.backward(dctx, gl, grads, need_input_grad=ctx.need_a)
         ctx.dctx = None
-        return (None, ga, None) + (tuple(grads[k] for k in names) if grads else (None,) * len(names))
+        return (None, None, None, ga, None) + (tuple(grads[k] for k in names) if grads else (None,) * len(names))
 
 
-class Discriminator1(nn.Module):
+class Discriminator1(_CoreModule, nn.Module):
     """reference :182-211 (spectral-norm PatchGAN). forward(img_A, img_B) -> logits [N,1,S/16,S/16] fp32.
     aux_classes=(2, 4, 3): the label-conditioned discriminator of TFCGAN_multigpu_patchFFT_debiased.py:194-233 -- aux_gender / aux_ethn / aux_age, each
     nn.Sequential(nn.Linear(6*h*w, C), nn.Softmax()) on the flattened input; forward then returns (logits, gender_hat, ethn_hat, age_hat)."""
+    _core_buffers = True                     # u / v of the spectral norm: the core updates them in place
 
     def __init__(self, img_shape, aux_classes=None):
         super().__init__()
@@ -387,14 +384,14 @@ class Discriminator1(nn.Module):
             for name, c in nets.D_AUX:
                 setattr(self, name, nn.Sequential(nn.Linear(channels * 2 * self.h * self.w, c), nn.Softmax(dim=1)))
         self.channels = channels
-        self.compute_dtype = None
-        self._core = None
-        self._core_key = None
-        self._weights_gen = 0
+        self._init_core()
 
     def named_core_params(self):
         sd = dict(self.named_parameters())
         return {k: sd[k] for k in nets.d_param_names(bool(self.aux_classes))}
+
+    def _make_core(self, dt):
+        return nets.DiscriminatorCore(dt, self.channels, self.aux_classes)
 
     def named_core_buffers(self):
         sd = dict(self.named_buffers())
@@ -404,21 +401,6 @@ class Discriminator1(nn.Module):
                 k = f"model.{i}.parametrizations.weight.0.{s}"
                 out[k] = sd[k]
         return out
-
-    def _core_for(self, device):
-        dt = ops.dt_of(self.compute_dtype or get_compute_dtype())
-        params, bufs = self.named_core_params(), self.named_core_buffers()
-        key = (dt, str(device), self._weights_gen) + tuple((p.data_ptr(), p._version) for p in params.values()) + tuple(b.data_ptr() for b in bufs.values())
-        if self._core is None or self._core.dt != dt:
-            self._core = nets.DiscriminatorCore(dt, self.channels, self.aux_classes)
-        if key != self._core_key:
-            for k, p in list(params.items()) + list(bufs.items()):
-                if p.dtype != torch.float32 or not p.is_cuda:
-                    raise ops._lib.TfcError(f"Discriminator1 tensor {k} must be an fp32 CUDA tensor (got {p.dtype}, {p.device})")
-            self._core.set_params({k: p.detach() for k, p in params.items()}, dict(bufs))
-            self._core.repack()
-            self._core_key = key
-        return self._core
 
     def forward(self, img_A, img_B):
         _refuse_replica(self)
@@ -433,34 +415,10 @@ class Discriminator1(nn.Module):
             hats = torch.split(probs, list(self.aux_classes), dim=1)
             return (logits.t[..., 0].reshape(N, 1, logits.H, logits.W).float(),) + tuple(h.contiguous() for h in hats)
         params = self.named_core_params()
-        return _DiscriminatorFn.apply(self, img_A, img_B, *params.values())
+        return _PatchGANFn.apply(self, tuple(params), {"power_iter": self.training}, img_A, img_B, *params.values())
 
 
-class _Pix2PixFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, module, img_a, img_b, *params):
-        core = module._core_for(img_a.device)
-        logits, dctx = core.forward(img_a.detach().float().contiguous(), img_b.detach().float().contiguous())
-        ctx.core, ctx.dctx = core, dctx
-        ctx.need_a = img_a.requires_grad
-        ctx.need_w = any(p.requires_grad for p in params)
-        N, H, W = logits.N, logits.H, logits.W
-        return logits.t[..., 0].reshape(N, 1, H, W).float()
-
-    @staticmethod
-    def backward(ctx, g):
-        core, dctx = ctx.core, ctx.dctx
-        N, _, H, W = g.shape
-        gl = ops.new_act(N, H, W, 8, core.dt, g.device, zero=True)
-        gl.t[..., 0] = g.reshape(N, H, W).to(gl.t.dtype)
-        names = nets.p2p_param_names()
-        grads = {k: torch.empty_like(core.params[k]) for k in names} if ctx.need_w else None
-        ga = core.backward(dctx, gl, grads, need_input_grad=ctx.need_a)
-        ctx.dctx = None
-        return (None, ga, None) + (tuple(grads[k] for k in names) if grads else (None,) * len(names))
-
-
-class Pix2PixDiscriminator(nn.Module):
+class Pix2PixDiscriminator(_CoreModule, nn.Module):
     """The plain pix2pix PatchGAN of TFC-STN/TFCGAN_STN21_Eur_DarkVisible.py:370-423 (its Discriminator1 / Discriminator2, and the same block in the
     archived STN scripts, cyclegan_og and ThermalGAN): four blocks Conv2d(k4, stride 2, p1, bias) -> [InstanceNorm2d, not the first] ->
     LeakyReLU(0.2), then ZeroPad2d((1, 0, 1, 0)) + Conv2d(512, 1, 4, padding=1, bias=False). No spectral norm, no BlurPool.
@@ -484,10 +442,7 @@ class Pix2PixDiscriminator(nn.Module):
         mods[nets.P2P_HEAD] = nn.Conv2d(cin, 1, kernel_size=4, padding=1, bias=False)
         assert sorted(mods) == list(range(nets.P2P_HEAD + 1))
         self.model = nn.Sequential(*(mods[i] for i in range(nets.P2P_HEAD + 1)))
-        self.compute_dtype = None
-        self._core = None
-        self._core_key = None
-        self._weights_gen = 0                # bumped by the step engines after each raw-pointer Adam update
+        self._init_core()
 
     def named_core_params(self):
         sd = dict(self.named_parameters())
@@ -496,25 +451,13 @@ class Pix2PixDiscriminator(nn.Module):
     def named_core_buffers(self):
         return {}
 
-    def _core_for(self, device):
-        dt = ops.dt_of(self.compute_dtype or get_compute_dtype())
-        params = self.named_core_params()
-        key = (dt, str(device), self._weights_gen) + tuple((p.data_ptr(), p._version) for p in params.values())
-        if self._core is None or self._core.dt != dt:
-            self._core = nets.Pix2PixCore(dt, self.channels)
-        if key != self._core_key:
-            for k, p in params.items():
-                if p.dtype != torch.float32 or not p.is_cuda:
-                    raise ops._lib.TfcError(f"Pix2PixDiscriminator parameter {k} must be an fp32 CUDA tensor (got {p.dtype}, {p.device})")
-            self._core.set_params({k: p.detach() for k, p in params.items()})
-            self._core.repack()
-            self._core_key = key
-        return self._core
+    def _make_core(self, dt):
+        return nets.Pix2PixCore(dt, self.channels)
 
     def forward(self, img_A, img_B):
         _refuse_replica(self)
         params = self.named_core_params()
-        return _Pix2PixFn.apply(self, img_A, img_B, *params.values())
+        return _PatchGANFn.apply(self, tuple(params), {}, img_A, img_B, *params.values())
 
 
 # The reference script names the class Discriminator1; older scripts of the same repo (TFC-STN/archive/*) call the identical

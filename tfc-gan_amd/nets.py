@@ -1,8 +1,13 @@
-"""Forward / backward orchestration of the two networks of the PATCH-16 path on the HIP kernels.
+"""Forward / backward orchestration of the networks on the HIP kernels.
 
 `GeneratorCore` mirrors GeneratorUNet (reference TFCGAN_multigpu_patchFFT_16P.py:136-174), `DiscriminatorCore` mirrors
-Discriminator1 (:182-211).  Both work on raw NHWC buffers and hand-written backward chains (no autograd inside); the
-nn.Module mirrors in models.py wrap them in torch.autograd.Function, and engine.py calls them directly.
+Discriminator1 (:182-211), `Pix2PixCore` the plain PatchGAN of the DarkVisible script.  All work on raw NHWC buffers and hand-written
+backward chains (no autograd inside); the nn.Module mirrors in models.py wrap them in torch.autograd.Function, and engine.py calls them directly.
+
+Layout: the side stream, the tables and parameter names, then the BLOCK STEPS -- every sequence of launches that more than one network runs (a
+block's forward, its activation backward, a parameter gradient on the side stream with its hooks, the PatchGAN head, operand-stream planning),
+each written once as a plain function -- and the three cores, whose loops are built from those steps. The stand-alone UNetDown / UNetUp of
+models.py call the same steps.
 
 Skip connections never copy: each UNetUp output and its skip tensor are two channel windows of ONE concat buffer,
 the down path writes its pooled output straight into the skip window, and the transposed convolution reads the whole
@@ -31,7 +36,7 @@ def set_wgrad_stream(on):
     return prev
 
 
-def _side_active():
+def side_stream_on():
     """side stream in use? Not under a gloo process group: its collectives on device tensors block the host until the stream they were issued on has
     drained, which serialises the two streams the hard way (one-card rehearsal, 2 ranks: 53 ms per step on one stream, 180-500 ms on two). RCCL's are
     stream-ordered and return at once."""
@@ -50,37 +55,30 @@ def _side_stream(dev):
     return st
 
 
-def _on_side(dev, fn, *tensors):
+def on_side(dev, fn, *tensors):
     """run fn() on the side stream behind everything queued on the current stream so far; `tensors` are temporaries fn reads that the caller drops
-    before the join (the caching allocator must not hand them out again until the side stream is done with them)"""
-    if not _side_active():
+    before the join (the caching allocator must not hand them out again until the side stream is done with them); a None among them is skipped"""
+    if not side_stream_on():
         return fn()
     cur, st = torch.cuda.current_stream(dev), _side_stream(dev)
     st.wait_stream(cur)
     with torch.cuda.stream(st):
         out = fn()
     for t in tensors:
-        (t.t if isinstance(t, View) else t).record_stream(st)
+        if t is not None:
+            (t.t if isinstance(t, View) else t).record_stream(st)
     return out
 
 
-def _join_side(dev):
-    if _side_active():
+def join_side(dev):
+    if side_stream_on():
         torch.cuda.current_stream(dev).wait_stream(_side_stream(dev))
-
-
-# the engine's names for the same three
-def side_stream_on():
-    return _side_active()
-
-
-on_side, join_side = _on_side, _join_side
 
 
 def side_mark(dev):
     """an event behind everything queued on the side stream so far (None when the side stream is not in use); wait_mark() makes the caller's stream wait
     for it -- a partial join: what was queued on the side stream AFTER the mark keeps running beside the caller"""
-    if not _side_active():
+    if not side_stream_on():
         return None
     ev = torch.cuda.Event()
     ev.record(_side_stream(dev))
@@ -173,6 +171,156 @@ class _Ctx:
     pass
 
 
+# ---- block steps: every sequence of launches that more than one network runs, written once ------------------------------------------------------
+# The cores below and the stand-alone blocks of models.py are loops and call sequences over these. A `core` argument is any of the three cores:
+# the steps read its dt and debug, and keep the persistent weight-gradient scratch in its _ws.
+
+def plan_streams(dt, entries, packed):
+    """one PackPlan for the operand streams of a network. entries: (slot, op, pass, weight, Cin, Cout); every stream is filed as packed[slot]"""
+    plan = ops.PackPlan(dt, [e[1:] for e in entries])
+    for (slot, *_), buf in zip(entries, plan.streams):
+        packed[slot] = buf
+    return plan
+
+
+def param_grad(dev, work, hook=None, keys=(), keep=()):
+    """a parameter gradient, the way every one of them runs: work() on the side stream, hook(key) for each of `keys` behind it in that order (the
+    bucket reducers count on it), the temporaries `keep` that work() reads held until the side stream is done with them. Returns what work() returns;
+    the caller's backward() joins."""
+    def run():
+        out = work()
+        if hook:
+            for k in keys:
+                hook(k)
+        return out
+    return on_side(dev, run, *keep)
+
+
+def bias_grad(sums, gbias, accumulate):
+    """bias gradient from the per-image sums [N, Cout] an activation backward left behind: zero unless accumulating, then their column sum.
+    sums None: a bias in front of an InstanceNorm, whose gradient is exactly zero."""
+    if not accumulate:
+        gbias.zero_()
+    if sums is not None:
+        N, cout = sums.shape
+        ops.colsum(ops.DT_F32, View(sums.view(N, 1, 1, cout), cout), gbias)
+
+
+def norm_act_bwd(dt, g, x, d_x, stats, slope, pool, drop_p=0.0, seed=0, bias_sums=None):
+    """backward of [InstanceNorm] -> activation(slope) -> [BlurPool(pool)] -> [Dropout] into d_x, which gives the sizes. stats (of the forward): the
+    reduction pass (mode 1) into fresh rstats, then the pass that uses them (mode 2). stats None: one pass (mode 0), which also leaves the per-image
+    sums of d_x -- the bias gradient of the convolution in front -- in bias_sums where the caller gives that buffer."""
+    N, H, W, C = d_x.N, d_x.H, d_x.W, d_x.C
+    if stats is not None:
+        rstats = ops.zeros_f32((N, C, 2), d_x.t.device)
+        ops.act_bwd(dt, 1, g, x, N, H, W, C, None, stats=stats, slope=slope, pool=pool, drop_p=drop_p, seed=seed, rstats=rstats)
+        ops.act_bwd(dt, 2, g, x, N, H, W, C, d_x, stats=stats, slope=slope, pool=pool, drop_p=drop_p, seed=seed, rstats=rstats)
+    else:
+        ops.act_bwd(dt, 0, g, x, N, H, W, C, d_x, stats=None, slope=slope, pool=pool, drop_p=drop_p, seed=seed, rstats=bias_sums)
+
+
+def down_block_fwd(dt, x, cin, cout, packed, dst, normalize, drop_p=0.0, seed=0):
+    """Conv2d(k4,s1,p1,no bias) -> [InstanceNorm2d] -> LeakyReLU(0.2) -> BlurPool(s2) -> [Dropout] into dst (unfused: the conv output is stored).
+    Returns (raw, stats) for the backward."""
+    dev = x.t.device
+    raw = new_act(x.N, x.H - 1, x.W - 1, cout, dt, dev)
+    stats = ops.zeros_f32((x.N, cout, 2), dev) if normalize else None
+    ops.conv_fwd(dt, OP_CONV, x, cin, cout, packed, raw, stats=stats)
+    ops.act_fwd(dt, raw, dst, stats=stats, slope=0.2, pool=2, drop_p=drop_p, seed=seed)
+    return raw, stats
+
+
+def up_block_fwd(dt, x, cin, cout, packed, dst, drop_p=0.0, seed=0):
+    """ConvTranspose2d(k4,s2,p1,no bias) -> BlurPool(s1) -> InstanceNorm2d -> ReLU -> [Dropout] into dst. Returns (blur, bstats) for the backward."""
+    dev = x.t.device
+    rawT = new_act(x.N, 2 * x.H, 2 * x.W, cout, dt, dev)
+    ops.conv_fwd(dt, OP_CONVT, x, cin, cout, packed, rawT)
+    blur = new_act(x.N, 2 * x.H, 2 * x.W, cout, dt, dev)
+    bstats = ops.zeros_f32((x.N, cout, 2), dev)
+    ops.act_fwd(dt, rawT, blur, stats=None, slope=1.0, pool=1, stats_out=bstats)
+    ops.act_fwd(dt, blur, dst, stats=bstats, slope=0.0, pool=0, drop_p=drop_p, seed=seed)
+    return blur, bstats
+
+
+def up_block_act_bwd(dt, g_out, blur, bstats, drop_p=0.0, seed=0):
+    """backward of up_block_fwd from the gradient of its output through to the transposed convolution's output. Returns (d_blur, d_rawT)."""
+    N, H, W, C = blur.N, blur.H, blur.W, blur.C
+    dev = blur.t.device
+    d_blur = new_act(N, H, W, C, dt, dev)
+    norm_act_bwd(dt, g_out, blur, d_blur, bstats, 0.0, 0, drop_p, seed)
+    d_rawT = new_act(N, H, W, C, dt, dev)
+    ops.act_bwd(dt, 0, d_blur, None, N, H, W, C, d_rawT, stats=None, slope=1.0, pool=1)
+    return d_blur, d_rawT
+
+
+def first_block_fwd(core, ctx, x, cin, cout, packed, dst, save, bias=None, oscale=None, act_in_conv=False, seed=0):
+    """conv [+ bias, x 1/sigma] -> LeakyReLU(0.2) -> BlurPool(s2) of a network's first block (8 padded input channels, no norm, no dropout) into dst,
+    one of three ways:
+      fused       ops.first_block_fwd: ONE kernel, the 266 MB conv output is never written; returns None for it. Not while core.debug is set.
+      sign words  ops.conv_first_fwd stores the conv output and leaves one sign bit per value, all the fused backward reads of it
+      plain       the convolution and the pooling pass of any down block (a layer the first-block kernels do not serve, or nothing to save)
+    ctx.mask1: the sign words of the first two (None: none written). Returns the stored conv output, or None.
+    act_in_conv: LeakyReLU in the convolution's epilogue -- the stored tensor is the ACTIVATED one, and the backward's slope test (y > 0) is the same
+    on y = LeakyReLU(z) as on z -- instead of in the pooling pass on the rounded conv output."""
+    dt, dev = core.dt, x.t.device
+    N, h = x.N, x.H
+    signs = ops.first_block_bwd_supported(dt, cin, cout)
+    fused = signs and core.debug is None and ops.first_block_fwd_supported()
+    ctx.mask1 = torch.empty((N, h - 1, h - 1, 8), dtype=torch.uint8, device=dev) if signs and save else None
+    if fused:
+        ops.first_block_fwd(dt, x, cin, cout, packed, dst, bias=bias, oscale=oscale, slope=0.2, act_after_rounding=not act_in_conv, sign_mask=ctx.mask1)
+        return None
+    raw = new_act(N, h - 1, h - 1, cout, dt, dev)
+    flags = ops.EP_LEAKY if act_in_conv else 0
+    if ctx.mask1 is not None:
+        ops.conv_first_fwd(dt, x, cin, cout, packed, raw, bias=bias, oscale=oscale, flags=flags, sign_mask=ctx.mask1)
+    else:
+        ops.conv_fwd(dt, OP_CONV, x, cin, cout, packed, raw, bias=bias, oscale=oscale, flags=flags)
+    ops.act_fwd(dt, raw, dst, stats=None, slope=1.0 if act_in_conv else 0.2, pool=2, seed=seed)
+    return raw
+
+
+def first_block_bwd(core, ctx, g, x, raw, cin, cout, want_d_raw, accumulate=False, bias_sums=None, seed=0):
+    """backward of first_block_fwd's block, from the gradient g of its pooled output. Returns (d_raw, wgrad); wgrad(dw) computes the weight gradient
+    into dw (for param_grad) and returns the scratch for core._ws.
+    Where nothing but the parameter gradients needs the 266 MB gradient of the conv output (want_d_raw False) it is never written: d_raw is None and
+    wgrad is ops.first_block_bwd_wgrad (igemm.hip: tfc_act_bwd(mode 0, pool 2) + tfc_conv_wgrad in one kernel, same bits), which also fills
+    bias_sums. Otherwise d_raw comes from the sign words (a fused forward stored no conv output: raw None) or from the stored tensor, with the
+    per-image sums in bias_sums, and wgrad is the plain convolution weight gradient. core.debug keeps the unfused form."""
+    dt = core.dt
+    N, Hc = x.N, x.H - 1
+    if not want_d_raw and core.debug is None and ops.first_block_bwd_supported(dt, cin, cout) and pooled(Hc) >= 2:
+        return None, lambda dw: ops.first_block_bwd_wgrad(dt, x, raw, g, cin, cout, dw, slope=0.2, accumulate=accumulate, ws=core._ws,
+                                                          bias_sums=bias_sums, sign_mask=ctx.mask1)
+    d_raw = new_act(N, Hc, Hc, cout, dt, x.t.device)
+    if raw is None:
+        ops.act_bwd_signs(dt, g, ctx.mask1, N, Hc, Hc, cout, d_raw, slope=0.2, rstats=bias_sums)
+    else:
+        norm_act_bwd(dt, g, raw, d_raw, None, 0.2, 2, seed=seed, bias_sums=bias_sums)
+    return d_raw, lambda dw: ops.conv_wgrad(dt, OP_CONV, x, d_raw, cin, cout, dw, accumulate, core._ws)
+
+
+def patchgan_head_fwd(dt, ctx, cur, weight, save):
+    """ZeroPad2d((1, 0, 1, 0)) + Conv2d(512, 1, 4, padding=1, no bias) of both discriminators. Returns (logits View, pitch 8, channel 0; ctx or None)"""
+    logits = new_act(ctx.N, cur.H, cur.W, 8, dt, cur.t.device)    # only channel 0 is ever written or read (bce: stride 8; modules: [..., 0])
+    ops.patchgan_head_fwd(dt, cur, weight, View(logits.t, 1, 0))
+    ctx.p4 = cur
+    return View(logits.t, 1, 0), (ctx if save else None)
+
+
+def patchgan_head_bwd(core, ctx, g_logits, grads, key, packed, accumulate, hook):
+    """backward of patchgan_head_fwd: the head's weight gradient (grads[key], where gradients are wanted) as a param_grad, and the gradient of the
+    512-channel features it read, which is returned. g_logits: View [N,h,w,8] (channel 0 = gradient, channels 1..7 zero)."""
+    dt, p4 = core.dt, ctx.p4
+    dev = g_logits.t.device
+    gl = View(g_logits.t, 8, 0)
+    if grads is not None:
+        core._ws = param_grad(dev, lambda: ops.conv_wgrad(dt, OP_PADCONV, p4, gl, 512, 1, grads[key], accumulate, core._ws), hook, (key,))
+    g_cur = new_act(ctx.N, p4.H, p4.W, 512, dt, dev)
+    ops.conv_dgrad(dt, OP_PADCONV, gl, ctx.N, p4.H, p4.W, 512, 1, packed, g_cur)
+    return g_cur
+
+
 class GeneratorCore:
     def __init__(self, dt=DT_BF16, channels=3, labels=0, mask=False):
         self.dt = dt
@@ -184,8 +332,10 @@ class GeneratorCore:
         self.in_channels = channels + (1 if (self.labels or self.mask) else 0)
         self.down = [(G_DOWN[0][0], self.in_channels) + G_DOWN[0][2:]] + G_DOWN[1:]
         self.params = None
-        self.packed = {}
-        self._ws = None
+        self.packed = {}                                          # (block name, "fwd" | "dgrad") -> operand stream
+        self._plan = None
+        self._ws = None                                           # persistent wgrad scratch (zeroed once, re-zeroed by the kernels)
+        self.debug = None                                         # tests: a dict that receives the stored gradients; selects the unfused first block
 
     # ---- weights ----
     def set_params(self, params):
@@ -196,26 +346,24 @@ class GeneratorCore:
 
     def repack(self):
         """re-pack every operand stream (fwd + dgrad) from the current weights: ONE launch over a device-resident plan"""
-        if getattr(self, "_plan", None) is None:
-            P, jobs, slots = self.params, [], []
+        if self._plan is None:
+            P, entries = self.params, []
             for name, cin, cout, _, _ in self.down:
-                jobs.append((OP_CONV, 0, P[down_weight_key(name)], cin, cout)); slots.append((name, "fwd"))
+                entries.append(((name, "fwd"), OP_CONV, 0, P[down_weight_key(name)], cin, cout))
                 if name != "down1":
-                    jobs.append((OP_CONV, 1, P[down_weight_key(name)], cin, cout)); slots.append((name, "dgrad"))
+                    entries.append(((name, "dgrad"), OP_CONV, 1, P[down_weight_key(name)], cin, cout))
             for name, cin, cout, _, _ in G_UP:
                 for pas, key in ((0, "fwd"), (1, "dgrad")):
-                    jobs.append((OP_CONVT, pas, P[f"{name}.model.0.weight"], cin, cout)); slots.append((name, key))
+                    entries.append(((name, key), OP_CONVT, pas, P[f"{name}.model.0.weight"], cin, cout))
             for pas, key in ((0, "fwd"), (1, "dgrad")):
-                jobs.append((OP_UPCONV, pas, P["final.2.weight"], 128, self.channels)); slots.append(("final", key))
-            self._plan = ops.PackPlan(self.dt, jobs)
-            for (name, key), buf in zip(slots, self._plan.streams):
-                self.packed.setdefault(name, {})[key] = buf
+                entries.append((("final", key), OP_UPCONV, pas, P["final.2.weight"], 128, self.channels))
+            self._plan = plan_streams(self.dt, entries, self.packed)
         self._plan.run()
 
     # ---- forward ----
     def forward(self, x, seed=0, train=True, save=True, labels=None, plane=None, plane_div=None):
         """x: fp32 NCHW [N,3,S,S] (S multiple of 64, >= 128). Returns (fake fp32 NCHW in (-1,1), ctx). down1 runs as ONE kernel (conv + LeakyReLU +
-        BlurPool, ops.first_block_fwd): its 266 MB conv output is never written, the backward needs its signs only and gets them as sign words.
+        BlurPool, first_block_fwd): its 266 MB conv output is never written, the backward needs its signs only and gets them as sign words.
         labels: fp32 [N,3] on the device, for a label-conditioned core (its fc plane is written as input channel 3 by the packing kernel).
         plane: fp32 [N,1,S,S] on the device, for a mask core: input channel 3 (plane_div: a device float it is divided by on the way, ops.MaskCtx.M)."""
         ops.require_gpu(x, labels, plane)
@@ -252,45 +400,23 @@ class GeneratorCore:
         ctx.raw, ctx.stats, ctx.dins = [], [], []
         cur = x8
         for i, (name, cin, cout, normalize, drop) in enumerate(self.down):
-            h = cur.H
             if i < 5:
-                up = skip_of[i]
-                upc = cat[up].C - cout
-                dst = cat[up].sub(upc, cout)
+                up = cat[skip_of[i]]
+                dst = up.sub(up.C - cout, cout)                   # the skip window of the concat buffer
             else:
                 dst = d6
-            first = i == 0 and not normalize and ops.first_block_bwd_supported(dt, cin, cout)
-            if first and drop == 0.0 and getattr(self, "debug", None) is None and ops.first_block_fwd_supported():
-                ctx.mask1 = torch.empty((N, h - 1, h - 1, 8), dtype=torch.uint8, device=dev) if save else None
-                ops.first_block_fwd(dt, cur, cin, cout, self.packed[name]["fwd"], dst, slope=0.2, act_after_rounding=True, sign_mask=ctx.mask1)
-                ctx.raw.append(None)
-                ctx.stats.append(None)
-                ctx.dins.append(cur)
-                cur = dst
-                continue
-            raw = new_act(N, h - 1, h - 1, cout, dt, dev)
-            stats = ops.zeros_f32((N, cout, 2), dev) if normalize else None
-            if first and save:
-                # the first convolution also leaves one sign bit per output value: all its fused backward (weight gradient only) reads of `raw`
-                ctx.mask1 = torch.empty((N, h - 1, h - 1, 8), dtype=torch.uint8, device=dev)
-                ops.conv_first_fwd(dt, cur, cin, cout, self.packed[name]["fwd"], raw, sign_mask=ctx.mask1)
+            if i == 0 and not normalize and drop == 0.0:
+                raw, stats = first_block_fwd(self, ctx, cur, cin, cout, self.packed[name, "fwd"], dst, save, seed=seed * 64 + i), None
             else:
-                ops.conv_fwd(dt, OP_CONV, cur, cin, cout, self.packed[name]["fwd"], raw, stats=stats)
-            ops.act_fwd(dt, raw, dst, stats=stats, slope=0.2, pool=2, drop_p=drop if train else 0.0, seed=seed * 64 + i)
+                raw, stats = down_block_fwd(dt, cur, cin, cout, self.packed[name, "fwd"], dst, normalize, drop if train else 0.0, seed * 64 + i)
             ctx.raw.append(raw)
             ctx.stats.append(stats)
             ctx.dins.append(cur)
             cur = dst
         ctx.blur, ctx.bstats, ctx.uins = [], [], []
         for j, (name, cin, cout, drop, skip) in enumerate(G_UP):
-            h = cur.H
-            rawT = new_act(N, 2 * h, 2 * h, cout, dt, dev)
-            ops.conv_fwd(dt, OP_CONVT, cur, cin, cout, self.packed[name]["fwd"], rawT)
-            blur = new_act(N, 2 * h, 2 * h, cout, dt, dev)
-            bstats = ops.zeros_f32((N, cout, 2), dev)
-            ops.act_fwd(dt, rawT, blur, stats=None, slope=1.0, pool=1, stats_out=bstats)
-            ops.act_fwd(dt, blur, cat[name].sub(0, cout), stats=bstats, slope=0.0, pool=0, drop_p=drop if train else 0.0,
-                        seed=seed * 64 + 16 + j)
+            blur, bstats = up_block_fwd(dt, cur, cin, cout, self.packed[name, "fwd"], cat[name].sub(0, cout), drop if train else 0.0,
+                                        seed * 64 + 16 + j)
             ctx.blur.append(blur)
             ctx.bstats.append(bstats)
             ctx.uins.append(cur)
@@ -299,7 +425,7 @@ class GeneratorCore:
         if dt == DT_BF16 and self.channels <= 4:                 # phases as columns of one 16-wide MFMA tile, filter in registers
             ops.upconv_head_fwd(dt, cur, self.params["final.2.weight"], self.params["final.2.bias"], fake)
         else:
-            ops.conv_fwd(dt, OP_UPCONV, cur, 128, self.channels, self.packed["final"]["fwd"], None, bias=self.params["final.2.bias"],
+            ops.conv_fwd(dt, OP_UPCONV, cur, 128, self.channels, self.packed["final", "fwd"], None, bias=self.params["final.2.bias"],
                          out_nchw=fake)
         ctx.u5 = cur
         ctx.fake = fake
@@ -312,7 +438,7 @@ class GeneratorCore:
         try:
             return self._backward(ctx, g_fake, grads, hook, accumulate, need_input_grad)
         finally:
-            _join_side(g_fake.device)                             # the weight gradients may have run on the side stream
+            join_side(g_fake.device)                              # the weight gradients may have run on the side stream
 
     def _backward(self, ctx, g_fake, grads, hook=None, accumulate=False, need_input_grad=False):
         """g_fake: fp32 NCHW gradient of the loss wrt fake. grads: dict key -> fp32 tensor (torch layout) that receives the
@@ -327,89 +453,53 @@ class GeneratorCore:
         if not accumulate:
             gb.zero_()
         dyf = ops.tanh_bwd_pack(dt, g_fake.contiguous().float(), ctx.fake, dbias=gb)
-        def _head_wgrad():
-            self._ws = ops.conv_wgrad(dt, OP_UPCONV, ctx.u5, dyf, 128, ch, grads["final.2.weight"], accumulate, self._ws)
-            if hook:
-                hook("final.2.weight")
-                hook("final.2.bias")
-        _on_side(dev, _head_wgrad, dyf)
+        self._ws = param_grad(dev, lambda: ops.conv_wgrad(dt, OP_UPCONV, ctx.u5, dyf, 128, ch, grads["final.2.weight"], accumulate, self._ws),
+                              hook, ("final.2.weight", "final.2.bias"), (dyf,))
         g_cat = new_act(N, ctx.u5.H, ctx.u5.W, ctx.u5.pitch, dt, dev)
         if dt == DT_BF16 and ch <= 8 and ctx.u5.pitch == 128:
             ops.upconv_head_dgrad(dt, dyf, N, ctx.u5.H, ctx.u5.W, self.params["final.2.weight"], g_cat)    # weights-stationary head kernel
         else:
-            ops.conv_dgrad(dt, OP_UPCONV, dyf, N, ctx.u5.H, ctx.u5.W, 128, ch, self.packed["final"]["dgrad"], g_cat)
-        dbg = getattr(self, "debug", None)
+            ops.conv_dgrad(dt, OP_UPCONV, dyf, N, ctx.u5.H, ctx.u5.W, 128, ch, self.packed["final", "dgrad"], g_cat)
+        dbg = self.debug
         if dbg is not None:
             dbg["dyf"], dbg["g_u5"] = dyf, ops.View(g_cat.t.clone(), g_cat.C)   # clone: the skip window is accumulated into later
         g_skip = [None] * 6                                       # gradient window of d1..d5 (views), g_d6 separately
         for j in range(4, -1, -1):
             name, cin, cout, drop, skip = G_UP[j]
-            blur, bstats, uin = ctx.blur[j], ctx.bstats[j], ctx.uins[j]
-            H = blur.H
+            uin = ctx.uins[j]
             g_out = g_cat.sub(0, cout)
             g_skip[skip] = g_cat.sub(cout, g_cat.pitch - cout)
-            rstats = ops.zeros_f32((N, cout, 2), dev)
-            dp = drop if ctx.train else 0.0
-            sd = ctx.seed * 64 + 16 + j
-            ops.act_bwd(dt, 1, g_out, blur, N, H, H, cout, None, stats=bstats, slope=0.0, pool=0, drop_p=dp, seed=sd, rstats=rstats)
-            d_blur = new_act(N, H, H, cout, dt, dev)
-            ops.act_bwd(dt, 2, g_out, blur, N, H, H, cout, d_blur, stats=bstats, slope=0.0, pool=0, drop_p=dp, seed=sd, rstats=rstats)
-            d_rawT = new_act(N, H, H, cout, dt, dev)
-            ops.act_bwd(dt, 0, d_blur, None, N, H, H, cout, d_rawT, stats=None, slope=1.0, pool=1)
+            d_blur, d_rawT = up_block_act_bwd(dt, g_out, ctx.blur[j], ctx.bstats[j], drop if ctx.train else 0.0, ctx.seed * 64 + 16 + j)
             key = f"{name}.model.0.weight"
             if dbg is not None:
                 dbg[f"{name}.g_out"] = ops.View(g_cat.t.clone(), g_cat.C)       # gradient of the whole concat buffer (up window | skip window)
                 dbg[f"{name}.d_blur"], dbg[f"{name}.d_rawT"] = d_blur, d_rawT
-            def _up_wgrad(uin=uin, d_rawT=d_rawT, cin=cin, cout=cout, key=key):
-                self._ws = ops.conv_wgrad(dt, OP_CONVT, uin, d_rawT, cin, cout, grads[key], accumulate, self._ws)
-                if hook:
-                    hook(key)
-            _on_side(dev, _up_wgrad, d_rawT)
+            self._ws = param_grad(dev, lambda: ops.conv_wgrad(dt, OP_CONVT, uin, d_rawT, cin, cout, grads[key], accumulate, self._ws),
+                                  hook, (key,), (d_rawT,))
             g_in = new_act(N, uin.H, uin.W, uin.pitch, dt, dev)
-            ops.conv_dgrad(dt, OP_CONVT, d_rawT, N, uin.H, uin.W, cin, cout, self.packed[name]["dgrad"], g_in)
+            ops.conv_dgrad(dt, OP_CONVT, d_rawT, N, uin.H, uin.W, cin, cout, self.packed[name, "dgrad"], g_in)
             if dbg is not None:
                 dbg[f"{name}.g_in"] = ops.View(g_in.t.clone(), g_in.C)          # before the down path accumulates into its skip window
             g_cat = g_in                                          # gradient of the next concat buffer (or of d6 when j == 0)
         g_cur = g_cat                                             # = gradient of d6
         for i in range(5, -1, -1):
             name, cin, cout, normalize, drop = self.down[i]
-            raw, stats, din = ctx.raw[i], ctx.stats[i], ctx.dins[i]
-            Hc = din.H - 1
-            dp = drop if ctx.train else 0.0
-            sd = ctx.seed * 64 + i
+            raw, din = ctx.raw[i], ctx.dins[i]
             key = down_weight_key(name)
-            if (i == 0 and not need_input_grad and not normalize and dp == 0.0 and dbg is None and ops.first_block_bwd_supported(dt, cin, cout)
-                    and pooled(Hc) >= 2):
-                # nothing but this weight gradient needs the 266 MB gradient of the first convolution's output: it is never written (igemm.hip:
-                # tfc_wgrad_c8_fusedm_kernel = tfc_act_bwd(mode 0, pool 2) + tfc_conv_wgrad in one kernel, same d_raw bits)
-                def _first_wgrad(din=din, raw=raw, g_cur=g_cur, cin=cin, cout=cout, key=key):
-                    self._ws = ops.first_block_bwd_wgrad(dt, din, raw, g_cur, cin, cout, grads[key], slope=0.2, accumulate=accumulate, ws=self._ws,
-                                                         sign_mask=getattr(ctx, "mask1", None))
-                    if hook:
-                        hook(key)
-                _on_side(dev, _first_wgrad, g_cur)
-                continue
-            d_raw = new_act(N, Hc, Hc, cout, dt, dev)
-            if raw is None:                                       # down1 of a fused forward: LeakyReLU' from the sign words
-                ops.act_bwd_signs(dt, g_cur, ctx.mask1, N, Hc, Hc, cout, d_raw, slope=0.2)
-            elif normalize:
-                rstats = ops.zeros_f32((N, cout, 2), dev)
-                ops.act_bwd(dt, 1, g_cur, raw, N, Hc, Hc, cout, None, stats=stats, slope=0.2, pool=2, drop_p=dp, seed=sd, rstats=rstats)
-                ops.act_bwd(dt, 2, g_cur, raw, N, Hc, Hc, cout, d_raw, stats=stats, slope=0.2, pool=2, drop_p=dp, seed=sd, rstats=rstats)
+            if i == 0 and not normalize and drop == 0.0:
+                d_raw, wgrad = first_block_bwd(self, ctx, g_cur, din, raw, cin, cout, need_input_grad, accumulate, seed=ctx.seed * 64 + i)
             else:
-                ops.act_bwd(dt, 0, g_cur, raw, N, Hc, Hc, cout, d_raw, stats=None, slope=0.2, pool=2, drop_p=dp, seed=sd)
-            key = down_weight_key(name)
+                d_raw = new_act(N, din.H - 1, din.H - 1, cout, dt, dev)
+                norm_act_bwd(dt, g_cur, raw, d_raw, ctx.stats[i], 0.2, 2, drop if ctx.train else 0.0, ctx.seed * 64 + i)
+                def wgrad(dw):
+                    return ops.conv_wgrad(dt, OP_CONV, din, d_raw, cin, cout, dw, accumulate, self._ws)
             if dbg is not None:
                 dbg[f"{name}.g_out"] = ops.View(g_cur.t[..., g_cur.coff:g_cur.coff + g_cur.C].clone(), g_cur.C)   # incl. the accumulated skip part
                 dbg[f"{name}.d_raw"] = d_raw
-            def _down_wgrad(din=din, d_raw=d_raw, cin=cin, cout=cout, key=key):
-                self._ws = ops.conv_wgrad(dt, OP_CONV, din, d_raw, cin, cout, grads[key], accumulate, self._ws)
-                if hook:
-                    hook(key)
-            _on_side(dev, _down_wgrad, d_raw)
+            self._ws = param_grad(dev, lambda: wgrad(grads[key]), hook, (key,), (g_cur if d_raw is None else d_raw,))
             if i > 0:
                 tgt = g_skip[i - 1]                               # window of d_{i} gradient already holding the skip-path part
-                ops.conv_dgrad(dt, OP_CONV, d_raw, N, din.H, din.W, cin, cout, self.packed[name]["dgrad"], tgt, accumulate=True)
+                ops.conv_dgrad(dt, OP_CONV, d_raw, N, din.H, din.W, cin, cout, self.packed[name, "dgrad"], tgt, accumulate=True)
                 g_cur = tgt
             elif need_input_grad:
                 w1 = self.params[key]
@@ -422,13 +512,9 @@ class GeneratorCore:
                 if not self.labels:
                     return gx
                 # channel 3 is the gradient of the label plane: d fc.weight / d fc.bias, the last gradients of the generator
-                def _fc_grad(gx=gx):                              # with the other parameter gradients and their hooks: on the side stream
-                    ops.label_plane_bwd(gx, ctx.labels, grads["fc.weight"], grads["fc.bias"], ch=self.channels, accumulate=accumulate)
-                    if hook:
-                        hook("fc.weight")
-                        hook("fc.bias")
-                _on_side(dev, _fc_grad, gx)
-                return gx[:, :self.channels].contiguous() if want_gx else None
+                param_grad(dev, lambda: ops.label_plane_bwd(gx, ctx.labels, grads["fc.weight"], grads["fc.bias"], ch=ch, accumulate=accumulate),
+                           hook, G_FC, (gx,))
+                return gx[:, :ch].contiguous() if want_gx else None
         return None
 
 
@@ -440,6 +526,10 @@ class DiscriminatorCore:
         self.params = None
         self.buffers = None
         self.head_packed = {}
+        self._plan = None
+        self._ws = None                                           # persistent wgrad scratch (zeroed once, re-zeroed by the kernels)
+        self._sn_ws = None
+        self.debug = None                                         # tests: a dict that receives the stored gradients; selects the unfused first block
 
     def set_params(self, params, buffers):
         """params: dict key -> fp32 tensor ('model.{0,3,6,9}.bias', '...parametrizations.weight.original', 'model.13.weight');
@@ -450,18 +540,13 @@ class DiscriminatorCore:
 
     def repack(self):
         """operand streams of the UN-normalised weights, once per weight update (one launch); 1/sigma is applied in the GEMM epilogue"""
-        if getattr(self, "_plan", None) is None:
-            jobs, slots = [], []
+        if self._plan is None:
             w = self.params["model.13.weight"]
-            jobs.append((OP_PADCONV, 0, w, 512, 1)); slots.append("fwd")
-            jobs.append((OP_PADCONV, 1, w, 512, 1)); slots.append("dgrad")
+            entries = [("fwd", OP_PADCONV, 0, w, 512, 1), ("dgrad", OP_PADCONV, 1, w, 512, 1)]
             for i, cin, cout in D_BLOCKS:
                 W = self.params[f"model.{i}.parametrizations.weight.original"]
-                jobs.append((OP_CONV, 0, W, cin, cout)); slots.append(f"f{i}")
-                jobs.append((OP_CONV, 1, W, cin, cout)); slots.append(f"d{i}")
-            self._plan = ops.PackPlan(self.dt, jobs)
-            for key, buf in zip(slots, self._plan.streams):
-                self.head_packed[key] = buf
+                entries += [(f"f{i}", OP_CONV, 0, W, cin, cout), (f"d{i}", OP_CONV, 1, W, cin, cout)]
+            self._plan = plan_streams(self.dt, entries, self.head_packed)
         self._plan.run()
 
     def forward(self, img_a, img_b, power_iter=True, save=True, after_sn=None):
@@ -495,11 +580,11 @@ class DiscriminatorCore:
         vsn = [snap[offs[L + k]:offs[L + k] + nv[k]] for k in range(L)]
         sig = [snap[offs[2 * L + k]:offs[2 * L + k] + 2] for k in range(L)]
         self._sn_ws = ops.spectral_norm_step_batched(Ws, us, vs, sig, power_iter=power_iter, u_snaps=usn if save else None,
-                                                     v_snaps=vsn if save else None, ws=getattr(self, "_sn_ws", None))
+                                                     v_snaps=vsn if save else None, ws=self._sn_ws)
         return usn, vsn, sig
 
     def chain(self, img_a, img_b, snapshot, save=True):
-        """the convolution chain of one call, given its sn_snapshot(). Block 1 runs as one kernel (ops.first_block_fwd) that keeps sign words
+        """the convolution chain of one call, given its sn_snapshot(). Block 1 runs as one kernel (first_block_fwd) that keeps sign words
         instead of its 266 MB conv output (all any backward reads of it)."""
         usn, vsn, sig = snapshot
         dt, dev = self.dt, img_a.device
@@ -512,37 +597,20 @@ class DiscriminatorCore:
         for bi, (i, cin, cout) in enumerate(D_BLOCKS):
             sigma2 = sig[bi]
             h = cur.H
-            first = bi == 0 and ops.first_block_bwd_supported(dt, cin, cout)
-            if first and getattr(self, "debug", None) is None and ops.first_block_fwd_supported():
-                ctx.mask1 = torch.empty((N, h - 1, h - 1, 8), dtype=torch.uint8, device=dev) if save else None
-                out = new_act(N, pooled(h - 1), pooled(h - 1), cout, dt, dev)
-                ops.first_block_fwd(dt, cur, cin, cout, self.head_packed[f"f{i}"], out, bias=self.params[f"model.{i}.bias"], oscale=sigma2[1:],
-                                    slope=0.2, act_after_rounding=False, sign_mask=ctx.mask1)
-                ctx.ins.append(cur)
-                ctx.raw.append(None)
-                ctx.sn.append((usn[bi], vsn[bi], sigma2) if save else None)
-                cur = out
-                continue
-            raw = new_act(N, h - 1, h - 1, cout, dt, dev)
-            # SN-conv + bias + LeakyReLU(0.2) in one kernel (P16:188-190): `raw` holds the ACTIVATED tensor; the backward's slope test
-            # (y > 0) is the same on y = LeakyReLU(z) as on z, so act_bwd below keeps slope = 0.2 on this tensor
-            if first and save:
-                ctx.mask1 = torch.empty((N, h - 1, h - 1, 8), dtype=torch.uint8, device=dev)       # sign bits for the fused backward of block 1
-                ops.conv_first_fwd(dt, cur, cin, cout, self.head_packed[f"f{i}"], raw, bias=self.params[f"model.{i}.bias"], oscale=sigma2[1:],
-                                   flags=ops.EP_LEAKY, sign_mask=ctx.mask1)
-            else:
-                ops.conv_fwd(dt, OP_CONV, cur, cin, cout, self.head_packed[f"f{i}"], raw, bias=self.params[f"model.{i}.bias"], oscale=sigma2[1:],
-                             flags=ops.EP_LEAKY)
+            bias, packed = self.params[f"model.{i}.bias"], self.head_packed[f"f{i}"]
             out = new_act(N, pooled(h - 1), pooled(h - 1), cout, dt, dev)
-            ops.act_fwd(dt, raw, out, stats=None, slope=1.0, pool=2)
+            # SN-conv + bias + LeakyReLU(0.2) in one kernel (P16:188-190): `raw` holds the ACTIVATED tensor, the pooling pass only blurs
+            if bi == 0:
+                raw = first_block_fwd(self, ctx, cur, cin, cout, packed, out, save, bias=bias, oscale=sigma2[1:], act_in_conv=True)
+            else:
+                raw = new_act(N, h - 1, h - 1, cout, dt, dev)
+                ops.conv_fwd(dt, OP_CONV, cur, cin, cout, packed, raw, bias=bias, oscale=sigma2[1:], flags=ops.EP_LEAKY)
+                ops.act_fwd(dt, raw, out, stats=None, slope=1.0, pool=2)
             ctx.ins.append(cur)
             ctx.raw.append(raw)
             ctx.sn.append((usn[bi], vsn[bi], sigma2) if save else None)
             cur = out
-        logits = new_act(N, cur.H, cur.W, 8, dt, dev)             # only channel 0 is ever written or read (bce: stride 8; modules: [..., 0])
-        ops.patchgan_head_fwd(dt, cur, self.params["model.13.weight"], View(logits.t, 1, 0))
-        ctx.p4 = cur
-        return View(logits.t, 1, 0), (ctx if save else None)
+        return patchgan_head_fwd(dt, ctx, cur, self.params["model.13.weight"], save)
 
     # ---- auxiliary classifier heads (label-conditioned discriminator): three Linear on the flattened 6 x S x S input ----
     def aux_params(self, src=None):
@@ -564,19 +632,14 @@ class DiscriminatorCore:
     def heads_wgrad(self, x_r, dl_r, x_f, dl_f, grads, accumulate=False, hook=None):
         """gradients of the six head parameters from the real pair and the fake pair, straight into the torch-layout views `grads`"""
         dws, dbs = self.aux_params(grads)
-
-        def _heads_wgrad():                                       # like every parameter gradient: on the side stream, hooks behind it; backward() joins
-            ops.aux_heads_wgrad(self.dt, x_r, dl_r, x_f, dl_f, dws, dbs, accumulate, self.aux_classes)
-            if hook:
-                for k in d_aux_names():
-                    hook(k)
-        _on_side(x_r.t.device, _heads_wgrad, dl_r, *([dl_f] if dl_f is not None else []))
+        param_grad(x_r.t.device, lambda: ops.aux_heads_wgrad(self.dt, x_r, dl_r, x_f, dl_f, dws, dbs, accumulate, self.aux_classes),
+                   hook, d_aux_names(), (dl_r, dl_f))
 
     def forward_pair(self, a1, b1, a2, b2, power_iter=True, save=True):
         """forward(a1, b1) then forward(a2, b2), same results as the two calls in that order (the second power iteration follows the first). With the
         side stream on, the second call's convolution chain runs beside the first's: two independent chains of MFMA-bound GEMMs and HBM-bound
         blur-pools that fill each other's gaps."""
-        if not _side_active() or os.environ.get("TFC_NO_FWD_PAIR", "0") not in ("", "0"):    # (A/B knob)
+        if not side_stream_on() or os.environ.get("TFC_NO_FWD_PAIR", "0") not in ("", "0"):    # (A/B knob)
             return self.forward(a1, b1, power_iter, save), self.forward(a2, b2, power_iter, save)
         dev = a1.device
         if not self.head_packed:
@@ -584,89 +647,59 @@ class DiscriminatorCore:
         box = {}
 
         def second():
-            box["r"] = _on_side(dev, lambda: self.forward(a2, b2, power_iter, save))
+            box["r"] = on_side(dev, lambda: self.forward(a2, b2, power_iter, save))
         first = self.forward(a1, b1, power_iter, save, after_sn=second)
-        _join_side(dev)
+        join_side(dev)
         return first, box["r"]
 
     def backward(self, ctx, g_logits, grads=None, need_input_grad=True, accumulate=False, hook=None, ws=None):
         try:
             return self._backward(ctx, g_logits, grads, need_input_grad, accumulate, hook, ws)
         finally:
-            _join_side(g_logits.t.device)                         # the weight gradients may have run on the side stream
+            join_side(g_logits.t.device)                          # the weight gradients may have run on the side stream
 
     def _backward(self, ctx, g_logits, grads=None, need_input_grad=True, accumulate=False, hook=None, ws=None):
         """g_logits: View [N,h,w,8] (channel 0 = gradient, channels 1..7 zero). grads: dict key -> fp32 tensor or None
         (skip all weight gradients: generator step). Returns fp32 NCHW gradient of img_a (first argument) or None."""
         dt, N = self.dt, ctx.N
         dev = g_logits.t.device
-        wsh = [getattr(self, "_ws", None) if ws is None else ws]  # persistent wgrad scratch (zeroed once, re-zeroed by the kernels)
-        gl = View(g_logits.t, 8, 0)
-        if grads is not None:
-            def _head_wgrad():
-                wsh[0] = ops.conv_wgrad(dt, OP_PADCONV, ctx.p4, gl, 512, 1, grads["model.13.weight"], accumulate, wsh[0])
-                if hook:
-                    hook("model.13.weight")
-            _on_side(dev, _head_wgrad)
-        g_cur = new_act(N, ctx.p4.H, ctx.p4.W, 512, dt, dev)
-        ops.conv_dgrad(dt, OP_PADCONV, gl, N, ctx.p4.H, ctx.p4.W, 512, 1, self.head_packed["dgrad"], g_cur)
-        g_in = None
+        if ws is not None:
+            self._ws = ws
+        g_cur = patchgan_head_bwd(self, ctx, g_logits, grads, "model.13.weight", self.head_packed["dgrad"], accumulate, hook)
         for bi in range(3, -1, -1):
             i, cin, cout = D_BLOCKS[bi]
             raw, xin = ctx.raw[bi], ctx.ins[bi]
             u, v, sigma2 = ctx.sn[bi]
-            Hc = xin.H - 1
-            gb_img = ops.zeros_f32((N, cout), dev) if grads is not None else None
-            fuse = (bi == 0 and grads is not None and not need_input_grad and getattr(self, "debug", None) is None
-                    and ops.first_block_bwd_supported(dt, cin, cout))
-            if fuse:
+            wkey, bkey = f"model.{i}.parametrizations.weight.original", f"model.{i}.bias"
+            W = self.params[wkey]
+            gb_img = ops.zeros_f32((N, cout), dev) if grads is not None else None      # per-image bias gradient, from the activation backward
+            if bi == 0:
                 # discriminator step: block 1's conv-output gradient (266 MB) feeds only its weight / bias gradients -> never written
-                def _first_wgrad(i=i, cin=cin, cout=cout, xin=xin, raw=raw, g_cur=g_cur, gb_img=gb_img, u=u, v=v, sigma2=sigma2):
-                    W = self.params[f"model.{i}.parametrizations.weight.original"]
-                    gsn = torch.empty_like(W)
-                    wsh[0] = ops.first_block_bwd_wgrad(dt, xin, raw, g_cur, cin, cout, gsn, slope=0.2, ws=wsh[0], bias_sums=gb_img,
-                                                       sign_mask=getattr(ctx, "mask1", None))
-                    gbias = grads[f"model.{i}.bias"]
-                    if not accumulate:
-                        gbias.zero_()
-                    ops.colsum(ops.DT_F32, View(gb_img.view(N, 1, 1, cout), cout), gbias)
-                    ops.spectral_norm_bwd(gsn, W, u, v, sigma2, grads[f"model.{i}.parametrizations.weight.original"], accumulate)
-                    if hook:
-                        hook(f"model.{i}.parametrizations.weight.original")
-                        hook(f"model.{i}.bias")
-                _on_side(dev, _first_wgrad, g_cur, gb_img)
-                continue
-            d_raw = new_act(N, Hc, Hc, cout, dt, dev)
-            if raw is None:                                       # block 1 of a fused forward: LeakyReLU' from the sign words
-                ops.act_bwd_signs(dt, g_cur, ctx.mask1, N, Hc, Hc, cout, d_raw, slope=0.2, rstats=gb_img)
+                d_raw, wgrad = first_block_bwd(self, ctx, g_cur, xin, raw, cin, cout, grads is None or need_input_grad, bias_sums=gb_img)
             else:
-                ops.act_bwd(dt, 0, g_cur, raw, N, Hc, Hc, cout, d_raw, stats=None, slope=0.2, pool=2, rstats=gb_img)   # + per-image bias gradient
-            ddbg = getattr(self, "debug", None)
-            if ddbg is not None:
-                ddbg[f"b{bi}.g_out"], ddbg[f"b{bi}.d_raw"] = g_cur, d_raw
-            W = self.params[f"model.{i}.parametrizations.weight.original"]
+                d_raw = new_act(N, xin.H - 1, xin.H - 1, cout, dt, dev)
+                norm_act_bwd(dt, g_cur, raw, d_raw, None, 0.2, 2, bias_sums=gb_img)
+                def wgrad(dw):
+                    return ops.conv_wgrad(dt, OP_CONV, xin, d_raw, cin, cout, dw, False, self._ws)
+            if self.debug is not None:
+                self.debug[f"b{bi}.g_out"], self.debug[f"b{bi}.d_raw"] = g_cur, d_raw
             if grads is not None:
-                def _block_wgrad(i=i, cin=cin, cout=cout, xin=xin, d_raw=d_raw, gb_img=gb_img, W=W, u=u, v=v, sigma2=sigma2):
-                    gbias = grads[f"model.{i}.bias"]
-                    if not accumulate:
-                        gbias.zero_()
-                    ops.colsum(ops.DT_F32, View(gb_img.view(N, 1, 1, cout), cout), gbias)
-                    gsn = torch.empty_like(W)
-                    wsh[0] = ops.conv_wgrad(dt, OP_CONV, xin, d_raw, cin, cout, gsn, False, wsh[0])
-                    ops.spectral_norm_bwd(gsn, W, u, v, sigma2, grads[f"model.{i}.parametrizations.weight.original"], accumulate)
-                    if hook:
-                        hook(f"model.{i}.parametrizations.weight.original")
-                        hook(f"model.{i}.bias")
-                _on_side(dev, _block_wgrad, d_raw, gb_img)
+                def sn_grads():
+                    gsn = torch.empty_like(W)                     # gradient of the normalised weight; spectral_norm_bwd takes it to W's
+                    if d_raw is None:                             # the fused kernel writes the bias sums itself: ahead of their column sum
+                        self._ws = wgrad(gsn)
+                    bias_grad(gb_img, grads[bkey], accumulate)
+                    if d_raw is not None:
+                        self._ws = wgrad(gsn)
+                    ops.spectral_norm_bwd(gsn, W, u, v, sigma2, grads[wkey], accumulate)
+                param_grad(dev, sn_grads, hook, (wkey, bkey), (g_cur if d_raw is None else d_raw, gb_img))
             if bi == 0 and need_input_grad and dt == DT_BF16 and self.channels <= 4 and cout == 64:
                 # gradient w.r.t. the generated image only (3 of the 6 input channels): rows-packed 16-wide MFMA kernel, fp32 NCHW out
-                self._ws = wsh[0]
                 return ops.conv_dgrad_image(dt, d_raw, N, xin.H, xin.W, cin, W, sigma2[1:], self.channels)
             if bi > 0 or need_input_grad:
                 g_in = new_act(N, xin.H, xin.W, xin.pitch, dt, dev)
                 ops.conv_dgrad(dt, OP_CONV, d_raw, N, xin.H, xin.W, cin, cout, self.head_packed[f"d{i}"], g_in, oscale=sigma2[1:])
                 g_cur = g_in
-        self._ws = wsh[0]
         if need_input_grad:
             return ops.unpack_nchw(dt, g_cur, self.channels, c0=0)
         return None
@@ -687,6 +720,8 @@ class Pix2PixCore:
         self.params = None
         self.packed = {}
         self._plan = None
+        self._ws = None                                           # persistent wgrad scratch (zeroed once, re-zeroed by the kernels)
+        self.debug = None                                         # tests: a dict that receives the stored gradients of every block
 
     def blocks(self):
         cin = 2 * self.channels
@@ -703,14 +738,11 @@ class Pix2PixCore:
     def repack(self):
         """operand streams of the nine convolution passes, once per weight update (one launch)"""
         if self._plan is None:
-            jobs, slots = [(OP_PADCONV, 1, self.params[f"model.{P2P_HEAD}.weight"], 512, 1)], ["dhead"]
+            entries = [("dhead", OP_PADCONV, 1, self.params[f"model.{P2P_HEAD}.weight"], 512, 1)]
             for i, cin, cout, _ in self.blocks():
                 W = self.params[f"model.{i}.weight"]
-                jobs.append((OP_CONV2, 0, W, cin, cout)); slots.append(f"f{i}")
-                jobs.append((OP_CONV2, 1, W, cin, cout)); slots.append(f"d{i}")
-            self._plan = ops.PackPlan(self.dt, jobs)
-            for key, buf in zip(slots, self._plan.streams):
-                self.packed[key] = buf
+                entries += [(f"f{i}", OP_CONV2, 0, W, cin, cout), (f"d{i}", OP_CONV2, 1, W, cin, cout)]
+            self._plan = plan_streams(self.dt, entries, self.packed)
         self._plan.run()
 
     def forward(self, img_a, img_b, save=True):
@@ -731,7 +763,7 @@ class Pix2PixCore:
             bias = self.params[f"model.{i}.bias"]
             if norm:
                 raw = new_act(N, h, w, cout, dt, dev)
-                st = torch.zeros((N, cout, 2), dtype=torch.float32, device=dev)
+                st = ops.zeros_f32((N, cout, 2), dev)
                 ops.conv_fwd(dt, OP_CONV2, cur, cin, cout, self.packed[f"f{i}"], raw, bias=bias, stats=st)
                 out = new_act(N, h, w, cout, dt, dev)
                 ops.act_fwd(dt, raw, out, stats=st, slope=0.2, pool=0)
@@ -744,68 +776,40 @@ class Pix2PixCore:
             ctx.raw.append(raw)
             ctx.stats.append(st)
             cur = out
-        logits = new_act(N, cur.H, cur.W, 8, dt, dev)             # only channel 0 is ever written or read
-        ops.patchgan_head_fwd(dt, cur, self.params[f"model.{P2P_HEAD}.weight"], View(logits.t, 1, 0))
-        ctx.p4 = cur
-        return View(logits.t, 1, 0), (ctx if save else None)
+        return patchgan_head_fwd(dt, ctx, cur, self.params[f"model.{P2P_HEAD}.weight"], save)
 
     def backward(self, ctx, g_logits, grads=None, need_input_grad=True, accumulate=False, hook=None):
         try:
             return self._backward(ctx, g_logits, grads, need_input_grad, accumulate, hook)
         finally:
-            _join_side(g_logits.t.device)                         # the weight gradients may have run on the side stream
+            join_side(g_logits.t.device)                          # the weight gradients may have run on the side stream
 
     def _backward(self, ctx, g_logits, grads, need_input_grad, accumulate, hook):
         """g_logits: View [N, h, w, 8] (channel 0 = gradient, channels 1..7 zero). grads: dict key -> fp32 tensor, or None (no parameter gradients: the
         generator step). Returns the fp32 NCHW gradient of img_a, or None."""
         dt, N = self.dt, ctx.N
         dev = g_logits.t.device
-        wsh = [getattr(self, "_ws", None)]                        # persistent wgrad scratch (zeroed once, re-zeroed by the kernels)
-        gl = View(g_logits.t, 8, 0)
-        p4 = ctx.p4
-        hk = f"model.{P2P_HEAD}.weight"
-        if grads is not None:
-            def _head_wgrad():
-                wsh[0] = ops.conv_wgrad(dt, OP_PADCONV, p4, gl, 512, 1, grads[hk], accumulate, wsh[0])
-                if hook:
-                    hook(hk)
-            _on_side(dev, _head_wgrad)
-        g_cur = new_act(N, p4.H, p4.W, 512, dt, dev)
-        ops.conv_dgrad(dt, OP_PADCONV, gl, N, p4.H, p4.W, 512, 1, self.packed["dhead"], g_cur)
+        g_cur = patchgan_head_bwd(self, ctx, g_logits, grads, f"model.{P2P_HEAD}.weight", self.packed["dhead"], accumulate, hook)
         blocks = list(self.blocks())
         for bi in range(len(blocks) - 1, -1, -1):
             i, cin, cout, norm = blocks[bi]
-            xin, raw, st = ctx.ins[bi], ctx.raw[bi], ctx.stats[bi]
-            Ho, Wo = raw.H, raw.W
-            d_raw = new_act(N, Ho, Wo, cout, dt, dev)
-            gb_img = None
-            if norm:
-                rst = torch.zeros((N, cout, 2), dtype=torch.float32, device=dev)
-                ops.act_bwd(dt, 1, g_cur, raw, N, Ho, Wo, cout, None, stats=st, slope=0.2, pool=0, rstats=rst)
-                ops.act_bwd(dt, 2, g_cur, raw, N, Ho, Wo, cout, d_raw, stats=st, slope=0.2, pool=0, rstats=rst)
-            else:
-                gb_img = torch.zeros((N, cout), dtype=torch.float32, device=dev) if grads is not None else None
-                ops.act_bwd(dt, 0, g_cur, raw, N, Ho, Wo, cout, d_raw, stats=None, slope=0.2, pool=0, rstats=gb_img)   # + per-image bias gradient
-            ddbg = getattr(self, "debug", None)                   # tests: the stored gradients of every block
-            if ddbg is not None:
-                ddbg[f"b{bi}.g_out"], ddbg[f"b{bi}.d_raw"] = g_cur, d_raw
+            xin, raw = ctx.ins[bi], ctx.raw[bi]
+            wkey, bkey = f"model.{i}.weight", f"model.{i}.bias"
+            d_raw = new_act(N, raw.H, raw.W, cout, dt, dev)
+            # block 1: the per-image bias gradient rides on the activation backward; behind InstanceNorm the bias gradient is exactly zero
+            gb_img = ops.zeros_f32((N, cout), dev) if grads is not None and not norm else None
+            norm_act_bwd(dt, g_cur, raw, d_raw, ctx.stats[bi], 0.2, 0, bias_sums=gb_img)
+            if self.debug is not None:
+                self.debug[f"b{bi}.g_out"], self.debug[f"b{bi}.d_raw"] = g_cur, d_raw
             if grads is not None:
-                def _block_wgrad(i=i, cin=cin, cout=cout, xin=xin, d_raw=d_raw, gb_img=gb_img):
-                    gbias = grads[f"model.{i}.bias"]
-                    if not accumulate:
-                        gbias.zero_()
-                    if gb_img is not None:                        # block 1; behind InstanceNorm the bias gradient is exactly zero
-                        ops.colsum(ops.DT_F32, View(gb_img.view(N, 1, 1, cout), cout), gbias)
-                    wsh[0] = ops.conv_wgrad(dt, OP_CONV2, xin, d_raw, cin, cout, grads[f"model.{i}.weight"], accumulate, wsh[0])
-                    if hook:
-                        hook(f"model.{i}.weight")
-                        hook(f"model.{i}.bias")
-                _on_side(dev, _block_wgrad, d_raw, *([gb_img] if gb_img is not None else []))
+                def block_grads():
+                    bias_grad(gb_img, grads[bkey], accumulate)
+                    self._ws = ops.conv_wgrad(dt, OP_CONV2, xin, d_raw, cin, cout, grads[wkey], accumulate, self._ws)
+                param_grad(dev, block_grads, hook, (wkey, bkey), (d_raw, gb_img))
             if bi > 0 or need_input_grad:
                 g_in = new_act(N, xin.H, xin.W, xin.pitch, dt, dev)
                 ops.conv_dgrad(dt, OP_CONV2, d_raw, N, xin.H, xin.W, cin, cout, self.packed[f"d{i}"], g_in)
                 g_cur = g_in
-        self._ws = wsh[0]
         if need_input_grad:
             return ops.unpack_nchw(dt, g_cur, self.channels, c0=0)
         return None

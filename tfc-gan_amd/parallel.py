@@ -152,6 +152,15 @@ def all_reduce_mean(t, group=None):
     return t
 
 
+def all_reduce_mean_scalars(scalars, group=None):
+    """the logged losses of a step, dict name -> device scalar: their means over the ranks from ONE collective, as fp32 windows of one packed tensor
+    (same keys, same order)"""
+    keys = list(scalars)
+    packed = torch.stack([scalars[k].reshape(()).float() for k in keys])
+    all_reduce_mean(packed, group)
+    return {k: packed[i] for i, k in enumerate(keys)}
+
+
 def all_gather_records(t, group=None):
     """the records of every rank, [world, *t.shape] in rank order (t: this rank's contiguous record, the same shape and dtype on every rank); t[None]
     without active collectives. The batch-coupled terms (the edge mask's batch extrema, the KL loss's batch softmax: DESIGN 3.4) exchange the state

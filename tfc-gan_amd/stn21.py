@@ -260,7 +260,7 @@ class STN21Step:
         parallel.broadcast_tensors([b for D in (self.D1, self.D2) for b in D.named_core_buffers().values()])
         self.gm, self.gv = torch.zeros_like(self.gflat.data), torch.zeros_like(self.gflat.data)
         self.dm, self.dv = torch.zeros_like(self.dflat.data), torch.zeros_like(self.dflat.data)
-        self.g_reduce = parallel.BucketReducer(self.gflat, self._bucket_bytes if hasattr(self, "_bucket_bytes") else 32 << 20)
+        self.g_reduce = parallel.BucketReducer(self.gflat, self._bucket_bytes)
         self.d_reduce = parallel.BucketReducer(self.dflat, 8 << 20)
         self._bump()
 
@@ -279,13 +279,67 @@ class STN21Step:
 
     def step(self, real_A, real_B):
         from . import ops
+        _refuse_bf16x3(type(self).__name__)
         with ops.batch_invariant_scope(self.batch_invariant):     # covers autograd's backward threads too: the setting is process-wide (_lib.load)
             return self._step(real_A, real_B)
 
+    _VALID, _FAKE = 0.9, 0.0                                      # STN:613-615
+
+    def _perc(self, fake_A, real_A, fake_B, real_B):
+        if self.lpips is None:
+            return fake_B.new_zeros(())
+        return (self.lpips(fake_A, real_A) + self.lpips(fake_B, real_B)).mean()           # a batch SUM inside lpips_pytorch (STN:641-643)
+
+    def _gan(self, fake_B, fake_A, real_A, real_B):
+        gan1 = _bce_rel(self.D1(fake_B, real_A), self.D1(real_B, real_A).detach(), self._VALID)
+        gan2 = _bce_rel(self.D2(fake_A, real_B), self.D2(real_A, real_B).detach(), self._VALID)
+        return gan1 + gan2                                        # (loss_GAN1 + loss_GAN2).mean() of two scalars
+
+    def _loss_G(self, t):
+        return t["loss_GAN"] + self.alpha2 * t["recon_loss"] + t["perc_loss"] + t["morph_loss"]
+
+    def _d_loss(self, pr, pf):
+        return 0.25 * (_bce_rel(pr, pf, self._VALID) + _bce_rel(pf, pr, self._FAKE))
+
+    def _g_update(self, loss):
+        """backward of the generator side's loss (the hooks issue the bucket all-reduces as gradients become final), then its Adam step"""
+        from . import ops
+        loss.backward()
+        gscale = self.g_reduce.finish()
+        ops.adam_step(self.gflat.data, self.gflat.grad, self.gm, self.gv, self.lr, self.b1, self.b2, self.eps, self.step_no, gscale)
+
+    def _d_step(self, real_A, real_B, fake_B, fake_A):
+        """the discriminator side (STN:668-676): D1 on (real_B | fake_B) given real_A, D2 on (real_A | fake_A) given real_B, backward, Adam.
+        Returns loss_D, loss_D1, loss_D2."""
+        from . import ops
+        self._d_requires_grad(True)
+        self.dflat.grad.zero_()
+
+        def disc(D, real, fake_img, cond):
+            pr, pf = D(real, cond), D(fake_img.detach(), cond)
+            return self._d_loss(pr, pf)
+        loss_D1, loss_D2 = disc(self.D1, real_B, fake_B, real_A), disc(self.D2, real_A, fake_A, real_B)
+        loss_D = 0.5 * (loss_D1 + loss_D2)
+        loss_D.backward()
+        dscale = self.d_reduce.finish()
+        ops.adam_step(self.dflat.data, self.dflat.grad, self.dm, self.dv, self.lr, self.b1, self.b2, self.eps, self.step_no, dscale)
+        self._bump()
+        return loss_D, loss_D1, loss_D2
+
+    def _logged(self, terms, d_losses, world, **images):
+        """what step() returns: loss_G of the terms, the terms, the discriminator losses -- over several ranks their means, which for these batch
+        means are the global-batch values (LPIPS, a batch sum: the sum) -- and the images"""
+        from . import parallel
+        terms = {k: v.detach() for k, v in terms.items()}
+        out = {"loss_G": self._loss_G(terms), **terms, **{k: v.detach() for k, v in zip(("loss_D", "loss_D1", "loss_D2"), d_losses)}}
+        if world > 1:
+            out = {k: v * (world if k == "perc_loss" else 1.0) for k, v in parallel.all_reduce_mean_scalars(out).items()}
+            out["loss_G"] = self._loss_G(out)
+        out.update({k: v.detach() for k, v in images.items()})
+        return out
+
     def _step(self, real_A, real_B):
-        _refuse_bf16x3()
-        from . import ops, parallel
-        valid, fake_t = 0.9, 0.0                                  # STN:613-615
+        from . import parallel
         self.step_no += 1
         world = parallel.world_size()
         # ---------------- generators + STN (STN:620-662) ----------------
@@ -296,41 +350,13 @@ class STN21Step:
         warped_B = self.net(real_A, fake_A1, real_B)
         fake_A2 = self.G2(warped_B)
         recon = F.l1_loss(fake_A2, real_A)
-        if self.lpips is not None:
-            perc = (self.lpips(fake_A2, real_A) + self.lpips(fake_B, real_B)).mean()      # a batch SUM inside lpips_pytorch (STN:641-643)
-        else:
-            perc = fake_B.new_zeros(())
+        perc = self._perc(fake_A2, real_A, fake_B, real_B)
         morph = stn.morph_triplet(real_A, real_B, warped_B)
-        gan1 = _bce_rel(self.D1(fake_B, real_A), self.D1(real_B, real_A).detach(), valid)
-        gan2 = _bce_rel(self.D2(fake_A2, real_B), self.D2(real_A, real_B).detach(), valid)
-        loss_gan = gan1 + gan2                                    # (loss_GAN1 + loss_GAN2).mean() of two scalars
-        loss_G = loss_gan + self.alpha2 * recon + perc + morph
-        (loss_gan + self.alpha2 * recon + perc * world + morph).backward()       # hooks issue the bucket all-reduces as gradients become final
-        gscale = self.g_reduce.finish()
-        ops.adam_step(self.gflat.data, self.gflat.grad, self.gm, self.gv, self.lr, self.b1, self.b2, self.eps, self.step_no, gscale)
-        # ---------------- discriminators (STN:668-676) ----------------
-        self._d_requires_grad(True)
-        self.dflat.grad.zero_()
-
-        def disc(D, real, fake_img, cond):
-            pr, pf = D(real, cond), D(fake_img.detach(), cond)
-            return 0.25 * (_bce_rel(pr, pf, valid) + _bce_rel(pf, pr, fake_t))
-        loss_D1, loss_D2 = disc(self.D1, real_B, fake_B, real_A), disc(self.D2, real_A, fake_A2, real_B)
-        loss_D = 0.5 * (loss_D1 + loss_D2)
-        loss_D.backward()
-        dscale = self.d_reduce.finish()
-        ops.adam_step(self.dflat.data, self.dflat.grad, self.dm, self.dv, self.lr, self.b1, self.b2, self.eps, self.step_no, dscale)
-        self._bump()
-        out = {"loss_G": loss_G.detach(), "loss_GAN": loss_gan.detach(), "recon_loss": recon.detach(), "perc_loss": perc.detach(),
-               "morph_loss": morph.detach(), "loss_D": loss_D.detach(), "loss_D1": loss_D1.detach(), "loss_D2": loss_D2.detach()}
-        if world > 1:                                             # batch means: the mean over ranks is the global-batch value (LPIPS: the sum)
-            keys = list(out)
-            packed = torch.stack([out[k].reshape(()).float() for k in keys])
-            parallel.all_reduce_mean(packed)
-            out = {k: packed[i] * (world if k == "perc_loss" else 1.0) for i, k in enumerate(keys)}
-            out["loss_G"] = out["loss_GAN"] + self.alpha2 * out["recon_loss"] + out["perc_loss"] + out["morph_loss"]
-        out.update({"fake_B": fake_B.detach(), "fake_A2": fake_A2.detach(), "warped_B": warped_B.detach()})
-        return out
+        loss_gan = self._gan(fake_B, fake_A2, real_A, real_B)
+        terms = {"loss_GAN": loss_gan, "recon_loss": recon, "perc_loss": perc, "morph_loss": morph}
+        self._g_update(loss_gan + self.alpha2 * recon + perc * world + morph)
+        d_losses = self._d_step(real_A, real_B, fake_B, fake_A2)
+        return self._logged(terms, d_losses, world, fake_B=fake_B, fake_A2=fake_A2, warped_B=warped_B)
 
 
 class DarkVisibleStep(STN21Step):
@@ -363,10 +389,14 @@ class DarkVisibleStep(STN21Step):
     def _make_net(self, img_shape, localiser, patch_size):
         return Net(img_shape, localiser=localiser, patch_size=patch_size, sample_align_corners=self._sample_align_corners)
 
+    def _loss_G(self, t):
+        return t["loss_GAN"] + t["recon_loss"] + t["perc_loss"] + t["loss_FFT"]
+
+    def _d_loss(self, pr, pf):
+        return _bce_rel(pr, pf, self._VALID) + _bce_rel(pf, pr, self._FAKE)
+
     def _step(self, real_A, real_B):
-        _refuse_bf16x3(type(self).__name__)
-        from . import losses, ops, parallel
-        valid, fake_t = 0.9, 0.0                                  # DV:670-672
+        from . import losses, parallel
         self.step_no += 1
         world = parallel.world_size()
         # ---------------- generators + STN (DV:677-718) ----------------
@@ -376,42 +406,14 @@ class DarkVisibleStep(STN21Step):
         warped_B = self.net(real_A, fake_B, real_B)
         fake_A = self.G2(warped_B)
         recon = F.l1_loss(warped_B, fake_B)
-        if self.lpips is not None:
-            perc = (self.lpips(fake_A, real_A) + self.lpips(fake_B, real_B)).mean()       # a batch SUM inside lpips_pytorch (DV:694-696)
-        else:
-            perc = fake_B.new_zeros(())
+        perc = self._perc(fake_A, real_A, fake_B, real_B)
         if self.fft:                                              # no gradient: the reference goes tensor -> PIL -> numpy (DV:551-569, :700-704)
             _, l_amp, l_pha = losses.global_fft_loss(fake_A.detach(), real_A.detach())
             loss_fft = (l_amp + l_pha).detach()
         else:
             loss_fft = fake_B.new_zeros(())
-        gan1 = _bce_rel(self.D1(fake_B, real_A), self.D1(real_B, real_A).detach(), valid)
-        gan2 = _bce_rel(self.D2(fake_A, real_B), self.D2(real_A, real_B).detach(), valid)
-        loss_gan = gan1 + gan2
-        loss_G = loss_gan + recon + perc + loss_fft
-        (loss_gan + recon + perc * world).backward()              # hooks issue the bucket all-reduces as gradients become final
-        gscale = self.g_reduce.finish()
-        ops.adam_step(self.gflat.data, self.gflat.grad, self.gm, self.gv, self.lr, self.b1, self.b2, self.eps, self.step_no, gscale)
-        # ---------------- discriminators (DV:725-734) ----------------
-        self._d_requires_grad(True)
-        self.dflat.grad.zero_()
-
-        def disc(D, real, fake_img, cond):
-            pr, pf = D(real, cond), D(fake_img.detach(), cond)
-            return _bce_rel(pr, pf, valid) + _bce_rel(pf, pr, fake_t)
-        loss_D1, loss_D2 = disc(self.D1, real_B, fake_B, real_A), disc(self.D2, real_A, fake_A, real_B)
-        loss_D = 0.5 * (loss_D1 + loss_D2)
-        loss_D.backward()
-        dscale = self.d_reduce.finish()
-        ops.adam_step(self.dflat.data, self.dflat.grad, self.dm, self.dv, self.lr, self.b1, self.b2, self.eps, self.step_no, dscale)
-        self._bump()
-        out = {"loss_G": loss_G.detach(), "loss_GAN": loss_gan.detach(), "recon_loss": recon.detach(), "perc_loss": perc.detach(),
-               "loss_FFT": loss_fft, "loss_D": loss_D.detach(), "loss_D1": loss_D1.detach(), "loss_D2": loss_D2.detach()}
-        if world > 1:                                             # batch means: the mean over ranks is the global-batch value (LPIPS: the sum)
-            keys = list(out)
-            packed = torch.stack([out[k].reshape(()).float() for k in keys])
-            parallel.all_reduce_mean(packed)
-            out = {k: packed[i] * (world if k == "perc_loss" else 1.0) for i, k in enumerate(keys)}
-            out["loss_G"] = out["loss_GAN"] + out["recon_loss"] + out["perc_loss"] + out["loss_FFT"]
-        out.update({"fake_B": fake_B.detach(), "fake_A": fake_A.detach(), "warped_B": warped_B.detach()})
-        return out
+        loss_gan = self._gan(fake_B, fake_A, real_A, real_B)
+        terms = {"loss_GAN": loss_gan, "recon_loss": recon, "perc_loss": perc, "loss_FFT": loss_fft}
+        self._g_update(loss_gan + recon + perc * world)
+        d_losses = self._d_step(real_A, real_B, fake_B, fake_A)   # DV:725-734
+        return self._logged(terms, d_losses, world, fake_B=fake_B, fake_A=fake_A, warped_B=warped_B)
