@@ -512,11 +512,16 @@ struct Tile2 {
 // sequence the offset cannot drift: per tile a half executes nst + 1 barriers (one per stage, one inside the epilogue), so with half 1 shifted by
 // (nst + 1) / 2 slots one half's epilogue (accumulators -> LDS -> global: no MFMA) always lies beside the other half's K-loop stages.
 // Both halves execute the SAME total number of barriers (dummy barriers pad the shorter sequence), so every wave reaches the end.
-template <int MT, int NT, int WM, int WN, int PAT, int HALVES = 1>
+// FC: the epilogue's flag set as a compile-time constant, or -1 = read `flags` at run time. The launcher instantiates FC for the flag sets the
+// training step issues (launch_igemm2_pat) and sends every other combination, and the two-half form, to FC = -1.
+template <int MT, int NT, int WM, int WN, int PAT, int HALVES = 1, int FC = -1>
 __global__ void __launch_bounds__(256 * HALVES, 2)
 tfc_igemm2_kernel(const TfcGather d, const bf16_t* __restrict__ in, const uint4* __restrict__ wp, bf16_t* out,
                   const float* __restrict__ bias, float* stats, float* dbg, const float* __restrict__ oscale,
                   int flags, int NB32, int nblkN, int buf_bytes, long long phase_wbytes, int nwork, int half_bytes, int shift_opts) {
+  // FC >= 0: the flag set is a constant of this instantiation and the epilogue is straight-line code; FC < 0: the flags are read at run time. The
+  // arithmetic per element is the same expression either way, so the stored bits do not depend on which instantiation runs.
+  const int fl = FC >= 0 ? FC : flags;
   const int shift = shift_opts & 255;
   const bool prio = (shift_opts >> 8) & 1;                        // (A/B knob TFC_IGEMM_PRIO) raise the wave priority inside the K loop
   static_assert(WM * WN == 4 && WM * MT == 4, "4 waves, 128-pixel tile");
@@ -580,7 +585,7 @@ tfc_igemm2_kernel(const TfcGather d, const bf16_t* __restrict__ in, const uint4*
   const int bstride = buf_bytes + xtra;                          // distance of the two halo buffers
   unsigned char* stage_fix = smem + 2 * buf_bytes;
   float* sstat = reinterpret_cast<float*>(IL ? smem + 2 * buf_bytes + xtra : stage_fix + 128 * ROWP);   // [4 waves][BN][2] statistics partials of the tile just stored (EP_STATS only)
-  float* sbias = sstat + ((flags & TFC_EP_STATS) ? 8 * BN : 0);  // bias of EVERY output channel of the layer (nblkN * BN floats), loaded once (EP_BIAS only)
+  float* sbias = sstat + ((fl & TFC_EP_STATS) ? 8 * BN : 0);     // bias of EVERY output channel of the layer (nblkN * BN floats), loaded once (EP_BIAS only)
 
   const int laneBase = ((2 * wm * MT + (r & 1)) * P + (r >> 1)) * 80 + h * 16;
   const unsigned lanepart = (unsigned)((IL ? wn : wn * NT) * 64 + lane) * 16u;
@@ -710,7 +715,7 @@ tfc_igemm2_kernel(const TfcGather d, const bf16_t* __restrict__ in, const uint4*
 #pragma unroll
   for (int i = 0; i < BD; ++i) loadB(cur.wbase + lanepart + (size_t)i * wstep_b, br[i]);
   const unsigned char* bptr = cur.wbase + lanepart + (size_t)BD * wstep_b;   // next fragment to request (per lane)
-  if (flags & TFC_EP_BIAS)
+  if (fl & TFC_EP_BIAS)
     for (int n = tid; n < nblkN * BN; n += 256) sbias[n] = n < d.Nout ? bias[n] : 0.f;
   halo_load(cur, 0);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -729,10 +734,18 @@ tfc_igemm2_kernel(const TfcGather d, const bf16_t* __restrict__ in, const uint4*
   int stat_lim = 0, tcount = 0;
   auto stat_flush = [&]() {                                       // wave 0
     if (stat_prev && wave == 0) {
+      // every slot read is requested before the first sum (the global stores may alias LDS for all the compiler knows: interleaved with them, each
+      // read waited alone); the sum keeps its order ((s0 + s1) + s2) + s3
+      constexpr int NI = (2 * BN) / 64;
+      float sl[NI][4];
 #pragma unroll
-      for (int i = lane; i < 2 * BN; i += 64) {
-        const float v = ((sstat[i] + sstat[2 * BN + i]) + sstat[4 * BN + i]) + sstat[6 * BN + i];
-        if (i < stat_lim) stat_prev[i] = v;
+      for (int k = 0; k < NI; ++k)
+#pragma unroll
+        for (int s = 0; s < 4; ++s) sl[k][s] = sstat[s * 2 * BN + lane + 64 * k];
+#pragma unroll
+      for (int k = 0; k < NI; ++k) {
+        const float v = ((sl[k][0] + sl[k][1]) + sl[k][2]) + sl[k][3];
+        if (lane + 64 * k < stat_lim) stat_prev[lane + 64 * k] = v;
       }
     }
   };
@@ -896,13 +909,20 @@ tfc_igemm2_kernel(const TfcGather d, const bf16_t* __restrict__ in, const uint4*
     }
 
     if (prio) asm volatile("s_setprio 0");
-    if (flags & TFC_EP_STATS) stat_flush();
+    if (fl & TFC_EP_STATS) stat_flush();
     // ---- epilogue: accumulators (channel rows x pixel lanes) -> 16-byte units -> staged tile in LDS ----
     TFC_STAMP_AT(2);
 #ifdef TFC_STAMP
     TFC_NOW(tk1); acc_main += tk1 - tk0; tk0 = tk1; ++ntile;
 #endif
     unsigned char* stage = IL ? smem + ((sc & 1) ? 0 : buf_bytes) : stage_fix;   // IL: beside the live halo buffer (parity sc & 1 after the last stage)
+    {
+    // the per-thread addresses of the epilogue are derived per tile from a thread id the compiler cannot see through, so that none of them is hoisted
+    // out of the tile loop and kept in a register across the K loop (the names shadow the launch-invariant ones)
+    unsigned tid_e = (unsigned)tid;
+    asm volatile("" : "+v"(tid_e));
+    __builtin_assume(tid_e < 256u);
+    const int tid = (int)tid_e, lane = tid_e & 63, h = lane >> 5, r = lane & 31, su = tid_e % UPR;
 #pragma unroll
     for (int ps = 0; ps < NPASS; ++ps) {                          // one pass per BNS staged channels (a single pass unless the tile is 256 wide)
 #pragma unroll
@@ -913,16 +933,17 @@ tfc_igemm2_kernel(const TfcGather d, const bf16_t* __restrict__ in, const uint4*
       float4 bq[4];
 #pragma unroll
       for (int q = 0; q < 4; ++q)
-        bq[q] = (flags & TFC_EP_BIAS) ? *reinterpret_cast<const float4*>(sbias + cur.nb_blk * BN + blk * 32 + 8 * q + 4 * h) : make_float4(0.f, 0.f, 0.f, 0.f);
+        bq[q] = (fl & TFC_EP_BIAS) ? *reinterpret_cast<const float4*>(sbias + cur.nb_blk * BN + blk * 32 + 8 * q + 4 * h) : make_float4(0.f, 0.f, 0.f, 0.f);
 #pragma unroll
       for (int mi = 0; mi < MT; ++mi) {
         uint32_t pk[4][2];
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
-          float v0 = acc[mi][nt][4 * q + 0] * osc + bq[q].x, v1 = acc[mi][nt][4 * q + 1] * osc + bq[q].y;
-          float v2 = acc[mi][nt][4 * q + 2] * osc + bq[q].z, v3 = acc[mi][nt][4 * q + 3] * osc + bq[q].w;
-          if (flags & TFC_EP_LEAKY) { v0 = fmaxf(v0, 0.2f * v0); v1 = fmaxf(v1, 0.2f * v1); v2 = fmaxf(v2, 0.2f * v2); v3 = fmaxf(v3, 0.2f * v3); }
-          if (flags & TFC_EP_RELU) { v0 = fmaxf(v0, 0.f); v1 = fmaxf(v1, 0.f); v2 = fmaxf(v2, 0.f); v3 = fmaxf(v3, 0.f); }
+          // one fused multiply-add, spelled out: what the compiler has always made of acc * osc + bias here must not depend on the instantiation
+          float v0 = __builtin_fmaf(acc[mi][nt][4 * q + 0], osc, bq[q].x), v1 = __builtin_fmaf(acc[mi][nt][4 * q + 1], osc, bq[q].y);
+          float v2 = __builtin_fmaf(acc[mi][nt][4 * q + 2], osc, bq[q].z), v3 = __builtin_fmaf(acc[mi][nt][4 * q + 3], osc, bq[q].w);
+          if (fl & TFC_EP_LEAKY) { v0 = fmaxf(v0, 0.2f * v0); v1 = fmaxf(v1, 0.2f * v1); v2 = fmaxf(v2, 0.2f * v2); v3 = fmaxf(v3, 0.2f * v3); }
+          if (fl & TFC_EP_RELU) { v0 = fmaxf(v0, 0.f); v1 = fmaxf(v1, 0.f); v2 = fmaxf(v2, 0.f); v3 = fmaxf(v3, 0.f); }
           pk[q][0] = pack_bf16x2(v0, v1);
           pk[q][1] = pack_bf16x2(v2, v3);
         }
@@ -964,32 +985,58 @@ tfc_igemm2_kernel(const TfcGather d, const bf16_t* __restrict__ in, const uint4*
       float s1[8], s2[8];
 #pragma unroll
       for (int e = 0; e < 8; ++e) { s1[e] = 0.f; s2[e] = 0.f; }
+      // The staged rows leave in groups of SG: the group's LDS reads are requested together (every staged row exists: no predicate), for EP_ACCUM its
+      // destination reads too (a lane outside the tile or past Nout reads the first unit of `out` instead -- an address inside the tensor, as the halo
+      // loads of the K loop do -- and its value is dropped), then the arithmetic, then the predicated stores: one LDS latency and one memory round
+      // trip per group instead of one per row. Groups of four rows at the most: all eight of a 128-channel pass in flight made the widest instantiations
+      // spill. The run-time-flag instantiation holds the accumulate AND the statistics registers, so on the 64-channel tile, which runs three
+      // workgroups per CU on a register budget of 168, it takes pairs.
+      constexpr int SG = NSK < 4 ? NSK : (FC < 0 && NSK == 4 ? 2 : 4);
 #pragma unroll
-      for (int kk = 0; kk < NSK; ++kk) {
-        const int rho = tid / UPR + kk * (256 / UPR);
-        const int rr = rho & 31;
-        const int ty = 2 * (rho >> 5) + (rr & 1), tx = rr >> 1;
-        if (ty < ylim && tx < xlim && n0 < d.Nout) {
-          T* po = obase + srel[kk];
-          uint4 v = *reinterpret_cast<const uint4*>(stage + rho * ROWP + su * 16);
-          if (flags & (TFC_EP_ACCUM | TFC_EP_STATS)) {
+      for (int k0 = 0; k0 < NSK; k0 += SG) {
+        bool ok[SG];
+        T* po[SG];
+        uint4 v[SG], gv[SG];
+#pragma unroll
+        for (int j = 0; j < SG; ++j) {
+          const int rho = tid / UPR + (k0 + j) * (256 / UPR);
+          const int rr = rho & 31;
+          const int ty = 2 * (rho >> 5) + (rr & 1), tx = rr >> 1;
+          ok[j] = ty < ylim && tx < xlim && n0 < d.Nout;
+          po[j] = obase + srel[k0 + j];
+          v[j] = *reinterpret_cast<const uint4*>(stage + rho * ROWP + su * 16);
+        }
+        if (fl & TFC_EP_ACCUM) {
+#pragma unroll
+          for (int j = 0; j < SG; ++j) gv[j] = *reinterpret_cast<const uint4*>(ok[j] ? po[j] : out);
+        }
+        __builtin_amdgcn_sched_barrier(0);                        // the requests above stay ahead of the first use
+        if (fl & (TFC_EP_ACCUM | TFC_EP_STATS)) {
+#pragma unroll
+          for (int j = 0; j < SG; ++j) {                          // statistics: per thread in row order, of the values stored
             float f[8];
-            unpack16<bf16_t>(v, f);
-            if (flags & TFC_EP_ACCUM) {
+            unpack16<bf16_t>(v[j], f);
+            if (fl & TFC_EP_ACCUM) {
               float g[8];
-              unpack16<bf16_t>(*reinterpret_cast<const uint4*>(po), g);
+              unpack16<bf16_t>(gv[j], g);
 #pragma unroll
               for (int e = 0; e < 8; ++e) f[e] += g[e];
-              v = pack16<bf16_t>(f);
-              if (flags & TFC_EP_STATS) unpack16<bf16_t>(v, f);
+              v[j] = pack16<bf16_t>(f);
+              if (fl & TFC_EP_STATS) unpack16<bf16_t>(v[j], f);
             }
+            if ((fl & TFC_EP_STATS) && ok[j]) {
+#pragma clang fp contract(off)                                    // the square is rounded before it is added, as it always was: a fused form would change the sums
 #pragma unroll
-            for (int e = 0; e < 8; ++e) { s1[e] += f[e]; s2[e] += f[e] * f[e]; }
+              for (int e = 0; e < 8; ++e) { s1[e] += f[e]; s2[e] += f[e] * f[e]; }
+            }
           }
-          store_stream16(po, v);
         }
+#pragma unroll
+        for (int j = 0; j < SG; ++j)
+          if (ok[j]) store_stream16(po[j], v[j]);
+        __builtin_amdgcn_sched_barrier(0);                        // the next group's requests stay behind this group's stores
       }
-      if (flags & TFC_EP_STATS) {
+      if (fl & TFC_EP_STATS) {
         // lanes with equal (lane % UPR) hold partial sums of the same 8 channels: butterfly over them (a fixed tree), then each wave stores its sums
         // into its own LDS slot; wave 0 adds the four slots in wave order one tile later (stat_flush) and writes the tile's 2 * BN sums as whole
         // 256-byte runs of part[img][tile][n][2]
@@ -1011,6 +1058,7 @@ tfc_igemm2_kernel(const TfcGather d, const bf16_t* __restrict__ in, const uint4*
     }
     if (IL) TFC_SYNC();                                           // the staged tile is rewritten by the next pass / by the next tile's first halo store
     }
+    }
     ++tcount;
     TFC_STAMP_AT(5);
 #ifdef TFC_STAMP
@@ -1022,8 +1070,8 @@ tfc_igemm2_kernel(const TfcGather d, const bf16_t* __restrict__ in, const uint4*
     w = w_next;
     w_next = item(round + 1);
   }
-  if (HALVES == 2 || (flags & TFC_EP_STATS)) TFC_SYNC();          // (HALVES == 2: always, so that the barrier count does not depend on the flags)
-  if (flags & TFC_EP_STATS) stat_flush();                         // the last tile's sums
+  if (HALVES == 2 || (fl & TFC_EP_STATS)) TFC_SYNC();             // (HALVES == 2: always, so that the barrier count does not depend on the flags)
+  if (fl & TFC_EP_STATS) stat_flush();                            // the last tile's sums
   if constexpr (HALVES == 2)
     for (; nbar < nbar_total; ++nbar) __builtin_amdgcn_s_barrier();
 #ifdef TFC_STAMP
@@ -3159,16 +3207,6 @@ static hipError_t launch_igemm2_pat(const TfcConvPlan& plan, const TfcGather& d,
     if (!part_ws || (long long)d.nimg * nparts * d.Nout * 2 > (long long)TFC_PART_WS_FLOATS) return hipErrorInvalidValue;
   }
   const int nwork = d.nimg * d.tiles_y * d.tiles_x * (d.ph_n > 1 ? d.ph_n : 1) * nblkN;
-  // resident workgroups per CU of THIS instantiation (2 for the 128-channel tile: 77 KB of LDS, ~195 VGPRs; 3 for the narrower tiles); a persistent
-  // grid never depends on co-residency for correctness (no inter-workgroup waits), so the occupancy query only sizes the grid
-  static thread_local int occ_cache = 0, occ_lds = -1;
-  if (!occ_cache || occ_lds != lds) {
-    int occ = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, tfc_igemm2_kernel<MT, NT, WM, WN, PAT, 1>, 256, (size_t)lds) != hipSuccess || occ < 1) occ = 2;
-    occ_cache = occ > 3 ? 3 : occ;
-    occ_lds = lds;
-  }
-  const int cap = occ_cache * tfc_num_cus();
   const long long phase_wbytes = (long long)tfc_packed_bytes(d, 2);
   if constexpr (BN <= 128) {
     const int nst = ((d.Cin_pad * 2) / 64) * d.nplanes;
@@ -3183,9 +3221,33 @@ static hipError_t launch_igemm2_pat(const TfcConvPlan& plan, const TfcGather& d,
       return hipGetLastError();
     }
   }
-  TFC_LAUNCH((tfc_igemm2_kernel<MT, NT, WM, WN, PAT>), dim3(nwork < cap ? nwork : cap), dim3(256), lds, st, d, (const bf16_t*)in, (const uint4*)wp,
-             (bf16_t*)out, bias, part_ws, dbg, oscale, flags, NB32, nblkN, buf_bytes, phase_wbytes, nwork, 0,
-             [] { static const int p = [] { const char* e = getenv("TFC_IGEMM_PRIO"); return e ? atoi(e) : 0; }(); return p ? 256 : 0; }());
+  // One instantiation per flag set that the training step issues (the epilogue is then straight-line code), one that reads the flags at run time for
+  // every other combination. Same arithmetic per element in all of them: the stored bits do not depend on which one runs.
+  auto launch = [&](auto fcc) {
+    constexpr int FC = decltype(fcc)::value;
+    // resident workgroups per CU of THIS instantiation (2 for the 128-channel tile: 77 KB of LDS, ~195 VGPRs; 3 for the narrower tiles); a persistent
+    // grid never depends on co-residency for correctness (no inter-workgroup waits), so the occupancy query only sizes the grid
+    static thread_local int occ_cache = 0, occ_lds = -1;
+    if (!occ_cache || occ_lds != lds) {
+      int occ = 0;
+      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, tfc_igemm2_kernel<MT, NT, WM, WN, PAT, 1, FC>, 256, (size_t)lds) != hipSuccess || occ < 1) occ = 2;
+      occ_cache = occ > 3 ? 3 : occ;
+      occ_lds = lds;
+    }
+    // test hook (tfc_debug_set_persistent_grid): n >= 1 replaces the cap, as in tfc_persistent_grid, so that a tiny shape walks many tiles per workgroup
+    const int cap = g_tfc_persistent_grid > 0 ? g_tfc_persistent_grid : occ_cache * tfc_num_cus();
+    TFC_LAUNCH((tfc_igemm2_kernel<MT, NT, WM, WN, PAT, 1, FC>), dim3(nwork < cap ? nwork : cap), dim3(256), lds, st, d, (const bf16_t*)in, (const uint4*)wp,
+               (bf16_t*)out, bias, part_ws, dbg, oscale, flags, NB32, nblkN, buf_bytes, phase_wbytes, nwork, 0,
+               [] { static const int p = [] { const char* e = getenv("TFC_IGEMM_PRIO"); return e ? atoi(e) : 0; }(); return p ? 256 : 0; }());
+  };
+  switch (flags) {
+    case 0: launch(std::integral_constant<int, 0>{}); break;                                              // no norm behind it; with an oscale: D input gradients
+    case TFC_EP_STATS: launch(std::integral_constant<int, TFC_EP_STATS>{}); break;                        // in front of an InstanceNorm
+    case TFC_EP_BIAS | TFC_EP_LEAKY: launch(std::integral_constant<int, TFC_EP_BIAS | TFC_EP_LEAKY>{}); break;   // D forward
+    case TFC_EP_ACCUM: launch(std::integral_constant<int, TFC_EP_ACCUM>{}); break;                        // input gradient added into a skip window
+    case TFC_EP_BIAS | TFC_EP_RELU: launch(std::integral_constant<int, TFC_EP_BIAS | TFC_EP_RELU>{}); break;     // VGG feature stack of LPIPS
+    default: launch(std::integral_constant<int, -1>{}); break;
+  }
   if (flags & TFC_EP_STATS) return tfc_launch_part_reduce(part_ws, stats, d.nimg, nparts, 2 * d.Nout, st);
   return hipGetLastError();
 }
