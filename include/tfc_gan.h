@@ -50,6 +50,14 @@ extern "C" {
                              input gradient (four output phases in one launch), weight gradient (bf16: the transposed convolution's phase-fused
                              launch with the two tensors exchanged; fp32 / bf16x3: one launch per parity plane into disjoint filter taps; slabs
                              added in a fixed order, no float atomics); every compute mode                                                 */
+#define TFC_OP_CONV3R 6   /* nn.ReflectionPad2d(1) + nn.Conv2d(C, C', 3)  (cyclegan_og/models.py:34-35, :38-39): the residual blocks of CycleGAN's
+                             GeneratorResNet. Output H x W; weights as for TFC_OP_CONV3 ([Cout][Cin][4][4], filter in rows / columns 0..2) and the same
+                             channel-byte rule; H >= 2 and W >= 2 (smaller is refused, as torch refuses it). Per axis source coordinate -1 reads 1 and H
+                             reads H - 2, at the IMAGE border only. Every compute mode, all three passes: forward (TFC_EP_BIAS | TFC_EP_STATS |
+                             TFC_EP_RELU), weight gradient (the forward's reflect halo; slabs added in a fixed order; the seven unused taps of the slot
+                             are written as zeros, or kept under `accumulate`), input gradient = the EXACT adjoint: the TFC_OP_CONV3 taps on the
+                             (H + 2) x (W + 2) grid of the padded input into scratch, then a fold pass that adds the one-pixel ring into the pixels the
+                             forward read it from (corners fold on both axes) and honours TFC_EP_ACCUM. The scratch: tfc_conv_dgrad_set_ws. No atomics */
 
 /* epilogue flags of tfc_conv_fwd / tfc_conv_dgrad */
 #define TFC_EP_BIAS 1       /* + bias[Cout]                                                                                   */
@@ -119,6 +127,12 @@ int tfc_conv_dgrad_image(void* stream, int dt, const void* dy, int dy_pitch, int
 /* ---- input gradient: dx = oscale * op^T(dy) (flags: TFC_EP_ACCUM) ------------------------------------------------ */
 int tfc_conv_dgrad(void* stream, int dt, int op, const void* dy, int dy_pitch, int N, int H, int W, int Cin, int Cout,
                    const void* packed, void* dx, int dx_pitch, const float* oscale, int flags);
+/* Scratch of the TFC_OP_CONV3R input gradient: tfc_conv_dgrad_ws_bytes() bytes (0 for every other op) = the padded gradient [N][H+2][W+2][pad8(Cin)]
+ * in the storage type; contents undefined between calls. tfc_conv_dgrad keeps its signature, so the buffer is registered per calling THREAD (as the
+ * test hooks are) and read at each TFC_OP_CONV3R call of that thread: 16-byte aligned, used by the launches of one stream at a time; the call refuses
+ * a missing or smaller buffer. ws = NULL withdraws it. Nothing is allocated or synchronised. */
+size_t tfc_conv_dgrad_ws_bytes(int dt, int op, int N, int H, int W, int Cin, int Cout);
+int tfc_conv_dgrad_set_ws(void* ws, size_t bytes);
 /* ---- weight gradient: dw (torch layout, fp32) = or += x (*) dy ; ws: tfc_conv_wgrad_ws_bytes() of scratch = [64 MiB of split-K
  *      slabs | fp32 accumulator]. Zero it once after allocation: the accumulator part must be ALL ZERO on entry and is left all
  *      zero on return (the slab part is scratch). One buffer sized for the largest layer may be shared by every layer. The slabs
@@ -143,6 +157,11 @@ int tfc_conv_wgrad(void* stream, int dt, int op, const void* x, int x_pitch, con
  */
 int tfc_act_fwd(void* stream, int dt, const void* x, int x_pitch, int N, int H, int W, int C, const float* stats, int norm,
                 float slope, int pool, float drop_p, uint32_t seed, void* y, int y_pitch, float* stats_out, float* part_ws);
+/* second half of a residual block (cyclegan_og/models.py:40, :44): y = res + InstanceNorm(x; stats), one pass, stored in the storage type of dt.
+ * stats [N][C][2] = (sum, sum of squares) of x as the convolution epilogue leaves them; the fp32 constants of tfc_act_fwd: m = s1 / HW,
+ * var = max(s2 / HW - m^2, 0), eps 1e-5. y may alias x or res. Backward: tfc_act_bwd (norm, slope 1, pool 0) through the norm, g itself to the skip. */
+int tfc_norm_add_fwd(void* stream, int dt, const void* x, int x_pitch, const void* res, int res_pitch, int N, int H, int W, int C,
+                     const float* stats, void* y, int y_pitch);
 int tfc_act_bwd(void* stream, int dt, int mode, const void* dy, int dy_pitch, const void* x, int x_pitch, int N, int H, int W, int C,
                 const float* stats, int norm, float slope, int pool, float drop_p, uint32_t seed, float* rstats, void* dx, int dx_pitch, float* part_ws);
 /* tfc_act_bwd(mode 0, pool 2, norm 0) for a 64-channel bf16 tensor x that was never stored: sign_mask = its sign words (uint8 [N][H][W][8], bit c of the
@@ -443,7 +462,8 @@ int tfc_lpips_head(void* stream, int dt, const void* fx, const void* fy, const f
 /* ---- measurement -------------------------------------------------------------------------------------------------- */
 /* When enabled every gather-GEMM / wgrad launch is bracketed by hipEvents on its own stream; tfc_prof_collect()
  * (call after synchronising) sums them per kernel class: 0 = tfc_igemm_kernel family, 1 = tfc_wgrad family (+ slab reduce),
- * 2 = the wgrad finish pass, 3 = the fused first-block backward (transposed blur + weight gradient in one launch). */
+ * 2 = the wgrad finish pass, 3 = the fused first-block backward (transposed blur + weight gradient in one launch), 4 = the fold pass of the
+ * TFC_OP_CONV3R input gradient (meta pass 4). */
 int tfc_prof_enable(int on);
 int tfc_prof_collect(int kclass, double* total_ms, double* algorithmic_flop, long long* launches);
 /* per-call detail of the records gathered on this thread since the last collect (kclass 2 = the wgrad finish pass): arrays of max_records entries,

@@ -11,6 +11,7 @@ the label-conditioned step of ..._debiased(.py|_V2.py|_V3.py) (TrainStep(labels=
 the edge-mask step of ..._experiment.py (TrainStep(mask=True), GeneratorUNet(mask=True), mask_maker, mask_l1_loss),
 FFT_Components / fft_components / calculate_ffts, and the fused TrainStep + data-parallel layer (batch_scope="global": the batch-coupled mask and
 KL terms take their extrema / softmax over the batch of all ranks).
+Of the CycleGAN baseline (cyclegan_og/models.py): ResidualBlock and GeneratorResNet, the residual trunk on the reflect-padded 3x3 convolution op.
 """
 import os as _os
 
@@ -36,11 +37,12 @@ from .losses import (ContrastiveLoss, FFT_Components, calculate_ffts, color_jitt
                      patch_triplet_loss, region_weights, regional_fft_components, regional_fft_loss, sample_spectra, temperature_triplet_loss,
                      vectorize_temps)
 from .metrics import EvalAccumulator, bhattacharyya, mutual_information, ncc, psnr, ssim, to_gray, to_uint8  # noqa: F401
-from .models import (BlurPool, Discriminator, Discriminator1, GeneratorUNet, Pix2PixDiscriminator, UNetDown, UNetUp, get_batch_invariant,  # noqa: F401
+from .models import (BlurPool, Discriminator, Discriminator1, GeneratorResNet, GeneratorUNet, Pix2PixDiscriminator, ResidualBlock, UNetDown, UNetUp,  # noqa: F401
+                     get_batch_invariant,
                      get_compute_dtype, set_batch_invariant, set_compute_dtype, weights_init_normal)
 
 __all__ = ["UNetDown", "UNetUp", "GeneratorUNet", "Discriminator1", "Discriminator", "BlurPool", "weights_init_normal",
            "make_16_patches", "make_4_patches", "patch_first_flat_index", "stitch_patches", "ContrastiveLoss", "patch_triplet_loss", "FFT_Components", "fft_components", "calculate_ffts",
            "patch_fft_loss", "global_fft_loss", "regional_fft_components", "regional_fft_loss", "region_weights", "debias_weights", "mask_weights", "mask_maker", "mask_l1_loss", "mse_spec", "other_spec", "psnr", "ssim", "bhattacharyya", "ncc", "mutual_information", "to_uint8", "to_gray",
            "EvalAccumulator", "sample_spectra", "vectorize_temps", "temperature_triplet_loss", "color_jitter_thermal",
-           "color_jitter_params", "synthetic_pairs", "synthetic_temperatures", "load_clean_state", "save_checkpoint", "stitch_16_patches", "global_grid", "TrainStep", "STN21Step", "DarkVisibleStep", "Pix2PixDiscriminator", "LPIPS", "ImageDataset", "LabelledImageDataset", "TestImageDataset", "DeviceLoader", "pair_resize_normalize", "Warp", "affine_warp", "morph_gradient", "morph_triplet", "triplet_margin_rows", "set_compute_dtype", "get_compute_dtype", "set_batch_invariant", "get_batch_invariant", "build", "TfcError", "all_gather_records"]
+           "color_jitter_params", "synthetic_pairs", "synthetic_temperatures", "load_clean_state", "save_checkpoint", "stitch_16_patches", "global_grid", "TrainStep", "STN21Step", "DarkVisibleStep", "Pix2PixDiscriminator", "GeneratorResNet", "ResidualBlock", "LPIPS", "ImageDataset", "LabelledImageDataset", "TestImageDataset", "DeviceLoader", "pair_resize_normalize", "Warp", "affine_warp", "morph_gradient", "morph_triplet", "triplet_margin_rows", "set_compute_dtype", "get_compute_dtype", "set_batch_invariant", "get_batch_invariant", "build", "TfcError", "all_gather_records"]

@@ -126,7 +126,7 @@ struct WeightMap { int Nreal, Creal; long long sn, sc; };
 
 static int out_hw(int op, int h) {
   if (op == TFC_OP_CONV2) return h / 2;
-  return op == TFC_OP_CONV ? h - 1 : ((op == TFC_OP_PADCONV || op == TFC_OP_CONV3) ? h : 2 * h);
+  return op == TFC_OP_CONV ? h - 1 : ((op == TFC_OP_PADCONV || op == TFC_OP_CONV3 || op == TFC_OP_CONV3R) ? h : 2 * h);
 }
 // phases = descriptors of one pass that are packed / launched one after the other: the four sub-pixel output phases of the 2x-upsampling ops (forward
 // and weight gradient) and of the stride-2 convolution's input gradient; the four source parity planes of the stride-2 convolution's weight gradient
@@ -218,6 +218,9 @@ static int build_desc(int op, int pass, int phase, int N, int H, int W, int Cin,
         if (wm) *wm = {Cout, Cin, (long long)Cin * 16, 16};
         break;
       }
+      case TFC_OP_CONV3R:                                         // the same gather with the reflect rule on the image's one-pixel ring (forward and weight gradient)
+        d.reflect = 1;
+        [[fallthrough]];
       case TFC_OP_CONV3: {
         // nn.Conv2d(k3, s1, p1) (VGG16 feature stack of LPIPS): the 3 x 3 filter is handed over zero-padded to the 4 x 4 torch layout of the other
         // ops ([Cout][Cin][4][4], taps (ky, kx) with ky, kx <= 2 used), so packing shares every code path; 3 x 3 raster = tap pattern 6
@@ -259,9 +262,15 @@ static int build_desc(int op, int pass, int phase, int N, int H, int W, int Cin,
         if (wm) *wm = {Cin, Cout, 16, (long long)Cin * 16};    // Conv2d weight [Cout][Cin][4][4], n = ci, c = co
         break;
       }
+      case TFC_OP_CONV3R:
+        // the gradient of the reflect-PADDED input, E[e] = sum_k dy[e - k] W[k] over e = 0 .. H + 1 (padded row e = i + 1): the taps and the packed stream of
+        // TFC_OP_CONV3 on a (H + 2) x (W + 2) result grid, zero outside dy. tfc_conv_dgrad folds the one-pixel ring of E into the interior (the exact
+        // adjoint of the padding) behind this launch.
+        d.OH = H + 2; d.OW = W + 2; d.GH = H + 2; d.GW = W + 2;
+        [[fallthrough]];
       case TFC_OP_CONV3: {
         TfcPlane& p = d.plane[0];                                 // dx[i] = sum_k dy[i + 1 - k] W[k], k = 0..2: plane offsets 0..2 from i - 1, flipped taps
-        p.dy0 = -1; p.dx0 = -1; p.hh = 10; p.hw = 18; p.ntaps = 9;
+        p.dy0 = op == TFC_OP_CONV3R ? -2 : -1; p.dx0 = p.dy0; p.hh = 10; p.hw = 18; p.ntaps = 9;
         for (int ky = 0; ky < 3; ++ky)
           for (int kx = 0; kx < 3; ++kx) { const int t = ky * 3 + kx; p.tap_dy[t] = ky; p.tap_dx[t] = kx; p.tap_mask[t] = 1 << ((2 - ky) * 4 + (2 - kx)); }
         if (wm) *wm = {Cin, Cout, 16, (long long)Cin * 16};
@@ -329,7 +338,8 @@ static int check_desc(const TfcGather& d, int dt) {
 
 static int check_common(int dt, int op, int N, int H, int W, int Cin, int Cout) {
   REQUIRE(dt == TFC_DT_BF16 || dt == TFC_DT_F32 || dt == TFC_DT_BF16X3, "bad dtype %d", dt);
-  REQUIRE(op >= 0 && op <= 5, "bad op %d", op);
+  REQUIRE(op >= 0 && op <= 6, "bad op %d", op);
+  REQUIRE(op != TFC_OP_CONV3R || (H >= 2 && W >= 2), "TFC_OP_CONV3R (reflection padding 1) needs H >= 2 and W >= 2 (H=%d W=%d)", H, W);
   REQUIRE(N > 0 && H > 1 && W > 1 && Cin > 0 && Cout > 0, "bad dims N=%d H=%d W=%d Cin=%d Cout=%d", N, H, W, Cin, Cout);
   REQUIRE(op != TFC_OP_CONV2 || (H % 2 == 0 && W % 2 == 0), "TFC_OP_CONV2 (stride 2) needs an even H and W (H=%d W=%d)", H, W);
   REQUIRE((long long)N * (2 * H) * (2 * W) * (long long)(pad8(Cin) > pad8(Cout) ? pad8(Cin) : pad8(Cout)) < 2147483647LL,
@@ -338,7 +348,8 @@ static int check_common(int dt, int op, int N, int H, int W, int Cin, int Cout) 
   REQUIRE(pad8(Cin) * es <= 64 || (pad8(Cin) * es) % 64 == 0, "Cin=%d: padded channel bytes must be <= 64 or a multiple of 64", Cin);
   REQUIRE(pad8(Cout) * es <= 64 || (pad8(Cout) * es) % 64 == 0, "Cout=%d: padded channel bytes must be <= 64 or a multiple of 64", Cout);
   // 9 taps do not fill whole 64-byte K chunks with narrow channels: the caller pads the image to 64 bytes of channels (lpips.py does)
-  REQUIRE(op != TFC_OP_CONV3 || ((pad8(Cin) * es) % 64 == 0 && (pad8(Cout) * es) % 64 == 0), "TFC_OP_CONV3 needs channel bytes in multiples of 64 (Cin=%d Cout=%d)", Cin, Cout);
+  REQUIRE((op != TFC_OP_CONV3 && op != TFC_OP_CONV3R) || ((pad8(Cin) * es) % 64 == 0 && (pad8(Cout) * es) % 64 == 0),
+          "TFC_OP_CONV3 / TFC_OP_CONV3R need channel bytes in multiples of 64 (Cin=%d Cout=%d)", Cin, Cout);
   return 0;
 }
 static int check_pitch(int dt, int pitch, int cpad, const char* what) {
@@ -367,7 +378,7 @@ static size_t phase_packed_offset(int dt, int op, int pass, int Cin, int Cout, i
 }
 
 extern "C" size_t tfc_conv_packed_bytes(int dt, int op, int pass, int Cin, int Cout) {
-  if (pass < 0 || pass > 1 || op < 0 || op > 5) return 0;
+  if (pass < 0 || pass > 1 || op < 0 || op > 6) return 0;
   return phase_packed_offset(dt, op, pass, Cin, Cout, num_phases(op, pass));
 }
 
@@ -387,7 +398,7 @@ extern "C" int tfc_conv_pack(void* stream, int dt, int op, int pass, const float
 
 static double conv_flop(int op, int N, int H, int W, int Cin, int Cout) {
   const double oh = out_hw(op, H), ow = out_hw(op, W);
-  const double taps = (op == TFC_OP_CONVT) ? 4.0 : (op == TFC_OP_CONV3 ? 9.0 : 16.0);
+  const double taps = (op == TFC_OP_CONVT) ? 4.0 : ((op == TFC_OP_CONV3 || op == TFC_OP_CONV3R) ? 9.0 : 16.0);
   return 2.0 * N * oh * ow * (double)Cin * Cout * taps;
 }
 
@@ -488,6 +499,22 @@ extern "C" int tfc_upconv_head_fwd(void* stream, int dt, const void* x, int x_pi
   return 0;
 }
 
+// Scratch of the TFC_OP_CONV3R input gradient: the padded gradient E [N][H + 2][W + 2][pad8(Cin)] in the storage type. tfc_conv_dgrad keeps its
+// signature, so the buffer is handed over per calling THREAD (like the other host-side hooks); it is used by the launches of one stream at a time.
+static thread_local void* g_dgrad_ws = nullptr;
+static thread_local size_t g_dgrad_ws_bytes = 0;
+extern "C" size_t tfc_conv_dgrad_ws_bytes(int dt, int op, int N, int H, int W, int Cin, int Cout) {
+  (void)Cout;
+  if (op != TFC_OP_CONV3R || N <= 0 || H < 2 || W < 2 || Cin <= 0) return 0;
+  return (size_t)N * (H + 2) * (W + 2) * pad8(Cin) * es_of(dt);
+}
+extern "C" int tfc_conv_dgrad_set_ws(void* ws, size_t bytes) {
+  REQUIRE(ws == nullptr || (((uintptr_t)ws) & 15) == 0, "ws must be 16-byte aligned");
+  g_dgrad_ws = ws;
+  g_dgrad_ws_bytes = ws ? bytes : 0;
+  return 0;
+}
+
 extern "C" int tfc_conv_dgrad(void* stream, int dt, int op, const void* dy, int dy_pitch, int N, int H, int W, int Cin, int Cout,
                               const void* packed, void* dx, int dx_pitch, const float* oscale, int flags) {
   if (int e = check_common(dt, op, N, H, W, Cin, Cout)) return e;
@@ -498,6 +525,28 @@ extern "C" int tfc_conv_dgrad(void* stream, int dt, int op, const void* dy, int 
   if (dt == TFC_DT_BF16 && Cin >= 8) REQUIRE(dx_pitch % 8 == 0 && (((uintptr_t)dx) & 15) == 0, "bf16 outputs are stored in 16-byte units: dx must be 16-byte aligned with pitch %% 8 == 0");
   REQUIRE((flags & ~TFC_EP_ACCUM) == 0, "dgrad supports only TFC_EP_ACCUM");
   TfcGather d;
+  if (op == TFC_OP_CONV3R) {
+    // The exact adjoint of reflection padding in two steps. (1) the TFC_OP_CONV3 taps on the (H + 2) x (W + 2) grid of the PADDED input -> E in the
+    // calling thread's scratch (tfc_conv_dgrad_set_ws). (2) the fold: every ring pixel of E goes back to the interior pixel the forward read it from
+    // (corners fold on both axes), TFC_EP_ACCUM adds the existing dx. A reflection of dy cannot express this: dx[1] gets dy[0] W[0] on top of its
+    // three zero-padding terms, a fourth tap that only the border rows have.
+    const size_t need = tfc_conv_dgrad_ws_bytes(dt, op, N, H, W, Cin, Cout);
+    REQUIRE(g_dgrad_ws != nullptr && g_dgrad_ws_bytes >= need && (((uintptr_t)g_dgrad_ws) & 15) == 0,
+            "TFC_OP_CONV3R input gradient needs %zu bytes of 16-byte aligned scratch on this thread (tfc_conv_dgrad_set_ws: %zu given)", need, g_dgrad_ws_bytes);
+    const int e_pitch = pad8(Cin);
+    if (int e = build_desc(op, 1, 0, N, H, W, Cin, Cout, dy_pitch, e_pitch, &d, nullptr)) return e;
+    if (int e = check_desc(d, dt)) return e;
+    {
+      ProfScope prof(0, conv_flop(op, N, H, W, Cin, Cout), (hipStream_t)stream, op, 1, N, H, W, Cin, Cout);
+      CHECK_HIP(tfc_launch_igemm(dt, d, dy, packed, g_dgrad_ws, nullptr, nullptr, nullptr, nullptr, oscale, 0, (hipStream_t)stream), "tfc_conv_dgrad");
+    }
+    if (int e = check_pitch(dt, dx_pitch, pad8(Cin), "dx")) return e;
+    if (int e = check_ptr16(dx, "dx")) return e;
+    ProfScope prof(4, 0.0, (hipStream_t)stream, op, 4, N, H, W, Cin, Cout);   // class 4: the fold pass (no algorithmic FLOP of its own)
+    CHECK_HIP(tfc_launch_reflect_fold(dt, g_dgrad_ws, e_pitch, dx, dx_pitch, N, H, W, pad8(Cin), (flags & TFC_EP_ACCUM) ? 1 : 0, (hipStream_t)stream),
+              "tfc_conv_dgrad (reflect fold)");
+    return 0;
+  }
   if (int e = build_desc(op, 1, 0, N, H, W, Cin, Cout, dy_pitch, dx_pitch, &d, nullptr)) return e;
   if (fold_phases(op, 1)) set_fold(d, op);                        // stride-2 convolution: the four output phases in one launch
   if (int e = check_desc(d, dt)) return e;
@@ -575,7 +624,7 @@ extern "C" int tfc_conv_wgrad(void* stream, int dt, int op, const void* x, int x
   if (int e = check_pitch(dt, x_pitch, pad8(Cin), "x")) return e;
   if (int e = check_pitch(dt, dy_pitch, pad8(Cout), "dy")) return e;
   REQUIRE(ws != nullptr && dw != nullptr, "ws / dw null");
-  REQUIRE(op != TFC_OP_CONV3, "TFC_OP_CONV3 (frozen VGG features of the LPIPS term) has no weight-gradient pass");
+  REQUIRE(op != TFC_OP_CONV3, "TFC_OP_CONV3 (frozen VGG features of the LPIPS term) has no weight-gradient pass");   // its reflect-padded sibling TFC_OP_CONV3R has
   hipStream_t st = (hipStream_t)stream;
   WeightMap wm{};                                                // the accumulator part of ws is all-zero on entry (caller zeroes it ONCE) and again on exit
   TfcWgradFin fin{dw, 0, 0, accumulate, false};
@@ -679,6 +728,19 @@ extern "C" int tfc_act_fwd(void* stream, int dt, const void* x, int x_pitch, int
   REQUIRE(!norm || stats, "stats is null");
   REQUIRE(!stats_out || part_ws, "stats_out needs part_ws");
   CHECK_HIP(tfc_launch_act_fwd(dt, p, x, stats, y, stats_out, part_ws, (hipStream_t)stream), "tfc_act_fwd");
+  return 0;
+}
+
+extern "C" int tfc_norm_add_fwd(void* stream, int dt, const void* x, int x_pitch, const void* res, int res_pitch, int N, int H, int W, int C,
+                                const float* stats, void* y, int y_pitch) {
+  ActParams p;
+  if (int e = fill_act(p, dt, N, H, W, C, x_pitch, y_pitch, 1, 1.f, 0, 0.f, 0)) return e;
+  if (int e = check_ptr16(x, "x")) return e;
+  if (int e = check_ptr16(res, "res")) return e;
+  if (int e = check_ptr16(y, "y")) return e;
+  REQUIRE(stats != nullptr, "stats is null");
+  REQUIRE(x_pitch >= C && y_pitch >= C && res_pitch >= C && res_pitch % (16 / es_of(dt)) == 0, "pitches: x %d, res %d, y %d must be >= C=%d in 16-byte units", x_pitch, res_pitch, y_pitch, C);
+  CHECK_HIP(tfc_launch_norm_add(dt, p, x, stats, res, res_pitch, y, (hipStream_t)stream), "tfc_norm_add_fwd");
   return 0;
 }
 
@@ -1520,12 +1582,17 @@ extern "C" int tfc_probe_mfma(void* stream, float* out) {
 //   pass 2: x [N][H][W][pad8(Cin)], w_host = dy [N][OH][OW][pad8(Cout)] -> y = dw (torch layout)
 // ---------------------------------------------------------------------------------------------------------------
 extern "C" int tfc_host_emulate_conv(int op, int pass, int es, const float* x, const float* w, float* y, int N, int H, int W, int Cin, int Cout) {
-  REQUIRE(pass >= 0 && pass <= 2 && op >= 0 && op <= 5 && (es == 2 || es == 4), "bad op/pass/es");
+  REQUIRE(pass >= 0 && pass <= 2 && op >= 0 && op <= 6 && (es == 2 || es == 4), "bad op/pass/es");
   REQUIRE(op != TFC_OP_CONV2 || (H % 2 == 0 && W % 2 == 0), "TFC_OP_CONV2 needs an even H and W");
+  REQUIRE(op != TFC_OP_CONV3R || (H >= 2 && W >= 2), "TFC_OP_CONV3R (reflection padding 1) needs H >= 2 and W >= 2 (H=%d W=%d)", H, W);
   const int UE = 16 / es;                                        // elements per 16-byte unit in the emulated geometry
   const int OH = out_hw(op, H), OW = out_hw(op, W);
   const int inC = pass == 1 ? pad8(Cout) : pad8(Cin);
   const int outC = pass == 1 ? pad8(Cin) : pad8(Cout);
+  // TFC_OP_CONV3R, pass 1: the gather fills the padded gradient E [N][H + 2][W + 2], which is folded into dx below (as tfc_conv_dgrad does)
+  std::vector<float> ering;
+  float* const dx_folded = y;
+  if (op == TFC_OP_CONV3R && pass == 1) { ering.assign((size_t)N * (H + 2) * (W + 2) * outC, 0.f); y = ering.data(); }
   if (pass == 2) {
     std::vector<double> acc((size_t)16 * Cout * Cin, 0.0);
     WeightMap wm{};
@@ -1540,7 +1607,8 @@ extern "C" int tfc_host_emulate_conv(int op, int pass, int es, const float* x, c
             const float* dyp = w + ((size_t)(img * d.OH + oy) * d.OW + ox) * outC;
             const int ta = a % TFC_TILE_H, tb = b % TFC_TILE_W, a0 = a - ta, b0 = b - tb;
             for (int t = 0; t < p.ntaps; ++t) {
-              const int sy = (a0 + p.dy0 + ta + p.tap_dy[t]) * d.SS + p.py, sx = (b0 + p.dx0 + tb + p.tap_dx[t]) * d.SS + p.px;
+              int sy = (a0 + p.dy0 + ta + p.tap_dy[t]) * d.SS + p.py, sx = (b0 + p.dx0 + tb + p.tap_dx[t]) * d.SS + p.px;
+              if (d.reflect) { sy = tfc_reflect1(sy, d.IH); sx = tfc_reflect1(sx, d.IW); }
               if (sy < 0 || sy >= d.IH || sx < 0 || sx >= d.IW) continue;
               const float* xp = x + ((size_t)(img * d.IH + sy) * d.IW + sx) * inC;
               for (int n = 0; n < Cout; ++n)
@@ -1597,8 +1665,9 @@ extern "C" int tfc_host_emulate_conv(int op, int pass, int es, const float* x, c
                     for (int s = 0; s < nsub; ++s, ++gs)
                       for (int h = 0; h < 2; ++h) {
                         const int u = 2 * s + h, tap = u / UPP, g = u % UPP;
-                        const int sy = (a0 + p.dy0 + ty + p.tap_dy[tap]) * d.SS + p.py;
-                        const int sx = (b0 + p.dx0 + tx + p.tap_dx[tap]) * d.SS + p.px;
+                        int sy = (a0 + p.dy0 + ty + p.tap_dy[tap]) * d.SS + p.py;
+                        int sx = (b0 + p.dx0 + tx + p.tap_dx[tap]) * d.SS + p.px;
+                        if (d.reflect) { sy = tfc_reflect1(sy, d.IH); sx = tfc_reflect1(sx, d.IW); }
                         if (sy < 0 || sy >= d.IH || sx < 0 || sx >= d.IW) continue;
                         const float* xp = x + ((size_t)(img * d.IH + sy) * d.IW + sx) * inC + cc * CK + g * UE;
                         const float* wq = &wp[((size_t)(gs * NB32 + nb) * 64 + (h * 32 + rn)) * UE];
@@ -1610,5 +1679,16 @@ extern "C" int tfc_host_emulate_conv(int op, int pass, int es, const float* x, c
             }
         }
   }
+  if (!ering.empty())                                            // dx[i][j] = sum of the padded positions that reflect onto (i, j): the adjoint of the padding
+    for (int img = 0; img < N; ++img)
+      for (int i = 0; i < H; ++i)
+        for (int j = 0; j < W; ++j)
+          for (int c = 0; c < outC; ++c) {
+            double acc = 0.0;
+            for (int ey = 0; ey < H + 2; ++ey)
+              for (int ex = 0; ex < W + 2; ++ex)
+                if (tfc_reflect1(ey - 1, H) == i && tfc_reflect1(ex - 1, W) == j) acc += ering[((size_t)(img * (H + 2) + ey) * (W + 2) + ex) * outC + c];
+            dx_folded[((size_t)(img * H + i) * W + j) * outC + c] = (float)acc;
+          }
   return 0;
 }

@@ -1255,6 +1255,98 @@ static hipError_t act_fwd_t(const ActParams& p, const void* x, const float* stat
 hipError_t tfc_launch_act_fwd(int dt, const ActParams& p, const void* x, const float* stats, void* out, float* stats_out, float* part_ws, hipStream_t st) {
   return dt == TFC_DT_BF16 ? act_fwd_t<bf16_t>(p, x, stats, out, stats_out, part_ws, st) : act_fwd_t<float>(p, x, stats, out, stats_out, part_ws, st);
 }
+// ---- second half of a residual block: y = res + InstanceNorm(x; stats). The thread / pixel map and the fp32 constants of tfc_act_fwd_kernel (pool 0). ----
+template <typename T>
+__global__ void __launch_bounds__(256)
+tfc_norm_add_kernel(const ActParams p, const T* x, const float* __restrict__ stats, const T* res, int res_pitch, T* out) {   // out may alias x or res
+  constexpr int UE = ElemTraits<T>::UE;
+  const int CV = p.C / UE;
+  const int PPB = 256 / CV;
+  const int cv = threadIdx.x % CV, pl = threadIdx.x / CV;
+  const int n = blockIdx.y;
+  const int npix = p.H * p.W;
+  if (pl >= PPB) return;
+  float mean[UE], rstd[UE];
+  const float inv = 1.f / (float)npix;
+#pragma unroll
+  for (int e = 0; e < UE; ++e) {
+    const float s1 = stats[((size_t)n * p.C + cv * UE + e) * 2 + 0];
+    const float s2 = stats[((size_t)n * p.C + cv * UE + e) * 2 + 1];
+    const float m = s1 * inv;
+    mean[e] = m;
+    rstd[e] = rsqrtf(fmaxf(s2 * inv - m * m, 0.f) + p.eps);
+  }
+  const size_t img = (size_t)n * npix;
+  for (int pix = blockIdx.x * PPB + pl; pix < npix; pix += gridDim.x * PPB) {
+    float v[UE], r[UE];
+    unpack16<T>(*reinterpret_cast<const uint4*>(x + (img + pix) * p.x_pitch + cv * UE), v);
+    unpack16<T>(*reinterpret_cast<const uint4*>(res + (img + pix) * res_pitch + cv * UE), r);
+#pragma unroll
+    for (int e = 0; e < UE; ++e) r[e] += (v[e] - mean[e]) * rstd[e];
+    *reinterpret_cast<uint4*>(out + (img + pix) * p.o_pitch + cv * UE) = pack16<T>(r);
+  }
+}
+hipError_t tfc_launch_norm_add(int dt, const ActParams& p, const void* x, const float* stats, const void* res, int res_pitch, void* out, hipStream_t st) {
+  const dim3 grid = act_grid(p.H * p.W, p.C, dt == TFC_DT_BF16 ? 8 : 4, p.N);
+  if (dt == TFC_DT_BF16)
+    hipLaunchKernelGGL(tfc_norm_add_kernel<bf16_t>, grid, dim3(256), 0, st, p, (const bf16_t*)x, stats, (const bf16_t*)res, res_pitch, (bf16_t*)out);
+  else
+    hipLaunchKernelGGL(tfc_norm_add_kernel<float>, grid, dim3(256), 0, st, p, (const float*)x, stats, (const float*)res, res_pitch, (float*)out);
+  return hipGetLastError();
+}
+
+// ---- fold pass of the TFC_OP_CONV3R input gradient: dx[i][j] (+)= the sum of the padded gradient e [N][H + 2][W + 2] over the padded positions that
+// nn.ReflectionPad2d(1) read from (i, j): itself, the ring row above / below when i is 1 / H - 2, the ring column alike, and the ring corner when both
+// hold. At most 3 x 3 terms (H == 3: row 1 takes both ring rows), added in fp32 in a fixed order, rounded once. One thread per 16-byte unit of dx. ----
+template <typename T>
+__global__ void __launch_bounds__(256)
+tfc_reflect_fold_kernel(const T* __restrict__ e, int e_pitch, T* dx, int dx_pitch, int H, int W, int CV, long long total, int accumulate) {
+  constexpr int UE = ElemTraits<T>::UE;
+  for (long long idx = (long long)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (long long)gridDim.x * 256) {
+    const int cv = (int)(idx % CV);
+    long long pix = idx / CV;
+    const int j = (int)(pix % W); pix /= W;
+    const int i = (int)(pix % H);
+    const long long n = pix / H;
+    int ys[3], xs[3], ny = 1, nx = 1;
+    ys[0] = i + 1; xs[0] = j + 1;                                // padded coordinates: pixel (i, j) sits at (i + 1, j + 1)
+    if (i == 1) ys[ny++] = 0;
+    if (i == H - 2) ys[ny++] = H + 1;
+    if (j == 1) xs[nx++] = 0;
+    if (j == W - 2) xs[nx++] = W + 1;
+    float acc[UE];
+#pragma unroll
+    for (int k = 0; k < UE; ++k) acc[k] = 0.f;
+    for (int a = 0; a < ny; ++a)
+      for (int b = 0; b < nx; ++b) {
+        float v[UE];
+        unpack16<T>(*reinterpret_cast<const uint4*>(e + ((n * (H + 2) + ys[a]) * (W + 2) + xs[b]) * e_pitch + cv * UE), v);
+#pragma unroll
+        for (int k = 0; k < UE; ++k) acc[k] += v[k];
+      }
+    T* o = dx + ((n * H + i) * W + j) * dx_pitch + cv * UE;
+    if (accumulate) {
+      float v[UE];
+      unpack16<T>(*reinterpret_cast<const uint4*>(o), v);
+#pragma unroll
+      for (int k = 0; k < UE; ++k) acc[k] += v[k];
+    }
+    *reinterpret_cast<uint4*>(o) = pack16<T>(acc);
+  }
+}
+hipError_t tfc_launch_reflect_fold(int dt, const void* e, int e_pitch, void* dx, int dx_pitch, int N, int H, int W, int C, int accumulate, hipStream_t st) {
+  const int ue = dt == TFC_DT_BF16 ? 8 : 4;
+  const int CV = C / ue;
+  const long long total = (long long)N * H * W * CV;
+  long long nb = (total + 255) / 256;
+  if (nb > 65536) nb = 65536;                                     // grid-stride beyond: a thread's units, not their sums, depend on the grid
+  if (dt == TFC_DT_BF16)
+    hipLaunchKernelGGL(tfc_reflect_fold_kernel<bf16_t>, dim3((unsigned)nb), dim3(256), 0, st, (const bf16_t*)e, e_pitch, (bf16_t*)dx, dx_pitch, H, W, CV, total, accumulate);
+  else
+    hipLaunchKernelGGL(tfc_reflect_fold_kernel<float>, dim3((unsigned)nb), dim3(256), 0, st, (const float*)e, e_pitch, (float*)dx, dx_pitch, H, W, CV, total, accumulate);
+  return hipGetLastError();
+}
+
 template <typename T, int MODE>
 static void act_bwd_launch(const dim3& grid, const ActParams& p, const void* dout, const void* x, const float* stats, float* rstats,
                            void* dx, int use_x, int dx_pitch, hipStream_t st) {

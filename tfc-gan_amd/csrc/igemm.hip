@@ -172,8 +172,9 @@ tfc_igemm_kernel(const TfcGather d, const T* __restrict__ in, const uint4* __res
         const int pix = idx >> upp_shift, g = idx & (UPP - 1);
         const int hy = pix / pd.hw, hx = pix - hy * pd.hw;
         hoff[i] = (hy * P + hx) * PS + g * 16;
-        const int y = (a0 + pd.dy0 + phy * d.ph_d0 + hy) * d.SS + pd.py;
-        const int x = (b0 + pd.dx0 + phx * d.ph_d0 + hx) * d.SS + pd.px;
+        int y = (a0 + pd.dy0 + phy * d.ph_d0 + hy) * d.SS + pd.py;
+        int x = (b0 + pd.dx0 + phx * d.ph_d0 + hx) * d.SS + pd.px;
+        if (d.reflect) { y = tfc_reflect1(y, d.IH); x = tfc_reflect1(x, d.IW); }   // image border only: (y, x) are source coordinates
         if (y >= 0 && y < d.IH && x >= 0 && x < d.IW)
           hv[i] = *reinterpret_cast<const uint4*>(in_img + ((size_t)(y * d.IW + x)) * d.in_pitch + cc * CK + g * UE);
       }
@@ -514,7 +515,7 @@ struct Tile2 {
 // Both halves execute the SAME total number of barriers (dummy barriers pad the shorter sequence), so every wave reaches the end.
 // FC: the epilogue's flag set as a compile-time constant, or -1 = read `flags` at run time. The launcher instantiates FC for the flag sets the
 // training step issues (launch_igemm2_pat) and sends every other combination, and the two-half form, to FC = -1.
-template <int MT, int NT, int WM, int WN, int PAT, int HALVES = 1, int FC = -1>
+template <int MT, int NT, int WM, int WN, int PAT, int HALVES = 1, int FC = -1, bool RF = false>   // RF: TfcGather::reflect, at compile time
 __global__ void __launch_bounds__(256 * HALVES, 2)
 tfc_igemm2_kernel(const TfcGather d, const bf16_t* __restrict__ in, const uint4* __restrict__ wp, bf16_t* out,
                   const float* __restrict__ bias, float* stats, float* dbg, const float* __restrict__ oscale,
@@ -637,8 +638,15 @@ tfc_igemm2_kernel(const TfcGather d, const bf16_t* __restrict__ in, const uint4*
     hvalid = 0;
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-      const bool ok = hoff[i] >= 0 && (unsigned)(Y0 + hyS[i]) < (unsigned)d.IH && (unsigned)(X0 + hxS[i]) < (unsigned)d.IW;
-      const bf16_t* src = ok ? base + hrel[i] : in;
+      int Y = Y0 + hyS[i], X = X0 + hxS[i], radj = 0;
+      if constexpr (RF) {                                         // the one-pixel ring of the IMAGE reads its mirror pixel (instantiations of their own:
+                                                                  // the other ops' kernels carry none of this)
+        const int Yr = tfc_reflect1(Y, d.IH), Xr = tfc_reflect1(X, d.IW);
+        radj = ((Yr - Y) * d.IW + (Xr - X)) * d.in_pitch;
+        Y = Yr; X = Xr;
+      }
+      const bool ok = hoff[i] >= 0 && (unsigned)Y < (unsigned)d.IH && (unsigned)X < (unsigned)d.IW;
+      const bf16_t* src = ok ? base + hrel[i] + radj : in;
       hvalid |= ok ? (1u << i) : 0u;
       asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(hv[i]) : "v"(src) : "memory");
     }
@@ -2041,8 +2049,9 @@ tfc_wgrad_kernel(const TfcGather d, const T* __restrict__ dO, const T* __restric
     for (int i = 0; i < NHA; ++i) {
       vha[i] = make_uint4(0, 0, 0, 0);
       if (hok[i]) {                                               // (hy, hx, channel) of a thread's halo units are tile-invariant: computed once per launch
-        const int y = (a0 + pd.dy0 + hyq[i]) * d.SS + pd.py;
-        const int x = (b0 + pd.dx0 + hxq[i]) * d.SS + pd.px;
+        int y = (a0 + pd.dy0 + hyq[i]) * d.SS + pd.py;
+        int x = (b0 + pd.dx0 + hxq[i]) * d.SS + pd.px;
+        if (d.reflect) { y = tfc_reflect1(y, d.IH); x = tfc_reflect1(x, d.IW); }   // the forward's reflect halo: dW[k] = sum dy[o] xr[o + k - 1]
         if (y >= 0 && y < d.IH && x >= 0 && x < d.IW)
           vha[i] = *reinterpret_cast<const uint4*>(in + ((size_t)(img * d.IH + y) * d.IW + x) * d.in_pitch + hcq[i]);
       }
@@ -3157,7 +3166,7 @@ void tfc_plan_igemm(int dt, const TfcGather& d, int flags, int ncu, bool inv, Tf
     const int nblkN = (nb + kFormNT[form] * kFormWN[form] - 1) / (kFormNT[form] * kFormWN[form]);
     const int nwork = ntiles * plan_phases(d) * nblkN;
     const int half_bytes = (igemm2_lds_bytes(d, kFormNT[form], kFormWN[form], flags, nullptr) + 255) & ~255;
-    if (halves_env == 2 && !inv && 2 * half_bytes <= 160 * 1024 && nwork >= 2 * ncu && (g_tfc_force_cfg < 0 || (g_tfc_force_cfg & 32)))   // test hook: forced tiles run the two-workgroup form unless bit 5 is set
+    if (halves_env == 2 && !inv && !d.reflect && 2 * half_bytes <= 160 * 1024 && nwork >= 2 * ncu && (g_tfc_force_cfg < 0 || (g_tfc_force_cfg & 32)))   // test hook: forced tiles run the two-workgroup form unless bit 5 is set
       p->kernel = TFC_K_IGEMM2_HALVES;
   }
   p->nparts = igemm_nparts(d, p->kernel != TFC_K_IGEMM, kFormWM[form]);
@@ -3223,6 +3232,29 @@ static hipError_t launch_igemm2_pat(const TfcConvPlan& plan, const TfcGather& d,
   }
   // One instantiation per flag set that the training step issues (the epilogue is then straight-line code), one that reads the flags at run time for
   // every other combination. Same arithmetic per element in all of them: the stored bits do not depend on which one runs.
+  if constexpr (PAT == 6) {
+    if (d.reflect) {
+      // the reflect-padded 3 x 3 convolution: the halo stage with the reflect rule compiled in. Two flag sets: none (its input gradient into the
+      // fold pass's scratch) and the run-time epilogue (bias + statistics of the residual blocks, and everything else)
+      auto launch_rf = [&](auto fcc) {
+        constexpr int FC = decltype(fcc)::value;
+        static thread_local int occ_cache = 0, occ_lds = -1;
+        if (!occ_cache || occ_lds != lds) {
+          int occ = 0;
+          if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, tfc_igemm2_kernel<MT, NT, WM, WN, PAT, 1, FC, true>, 256, (size_t)lds) != hipSuccess || occ < 1) occ = 2;
+          occ_cache = occ > 3 ? 3 : occ;
+          occ_lds = lds;
+        }
+        const int cap = g_tfc_persistent_grid > 0 ? g_tfc_persistent_grid : occ_cache * tfc_num_cus();
+        TFC_LAUNCH((tfc_igemm2_kernel<MT, NT, WM, WN, PAT, 1, FC, true>), dim3(nwork < cap ? nwork : cap), dim3(256), lds, st, d, (const bf16_t*)in,
+                   (const uint4*)wp, (bf16_t*)out, bias, part_ws, dbg, oscale, flags, NB32, nblkN, buf_bytes, phase_wbytes, nwork, 0, 0);
+      };
+      if (flags == 0) launch_rf(std::integral_constant<int, 0>{});
+      else launch_rf(std::integral_constant<int, -1>{});
+      if (flags & TFC_EP_STATS) return tfc_launch_part_reduce(part_ws, stats, d.nimg, nparts, 2 * d.Nout, st);
+      return hipGetLastError();
+    }
+  }
   auto launch = [&](auto fcc) {
     constexpr int FC = decltype(fcc)::value;
     // resident workgroups per CU of THIS instantiation (2 for the 128-channel tile: 77 KB of LDS, ~195 VGPRs; 3 for the narrower tiles); a persistent

@@ -51,8 +51,14 @@ struct TfcGather {
   int out_pitch, Nout;        // output pixel pitch (elements), real output channels
   int ph_n;                   // sub-pixel phases folded into ONE launch (1 or 4): phase (py,px) = (ph >> 1, ph & 1)
   int ph_d0, ph_oo;           // per phase bit: shift of the halo origin (dy0/dx0) and of the output offset (OOY/OOX)
+  int reflect;                // 1: nn.ReflectionPad2d(1) instead of zero padding (TFC_OP_CONV3R): source row -1 reads row 1, row IH reads row IH - 2 (columns
+                              // alike); every halo stage a 3 x 3 shape reaches applies tfc_reflect1 to the SOURCE coordinate, so a tile border never reflects
   struct TfcPlane plane[TFC_MAX_PLANES];
 };
+
+// The reflect rule of TfcGather::reflect, per axis: only the one-pixel ring is remapped (a halo pixel further out serves outputs past the image
+// alone and stays zero). n >= 2; with n == 2 both borders land on the image's own two rows.
+static inline __host__ __device__ int tfc_reflect1(int v, int n) { return v == -1 ? 1 : (v == n ? n - 2 : v); }
 
 // Derived constants (host and device agree through these helpers).
 static inline __host__ __device__ int tfc_pb(int cin_pad, int es) { int b = cin_pad * es; return b < 64 ? b : 64; }  // chunk bytes per pixel
@@ -171,6 +177,8 @@ struct SnBatch {
 };
 hipError_t tfc_launch_sn_step_batched(const SnBatch& b, int power_iter, float eps, hipStream_t st);
 hipError_t tfc_launch_act_fwd(int dt, const ActParams& p, const void* x, const float* stats, void* out, float* stats_out, float* part_ws, hipStream_t st);
+hipError_t tfc_launch_norm_add(int dt, const ActParams& p, const void* x, const float* stats, const void* res, int res_pitch, void* out, hipStream_t st);
+hipError_t tfc_launch_reflect_fold(int dt, const void* e, int e_pitch, void* dx, int dx_pitch, int N, int H, int W, int C, int accumulate, hipStream_t st);
 hipError_t tfc_launch_act_bwd(int dt, int mode, const ActParams& p, const void* dout, const void* x, const float* stats, float* rstats, void* dx, int use_x, int dx_pitch, float* part_ws, hipStream_t st);
 hipError_t tfc_launch_act_pool2_bwd_signs(const ActParams& p, const void* dout, const unsigned char* sign_mask, float* rstats, void* dx, int dx_pitch, float* part_ws, hipStream_t st);
 hipError_t tfc_launch_colsum(int dt, const void* x, long long rows, int pitch, int C, float* out, float* part_ws, hipStream_t st);

@@ -460,6 +460,133 @@ class Pix2PixDiscriminator(_CoreModule, nn.Module):
         return _PatchGANFn.apply(self, tuple(params), {}, img_A, img_B, *params.values())
 
 
+class _TrunkFn(torch.autograd.Function):
+    """the residual trunk (nets.ResNetTrunkCore) at the fp32 NCHW module boundary: one pack to NHWC in front of it, one unpack behind it.
+    `params` are the module's named_core_params() in the order of its core's param_names()."""
+
+    @staticmethod
+    def forward(ctx, module, x, *params):
+        ops.require_gpu(x)
+        core = module._core_for(x.device)
+        y, tctx = core.forward(_to_nhwc(x, core.dt))
+        ctx.core, ctx.tctx = core, tctx
+        ctx.need_w = any(p.requires_grad for p in params)
+        return _to_nchw(y, x)
+
+    @staticmethod
+    def backward(ctx, g):
+        core = ctx.core
+        names = core.param_names()
+        grads = {k: torch.empty_like(core.params[k]) for k in names} if ctx.need_w else None
+        gv = _to_nhwc(g, core.dt)
+        if gv.t.data_ptr() == g.data_ptr():                       # a channels-last fp32 gradient: the core updates its argument in place
+            gv = ops.View(gv.t.clone(), gv.C)
+        gx = core.backward(ctx.tctx, gv, grads)
+        ctx.tctx = None
+        return (None, _to_nchw(gx, g)) + (tuple(grads[k] for k in names) if grads else (None,) * len(names))
+
+
+def _reflect_pad(x, p):
+    """nn.ReflectionPad2d(p) as slices, flips and concatenations: the same values, and a backward of plain additions -- torch's own
+    reflection_pad2d backward scatters with float atomics on the GPU, which would make every gradient in front of it vary from run to run"""
+    x = torch.cat((x[..., 1:p + 1].flip(-1), x, x[..., -p - 1:-1].flip(-1)), -1)
+    return torch.cat((x[..., 1:p + 1, :].flip(-2), x, x[..., -p - 1:-1, :].flip(-2)), -2)
+
+
+def _run_layers(layers, x):
+    """the torch layers of a GeneratorResNet in order, its ReflectionPad2d modules (which hold nothing) through _reflect_pad"""
+    for m in layers:
+        if isinstance(m, nn.ReflectionPad2d):
+            x = _reflect_pad(x, m.padding[0])
+        else:
+            x = m.forward_torch(x) if isinstance(m, ResidualBlock) else m(x)
+    return x
+
+
+class ResidualBlock(_CoreModule, nn.Module):
+    """cyclegan_og/models.py:29-46: x + [ReflectionPad2d(1), Conv2d(C, C, 3), InstanceNorm2d, ReLU, ReflectionPad2d(1), Conv2d(C, C, 3),
+    InstanceNorm2d](x). state_dict keys block.{1,5}.{weight,bias}. forward: fp32 NCHW in and out on the HIP kernels (one-block nets.ResNetTrunkCore);
+    the stock torch modules inside `.block` hold the parameters and serve forward_torch(), the A/B partner and the CPU path."""
+
+    def __init__(self, in_features):
+        super().__init__()
+        C = int(in_features)
+        self.block = nn.Sequential(nn.ReflectionPad2d(1), nn.Conv2d(C, C, 3), nn.InstanceNorm2d(C), nn.ReLU(inplace=True),
+                                   nn.ReflectionPad2d(1), nn.Conv2d(C, C, 3), nn.InstanceNorm2d(C))
+        self.features = C
+        self._init_core()
+
+    def named_core_params(self):
+        sd = dict(self.named_parameters())
+        return {k: sd[k] for k in nets.res_block_keys("")}
+
+    def _make_core(self, dt):
+        return nets.ResNetTrunkCore(dt, self.features, 1, prefixes=[""])
+
+    def forward_torch(self, x):
+        return x + _run_layers(self.block, x)
+
+    def forward(self, x):
+        _refuse_replica(self)
+        return _TrunkFn.apply(self, x, *self.named_core_params().values())
+
+
+RESNET_TRUNK_FIRST = 10                  # index of the first residual block inside GeneratorResNet.model
+
+
+class GeneratorResNet(_CoreModule, nn.Module):
+    """CycleGAN's generator, cyclegan_og/models.py:49-102, with the reference's state_dict keys (model.1 / .4 / .7 the stem and the two stride-2
+    convolutions, model.10 ... model.{9 + n} the residual blocks, then the two upsample convolutions and the 7 x 7 head: model.20 / .24 / .28 at n = 9).
+    forward(x [N, channels, H, W]) -> fp32 NCHW in (-1, 1); H and W multiples of 4.
+    trunk="hip": the residual blocks -- 76 % of the arithmetic at 256 x 256 with 9 blocks -- run on nets.ResNetTrunkCore; the stem, the two stride-2
+    convolutions, the two upsample convolutions and the head are torch layers in fp32. trunk="torch": the whole module as torch layers (the A/B
+    partner, and the CPU path)."""
+
+    def __init__(self, input_shape, num_residual_blocks, trunk="hip"):
+        super().__init__()
+        if trunk not in ("hip", "torch"):
+            raise ops._lib.TfcError(f"GeneratorResNet: trunk={trunk!r} (\"hip\": residual blocks on the HIP kernels, \"torch\": torch layers throughout)")
+        channels = int(input_shape[0])
+        self.channels, self.num_residual_blocks, self.trunk = channels, int(num_residual_blocks), trunk
+        feats = 64
+        # the reference pads by `channels` in front of its 7 x 7 convolutions (3 only because the images have 3 channels); kept as it is
+        layers = [nn.ReflectionPad2d(channels), nn.Conv2d(channels, feats, 7), nn.InstanceNorm2d(feats), nn.ReLU(inplace=True)]
+        for _ in range(2):
+            layers += [nn.Conv2d(feats, 2 * feats, 3, stride=2, padding=1), nn.InstanceNorm2d(2 * feats), nn.ReLU(inplace=True)]
+            feats *= 2
+        assert len(layers) == RESNET_TRUNK_FIRST
+        self.features = feats
+        layers += [ResidualBlock(feats) for _ in range(self.num_residual_blocks)]
+        for _ in range(2):
+            layers += [nn.Upsample(scale_factor=2), nn.Conv2d(feats, feats // 2, 3, stride=1, padding=1), nn.InstanceNorm2d(feats // 2),
+                       nn.ReLU(inplace=True)]
+            feats //= 2
+        layers += [nn.ReflectionPad2d(channels), nn.Conv2d(feats, channels, 7), nn.Tanh()]
+        self.model = nn.Sequential(*layers)
+        self._init_core()
+
+    def _prefixes(self):
+        return nets.res_prefixes(self.num_residual_blocks, RESNET_TRUNK_FIRST, "model.")
+
+    def named_core_params(self):
+        sd = dict(self.named_parameters())
+        return {k: sd[k] for p in self._prefixes() for k in nets.res_block_keys(p)}
+
+    def _make_core(self, dt):
+        return nets.ResNetTrunkCore(dt, self.features, self.num_residual_blocks, prefixes=self._prefixes())
+
+    def forward(self, x):
+        _refuse_replica(self)
+        end = RESNET_TRUNK_FIRST + self.num_residual_blocks
+        if self.trunk == "torch":
+            return _run_layers(self.model, x)
+        ops.require_gpu(x)
+        x = _run_layers(self.model[:RESNET_TRUNK_FIRST], x.float())
+        if self.num_residual_blocks:
+            x = _TrunkFn.apply(self, x, *self.named_core_params().values())
+        return _run_layers(self.model[end:], x)
+
+
 # The reference script names the class Discriminator1; older scripts of the same repo (TFC-STN/archive/*) call the identical
 # class Discriminator -- north_star uses that name.
 Discriminator = Discriminator1

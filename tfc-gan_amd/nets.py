@@ -1,7 +1,8 @@
 """Forward / backward orchestration of the networks on the HIP kernels.
 
 `GeneratorCore` mirrors GeneratorUNet (reference TFCGAN_multigpu_patchFFT_16P.py:136-174), `DiscriminatorCore` mirrors
-Discriminator1 (:182-211), `Pix2PixCore` the plain PatchGAN of the DarkVisible script.  All work on raw NHWC buffers and hand-written
+Discriminator1 (:182-211), `Pix2PixCore` the plain PatchGAN of the DarkVisible script, `ResNetTrunkCore` the residual blocks of CycleGAN's
+GeneratorResNet (cyclegan_og/models.py:29-46).  All work on raw NHWC buffers and hand-written
 backward chains (no autograd inside); the nn.Module mirrors in models.py wrap them in torch.autograd.Function, and engine.py calls them directly.
 
 Layout: the side stream, the tables and parameter names, then the BLOCK STEPS -- every sequence of launches that more than one network runs (a
@@ -19,7 +20,7 @@ import os
 import torch
 
 from . import ops
-from .ops import (DT_BF16, OP_CONV, OP_CONV2, OP_CONVT, OP_PADCONV, OP_UPCONV, View, new_act)
+from .ops import (DT_BF16, OP_CONV, OP_CONV2, OP_CONV3R, OP_CONVT, OP_PADCONV, OP_UPCONV, View, new_act)
 
 # Weight gradients on a second HIP stream. The weight gradient of layer i needs only the gradient of its output, which the main chain (input gradient ->
 # activation backward -> next layer) has finished with, so it runs beside that chain and fills the tails of its persistent launches (same-box A/B:
@@ -813,3 +814,170 @@ class Pix2PixCore:
         if need_input_grad:
             return ops.unpack_nchw(dt, g_cur, self.channels, c0=0)
         return None
+
+
+# ---- the residual trunk of CycleGAN's GeneratorResNet (cyclegan_og/models.py:29-46, :79-80) -----------------------------------------------------
+RES_CONVS = (1, 5)                      # indices of the two convolutions inside a block's nn.Sequential
+
+
+def res_block_keys(prefix):
+    """state_dict keys of one residual block in forward order: (weight, bias) of block.1, then of block.5"""
+    return [f"{prefix}block.{i}.{s}" for i in RES_CONVS for s in ("weight", "bias")]
+
+
+def res_prefixes(n_blocks, first=0, stem=""):
+    """key prefixes of n_blocks consecutive blocks: GeneratorResNet holds them as model.{10 + b}."""
+    return [f"{stem}{first + b}." for b in range(n_blocks)]
+
+
+class ResNetTrunkCore:
+    """n_blocks x [ReflectionPad2d(1) -> Conv2d(C, C, 3) -> InstanceNorm2d -> ReLU -> ReflectionPad2d(1) -> Conv2d(C, C, 3) -> InstanceNorm2d, + x] on
+    NHWC Views. Per block: TFC_OP_CONV3R with bias and the InstanceNorm statistics in its epilogue, the fused normalise + ReLU pass, TFC_OP_CONV3R
+    again, and tfc_norm_add_fwd (normalise + skip in one pass). The backward mirrors it; the input gradient of a block's first convolution is
+    ACCUMULATED onto the skip gradient in place (the fold pass of the convolution's input gradient honours TFC_EP_ACCUM).
+
+    The state_dict holds 3 x 3 filters and the convolution op takes [C][C][4][4] slots: the core keeps one zero-padded copy of all its filters
+    (refreshed by repack(), ahead of the one packing launch) and one 4 x 4 staging slot for the weight gradients.
+    prefixes: the key prefix of every block (default "0.", "1.", ...); a block's keys are prefix + block.{1,5}.{weight,bias}."""
+
+    def __init__(self, dt, features, n_blocks, prefixes=None):
+        self.dt = dt
+        self.features = int(features)
+        self.n_blocks = int(n_blocks)
+        self.prefixes = list(prefixes) if prefixes is not None else res_prefixes(self.n_blocks)
+        assert len(self.prefixes) == self.n_blocks
+        unit = 32 if dt == DT_BF16 else 16
+        if self.features % unit:
+            raise ops._lib.TfcError(f"ResNetTrunkCore: {self.features} features; the reflect-padded 3x3 convolution needs channel bytes in multiples of 64 "
+                                    f"(a multiple of {unit} channels in this compute mode)")
+        self.params = None
+        self.packed = {}                                          # (block, conv, "fwd" | "dgrad") -> operand stream
+        self._plan = None
+        self._w4 = None                                           # [2 * n_blocks, C, C, 4, 4]: the filters in the op's 4 x 4 slots
+        self._g4 = None                                           # [C, C, 4, 4]: staging slot of a weight gradient
+        self._ws = None                                           # persistent wgrad scratch (zeroed once, re-zeroed by the kernels)
+        self.debug = None                                         # tests: a dict that receives the stored gradients of every block
+
+    def param_names(self):
+        return [k for p in self.prefixes for k in res_block_keys(p)]
+
+    def backward_order(self):
+        """parameter names in the order their gradients become final during backward"""
+        out = []
+        for p in reversed(self.prefixes):
+            w1, b1, w2, b2 = res_block_keys(p)
+            out += [w2, b2, w1, b1]
+        return out
+
+    def set_params(self, params):
+        """params: dict key -> fp32 CUDA tensor: weights [C, C, 3, 3] and biases [C] under param_names()"""
+        self.params = params
+        self.packed = {}
+        self._plan = None
+
+    def _weights(self):
+        return [self.params[f"{p}block.{i}.weight"] for p in self.prefixes for i in RES_CONVS]
+
+    def repack(self):
+        """refresh the 4 x 4 copies of the filters, then re-pack every operand stream (fwd + dgrad): ONE packing launch over a device-resident plan"""
+        C = self.features
+        ws = self._weights()
+        if self._plan is None:
+            for w in ws:
+                if tuple(w.shape) != (C, C, 3, 3):
+                    raise ops._lib.TfcError(f"ResNetTrunkCore: a filter of shape {tuple(w.shape)} (expected {(C, C, 3, 3)})")
+            self._w4 = torch.zeros((len(ws), C, C, 4, 4), dtype=torch.float32, device=ws[0].device)
+            entries = []
+            for b in range(self.n_blocks):
+                for c in range(2):
+                    w4 = self._w4[2 * b + c]
+                    entries += [((b, c, "fwd"), OP_CONV3R, 0, w4, C, C), ((b, c, "dgrad"), OP_CONV3R, 1, w4, C, C)]
+            self._plan = plan_streams(self.dt, entries, self.packed)
+        self._w4[..., :3, :3].copy_(torch.stack([w.detach() for w in ws]))
+        self._plan.run()
+
+    # ---- forward ----
+    def forward(self, x: View, save=True):
+        """x: NHWC View of `features` channels in the compute dtype (H, W >= 2). Returns (output View, ctx or None)."""
+        ops.require_gpu(x.t)
+        if x.C != self.features:
+            raise ops._lib.TfcError(f"ResNetTrunkCore: input of {x.C} channels for a trunk of {self.features}")
+        if not self.packed:
+            self.repack()
+        dt, dev, C = self.dt, x.t.device, self.features
+        N, H, W = x.N, x.H, x.W
+        ctx = _Ctx()
+        ctx.N, ctx.H, ctx.W = N, H, W
+        ctx.blocks = []
+        cur = x
+        for b, p in enumerate(self.prefixes):
+            _, b1, _, b2 = res_block_keys(p)
+            raw1, st1 = new_act(N, H, W, C, dt, dev), ops.zeros_f32((N, C, 2), dev)
+            ops.conv_fwd(dt, OP_CONV3R, cur, C, C, self.packed[b, 0, "fwd"], raw1, bias=self.params[b1], stats=st1)
+            a1 = new_act(N, H, W, C, dt, dev)
+            ops.act_fwd(dt, raw1, a1, stats=st1, slope=0.0, pool=0)
+            raw2, st2 = new_act(N, H, W, C, dt, dev), ops.zeros_f32((N, C, 2), dev)
+            ops.conv_fwd(dt, OP_CONV3R, a1, C, C, self.packed[b, 1, "fwd"], raw2, bias=self.params[b2], stats=st2)
+            out = new_act(N, H, W, C, dt, dev)
+            ops.norm_add_fwd(dt, raw2, cur, st2, out)
+            if save:
+                ctx.blocks.append((cur, raw1, st1, a1, raw2, st2))
+            cur = out
+        if self.debug is not None:
+            self.debug["ctx"] = ctx                               # the stored tensors and statistics of every block, for the per-stage tests
+        return cur, (ctx if save else None)
+
+    # ---- backward ----
+    def backward(self, ctx, g: View, grads, hook=None, accumulate=False):
+        try:
+            return self._backward(ctx, g, grads, hook, accumulate)
+        finally:
+            join_side(g.t.device)                                 # the parameter gradients may have run on the side stream
+
+    def _conv_grads(self, x, d_raw, wkey, bkey, grads, accumulate, hook):
+        """weight and bias gradient of one convolution on the side stream: the weight gradient through the 4 x 4 staging slot into the 3 x 3 tensor,
+        the bias gradient as the per-channel sums of the gradient that enters the convolution"""
+        dt, C = self.dt, self.features
+        dev = d_raw.t.device
+
+        def work():
+            if self._g4 is None:
+                self._g4 = torch.zeros((C, C, 4, 4), dtype=torch.float32, device=dev)
+            self._ws = ops.conv_wgrad(dt, OP_CONV3R, x, d_raw, C, C, self._g4, False, self._ws)
+            if accumulate:
+                grads[wkey].add_(self._g4[..., :3, :3])
+            else:
+                grads[wkey].copy_(self._g4[..., :3, :3])
+                grads[bkey].zero_()
+            ops.colsum(dt, d_raw, grads[bkey])
+        param_grad(dev, work, hook, (wkey, bkey), (d_raw,))
+
+    def _backward(self, ctx, g, grads, hook, accumulate):
+        """g: NHWC View, the gradient of the trunk's output; it is UPDATED IN PLACE block by block and returned as the gradient of the trunk's input.
+        grads: dict key -> fp32 tensor (3 x 3 filters, biases) that receives the parameter gradients (overwritten, or accumulated when `accumulate`),
+        or None (input gradient only). hook(key) fires when a gradient is final."""
+        dt, C = self.dt, self.features
+        N, H, W = ctx.N, ctx.H, ctx.W
+        dev = g.t.device
+        dbg = self.debug
+        for b in range(self.n_blocks - 1, -1, -1):
+            x, raw1, st1, a1, raw2, st2 = ctx.blocks[b]
+            w1, b1, w2, b2 = res_block_keys(self.prefixes[b])
+            if dbg is not None:
+                dbg[f"{b}.g_out"] = View(g.t.clone(), g.C)
+            # the skip's gradient is g itself; through the second InstanceNorm (no activation: slope 1)
+            d_raw2 = new_act(N, H, W, C, dt, dev)
+            norm_act_bwd(dt, g, raw2, d_raw2, st2, 1.0, 0)
+            if grads is not None:
+                self._conv_grads(a1, d_raw2, w2, b2, grads, accumulate, hook)
+            d_a1 = new_act(N, H, W, C, dt, dev)
+            ops.conv_dgrad(dt, OP_CONV3R, d_raw2, N, H, W, C, C, self.packed[b, 1, "dgrad"], d_a1)
+            d_raw1 = new_act(N, H, W, C, dt, dev)
+            norm_act_bwd(dt, d_a1, raw1, d_raw1, st1, 0.0, 0)
+            if grads is not None:
+                self._conv_grads(x, d_raw1, w1, b1, grads, accumulate, hook)
+            ops.conv_dgrad(dt, OP_CONV3R, d_raw1, N, H, W, C, C, self.packed[b, 0, "dgrad"], g, accumulate=True)   # onto the skip gradient
+            if dbg is not None:
+                dbg[f"{b}.d_raw2"], dbg[f"{b}.d_a1"], dbg[f"{b}.d_raw1"] = d_raw2, d_a1, d_raw1
+                dbg[f"{b}.g_in"] = View(g.t.clone(), g.C)
+        return g

@@ -10,8 +10,8 @@ from dataclasses import dataclass
 import torch
 
 from . import _lib, parallel
-from ._lib import (DT_BF16, DT_BF16X3, DT_F32, EP_ACCUM, EP_BIAS, EP_LEAKY, EP_RELU, EP_STATS, EP_TANH_NCHW, OP_CONV, OP_CONV2, OP_CONV3, OP_CONVT, OP_PADCONV, OP_UPCONV,
-                   check)
+from ._lib import (DT_BF16, DT_BF16X3, DT_F32, EP_ACCUM, EP_BIAS, EP_LEAKY, EP_RELU, EP_STATS, EP_TANH_NCHW, OP_CONV, OP_CONV2, OP_CONV3, OP_CONV3R, OP_CONVT, OP_PADCONV,
+                   OP_UPCONV, check)
 
 
 def lib():
@@ -177,7 +177,7 @@ def part_ws(device):
 
 
 OUT_HW = {OP_CONV: lambda h: h - 1, OP_PADCONV: lambda h: h, OP_CONVT: lambda h: 2 * h, OP_UPCONV: lambda h: 2 * h, OP_CONV3: lambda h: h,
-          OP_CONV2: lambda h: h // 2}
+          OP_CONV2: lambda h: h // 2, OP_CONV3R: lambda h: h}
 
 
 # ---- convolution family ---------------------------------------------------------------------------------------
@@ -298,7 +298,25 @@ def patchgan_head_fwd(dt, x: View, w, y: View):
     check(lib().tfc_patchgan_head_fwd(stream_ptr(), dt, x.ptr, x.pitch, x.N, x.H, x.W, x.C, _p(w), y.ptr, y.pitch), "tfc_patchgan_head_fwd")
 
 
+# Scratch of the reflect-padded convolution's input gradient (the padded gradient that its fold pass reads; include/tfc_gan.h): one buffer per
+# (device, stream), as for part_ws, grown to the largest call so far and handed to the library for the calling thread in front of each call.
+_DGRAD_WS = {}
+
+
+def _dgrad_ws(dt, op, N, H, W, Cin, Cout, device):
+    need = lib().tfc_conv_dgrad_ws_bytes(dt, op, N, H, W, Cin, Cout)
+    if not need:
+        return
+    key = (torch.device(device), torch.cuda.current_stream(device).cuda_stream)
+    ws = _DGRAD_WS.get(key)
+    if ws is None or ws.numel() < need:
+        ws = _DGRAD_WS[key] = torch.empty(need, dtype=torch.uint8, device=device)
+    check(lib().tfc_conv_dgrad_set_ws(_p(ws), ws.numel()), "tfc_conv_dgrad_set_ws")
+
+
 def conv_dgrad(dt, op, dy: View, N, H, W, Cin, Cout, packed, dx: View, accumulate=False, oscale=None):
+    if op == OP_CONV3R:
+        _dgrad_ws(dt, op, N, H, W, Cin, Cout, dy.t.device)
     check(lib().tfc_conv_dgrad(stream_ptr(), dt, op, dy.ptr, dy.pitch, N, H, W, Cin, Cout, _p(packed), dx.ptr, dx.pitch,
                                _p(oscale), EP_ACCUM if accumulate else 0), "tfc_conv_dgrad")
 
@@ -318,6 +336,11 @@ def conv_wgrad(dt, op, x: View, dy: View, Cin, Cout, dw, accumulate=False, ws=No
 def act_fwd(dt, x: View, y: View, stats=None, slope=0.2, pool=0, drop_p=0.0, seed=0, stats_out=None):
     check(lib().tfc_act_fwd(stream_ptr(), dt, x.ptr, x.pitch, x.N, x.H, x.W, x.C, _p(stats), 0 if stats is None else 1, slope, pool,
                             drop_p, seed & 0xFFFFFFFF, y.ptr, y.pitch, _p(stats_out), part_ws(x.t.device) if stats_out is not None else None), "tfc_act_fwd")
+
+
+def norm_add_fwd(dt, x: View, res: View, stats, y: View):
+    """y = res + InstanceNorm(x; stats): the second half of a residual block in one pass (y may be x or res)"""
+    check(lib().tfc_norm_add_fwd(stream_ptr(), dt, x.ptr, x.pitch, res.ptr, res.pitch, x.N, x.H, x.W, x.C, _p(stats), y.ptr, y.pitch), "tfc_norm_add_fwd")
 
 
 def act_bwd(dt, mode, dy: View, x: View, N, H, W, C, dx: View = None, stats=None, slope=0.2, pool=0, drop_p=0.0, seed=0, rstats=None):
