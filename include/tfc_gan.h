@@ -154,6 +154,7 @@ int tfc_conv_wgrad(void* stream, int dt, int op, const void* x, int x_pitch, con
  *            mode 2: dx = rstd * (g' - mean g' - xhat * mean(g' xhat))   (apply phase)
  *            g' = Blur^T(dropmask * dy) * Act'(xhat) ; x == NULL => Act' = 1
  *   part_ws: needed whenever stats_out (forward) or a reduction into rstats (backward mode 1, mode 0 with rstats) is requested
+ *   C / (one 16-byte unit) must divide 256; every pitch (x, y, dy, dx, res) is a multiple of one 16-byte unit (8 bf16 / 4 fp32), or the call is refused
  */
 int tfc_act_fwd(void* stream, int dt, const void* x, int x_pitch, int N, int H, int W, int C, const float* stats, int norm,
                 float slope, int pool, float drop_p, uint32_t seed, void* y, int y_pitch, float* stats_out, float* part_ws);

@@ -754,6 +754,7 @@ extern "C" int tfc_act_bwd(void* stream, int dt, int mode, const void* dy, int d
   REQUIRE(!norm || (stats && x), "norm needs stats and x");
   REQUIRE(mode == 0 || (norm && rstats), "modes 1/2 need norm and rstats");   // mode 0: rstats (nullable) = float[C] += column sums of dx
   REQUIRE(mode == 1 || dx, "dx is null");
+  REQUIRE(!dx || dx_pitch % (16 / es_of(dt)) == 0, "dx pitch %d must be a multiple of %d", dx_pitch, 16 / es_of(dt));
   REQUIRE(!(mode == 1 || (mode == 0 && rstats)) || part_ws, "a reduction into rstats needs part_ws");
   const void* xx = x ? x : dy;
   CHECK_HIP(tfc_launch_act_bwd(dt, mode, p, dy, xx, stats, rstats, dx ? dx : (void*)dy, x ? 1 : 0, dx_pitch, part_ws, (hipStream_t)stream), "tfc_act_bwd");
@@ -767,6 +768,7 @@ extern "C" int tfc_act_bwd_signs(void* stream, int dt, const void* dy, int dy_pi
   if (int e = fill_act(p, dt, N, H, W, C, C, dy_pitch, 0, slope, 2, 0.f, 0)) return e;
   if (int e = check_ptr16(dy, "dy")) return e;
   REQUIRE(sign_mask && dx, "sign_mask / dx is null");
+  REQUIRE(dx_pitch % 8 == 0, "dx pitch %d must be a multiple of 8", dx_pitch);
   REQUIRE(!rstats || part_ws, "a reduction into rstats needs part_ws");
   CHECK_HIP(tfc_launch_act_pool2_bwd_signs(p, dy, sign_mask, rstats, dx, dx_pitch, part_ws, (hipStream_t)stream), "tfc_act_bwd_signs");
   return 0;
