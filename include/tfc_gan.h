@@ -480,8 +480,7 @@ int tfc_host_emulate_conv(int op, int pass, int elem_size, const float* x_host, 
 int tfc_debug_set_igemm_config(int cfg);
 /* A hook for tests, not an option for users (no Python wrapper, no environment variable): cap the grid of the persistent layer kernels
  * (tfc_conv_first_fwd, tfc_upconv_head_fwd, tfc_conv_dgrad_image, tfc_upconv_head_dgrad) and of the persistent gather GEMM (tfc_conv_fwd / tfc_conv_dgrad
- * in bf16; not its two-half form, whose grid is one workgroup per compute unit) at `workgroups` >= 1, so that small shapes reach walks of
- * several tiles and of unequal length; 0 = the default, min(tiles, occupancy x compute units). Per calling thread. The results do not depend on it. */
+ * in bf16) at `workgroups` >= 1, so that small shapes reach walks of several tiles and of unequal length; 0 = the default, min(tiles, occupancy x compute units). Per calling thread. The results do not depend on it. */
 int tfc_debug_set_persistent_grid(int workgroups);
 /* Batch-invariant mode (per calling thread; 0 = off, the default): every launch choice that shapes the arithmetic of one sample -- tile form, kernel
  * variant, InstanceNorm / bias partial slots per image, split count, workgroups per image -- is taken from the layer's per-image geometry alone (the rules

@@ -177,7 +177,7 @@ def main():
             f.write(report(line))
 
 
-KERNELS = {0: "tfc_igemm_kernel", 1: "tfc_igemm2_kernel", 2: "tfc_igemm2_kernel (two halves)", 3: "tfc_conv_c8_kernel", 10: "tfc_wgrad_kernel x4",
+KERNELS = {0: "tfc_igemm_kernel", 1: "tfc_igemm2_kernel", 3: "tfc_conv_c8_kernel", 10: "tfc_wgrad_kernel x4",
            11: "tfc_wgrad22_kernel x4", 13: "tfc_wgrad_kernel<bf16x3> x4", 15: "tfc_wgradT_kernel<NH=1>", 16: "tfc_wgradT_kernel<NH=2>"}
 
 

@@ -209,7 +209,7 @@ def main():
             f.write(report(line))
 
 
-KERNELS = {0: "tfc_igemm_kernel", 1: "tfc_igemm2_kernel", 2: "tfc_igemm2_kernel (two halves)", 10: "tfc_wgrad_kernel", 13: "tfc_wgrad_kernel<bf16x3>"}
+KERNELS = {0: "tfc_igemm_kernel", 1: "tfc_igemm2_kernel", 10: "tfc_wgrad_kernel", 13: "tfc_wgrad_kernel<bf16x3>"}
 
 
 def report(r):

@@ -505,36 +505,50 @@ struct Tile2 {
   const unsigned char* wbase;                                    // this tile's weight stream (phase, n-block), wave part excluded
 };
 
-// HALVES == 2 (round 3): ONE 512-thread workgroup per CU whose two 4-wave halves each do what a workgroup of the HALVES == 1 form does (own tiles, own LDS
-// region of half_bytes) but share the workgroup barrier, and half 1 runs `shift` barrier slots BEHIND half 0. Why: two independent workgroups on a CU
-// phase-lock -- a workgroup whose SIMD partner is in its epilogue has the matrix pipe to itself, finishes its K loop early and catches up, so both end up
-// in their K loops together (sharing the pipe) and in their MFMA-free epilogues together (pipe idle: 8.2 k MFMA cycles per wave and tile inside a 27-32 k
-// cycle tile period, SQ_VALU_MFMA_BUSY 50-60 %; a start stagger re-locks within a few tiles, measured neutral in round 2). With a common barrier
-// sequence the offset cannot drift: per tile a half executes nst + 1 barriers (one per stage, one inside the epilogue), so with half 1 shifted by
-// (nst + 1) / 2 slots one half's epilogue (accumulators -> LDS -> global: no MFMA) always lies beside the other half's K-loop stages.
-// Both halves execute the SAME total number of barriers (dummy barriers pad the shorter sequence), so every wave reaches the end.
+// Diagnostic build only (-DTFC_STAMP, scripts/stamp_igemm2.py): every wave adds up the s_memtime laps of its phases and writes the sums to `dbg` (a
+// buffer of their own, 16 words per wave) when it ends. The sites in the kernel are single macro lines that expand to nothing in the shipped library.
+#ifdef TFC_STAMP
+struct TfcStamp2 {
+  unsigned long long tile, stage;                                // lap starts: phases of a tile, phases of a stage
+  unsigned long long main, ep1, bar, store, sync, halo, frag;    // lap sums (the rows of stamp_igemm2.py)
+  unsigned long long rt_begin, mt_begin;
+};
+#define TFC_NOW(v) asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(v) :: "memory")
+#define TFC_STAMP2_BEGIN(s) TfcStamp2 s = {}; s.rt_begin = __builtin_amdgcn_s_memrealtime(); s.mt_begin = __builtin_amdgcn_s_memtime()
+#define TFC_STAMP2_MARK(t) TFC_NOW(t)                             // a lap starts here
+#define TFC_STAMP2_LAP(sum, t) do { unsigned long long n_; TFC_NOW(n_); sum += n_ - t; t = n_; } while (0)   // a lap ends (and the next one starts)
+#define TFC_STAMP2_LDS_DRAIN() asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory")   // the lap that ends next includes the LDS reads in flight
+#define TFC_STAMP2_WRITE(s, ntile) tfc_stamp2_write(s, ntile, dbg, lane, wave)
+__device__ __forceinline__ void tfc_stamp2_write(const TfcStamp2& s, int ntile, float* dbg, int lane, int wave) {
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  if (lane == 0 && dbg) {
+    unsigned long long* o = reinterpret_cast<unsigned long long*>(dbg) + ((size_t)blockIdx.x * 4 + wave) * 16;
+    o[0] = __builtin_amdgcn_s_memtime() - s.mt_begin;             // wave lifetime in shader cycles ...
+    o[6] = __builtin_amdgcn_s_memrealtime() - s.rt_begin;         // ... and in 100 MHz ticks
+    o[1] = s.sync; o[2] = s.main; o[3] = s.ep1; o[4] = s.bar; o[5] = s.store; o[7] = (unsigned long long)ntile; o[8] = s.halo; o[9] = s.frag;
+  }
+}
+#else
+#define TFC_STAMP2_BEGIN(s) do { } while (0)
+#define TFC_STAMP2_MARK(t) do { } while (0)
+#define TFC_STAMP2_LAP(sum, t) do { } while (0)
+#define TFC_STAMP2_LDS_DRAIN() do { } while (0)
+#define TFC_STAMP2_WRITE(s, ntile) do { } while (0)
+#endif
+
 // FC: the epilogue's flag set as a compile-time constant, or -1 = read `flags` at run time. The launcher instantiates FC for the flag sets the
-// training step issues (launch_igemm2_pat) and sends every other combination, and the two-half form, to FC = -1.
-template <int MT, int NT, int WM, int WN, int PAT, int HALVES = 1, int FC = -1, bool RF = false>   // RF: TfcGather::reflect, at compile time
-__global__ void __launch_bounds__(256 * HALVES, 2)
+// training step issues (launch_igemm2_pat) and sends every other combination to FC = -1.
+template <int MT, int NT, int WM, int WN, int PAT, int FC = -1, bool RF = false>   // RF: TfcGather::reflect, at compile time
+__global__ void __launch_bounds__(256, 2)
 tfc_igemm2_kernel(const TfcGather d, const bf16_t* __restrict__ in, const uint4* __restrict__ wp, bf16_t* out,
                   const float* __restrict__ bias, float* stats, float* dbg, const float* __restrict__ oscale,
-                  int flags, int NB32, int nblkN, int buf_bytes, long long phase_wbytes, int nwork, int half_bytes, int shift_opts) {
+                  int flags, int NB32, int nblkN, int buf_bytes, long long phase_wbytes, int nwork) {
   // FC >= 0: the flag set is a constant of this instantiation and the epilogue is straight-line code; FC < 0: the flags are read at run time. The
   // arithmetic per element is the same expression either way, so the stored bits do not depend on which instantiation runs.
   const int fl = FC >= 0 ? FC : flags;
-  const int shift = shift_opts & 255;
-  const bool prio = (shift_opts >> 8) & 1;                        // (A/B knob TFC_IGEMM_PRIO) raise the wave priority inside the K loop
   static_assert(WM * WN == 4 && WM * MT == 4, "4 waves, 128-pixel tile");
   static_assert(PAT != 0, "compile-time tap patterns only");
-  static_assert(HALVES == 1 || HALVES == 2, "one or two 4-wave halves");
-  static_assert(HALVES == 1 || 32 * NT * WN <= 128, "the two-half form has no 256-channel tile");
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem_all[];
-  const int half = HALVES == 2 ? __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 8) : 0;
-  unsigned char* const smem = smem_all + half * half_bytes;
-  int nbar = 0;                                                  // workgroup barriers executed so far by this wave (HALVES == 2: padded to a common total)
-#define TFC_BAR() do { __builtin_amdgcn_s_barrier(); ++nbar; } while (0)
-#define TFC_SYNC() do { __syncthreads(); ++nbar; } while (0)
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   typedef bf16_t T;
   constexpr int P = TFC_LDS_P;
   constexpr int NSR = TapPat<PAT>::COLS * 2;
@@ -550,46 +564,26 @@ tfc_igemm2_kernel(const TfcGather d, const bf16_t* __restrict__ in, const uint4*
   static_assert(BD <= TFC_WPAD, "the packed stream carries TFC_WPAD slack k-substeps for the ring's read-ahead");
   static_assert((ROWS * NSR) % BD == 0, "register ring must realign every stage");
   constexpr int BN = 32 * NT * WN;
-  // 256-channel workgroup tile (a wave owns 128 pixels x 64 channels: half the LDS operand traffic per MFMA of <4,1,1,4>): wave wn owns the
-  // 32-channel blocks {wn, wn + WN, ...} (INTERLEAVED, so that every wave takes part in each 128-channel pass of the epilogue) and the
-  // staged tile holds one 128-channel pass at a time (77 KB of LDS per workgroup: two workgroups per CU)
-  constexpr bool IL = BN > 128;
-  constexpr int NPASS = IL ? NT : 1;                             // epilogue passes of BNS channels
-  constexpr int BNS = IL ? 32 * WN : BN;
-  constexpr int ROWP = BNS * 2 + 16;                             // staged tile: bytes per pixel row (pitch = 4 banks mod 32)
-  constexpr int UPR = BNS / 8;                                   // 16-byte units per pixel row
-  constexpr int BSTEP = IL ? WN * 1024 : 1024;                   // byte distance of a wave's consecutive weight fragments in the stream
-  float* out_nchw = dbg;                                         // TFC_STAMP_AT writes here in the diagnostic build
-  (void)out_nchw;
+  constexpr int ROWP = BN * 2 + 16;                              // staged tile: bytes per pixel row (pitch = 4 banks mod 32)
+  constexpr int UPR = BN / 8;                                    // 16-byte units per pixel row
 
-  const int tid = threadIdx.x & 255;
+  const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave / WN, wn = wave % WN;
   const int h = lane >> 5, r = lane & 31;
-  const int G = gridDim.x * HALVES;
-  TFC_STAMP_AT(0);
-#ifdef TFC_STAMP
-#define TFC_NOW(v) asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(v) :: "memory")
-  unsigned long long tk0 = 0, tk1 = 0, acc_main = 0, acc_ep1 = 0, acc_bar = 0, acc_store = 0, ntile = 0, ts0 = 0, ts1 = 0, acc_sync = 0, tq0 = 0, tq1 = 0, tq2 = 0, acc_h = 0, acc_f = 0;
-  const unsigned long long rt_begin = __builtin_amdgcn_s_memrealtime(), mt_begin = __builtin_amdgcn_s_memtime();
-#else
-#define TFC_NOW(v) do { } while (0)
-#endif
+  const int G = gridDim.x;
+  TFC_STAMP2_BEGIN(stamp);
 
   const int nchunks = (d.Cin_pad * 2) / 64;
   const int nst = nchunks * d.nplanes;
-  // LDS map.  Narrow tiles: [halo 0 | halo 1 | staged tile | statistics | bias].  256-channel tile: [halo 0 | X | halo 1 | statistics | bias] -- the
-  // staged tile of the epilogue OVERLAYS the halo buffer the K loop has just consumed plus the gap X (the other one already holds the next
-  // tile's first chunk): [halo 0 | X] or [X | halo 1], 62 KB per workgroup instead of 83 KB, i.e. two workgroups per CU.
-  const int xtra = IL ? (128 * ROWP > buf_bytes ? 128 * ROWP - buf_bytes : 0) : 0;
-  const int bstride = buf_bytes + xtra;                          // distance of the two halo buffers
-  unsigned char* stage_fix = smem + 2 * buf_bytes;
-  float* sstat = reinterpret_cast<float*>(IL ? smem + 2 * buf_bytes + xtra : stage_fix + 128 * ROWP);   // [4 waves][BN][2] statistics partials of the tile just stored (EP_STATS only)
+  // LDS map: [halo 0 | halo 1 | staged tile | statistics | bias]
+  unsigned char* stage = smem + 2 * buf_bytes;
+  float* sstat = reinterpret_cast<float*>(stage + 128 * ROWP);   // [4 waves][BN][2] statistics partials of the tile just stored (EP_STATS only)
   float* sbias = sstat + ((fl & TFC_EP_STATS) ? 8 * BN : 0);     // bias of EVERY output channel of the layer (nblkN * BN floats), loaded once (EP_BIAS only)
 
   const int laneBase = ((2 * wm * MT + (r & 1)) * P + (r >> 1)) * 80 + h * 16;
-  const unsigned lanepart = (unsigned)((IL ? wn : wn * NT) * 64 + lane) * 16u;
+  const unsigned lanepart = (unsigned)(wn * NT * 64 + lane) * 16u;
   const size_t wstep_b = (size_t)NB32 * 1024;
   const float osc = oscale ? *oscale : 1.f;
 
@@ -663,15 +657,10 @@ tfc_igemm2_kernel(const TfcGather d, const bf16_t* __restrict__ in, const uint4*
   auto loadB = [&](const unsigned char* p, u32x4_t (&b)[NT]) {    // p: this lane's address of the fragment of n-block 0
 #pragma unroll
     for (int nt = 0; nt < NT; ++nt) {
-      if constexpr (IL) {
-        const unsigned char* pn = p + nt * BSTEP;                 // 4096 does not fit the instruction's 13-bit signed offset
-        asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(b[nt]) : "v"(pn) : "memory");
-      } else {
-        if (nt == 0) asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(b[0]) : "v"(p) : "memory");
-        if (nt == 1) asm volatile("global_load_dwordx4 %0, %1, off offset:1024" : "=v"(b[1]) : "v"(p) : "memory");
-        if (nt == 2) asm volatile("global_load_dwordx4 %0, %1, off offset:2048" : "=v"(b[2]) : "v"(p) : "memory");
-        if (nt == 3) asm volatile("global_load_dwordx4 %0, %1, off offset:3072" : "=v"(b[3]) : "v"(p) : "memory");
-      }
+      if (nt == 0) asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(b[0]) : "v"(p) : "memory");
+      if (nt == 1) asm volatile("global_load_dwordx4 %0, %1, off offset:1024" : "=v"(b[1]) : "v"(p) : "memory");
+      if (nt == 2) asm volatile("global_load_dwordx4 %0, %1, off offset:2048" : "=v"(b[2]) : "v"(p) : "memory");
+      if (nt == 3) asm volatile("global_load_dwordx4 %0, %1, off offset:3072" : "=v"(b[3]) : "v"(p) : "memory");
     }
   };
   const unsigned lds0 = (unsigned)(size_t)LDS_PTR(unsigned char, smem);   // LDS byte address of the dynamic region
@@ -694,26 +683,10 @@ tfc_igemm2_kernel(const TfcGather d, const bf16_t* __restrict__ in, const uint4*
   //      kept: pulling items from per-CU-pair counters (balances the pair -- the first-dispatched workgroup of a CU wins every arbitration and
   //      finishes its equal share ~25 % earlier -- but each returning atomic sits on the in-order vmcnt queue), a half-period start stagger of the
   //      second workgroup, s_setprio schemes.
-  // HALVES == 2: worker id = 2 * r(blockIdx) + half -- the two halves of a workgroup hold neighbouring tiles (shared halo columns in one L2 / L1)
-  const int worker2 = 2 * tfc_xcd_remap(blockIdx.x, gridDim.x) + half;
   auto item = [&](int k) {
-    if constexpr (HALVES == 2) return k * G + worker2 < nwork ? k * G + worker2 : -1;
     const int cnt = (nwork - k * G) < G ? (nwork - k * G) : G;   // the last round may be partial
     return (int)blockIdx.x < cnt ? k * G + tfc_xcd_remap(blockIdx.x, cnt) : -1;
   };
-  int nbar_total = 0;
-  if constexpr (HALVES == 2) {
-    // barriers each half will execute: [shift dummies (half 1)] + 1 (prologue) + (nst + 1) per tile + 1 (last statistics flush); pad to the larger
-    const int S = nst + 1, wa = worker2 - half, wb = wa + 1;
-    const int na = wa < nwork ? (nwork - wa + G - 1) / G : 0, nb = wb < nwork ? (nwork - wb + G - 1) / G : 0;
-    const int ta = na ? 2 + na * S : 0, tb = nb ? shift + 2 + nb * S : 0;
-    nbar_total = ta > tb ? ta : tb;
-    if ((half ? nb : na) == 0) {                                  // nothing for this half (a ragged last round): keep the other half's barriers company
-      for (; nbar < nbar_total; ++nbar) __builtin_amdgcn_s_barrier();
-      return;
-    }
-    if (half) for (int i = 0; i < shift; ++i) TFC_BAR();
-  }
   int round = 0;
   int w = item(0), w_next = item(1);
   Tile2 cur, nxt;
@@ -729,8 +702,7 @@ tfc_igemm2_kernel(const TfcGather d, const bf16_t* __restrict__ in, const uint4*
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   halo_store(smem);
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  TFC_BAR();
-  TFC_STAMP_AT(1);
+  __builtin_amdgcn_s_barrier();
   int sc = 0;                                                    // running stage counter: halo buffer parity across tiles
 
   // InstanceNorm statistics. Deterministic (round 3): the four waves' sums of a tile go to FOUR LDS slots with plain stores (the LDS float atomics they
@@ -761,7 +733,6 @@ tfc_igemm2_kernel(const TfcGather d, const bf16_t* __restrict__ in, const uint4*
     const bool has_next = w_next >= 0;
     if (has_next) decode(w_next, nxt);
 
-
     f32x16_t acc[MT][NT];
 #pragma unroll
     for (int mi = 0; mi < MT; ++mi)
@@ -770,71 +741,28 @@ tfc_igemm2_kernel(const TfcGather d, const bf16_t* __restrict__ in, const uint4*
 #pragma unroll
         for (int j = 0; j < 16; ++j) acc[mi][nt][j] = 0.f;
 
-    TFC_NOW(tk0);
-    if (prio) asm volatile("s_setprio 2");                        // K loop: this wave's MFMAs go ahead of the partner wave's epilogue VALU / LDS work
+    TFC_STAMP2_MARK(stamp.tile);
     for (int st = 0; st < nst; ++st) {
       const bool last = (st + 1) == nst;
       const bool more = !last || has_next;
       // always FOUR loads (static vmcnt counts): the next stage's halo, or -- nothing follows -- a harmless re-read that is never stored
-#ifdef TFC_STAMP
-      TFC_NOW(tq0);
-#endif
+      TFC_STAMP2_MARK(stamp.stage);
       halo_load((last && has_next) ? nxt : cur, last ? 0 : st + 1);
-#ifdef TFC_STAMP
-      TFC_NOW(tq1); acc_h += tq1 - tq0;
-#endif
-      const unsigned abase = lds0 + (sc & 1) * bstride + laneBase;
+      TFC_STAMP2_LAP(stamp.halo, stamp.stage);
+      const unsigned abase = lds0 + (sc & 1) * buf_bytes + laneBase;
       constexpr int Q = ROWS * NSR;                               // k-substeps of one stage, one straight-line pipeline
-      u32x4_t a[IL ? 1 : 2][MT];                                  // IL: ONE set, each fragment re-requested right after its last MFMA (16 VGPRs less)
+      u32x4_t a[2][MT];
       tfc_static_for<0, MT>([&](auto mic) {
         constexpr int mi = decltype(mic)::value;
         lds_rd<(TapPat<PAT>::dy(0) * P + TapPat<PAT>::dx(0)) * 80 + mi * (2 * P * 80)>(a[0][mi], abase);
       });
-#ifdef TFC_STAMP
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      TFC_NOW(tq2); acc_f += tq2 - tq1;
-#endif
+      TFC_STAMP2_LDS_DRAIN();
+      TFC_STAMP2_LAP(stamp.frag, stamp.stage);
       tfc_static_for<0, Q>([&](auto qc) {
         constexpr int q = decltype(qc)::value;
-        if constexpr (IL) {
-          // 256-channel tile: pixel-fragment-major MFMA order (mi, nt) -- a[mi] is free after its NT MFMAs and is re-requested for k-substep
-          // q + 1 into the same registers, six MFMAs ahead of its next use.  LDS returns in order: before the MFMAs of fragment mi exactly the
-          // MT - 1 younger requests may be outstanding (fewer in the last k-substep of a stage, which requests nothing).
-          if constexpr (q < BD) asm volatile("s_waitcnt vmcnt(%0)" :: "n"((BD - 1) * NT + 4) : "memory");
-          else asm volatile("s_waitcnt vmcnt(%0)" :: "n"((BD - 1) * NT) : "memory");
-#pragma unroll
-          for (int nt = 0; nt < NT; ++nt) asm volatile("" : "+v"(br[q % BD][nt]));
-          if constexpr (q + BD == Q) { if (last && has_next) bptr = nxt.wbase + lanepart; }
-          tfc_static_for<0, MT>([&](auto mc) {
-            constexpr int mi = decltype(mc)::value;
-            asm volatile("s_waitcnt lgkmcnt(%0)" :: "n"(q + 1 < Q ? MT - 1 : MT - 1 - mi) : "memory");
-            asm volatile("" : "+v"(a[0][mi]));
-            tfc_static_for<0, NT>([&](auto nc) {
-              constexpr int nt = decltype(nc)::value;
-              acc[mi][nt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, br[q % BD][nt]),
-                                                                    __builtin_bit_cast(bf16x8_t, a[0][mi]), acc[mi][nt], 0, 0, 0);
-              __builtin_amdgcn_sched_barrier(0);
-              if constexpr (nt == NT - 1 && q + 1 < Q) {
-                constexpr int r1 = (q + 1) / NSR, s1 = (q + 1) % NSR;
-                constexpr int off = (TapPat<PAT>::dy(r1) * P + TapPat<PAT>::dx(s1 >> 1)) * 80 + (s1 & 1) * 32;
-                lds_rd<off + mi * (2 * P * 80)>(a[0][mi], abase);
-              }
-              if constexpr (mi == MT - 1) {                       // br[q % BD][nt] has fed its last MFMA: request the fragment BD k-substeps ahead
-                const unsigned char* pn = bptr + nt * BSTEP;
-                asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(br[q % BD][nt]) : "v"(pn) : "memory");
-              }
-              __builtin_amdgcn_sched_barrier(0);
-            });
-          });
-          bptr += wstep_b;
-        } else {
         // operands of this k-substep.  A(q) was requested during k-substep q - 1 (nothing younger on the LDS queue); of the weight loads
         // (BD - 1) * NT are younger than B(q), plus -- during the first BD k-substeps of a stage -- the four halo loads issued at its start
-#ifdef TFC_ABL_LGKM0
-        constexpr bool CNT_LGKM = false;
-#else
         constexpr bool CNT_LGKM = NT == 1;                        // counted per-fragment LDS waits (below); measured worse for the two-fragment tiles
-#endif
         if constexpr (!CNT_LGKM) {
           asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
 #pragma unroll
@@ -845,12 +773,10 @@ tfc_igemm2_kernel(const TfcGather d, const bf16_t* __restrict__ in, const uint4*
 #pragma unroll
         for (int nt = 0; nt < NT; ++nt) asm volatile("" : "+v"(br[q % BD][nt]));
         if constexpr (q + BD == Q) { if (last && has_next) bptr = nxt.wbase + lanepart; }
-#ifndef TFC_ABL_HS_END
         // the next stage's halo goes to LDS HERE, not at the end of the stage: the four halo loads are older than B(q) for q >= BD, so the wait above has
         // landed them; the buffer they go to was last read a stage ago (behind that stage's barrier).  The end of the stage is then a bare s_barrier instead of
         // wait -> 4 x ds_write_b128 -> lgkmcnt(0) -> barrier in series (~0.6 k cycles per stage, 15 % of a 128-MFMA stage).
-        if constexpr (Q > BD && q == BD) { if (more) halo_store(smem + ((sc + 1) & 1) * bstride); }
-#endif
+        if constexpr (Q > BD && q == BD) { if (more) halo_store(smem + ((sc + 1) & 1) * buf_bytes); }
         // One wave issues in order: memory instructions bunched behind the last MFMA of a k-substep all land in ONE 32-cycle MFMA gap and overrun
         // it (measured: ~60 idle matrix-pipe cycles per k-substep for a wave alone on its SIMD).  They are therefore dealt out over the gaps,
         // at most two per gap, and the order is pinned with sched_barrier (the MFMAs are builtins: nothing else keeps hipcc from re-bunching):
@@ -871,7 +797,6 @@ tfc_igemm2_kernel(const TfcGather d, const bf16_t* __restrict__ in, const uint4*
           acc[mi][nt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, br[q % BD][nt]),      // swapped operands: rows =
                                                                 __builtin_bit_cast(bf16x8_t, a[q & 1][mi]), acc[mi][nt], 0, 0, 0);   // channels, lanes = pixels
           __builtin_amdgcn_sched_barrier(0);
-#ifndef TFC_ABL_NOA
           if constexpr (q + 1 < Q) {
             constexpr int r1 = (q + 1) / NSR, s1 = (q + 1) % NSR;
             constexpr int off = (TapPat<PAT>::dy(r1) * P + TapPat<PAT>::dx(s1 >> 1)) * 80 + (s1 & 1) * 32;
@@ -881,49 +806,32 @@ tfc_igemm2_kernel(const TfcGather d, const bf16_t* __restrict__ in, const uint4*
               lds_rd<off + m2 * (2 * P * 80)>(a[(q + 1) & 1][m2], abase);
             });
           }
-#endif
-#ifndef TFC_ABL_NOB
           if constexpr (mi == MT - 1) {
             if constexpr (nt == 0) asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(br[q % BD][0]) : "v"(bptr) : "memory");
             if constexpr (nt == 1) asm volatile("global_load_dwordx4 %0, %1, off offset:1024" : "=v"(br[q % BD][1]) : "v"(bptr) : "memory");
             if constexpr (nt == 2) asm volatile("global_load_dwordx4 %0, %1, off offset:2048" : "=v"(br[q % BD][2]) : "v"(bptr) : "memory");
             if constexpr (nt == 3) asm volatile("global_load_dwordx4 %0, %1, off offset:3072" : "=v"(br[q % BD][3]) : "v"(bptr) : "memory");
           }
-#endif
           if constexpr (i == MT * NT - 1) bptr += wstep_b;
           __builtin_amdgcn_sched_barrier(0);
         });
-        }
       });
       // the halo loads are older than every weight load of this stage: with at most BD * NT vector-memory operations left they have landed
-#ifdef TFC_STAMP
-      TFC_NOW(ts0);
-#endif
-#ifndef TFC_ABL_HS_END
-      constexpr bool HS_MID = !IL && Q > BD;                      // halo already stored inside the K loop (see there)
-#else
-      constexpr bool HS_MID = false;
-#endif
+      TFC_STAMP2_MARK(stamp.stage);
+      constexpr bool HS_MID = Q > BD;                             // halo already stored inside the K loop (see there)
       if constexpr (!HS_MID) {
         asm volatile("s_waitcnt vmcnt(%0)" :: "n"(BD * NT) : "memory");
-        if (more) halo_store(smem + ((sc + 1) & 1) * bstride);
+        if (more) halo_store(smem + ((sc + 1) & 1) * buf_bytes);
       }
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      TFC_BAR();
-#ifdef TFC_STAMP
-      TFC_NOW(ts1); acc_sync += ts1 - ts0;
-#endif
+      __builtin_amdgcn_s_barrier();
+      TFC_STAMP2_LAP(stamp.sync, stamp.stage);
       ++sc;
     }
 
-    if (prio) asm volatile("s_setprio 0");
     if (fl & TFC_EP_STATS) stat_flush();
     // ---- epilogue: accumulators (channel rows x pixel lanes) -> 16-byte units -> staged tile in LDS ----
-    TFC_STAMP_AT(2);
-#ifdef TFC_STAMP
-    TFC_NOW(tk1); acc_main += tk1 - tk0; tk0 = tk1; ++ntile;
-#endif
-    unsigned char* stage = IL ? smem + ((sc & 1) ? 0 : buf_bytes) : stage_fix;   // IL: beside the live halo buffer (parity sc & 1 after the last stage)
+    TFC_STAMP2_LAP(stamp.main, stamp.tile);
     {
     // the per-thread addresses of the epilogue are derived per tile from a thread id the compiler cannot see through, so that none of them is hoisted
     // out of the tile loop and kept in a register across the K loop (the names shadow the launch-invariant ones)
@@ -932,16 +840,12 @@ tfc_igemm2_kernel(const TfcGather d, const bf16_t* __restrict__ in, const uint4*
     __builtin_assume(tid_e < 256u);
     const int tid = (int)tid_e, lane = tid_e & 63, h = lane >> 5, r = lane & 31, su = tid_e % UPR;
 #pragma unroll
-    for (int ps = 0; ps < NPASS; ++ps) {                          // one pass per BNS staged channels (a single pass unless the tile is 256 wide)
-#pragma unroll
     for (int nt = 0; nt < NT; ++nt) {
-      if (IL && nt != ps) continue;
-      const int blk = IL ? nt * WN + wn : wn * NT + nt;           // this accumulator's 32-channel block inside the n-block ...
-      const int col = IL ? wn : wn * NT + nt;                     // ... and inside the staged pass
+      const int col = wn * NT + nt;                               // this accumulator's 32-channel block inside the n-block and the staged tile
       float4 bq[4];
 #pragma unroll
       for (int q = 0; q < 4; ++q)
-        bq[q] = (fl & TFC_EP_BIAS) ? *reinterpret_cast<const float4*>(sbias + cur.nb_blk * BN + blk * 32 + 8 * q + 4 * h) : make_float4(0.f, 0.f, 0.f, 0.f);
+        bq[q] = (fl & TFC_EP_BIAS) ? *reinterpret_cast<const float4*>(sbias + cur.nb_blk * BN + col * 32 + 8 * q + 4 * h) : make_float4(0.f, 0.f, 0.f, 0.f);
 #pragma unroll
       for (int mi = 0; mi < MT; ++mi) {
         uint32_t pk[4][2];
@@ -966,30 +870,20 @@ tfc_igemm2_kernel(const TfcGather d, const bf16_t* __restrict__ in, const uint4*
         }
       }
     }
-    if (ps == 0) {
-      TFC_STAMP_AT(3);
-#ifdef TFC_STAMP
-      TFC_NOW(tk1); acc_ep1 += tk1 - tk0; tk0 = tk1;
-#endif
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");           // the next tile's first weight fragments (requested ~2.5k cycles ago) land BEFORE the stores below
+    TFC_STAMP2_LAP(stamp.ep1, stamp.tile);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");             // the next tile's first weight fragments (requested ~2.5k cycles ago) land BEFORE the stores below
 #pragma unroll
-      for (int i = 0; i < BD; ++i)
+    for (int i = 0; i < BD; ++i)
 #pragma unroll
-        for (int nt = 0; nt < NT; ++nt) asm volatile("" : "+v"(br[i][nt]));
-    }
-    TFC_SYNC();
-    if (ps == 0) {
-      TFC_STAMP_AT(4);
-#ifdef TFC_STAMP
-      TFC_NOW(tk1); acc_bar += tk1 - tk0; tk0 = tk1;
-#endif
-    }
+      for (int nt = 0; nt < NT; ++nt) asm volatile("" : "+v"(br[i][nt]));
+    __syncthreads();
+    TFC_STAMP2_LAP(stamp.bar, stamp.tile);
     {
-      const int n0 = cur.nb_blk * BN + ps * BNS + su * 8;
+      const int n0 = cur.nb_blk * BN + su * 8;
       const int ylim = d.GH - cur.a0, xlim = d.GW - cur.b0;
       // wave-uniform part of the output address of this tile (the per-thread part srel[k] is tile-invariant)
       bf16_t* obase = out + ((long long)(cur.img * d.OH + cur.a0 * d.OS + d.OOY + cur.phy * d.ph_oo) * d.OW + cur.b0 * d.OS + d.OOX + cur.phx * d.ph_oo) * d.out_pitch +
-                      cur.nb_blk * BN + ps * BNS;
+                      cur.nb_blk * BN;
       float s1[8], s2[8];
 #pragma unroll
       for (int e = 0; e < 8; ++e) { s1[e] = 0.f; s2[e] = 0.f; }
@@ -1054,7 +948,7 @@ tfc_igemm2_kernel(const TfcGather d, const bf16_t* __restrict__ in, const uint4*
           for (int o = 32; o >= UPR; o >>= 1) { s1[e] += __shfl_xor(s1[e], o, 64); s2[e] += __shfl_xor(s2[e], o, 64); }
         }
         if (lane < UPR) {
-          float2* sp = reinterpret_cast<float2*>(sstat + wave * 2 * BN + ps * 2 * BNS) + su * 8;
+          float2* sp = reinterpret_cast<float2*>(sstat + wave * 2 * BN) + su * 8;
 #pragma unroll
           for (int e = 0; e < 8; ++e) sp[e] = make_float2(s1[e], s2[e]);
         }
@@ -1064,41 +958,20 @@ tfc_igemm2_kernel(const TfcGather d, const bf16_t* __restrict__ in, const uint4*
         stat_lim = 2 * (d.Nout - cur.nb_blk * BN);                // floats of this n-block that exist
       }
     }
-    if (IL) TFC_SYNC();                                           // the staged tile is rewritten by the next pass / by the next tile's first halo store
-    }
     }
     ++tcount;
-    TFC_STAMP_AT(5);
-#ifdef TFC_STAMP
-    TFC_NOW(tk1); acc_store += tk1 - tk0;
-#endif
+    TFC_STAMP2_LAP(stamp.store, stamp.tile);
     if (!has_next) break;
     cur = nxt;
     ++round;
     w = w_next;
     w_next = item(round + 1);
   }
-  if (HALVES == 2 || (fl & TFC_EP_STATS)) TFC_SYNC();             // (HALVES == 2: always, so that the barrier count does not depend on the flags)
-  if (fl & TFC_EP_STATS) stat_flush();                            // the last tile's sums
-  if constexpr (HALVES == 2)
-    for (; nbar < nbar_total; ++nbar) __builtin_amdgcn_s_barrier();
-#ifdef TFC_STAMP
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  TFC_STAMP_AT(6);
-  if (lane == 0 && dbg) {
-    unsigned long long* o = reinterpret_cast<unsigned long long*>(dbg) + ((size_t)blockIdx.x * 4 + wave) * 16;
-    o[2] = acc_main; o[3] = acc_ep1; o[4] = acc_bar; o[5] = acc_store; o[7] = ntile; o[1] = acc_sync; o[8] = acc_h; o[9] = acc_f;
-    unsigned hwid, xcc;
-    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hwid));
-    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-    o[6] = ((unsigned long long)xcc << 32) | hwid;
-    o[0] = __builtin_amdgcn_s_memtime() - mt_begin;               // wave lifetime in shader cycles ...
-    o[6] = __builtin_amdgcn_s_memrealtime() - rt_begin;            // ... and in 100 MHz ticks (replaces the placement word)
+  if (fl & TFC_EP_STATS) {                                        // the last tile's sums
+    __syncthreads();
+    stat_flush();
   }
-#endif
-#undef TFC_NOW
-#undef TFC_BAR
-#undef TFC_SYNC
+  TFC_STAMP2_WRITE(stamp, tcount);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -2028,9 +1901,6 @@ tfc_wgrad_kernel(const TfcGather d, const T* __restrict__ dO, const T* __restric
     }
   }
   auto tile_load = [&](int tl) {
-#ifdef TFC_ABL_WG_SAMETILE
-    tl = sp;                                                     // ablation: every load hits the workgroup's first (cache-hot) tile
-#endif
     int img, a0, b0;
     tfc_tile_decode(tl, d.tiles_x, d.tiles_y, img, a0, b0);
 #pragma unroll
@@ -3091,7 +2961,7 @@ static int match_pattern(const TfcGather& d, int es) {
 // ---------------------------------------------------------------------------------------------------
 thread_local int g_tfc_batch_invariant = 0;
 static inline int plan_phases(const TfcGather& d) { return d.ph_n > 1 ? d.ph_n : 1; }
-static const int kFormNT[5] = {2, 1, 1, 1, 2}, kFormWM[5] = {2, 2, 4, 1, 1}, kFormWN[5] = {2, 2, 1, 4, 4};   // <2,2,2,2> <2,1,2,2> <1,1,4,1> <4,1,1,4> <4,2,1,4>
+static const int kFormNT[4] = {2, 1, 1, 1}, kFormWM[4] = {2, 2, 4, 1}, kFormWN[4] = {2, 2, 1, 4};   // <2,2,2,2> <2,1,2,2> <1,1,4,1> <4,1,1,4>
 // InstanceNorm partial slots per image: one per (tile, phase) of the persistent kernel, one per (tile, phase, M-wave) of the one-tile-per-workgroup kernel
 static inline int igemm_nparts(const TfcGather& d, bool persistent, int WM) { return d.tiles_y * d.tiles_x * plan_phases(d) * (persistent ? 1 : WM); }
 // dynamic LDS of the persistent kernel (see its LDS map): halo x 2 | staged tile | per-wave statistics slots (EP_STATS) | bias table (EP_BIAS)
@@ -3101,12 +2971,9 @@ static int igemm2_lds_bytes(const TfcGather& d, int NT, int WN, int flags, int* 
   for (int pl = 0; pl < d.nplanes; ++pl) maxhh = d.plane[pl].hh > maxhh ? d.plane[pl].hh : maxhh;
   const int buf_bytes = maxhh * TFC_LDS_P * 80;
   const int BN = 32 * NT * WN;
-  const int BNS = BN > 128 ? 32 * WN : BN;                        // channels of one staged epilogue pass
-  const int STG = 128 * (BNS * 2 + 16);
+  const int STG = 128 * (BN * 2 + 16);
   if (buf_bytes_out) *buf_bytes_out = buf_bytes;
-  // 256-channel tile: the staged tile overlays a consumed halo buffer
-  return (BN > 128 ? 2 * buf_bytes + (STG > buf_bytes ? STG - buf_bytes : 0) : 2 * buf_bytes + STG) + ((flags & TFC_EP_STATS) ? 8 * BN * 4 : 0) +
-         ((flags & TFC_EP_BIAS) ? nblkN * BN * 4 : 0);
+  return 2 * buf_bytes + STG + ((flags & TFC_EP_STATS) ? 8 * BN * 4 : 0) + ((flags & TFC_EP_BIAS) ? nblkN * BN * 4 : 0);
 }
 void tfc_plan_igemm(int dt, const TfcGather& d, int flags, int ncu, bool inv, TfcConvPlan* p) {
   *p = TfcConvPlan{};
@@ -3121,11 +2988,7 @@ void tfc_plan_igemm(int dt, const TfcGather& d, int flags, int ncu, bool inv, Tf
   const int ntiles = nimg * d.tiles_y * d.tiles_x;
   const int target = 512;
   int form = -1;
-#ifdef TFC_PROBE_W64
-  if (b16 && fcfg == 4 && nb >= 8) form = 4;
-#endif
-  if (form >= 0) {}
-  else if (fcfg == 3 && nb >= 4) form = 3;
+  if (fcfg == 3 && nb >= 4) form = 3;
   else if (fcfg == 0 && nb >= 4) form = 0;
   else if ((fcfg == 0 || fcfg == 1) && nb >= 2) form = 1;
   else if (fcfg >= 0 && fcfg != 15) form = 2;
@@ -3136,10 +2999,8 @@ void tfc_plan_igemm(int dt, const TfcGather& d, int flags, int ncu, bool inv, Tf
       // it still gives every CU a workgroup -- measured at batch 32: conv 16x16 512->512 70 -> 66 us, convT 16x16 1024->256 86 -> 67 us,
       // convT 8x8 1024->512 84 -> 66 us, convT 4x4 512->512 44 -> 32 us, convT 32x32 512->128 100 -> 69 us (conv 8x8 512->512 would leave half
       // the CUs idle: 50 -> 57 us, excluded; the four sub-pixel phases of a transposed convolution count as tiles).
-      static const bool old_rule_env = [] { const char* e = getenv("TFC_TILE_RULE_OLD"); return e && atoi(e) != 0; }();   // A/B knob for profiling
-      const bool old_rule = old_rule_env && !inv;
       const int w128 = ntiles * plan_phases(d) * ((nb + 3) / 4);
-      if (!old_rule && nb >= 4 && d.Cin_pad >= 64 && w128 >= ncu && (w128 < 2048 || d.Cin_pad >= 128))   // (128 -> 256 at 64 x 64: 130 -> 124 us; 64 -> 128 at 128 x 128 stays on <2,2,2,2>: 132 vs 157)   // (also 1-3 % ahead of <2,2,2,2> at 32 x 32 256->512; the two are equal beyond)
+      if (nb >= 4 && d.Cin_pad >= 64 && w128 >= ncu && (w128 < 2048 || d.Cin_pad >= 128))   // (128 -> 256 at 64 x 64: 130 -> 124 us; 64 -> 128 at 128 x 128 stays on <2,2,2,2>: 132 vs 157)   // (also 1-3 % ahead of <2,2,2,2> at 32 x 32 256->512; the two are equal beyond)
         form = 3;
     }
     if (form >= 0) {}
@@ -3154,20 +3015,8 @@ void tfc_plan_igemm(int dt, const TfcGather& d, int flags, int ncu, bool inv, Tf
   p->kernel = TFC_K_IGEMM;
   if (b16) {
     // bf16, compile-time tap pattern, whole 16-byte output units, NHWC output: the persistent kernel (test hook: config | 16 = one tile per workgroup)
-    static const bool legacy_env = [] { const char* e = getenv("TFC_LEGACY_IGEMM"); return e && atoi(e) != 0; }();   // A/B knob for profiling
-    if (p->pat != 0 && d.Nout % 8 == 0 && !(flags & TFC_EP_TANH_NCHW) && !(g_tfc_force_cfg >= 0 && (g_tfc_force_cfg & 16)) && !(legacy_env && !inv))
+    if (p->pat != 0 && d.Nout % 8 == 0 && !(flags & TFC_EP_TANH_NCHW) && !(g_tfc_force_cfg >= 0 && (g_tfc_force_cfg & 16)))
       p->kernel = TFC_K_IGEMM2;
-  }
-  if (p->kernel == TFC_K_IGEMM2 && 32 * kFormNT[form] * kFormWN[form] <= 128) {
-    // two-half form (see the kernel): one 512-thread workgroup per CU, halves (nst + 1) / 2 barrier slots apart. Needs two LDS regions (<= 160 KiB) and
-    // enough work for both halves of every CU. MEASURED NEUTRAL (scripts/ab_halves.py, DESIGN 3.1: conv shapes x0.98-1.02, transposed x0.87-0.93, with or
-    // without s_setprio in the K loop or a deeper weight ring), so it is OFF by default: TFC_IGEMM_HALVES=2 or test config | 32 select it
-    static const int halves_env = [] { const char* e = getenv("TFC_IGEMM_HALVES"); return e ? atoi(e) : 1; }();
-    const int nblkN = (nb + kFormNT[form] * kFormWN[form] - 1) / (kFormNT[form] * kFormWN[form]);
-    const int nwork = ntiles * plan_phases(d) * nblkN;
-    const int half_bytes = (igemm2_lds_bytes(d, kFormNT[form], kFormWN[form], flags, nullptr) + 255) & ~255;
-    if (halves_env == 2 && !inv && !d.reflect && 2 * half_bytes <= 160 * 1024 && nwork >= 2 * ncu && (g_tfc_force_cfg < 0 || (g_tfc_force_cfg & 32)))   // test hook: forced tiles run the two-workgroup form unless bit 5 is set
-      p->kernel = TFC_K_IGEMM2_HALVES;
   }
   p->nparts = igemm_nparts(d, p->kernel != TFC_K_IGEMM, kFormWM[form]);
 }
@@ -3203,12 +3052,11 @@ static hipError_t launch_igemm_pat(const TfcGather& d, const void* in, const voi
 
 // persistent bf16 kernel: 2 workgroups per CU walk the work items (tile x n-block x phase)
 template <int MT, int NT, int WM, int WN, int PAT>
-static hipError_t launch_igemm2_pat(const TfcConvPlan& plan, const TfcGather& d, const void* in, const void* wp, void* out, const float* bias,
+static hipError_t launch_igemm2_pat(const TfcGather& d, const void* in, const void* wp, void* out, const float* bias,
                                     float* stats, float* part_ws, float* dbg, const float* oscale, int flags, hipStream_t st) {
   const int NB32 = tfc_nb32_padded(d.Nout);
   const int per_blk = NT * WN;
   const int nblkN = (tfc_nb32(d.Nout) + per_blk - 1) / per_blk;
-  constexpr int BN = 32 * NT * WN;
   int buf_bytes = 0;
   const int lds = igemm2_lds_bytes(d, NT, WN, flags, &buf_bytes);
   const int nparts = igemm_nparts(d, true, WM);                   // part_ws[img][phase][tile][Nout][2]
@@ -3217,19 +3065,6 @@ static hipError_t launch_igemm2_pat(const TfcConvPlan& plan, const TfcGather& d,
   }
   const int nwork = d.nimg * d.tiles_y * d.tiles_x * (d.ph_n > 1 ? d.ph_n : 1) * nblkN;
   const long long phase_wbytes = (long long)tfc_packed_bytes(d, 2);
-  if constexpr (BN <= 128) {
-    const int nst = ((d.Cin_pad * 2) / 64) * d.nplanes;
-    const int half_bytes = (lds + 255) & ~255;
-    if (plan.kernel == TFC_K_IGEMM2_HALVES) {                     // the two-half form (tfc_plan_igemm)
-      static const int shift_env = [] { const char* e = getenv("TFC_IGEMM_SHIFT"); return e ? atoi(e) : -1; }();
-      static const int prio_env = [] { const char* e = getenv("TFC_IGEMM_PRIO"); return e ? atoi(e) : 0; }();
-      const int shift = (shift_env >= 0 ? shift_env : (nst + 1) / 2) | (prio_env ? 256 : 0);
-      TFC_LAUNCH((tfc_igemm2_kernel<MT, NT, WM, WN, PAT, 2>), dim3(tfc_num_cus()), dim3(512), 2 * half_bytes, st, d, (const bf16_t*)in, (const uint4*)wp,
-                 (bf16_t*)out, bias, part_ws, dbg, oscale, flags, NB32, nblkN, buf_bytes, phase_wbytes, nwork, half_bytes, shift);
-      if (flags & TFC_EP_STATS) return tfc_launch_part_reduce(part_ws, stats, d.nimg, nparts, 2 * d.Nout, st);
-      return hipGetLastError();
-    }
-  }
   // One instantiation per flag set that the training step issues (the epilogue is then straight-line code), one that reads the flags at run time for
   // every other combination. Same arithmetic per element in all of them: the stored bits do not depend on which one runs.
   if constexpr (PAT == 6) {
@@ -3241,13 +3076,13 @@ static hipError_t launch_igemm2_pat(const TfcConvPlan& plan, const TfcGather& d,
         static thread_local int occ_cache = 0, occ_lds = -1;
         if (!occ_cache || occ_lds != lds) {
           int occ = 0;
-          if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, tfc_igemm2_kernel<MT, NT, WM, WN, PAT, 1, FC, true>, 256, (size_t)lds) != hipSuccess || occ < 1) occ = 2;
+          if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, tfc_igemm2_kernel<MT, NT, WM, WN, PAT, FC, true>, 256, (size_t)lds) != hipSuccess || occ < 1) occ = 2;
           occ_cache = occ > 3 ? 3 : occ;
           occ_lds = lds;
         }
         const int cap = g_tfc_persistent_grid > 0 ? g_tfc_persistent_grid : occ_cache * tfc_num_cus();
-        TFC_LAUNCH((tfc_igemm2_kernel<MT, NT, WM, WN, PAT, 1, FC, true>), dim3(nwork < cap ? nwork : cap), dim3(256), lds, st, d, (const bf16_t*)in,
-                   (const uint4*)wp, (bf16_t*)out, bias, part_ws, dbg, oscale, flags, NB32, nblkN, buf_bytes, phase_wbytes, nwork, 0, 0);
+        TFC_LAUNCH((tfc_igemm2_kernel<MT, NT, WM, WN, PAT, FC, true>), dim3(nwork < cap ? nwork : cap), dim3(256), lds, st, d, (const bf16_t*)in,
+                   (const uint4*)wp, (bf16_t*)out, bias, part_ws, dbg, oscale, flags, NB32, nblkN, buf_bytes, phase_wbytes, nwork);
       };
       if (flags == 0) launch_rf(std::integral_constant<int, 0>{});
       else launch_rf(std::integral_constant<int, -1>{});
@@ -3262,15 +3097,14 @@ static hipError_t launch_igemm2_pat(const TfcConvPlan& plan, const TfcGather& d,
     static thread_local int occ_cache = 0, occ_lds = -1;
     if (!occ_cache || occ_lds != lds) {
       int occ = 0;
-      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, tfc_igemm2_kernel<MT, NT, WM, WN, PAT, 1, FC>, 256, (size_t)lds) != hipSuccess || occ < 1) occ = 2;
+      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, tfc_igemm2_kernel<MT, NT, WM, WN, PAT, FC>, 256, (size_t)lds) != hipSuccess || occ < 1) occ = 2;
       occ_cache = occ > 3 ? 3 : occ;
       occ_lds = lds;
     }
     // test hook (tfc_debug_set_persistent_grid): n >= 1 replaces the cap, as in tfc_persistent_grid, so that a tiny shape walks many tiles per workgroup
     const int cap = g_tfc_persistent_grid > 0 ? g_tfc_persistent_grid : occ_cache * tfc_num_cus();
-    TFC_LAUNCH((tfc_igemm2_kernel<MT, NT, WM, WN, PAT, 1, FC>), dim3(nwork < cap ? nwork : cap), dim3(256), lds, st, d, (const bf16_t*)in, (const uint4*)wp,
-               (bf16_t*)out, bias, part_ws, dbg, oscale, flags, NB32, nblkN, buf_bytes, phase_wbytes, nwork, 0,
-               [] { static const int p = [] { const char* e = getenv("TFC_IGEMM_PRIO"); return e ? atoi(e) : 0; }(); return p ? 256 : 0; }());
+    TFC_LAUNCH((tfc_igemm2_kernel<MT, NT, WM, WN, PAT, FC>), dim3(nwork < cap ? nwork : cap), dim3(256), lds, st, d, (const bf16_t*)in, (const uint4*)wp,
+               (bf16_t*)out, bias, part_ws, dbg, oscale, flags, NB32, nblkN, buf_bytes, phase_wbytes, nwork);
   };
   switch (flags) {
     case 0: launch(std::integral_constant<int, 0>{}); break;                                              // no norm behind it; with an oscale: D input gradients
@@ -3287,10 +3121,10 @@ template <int MT, int NT, int WM, int WN>
 static hipError_t launch_igemm2_cfg(const TfcConvPlan& plan, const TfcGather& d, const void* in, const void* wp, void* out, const float* bias,
                                     float* stats, float* part_ws, float* dbg, const float* oscale, int flags, hipStream_t st) {
   switch (plan.pat) {
-    case 1: return launch_igemm2_pat<MT, NT, WM, WN, 1>(plan, d, in, wp, out, bias, stats, part_ws, dbg, oscale, flags, st);
-    case 2: return launch_igemm2_pat<MT, NT, WM, WN, 2>(plan, d, in, wp, out, bias, stats, part_ws, dbg, oscale, flags, st);
-    case 3: return launch_igemm2_pat<MT, NT, WM, WN, 3>(plan, d, in, wp, out, bias, stats, part_ws, dbg, oscale, flags, st);
-    default: return launch_igemm2_pat<MT, NT, WM, WN, 6>(plan, d, in, wp, out, bias, stats, part_ws, dbg, oscale, flags, st);
+    case 1: return launch_igemm2_pat<MT, NT, WM, WN, 1>(d, in, wp, out, bias, stats, part_ws, dbg, oscale, flags, st);
+    case 2: return launch_igemm2_pat<MT, NT, WM, WN, 2>(d, in, wp, out, bias, stats, part_ws, dbg, oscale, flags, st);
+    case 3: return launch_igemm2_pat<MT, NT, WM, WN, 3>(d, in, wp, out, bias, stats, part_ws, dbg, oscale, flags, st);
+    default: return launch_igemm2_pat<MT, NT, WM, WN, 6>(d, in, wp, out, bias, stats, part_ws, dbg, oscale, flags, st);
   }
 }
 
@@ -3734,9 +3568,6 @@ static hipError_t launch_igemm_t(int dt, const TfcGather& d, const void* in, con
   tfc_plan_igemm(dt, d, flags, tfc_num_cus(), g_tfc_batch_invariant != 0, &plan);
   if constexpr (sizeof(T) == 2) {
     if (plan.kernel == TFC_K_CONV_C8) return tfc_launch_conv_c8(d, in, wp, out, bias, oscale, flags, nullptr, st);
-#ifdef TFC_PROBE_W64
-    if (plan.form == 4) return launch_igemm2_cfg<4, 2, 1, 4>(plan, d, in, wp, out, bias, stats, part_ws, out_nchw, oscale, flags, st);
-#endif
   }
   switch (plan.form) {
     case 0: return launch_igemm_cfg<T, 2, 2, 2, 2>(plan, d, in, wp, out, bias, stats, part_ws, out_nchw, oscale, flags, st);

@@ -93,14 +93,14 @@ extern thread_local int g_tfc_batch_invariant;    // tfc_set_batch_invariant: la
 #define TFC_REF_BATCH 32
 #define TFC_REF_CUS 256
 enum {
-  TFC_K_IGEMM = 0, TFC_K_IGEMM2 = 1, TFC_K_IGEMM2_HALVES = 2, TFC_K_CONV_C8 = 3,                      // forward / dgrad gather GEMM
+  TFC_K_IGEMM = 0, TFC_K_IGEMM2 = 1, TFC_K_CONV_C8 = 3,                                               // forward / dgrad gather GEMM (profiles record the ids: 2 stays free)
   TFC_K_WGRAD = 10, TFC_K_WGRAD22 = 11, TFC_K_WGRAD_C8 = 12, TFC_K_WGRAD_X3 = 13,                     // weight gradient
   TFC_K_WGRADT_UP = 14, TFC_K_WGRADT = 15, TFC_K_WGRADT2 = 16, TFC_K_WGRAD_HEAD = 17,
   TFC_K_FIRST_FWD = 20, TFC_K_FIRST_BWD = 21                                                            // fused first block
 };
 struct TfcConvPlan {
   int kernel;                 // TFC_K_*
-  int form;                   // tile form 0 <2,2,2,2>, 1 <2,1,2,2>, 2 <1,1,4,1>, 3 <4,1,1,4> (4: probe builds); -1 = the kernel has one form
+  int form;                   // tile form 0 <2,2,2,2>, 1 <2,1,2,2>, 2 <1,1,4,1>, 3 <4,1,1,4>; -1 = the kernel has one form
   int nparts;                 // partial slots per image that tfc_part_reduce_kernel adds in order (0: the pass keeps no per-image sums)
   int nsplit;                 // split count over pixel tiles (weight gradients; 1 otherwise)
   int wpi;                    // workgroups per image where the kernel's slot layout depends on it (first-block backward; 0 otherwise)
